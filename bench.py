@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- Mreads/s of the BGREAT mapping hot path (greedy, k=31, 150 bp, m=2) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one mapping launch (bgr_align_device of the C-ABI) over one batch of synthetic reads that is already resident
 in HBM as ASCII (what the reference's getReads hands over): the pre-pass that packs the reads to 2 bits and the passes of
 the mapping kernels, enqueued back to back on one stream.  Workload = BASELINE.json configs[2] ("Synthetic 50M x 150 bp
 reads, k=31, m=2, E.coli-scale graph (~100k unitigs), greedy"): with the defaults (10 steps x 5M reads) one run maps
-exactly that read set on one GPU.  With N>1 every rank maps its own equally sized shard (weak scaling); the read-only
-graph blob is built on rank 0 and broadcast once over RCCL.
+exactly that read set on one GPU.  At most MAX_BATCHES distinct batches are resident; more steps take them in turn.
+With N>1 every rank maps its own equally sized shard (weak scaling); the read-only graph blob is built on rank 0 and
+broadcast once over RCCL.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Besides `value` (device-resident) it carries
+A plain run sets up, warms up, times the K steps, writes the last step's results if --dump-outputs DIR is given (see
+dump_outputs) and prints the line with the headline figure: metric, value, unit, higher_is_better, dtype, ms_per_step,
+config and counters.  Everything else below (roofline and its counter passes, parity sample against the oracle, the
+other configs' sub-records, PCIe-inclusive and end-to-end legs, the CPU baseline, the N > 1 one-process forms) runs
+only with --full; the line then carries it as well.
+
+Prints ONE JSON line on rank 0 (contract in the task statement).  With --full, besides `value` (device-resident) it carries
   roofline       algorithmic bytes (SURVEY 8d formula, oracle counter mode) / launch time, plus what bounds the launch in
                  fact: HBM traffic measured in this run (rocprofv3 PMC passes over a short child run of this script) and
                  the VALU issue fraction
@@ -41,6 +48,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 CLOCK_GHZ = 2.4         # hipDeviceAttributeClockRate on the box; profiles/r02_valu_rates.txt is priced at it
 N_SIMD = 1024           # 256 CUs x 4
+MAX_BATCHES = 20        # distinct read batches resident per GPU (20 x 5M x 150 bp = 15 GB of HBM); more steps take them in turn
+DUMP_BYTES = 60 << 20   # --dump-outputs: the sample's size bound (under 64 MB even if every path held its read's maximum of ints)
+DUMP_SEED = 20261015    # --dump-outputs: which reads of the last batch are sampled
 
 
 def log(*a):
@@ -52,6 +62,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline figure: roofline and counter passes, parity sample, sub-records, "
+                                                          "PCIe-inclusive and end-to-end legs, CPU baseline, N > 1 one-process forms (off: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (a fixed, seeded sample of its "
+                                                                          "per-read results, and the counters) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--reads-per-step", type=int, default=5_000_000, help="reads per launch per GPU")
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--k", type=int, default=31)
@@ -190,13 +204,13 @@ def main():
     if args.dry_run:
         return dry_run(args, mode, world, rank, local_rank)
     pmc = None
-    if not args.pmc_child and not args.no_pmc and world == 1:
+    if args.full and not args.pmc_child and not args.no_pmc and world == 1:
         # child processes; this process has not initialised the GPU yet.  Never nested inside another profiler run.
         pmc = {"error": "already running under a profiler: counter passes skipped"} if under_profiler() else run_pmc_passes(args)
         log("pmc passes:", {k: v for k, v in pmc.items() if not k.startswith("_per")} if pmc else None)
 
     subs = None
-    if world == 1 and args.workload == "ecoli" and mode == 0 and not (args.pmc_child or args.sub_record or args.no_sub):
+    if args.full and world == 1 and args.workload == "ecoli" and mode == 0 and not (args.pmc_child or args.sub_record or args.no_sub):
         subs = run_sub_records(args)   # child processes, one after the other; this process has not initialised the GPU yet
 
     import torch
@@ -312,21 +326,22 @@ def main():
     offs_t = B.DeviceBuffer(dev, offs_np)   # parked in HBM through the C-ABI (bgr_device_alloc / bgr_device_upload): torch only synchronises and reduces
     batches = []
     first_host = None
-    for s in range(K):
+    n_batches = min(K, MAX_BATCHES)   # step i maps batch i % n_batches: HBM and set-up time stay bounded however many steps are timed
+    for s in range(n_batches):
         arr, _ = syn.reads((rank * K + s) * R, R, L, args.mismatch, seed_reads, threads=ncpu)
         if args.sorted_reads:
             order = np.argsort(syn.read_starts((rank * K + s) * R, R, L, seed_reads), kind="stable")
             arr = arr.reshape(R, L)[order].reshape(-1)
-        if s == 0 and rank == 0 and not args.pmc_child:
+        if s == 0 and rank == 0 and args.full and not args.pmc_child:
             first_host = arr[: max(args.cpu_sample, args.alg_sample) * L].copy()
         batches.append(B.DeviceBuffer(dev, arr))
         del arr
     torch.cuda.synchronize()
     if rank == 0:
-        log("reads: %d x %d x %d bp per GPU resident in HBM (%.1fs)" % (K, R, L, time.time() - t0))
+        log("reads: %d x %d x %d bp per GPU resident in HBM (%.1fs)" % (n_batches, R, L, time.time() - t0))
 
     def step(i):
-        b = batches[i % K]
+        b = batches[i % n_batches]
         al.align_device(b.data_ptr(), offs_t.data_ptr(), R, R * L, L, m=args.mismatch, effort=args.effort, mode=mode)
 
     for i in range(W):
@@ -355,6 +370,8 @@ def main():
     pass_counts = al.pass_counts()
     if dist is not None:  # C2: sum the aligner.h:68 counters over ranks
         counters = D.reduce_counters(counters, dist, device=coll_dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(al, args.dump_outputs, R, L, counters)   # before anything below maps another batch on this aligner
 
     # ---- rank 0: everything the line needs from the device-resident leg (value, roofline, parity sample) BEFORE the optional legs below, so
     # that a leg that never returns (a collective between real devices that this container has never run, a wedged file system) costs
@@ -364,6 +381,26 @@ def main():
     if rank == 0:
         total_reads = world * K * R
         value = total_reads / elapsed / 1e6
+        config = {"workload": "%s: synthetic %.1fM x %d bp reads per GPU (%d steps x %d), k=%d, m=%d, effort=%d, %s, graph of %d unitigs (genome %d bp, %d alleles every ~%d bp); "
+                              "reads resident in HBM as ASCII before the timed region, results left in HBM"
+                  % ({"ecoli": "BASELINE configs[2]", "small": "BASELINE configs[1]", "chr1": "BASELINE configs[3] graph scale, one GPU's share", "branchy": "BASELINE configs[4] graph, one GPU's share"}[args.workload],
+                     K * R / 1e6, L, K, R, args.k, args.mismatch, args.effort, ("greedy", "exhaustive", "greedy from k-mer anchors (-G)")[mode], graph_info["n_unitigs"], args.genome, args.alleles, args.site_spacing),
+                  "reads_per_step_per_gpu": R, "read_len": L, "k": args.k, "m": args.mismatch, "effort": args.effort, "distinct_batches": n_batches,
+                  "parallelism": "reads sharded over %d GPU(s); graph blob broadcast once" % world, "launch": al.launch_info(),
+                  "pass_counts_last_launch": pass_counts}
+        # the keys of the --full line in its order; a plain run leaves what only --full measures null
+        line = {
+            "metric": "Mreads/s aligned (k=%d, %dbp, m=%d)" % (args.k, L, args.mismatch), "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "config": config,
+            # SURVEY 8d's two metrics beside `value` (the device-resident kernel/roofline anchor): (i) H2D + launch + CSR + D2H from page-locked
+            # host buffers, one blocking caller; (ii) file in -> paths / notAligned.fa out, median of the runs (spread in e2e.runs_mreads_per_s)
+            "value_pcie_inclusive": None, "value_e2e": None,
+            "roofline": None, "pcie_inclusive": None, "e2e": None, "cpu_baseline": None, "multi_gpu": multi, "one_process_all_gpus": None,
+            "other_configs": subs,
+            "counters": counters, "parity_sample": None, "oracle_work_per_read": None,
+        }
+    if rank == 0 and args.full:
         avg_launch_ms = kernel_ms / max(1, launches)
 
         # ---- ALGORITHMIC bytes per read: SURVEY.md 8d formula, counted by the oracle on a sample of this workload ----
@@ -471,29 +508,13 @@ def main():
         elif pmc:
             roofline["traffic_note"] = "not measured in this run: " + pmc["error"]
 
-        line = {
-            "metric": "Mreads/s aligned (k=%d, %dbp, m=%d)" % (args.k, L, args.mismatch), "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": "%s: synthetic %.1fM x %d bp reads per GPU (%d steps x %d), k=%d, m=%d, effort=%d, %s, graph of %d unitigs (genome %d bp, %d alleles every ~%d bp); "
-                                   "reads resident in HBM as ASCII before the timed region, results left in HBM"
-                       % ({"ecoli": "BASELINE configs[2]", "small": "BASELINE configs[1]", "chr1": "BASELINE configs[3] graph scale, one GPU's share", "branchy": "BASELINE configs[4] graph, one GPU's share"}[args.workload],
-                          K * R / 1e6, L, K, R, args.k, args.mismatch, args.effort, ("greedy", "exhaustive", "greedy from k-mer anchors (-G)")[mode], graph_info["n_unitigs"], args.genome, args.alleles, args.site_spacing),
-                       "reads_per_step_per_gpu": R, "read_len": L, "k": args.k, "m": args.mismatch, "effort": args.effort,
-                       "parallelism": "reads sharded over %d GPU(s); graph blob broadcast once" % world, "launch": al.launch_info(),
-                       "pass_counts_last_launch": pass_counts},
-            # SURVEY 8d's two metrics beside `value` (the device-resident kernel/roofline anchor): (i) H2D + launch + CSR + D2H from page-locked
-            # host buffers, one blocking caller; (ii) file in -> paths / notAligned.fa out, median of the runs (spread in e2e.runs_mreads_per_s)
-            "value_pcie_inclusive": None, "value_e2e": None,
-            "roofline": roofline, "pcie_inclusive": None, "e2e": None, "cpu_baseline": None, "multi_gpu": multi, "one_process_all_gpus": None,
-            "other_configs": subs,
-            "counters": counters, "parity_sample": {"reads": ns, "gpu_equals_oracle": parity_ok},
-            "oracle_work_per_read": {k: round(v / ns, 2) for k, v in work.items() if k not in ("reads",)},
-        }
+        line.update({"roofline": roofline, "parity_sample": {"reads": ns, "gpu_equals_oracle": parity_ok},
+                     "oracle_work_per_read": {k: round(v / ns, 2) for k, v in work.items() if k not in ("reads",)}})
     guard.arm(line)
 
     # ---- end to end: file in -> paths / notAligned.fa out (every rank its own shard file and GPU) ---------------
     e2e = None
-    if args.e2e_reads > 0 and mode == 0:
+    if args.full and args.e2e_reads > 0 and mode == 0:
         guard.stage("e2e")
         e2e = run_e2e(args, B, syn, g, rank, world, dev, ncpu, dist, D if dist is not None else None, coll_dev, seed_reads)
 
@@ -501,7 +522,7 @@ def main():
     # then device to device over xGMI: RCCL broadcast or peer copies) and one aligner + one host thread per device; rank 0 runs it
     # while the other ranks wait (their batches stay parked: the devices are otherwise idle)
     one_proc = None
-    if world > 1:
+    if args.full and world > 1:
         guard.stage("one_process_all_gpus")
         one_proc = rank0_alone(dist, rank, "one_process_threads", lambda: run_one_process_all_gpus(args, B, g, syn, world, mode, seed_reads, ncpu, rehearsal))
 
@@ -511,14 +532,14 @@ def main():
 
     # ---- PCIe inclusive: pinned host buffers through bgr_align_batch (H2D + launch + CSR + D2H), N=1 only ---------
     pcie = None
-    if world == 1 and args.pcie_steps > 0 and mode == 0:
+    if args.full and world == 1 and args.pcie_steps > 0 and mode == 0:
         pcie = run_pcie(args, B, g, al, syn, seed_reads, ncpu, dev)
 
     # ---- CPU baseline: the compiled reference (oracle/_ref/bgreat -t cores) on a bounded sample, N=1 only -------
     cpu = None
-    if world == 1 and args.cpu_sample > 0 and mode == 0 and not args.sub_record:
+    if args.full and world == 1 and args.cpu_sample > 0 and mode == 0 and not args.sub_record:
         cpu = run_cpu_baseline(args, al, syn, first_host, ncpu, seed_reads)
-    if world == 1 and args.cpu_sample_exh > 0 and mode == 1:
+    if args.full and world == 1 and args.cpu_sample_exh > 0 and mode == 1:
         cpu = run_cpu_baseline_exhaustive(args, al, syn, first_host, ncpu, seed_reads)
 
     if world == 1 and args.full_parity and not args.sub_record:
@@ -534,6 +555,37 @@ def main():
     line.update({"value_pcie_inclusive": (pcie or {}).get("value"), "value_e2e": (e2e or {}).get("value"), "pcie_inclusive": pcie, "e2e": e2e, "cpu_baseline": cpu,
                  "one_process_all_gpus": one_proc})
     guard.finish(line, dist)
+
+
+def dump_outputs(al, out_dir, R, L, counters):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of bgr_align_device receives it (bgr_aligner_fetch: per read a
+    status byte and its path ints, in input order), for a fixed, seeded sample of that batch's reads; the inputs are seeded as well, so two
+    builds run with the same arguments can be compared file by file.  Written as DIR/<name>.npy:
+      read_index   float64 [S]    the sampled reads' positions in the batch (all R reads when S = R)
+      status       float32 [S]    their status bytes
+      path_offsets float64 [S+1]  offsets of their paths in `paths`
+      paths        float64 [P]    their path ints, concatenated (float64: exact for every int32)
+      counters     float64 [5]    the line's counters over the timed steps: reads, no_overlap, aligned, not_aligned, overlaps
+    S is sized so that the files stay under 64 MB if no path holds more than max_read_len + 8 ints (the library's bound per batch);
+    a sample whose paths hold more is cut to its first reads that fit."""
+    t0 = time.time()
+    paths, poffs, status = al.fetch(R, R * (L + 8) + 8)   # (the library's own bound on path ints; only what is written is touched)
+    S = min(R, DUMP_BYTES // ((L + 8) * 8 + 20))
+    idx = np.arange(R, dtype=np.int64) if S == R else np.sort(np.random.default_rng(DUMP_SEED).choice(R, S, replace=False))
+    starts = poffs[idx].astype(np.int64)
+    lens = poffs[idx + 1].astype(np.int64) - starts
+    out_offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    if out_offs[-1] * 8 > DUMP_BYTES - S * 20:
+        S = int(np.searchsorted(out_offs, (DUMP_BYTES - S * 20) // 8, side="right")) - 1
+        idx, starts, lens, out_offs = idx[:S], starts[:S], lens[:S], out_offs[: S + 1]
+    rows = np.arange(int(out_offs[-1]), dtype=np.int64) - np.repeat(out_offs[:-1], lens) + np.repeat(starts, lens)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"read_index": idx.astype(np.float64), "status": status[idx].astype(np.float32), "path_offsets": out_offs.astype(np.float64),
+              "paths": paths[rows].astype(np.float64),
+              "counters": np.array([counters[k] for k in ("reads", "no_overlap", "aligned", "not_aligned", "overlaps")], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs: %d of %d reads of the last step, %d path ints -> %s (%.1fs)" % (S, R, len(rows), out_dir, time.time() - t0))
 
 
 def dry_run(args, mode, world, rank, local_rank):
@@ -1030,7 +1082,7 @@ def run_sub_records(args):
     out = {}
     for w in ("small", "chr1", "branchy"):
         t0 = time.time()
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--sub-record", "--steps", str(args.steps), "--warmup", str(args.warmup),
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--sub-record", "--full", "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--cpu-threads", str(args.cpu_threads), "--pmc-steps", str(args.pmc_steps)]
         if args.no_pmc:
             cmd.append("--no-pmc")

@@ -30,6 +30,7 @@ int bgr_graph_unitigs(const bgr_graph*, const char**, const uint64_t**, uint64_t
 int bgr_graph_upload(bgr_graph*, int) { return BGR_OK; }
 int bgr_aligner_create(bgr_graph*, int device, bgr_aligner** out) { *out = new bgr_aligner(); (*out)->device = device; return BGR_OK; }
 void bgr_aligner_destroy(bgr_aligner* a) { delete a; }
+int bgr_aligner_set_knob(bgr_aligner* a, uint32_t, uint64_t) { return a ? BGR_OK : BGR_E_ARG; }
 int bgr_device_local_cpus(int, char*, uint64_t) { return BGR_E_IO; }
 int bgr_host_alloc(uint64_t bytes, void** out) { *out = malloc(bytes ? bytes : 1); return *out ? BGR_OK : BGR_E_HIP; }
 int bgr_host_free(void* p) { free(p); return BGR_OK; }

@@ -934,7 +934,7 @@ def test_bench_line_contract():
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads-per-step", "200000", "--e2e-reads", "200000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--reads-per-step", "200000", "--e2e-reads", "200000",
            "--pcie-steps", "1", "--cpu-sample", "20000", "--cpu-sample-all", "30000", "--alg-sample", "4000", "--no-pmc", "--no-sub", "--genome", "400000",
            "--full-parity", "--full-parity-scale", "0.002"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -976,6 +976,46 @@ def test_bench_line_contract():
     assert fp["equal"] is True and fp["c1_equal"] and fp["c2_equal"] and fp["c4_equal"] and fp["c2_reads"] == 100000 and d["config"]["full_parity_equal"] is True
 
 
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the steps and prints the headline line without the legs of --full; --dump-outputs writes
+    what the last step computed for a seeded sample of its reads (float32 / float64 .npy, under 64 MB), and that is what the oracle
+    computes for the same reads."""
+    import json
+    import subprocess
+    import sys
+    K, R, L, genome = 3, 100000, 150, 400000
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", "1", "--reads-per-step", str(R), "--genome", str(genome),
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == 1 and d["unit"] == "Mreads/s" and d["higher_is_better"] is True and d["dtype"] == "u64" and d["value"] > 0
+    assert abs(R / (d["ms_per_step"] / 1e3) / 1e6 - d["value"]) <= 0.01 * d["value"]
+    assert d["counters"]["reads"] == K * R and d["config"]["distinct_batches"] == K
+    for key in ("roofline", "parity_sample", "pcie_inclusive", "e2e", "cpu_baseline", "other_configs", "one_process_all_gpus"):
+        assert d[key] is None, key
+    names = ("read_index", "status", "path_offsets", "paths", "counters")
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(out / (n + ".npy")) for n in names) <= 64 << 20
+    a = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["counters"].tolist() == [float(d["counters"][k]) for k in ("reads", "no_overlap", "aligned", "not_aligned", "overlaps")]
+    idx = a["read_index"].astype(np.int64)
+    assert 1000 < len(idx) <= R and np.all(np.diff(idx) > 0) and idx[-1] < R
+    # the last step mapped batch K - 1: bench.py's seeds, graph and read draw
+    syn = Synth(genome, 140, 2, 31, 20261003)
+    seqs, offs = syn.unitigs()
+    reads, _ = syn.reads((K - 1) * R, R, L, 2, 77)
+    s_reads = np.ascontiguousarray(reads.reshape(R, L)[idx]).reshape(-1)
+    s_offs = np.arange(len(idx) + 1, dtype=np.uint64) * np.uint64(L)
+    p2, po2, st2 = oracle_py.Oracle(31, seqs, offs).align(s_reads, s_offs, m=2, effort=2)
+    assert np.array_equal(a["status"], st2.astype(np.float32))
+    assert np.array_equal(a["path_offsets"], po2.astype(np.float64)) and np.array_equal(a["paths"], p2.astype(np.float64))
+
+
 def test_bench_sub_record_of_the_exhaustive_config():
     """The default bench line carries configs[1], [3] and [4] as sub-records (children `bench.py --workload W --sub-record`); here the
     exhaustive one on a small graph: one JSON line, the device-resident leg only, a parity sample, and the reference's -b counters on
@@ -983,7 +1023,7 @@ def test_bench_sub_record_of_the_exhaustive_config():
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "branchy", "--sub-record", "--steps", "2", "--warmup", "1", "--reads-per-step", "100000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "branchy", "--sub-record", "--full", "--steps", "2", "--warmup", "1", "--reads-per-step", "100000",
            "--genome", "300000", "--cpu-sample-exh", "5000", "--alg-sample", "2000", "--no-pmc"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -1008,7 +1048,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     import sys
     env = dict(os.environ, BGR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29517",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads-per-step", "300000", "--e2e-reads", "400000",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads-per-step", "300000", "--e2e-reads", "400000",
            "--alg-sample", "3000", "--genome", "400000", "--no-pmc"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -1040,7 +1080,7 @@ def test_bench_line_comes_out_when_an_optional_leg_hangs():
     import sys
     env = dict(os.environ, BGR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", BGR_BENCH_TEST_HANG="one_process_all_gpus", BGR_BENCH_DEADLINE="25")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29519",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads-per-step", "200000", "--e2e-reads", "0",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads-per-step", "200000", "--e2e-reads", "0",
            "--alg-sample", "2000", "--genome", "400000", "--no-pmc"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -1,11 +1,12 @@
 #!/bin/bash
 # tools/ab_pmc.sh TAG [bench flags...] -- GPU box: device-resident leg of one workload WITH the counter passes; prints value, kernel times, VALU / SALU per read, issue fraction
 T=$1; shift
-mkdir -p gpurun_out/qb
-timeout -k 10 400 python bench.py --no-sub --e2e-reads 0 --pcie-steps 0 --cpu-sample 0 --cpu-sample-exh 0 --steps 20 --warmup 3 "$@" > gpurun_out/qb/$T.json 2> gpurun_out/qb/$T.err || echo FAILED
+OUT=${OUT_DIR:-out}/qb   # (OUT_DIR: where the tools write, relative to the repository root; default out/)
+mkdir -p $OUT
+timeout -k 10 400 python bench.py --full --no-sub --e2e-reads 0 --pcie-steps 0 --cpu-sample 0 --cpu-sample-exh 0 --steps 20 --warmup 3 "$@" > $OUT/$T.json 2> $OUT/$T.err || echo FAILED
 python - <<PY
 import json
-d = json.loads(open("gpurun_out/qb/$T.json").read().strip().splitlines()[-1])
+d = json.loads(open("$OUT/$T.json").read().strip().splitlines()[-1])
 r = d["roofline"]; v = r.get("valu_issue") or {}
 print("%-14s %8.1f Mreads/s  kernels %s" % ("$T", d["value"], [(k["kernel"].split(" ")[0][-24:], k["avg_ms"]) for k in r["kernels_ms"]]))
 print("               valu/read %s salu/read %s issue frac %s paired %s cycles/inst %s  l2 hit %s traffic B/read %s" % (v.get("valu_insts_per_read"), v.get("salu_insts_per_read"), v.get("frac"), v.get("paired_share"), v.get("cycles_per_valu_inst"), r.get("l2_hit_rate"), r.get("traffic_bytes_per_read")))

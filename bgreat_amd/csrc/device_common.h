@@ -175,6 +175,77 @@ __device__ __forceinline__ uint32_t find_key(const BgrDeviceGraph& g, TP tab, u6
     return res;
 }
 
+// find_key for the anchor scan of bgr_align_greedy_multi_kernel with its key table staged in LDS: the 64 lanes hold 64 consecutive read
+// positions, lane order = position order, and the step only asks for the first key in lane order and -- need2 -- the second one.  The answer
+// is find_key's in every lane up to and including that hit (in all lanes when there are fewer hits); a lane behind it may say BGR_NONE
+// although it holds a key (it never names a slot that is not its key's).
+// The common step (no lane with two fingerprint candidates) costs one key load per candidate lane and no loop:
+//  - fingerprints: one broadcast, and per bucket word the short zero-byte test (x - 0x01..) & ~x & 0x80..: exact up to the lowest zero byte,
+//    above it a byte 0x01 can be flagged as well -- a candidate the key compare rejects, never a lost one;
+//  - each lane confirms its FIRST candidate (bucket 1's lowest, else bucket 2's) with one load and one compare;
+//  - only lanes whose first candidate failed and that have more (fingerprint collisions in both buckets or twice in one: a few steps in a
+//    hundred), and that lie before the step's first (need2: second) confirmed hit, go through find_key's general loop for the rest.
+// (inactive lanes read their two bucket words as well -- the buckets of any key lie inside the table -- and confirm nothing)
+template <typename TP>
+__device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP tab, u64 key, bool active, bool need2, uint32_t lane) {
+    const u64 m = bgr_mix64(key);
+    const uint32_t b1 = __umulhi((uint32_t)m, g.n_buckets), b2 = __umulhi((uint32_t)(m >> 32), g.n_buckets);
+    const uint32_t w1 = tab[b1], w2 = tab[b2];
+    const uint32_t f4 = __builtin_amdgcn_perm(0u, bgr_tab_fp(m), 0u);  // the fingerprint in all four bytes
+    const uint32_t x1 = w1 ^ f4, x2 = w2 ^ f4;
+    uint32_t c1 = (uint32_t)__builtin_amdgcn_bitop3_b32((int)(x1 - 0x01010101u), (int)x1, (int)0x80808080u, 0x20);  // a & ~b & c
+    uint32_t c2 = (uint32_t)__builtin_amdgcn_bitop3_b32((int)(x2 - 0x01010101u), (int)x2, (int)0x80808080u, 0x20);
+    const bool first1 = c1 != 0;
+    uint32_t res = BGR_NONE, ncand = 0;  // ncand: the lane's candidates when its first one failed, else 0 (>= 2: more to confirm)
+    if (active && (c1 | c2)) {
+        const uint32_t slot = (first1 ? b1 : b2) * 4 + ((uint32_t)__builtin_ctz(first1 ? c1 : c2) >> 3);
+        ncand = (uint32_t)__builtin_popcount(c1) + (uint32_t)__builtin_popcount(c2);
+        if (g.keys[slot].key == key) { res = slot; ncand = 0; }
+    }
+    u64 hits;
+    uint32_t upto;
+    if (__ballot(ncand >= 2)) {  // rare: the rest of the candidates, as find_key does
+        // lanes up to the step's first (need2: second) hit so far: what lies behind it cannot change the answer
+        hits = __ballot(res != BGR_NONE);
+        if (need2) hits &= hits - 1;
+        upto = (uint32_t)__builtin_popcountll(hits ^ (hits - 1));  // the lanes below this number (no such hit: all lanes)
+        if (ncand >= 2 && lane < upto) {
+            if (first1) c1 &= c1 - 1;
+            else c2 &= c2 - 1;
+        } else {
+            c1 = 0;
+            c2 = 0;
+        }
+        while (wave_any((c1 | c2) != 0)) {
+            if (c1 | c2) {
+                const bool first = c1 != 0;
+                const uint32_t c = first ? c1 : c2;
+                const uint32_t idx = (first ? b1 : b2) * 4 + ((uint32_t)(__ffs((int)c) - 1) >> 3);
+                if (g.keys[idx].key == key) { res = idx; c1 = 0; c2 = 0; }
+                else if (first) c1 &= c1 - 1;
+                else c2 &= c2 - 1;
+            }
+        }
+    }
+    if (g.flags & BGR_GF_HAS_FALLBACK) {
+        hits = __ballot(res != BGR_NONE);
+        if (need2) hits &= hits - 1;
+        upto = (uint32_t)__builtin_popcountll(hits ^ (hits - 1));
+        const bool look = active && res == BGR_NONE && lane < upto;
+        if (wave_any(look) && look) {  // bisection in the sorted fallback list, as in find_key
+            const uint32_t nfb = (uint32_t)g.hdr->n_fallback;
+            const u64* fb = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(g.hdr) + g.hdr->off_fallback);
+            uint32_t lo = 0, hi = nfb;
+            while (lo < hi) {
+                uint32_t mid = (lo + hi) >> 1;
+                if (fb[mid] < key) lo = mid + 1; else hi = mid;
+            }
+            if (lo < nfb && fb[lo] == key) res = 4u * g.n_buckets + lo;
+        }
+    }
+    return res;
+}
+
 // Minimizer filter, scan side.  h = bgr_mmx_hash of the 16-mer that starts at the lane's read position (0 where the read has none).
 // Returns, for the (k-1)-mer that starts there, the largest h over its W = k-16 16-mers -- bgr_mmx_of_key of it -- in lanes
 // 0 .. 64-W (the lanes behind lack their right neighbours: a scan advances by 65-W positions per step).  Whole-wave DPP shifts

@@ -307,7 +307,10 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                 const uint32_t mblock = (STAGE || !mmx_w) ? 0u
                                       : wide_scan ? scan_mblock_wide(g, win, i + BGR_MMX_BASES <= Lq, i + 2 * BGR_MMX_BASES <= Lq, mmx_w)
                                                   : scan_mblock(g, win, i + BGR_MMX_BASES <= Lq, mmx_w);
-                uint32_t idx = find_key<!STAGE>(g, ktab, num < rcn ? num : rcn, valid, mblock);
+                // (table in LDS: the scan's own lookup, which confirms only the hits the step can use)
+                uint32_t idx;
+                if constexpr (STAGE) idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, left_q >= 2, (uint32_t)lane);
+                else idx = find_key<true>(g, ktab, num < rcn ? num : rcn, valid, mblock);
                 const u64 mask = __ballot(idx != BGR_NONE);
                 if (mask) {
                     if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;

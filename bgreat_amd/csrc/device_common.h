@@ -730,11 +730,48 @@ __device__ __forceinline__ bool greedy_from_anchor(const BgrDeviceGraph& g, cons
 }
 
 // ---- the extension step of the several-reads-per-wave kernels (greedy mode, anchors mode) ----------------------------------------
+// The compare loop of g4_step for graphs without exception bases: the mismatches between the unitig bases from base `ub` of seq word `fw` on
+// and the read bases from base `rb` of FW on, for `v` bases (<= 0: the lane compares nothing), in 32-base chunks `ql` chunks apart.  What
+// ham_chunk(g, FW, nullptr, false, ...) counts per chunk, summed, with what stays the same from chunk to chunk taken out of the loop:
+//  - both funnel shift amounts (a chunk lies 32 ql bases behind the one before it, at the same offsets inside its words) and the
+//    addresses, which advance by 8 ql bytes per round;
+//  - the valid-bases mask as one 64-bit shift of the even-bit mask by max(64 - 2 v, 0), kept as the loop variable e = 64 - 2 v
+//    (a lane takes part while e < 64);
+//  - the mismatch bits (x | x >> 1) & mask per 32-bit half: the bit that would cross the halves is an odd one, masked off anyway;
+//  - no exception-plane branch in the loop (ham_chunk tests BGR_GF_HAS_EXC per chunk, and its plane path keeps registers live).
+__device__ __forceinline__ uint32_t g4_lean_compare(const u64* seq, const u64* FW, uint32_t fw, uint32_t ub, uint32_t rb, int32_t v, uint32_t ql) {
+    const uint32_t su = (ub & 31) * 2, sr = (rb & 31) * 2;
+    uint32_t uoff = (fw + (ub >> 5)) << 3;  // byte offset into seq, < 4 GiB (checked when the graph is built)
+    const u64* rp = FW + (rb >> 5);
+    const uint32_t ustep = 8 * ql;
+    int32_t e = 64 - 2 * v;
+    uint32_t cnt = 0;
+    while (wave_any(e < 64)) {
+        if (e < 64) {
+            const u64* up = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(seq) + uoff);
+            const u64 uw0 = up[0], uw1 = up[1];  // (issued ahead of the LDS read: the HBM/L2 latency is the longer one)
+            const u64 r = (rp[0] << sr) | ((rp[1] >> 1) >> (63 - sr));
+            const u64 u0 = uw0 << su, u1 = (uw1 >> 1) >> (63 - su);
+            // x = u ^ r per half, the funnel's OR folded in: (u0 | u1) ^ r = one v_bitop3 (truth table 0x56)
+            const uint32_t xh = (uint32_t)__builtin_amdgcn_bitop3_b32((int)(u0 >> 32), (int)(u1 >> 32), (int)(r >> 32), 0x56);
+            const uint32_t xl = (uint32_t)__builtin_amdgcn_bitop3_b32((int)u0, (int)u1, (int)r, 0x56);
+            const u64 em = EVEN_BITS << (uint32_t)(e > 0 ? e : 0);
+            cnt += __popc((xh | (xh >> 1)) & (uint32_t)(em >> 32)) + __popc((xl | (xl >> 1)) & (uint32_t)em);
+        }
+        e += 64 * (int32_t)ql;
+        uoff += ustep;
+        rp += ql;
+    }
+    return cnt;
+}
+
 // One extension step for up to 64 / GL walks, one per GL-lane group (GL = 16, 8 or 4: four, two or one lane per candidate slot).  `phase` (uniform within a group): 0 = the group sits
 // out, 1 = left step (checkBeginGreedy / mapOnLeftEndGreedy), 2 = first right step (checkEndGreedy: the read slice starts
 // behind the k-1 overlap), 3 = later right step (mapOnRightEndGreedy: the slice includes the overlap).  alignerGreedy.cpp:167-364.
 // Result, uniform within a group: next record | next canonical << 28 | fits << 29 | found << 30; miss; ext; sid.
-template <int GL = 16>
+// LEAN: the compare loop of g4_lean_compare instead of ham_chunk's -- for graphs without exception bases only (BGR_GF_HAS_EXC clear; the
+// launch planner never sends other graphs to the several-reads-per-wave kernels, launch_plan.h).
+template <int GL = 16, bool LEAN = false>
 __device__ __forceinline__ uint32_t g4_step(const BgrDeviceGraph& g, const u64* FW, uint32_t L, uint32_t K1, uint32_t phase, uint32_t rec, uint32_t canon,
                                             uint32_t pos, uint32_t budget, int lane, uint32_t* miss, uint32_t* ext_o, int32_t* sid_o) {
     constexpr uint32_t QL = GL / 4;  // lanes per candidate slot: each takes 32 bases per round of the compare
@@ -784,8 +821,11 @@ __device__ __forceinline__ uint32_t g4_step(const BgrDeviceGraph& g, const u64* 
     // instruction issue and the second compare path cost more than the load it saves -- chr1-scale 1 331 with, 1 359 Mreads/s without;
     // E. coli scale 1 206 / 1 286 -- so this step always reads the bases from `seq`)
     uint32_t cnt = 0;
-    for (uint32_t b = q * 32; wave_any(b < n); b += 32 * ql)
-        if (b < n) cnt += ham_chunk(g, FW, nullptr, false, fw, fo + ustart + b, rstart + b, n - b);
+    if constexpr (LEAN) cnt = g4_lean_compare(g.seq, FW, fw, fo + ustart + q * 32, rstart + q * 32, (int32_t)n - (int32_t)(q * 32), ql);
+    else {
+        for (uint32_t b = q * 32; wave_any(b < n); b += 32 * ql)
+            if (b < n) cnt += ham_chunk(g, FW, nullptr, false, fw, fo + ustart + b, rstart + b, n - b);
+    }
     if (QL >= 2) cnt += quad_xor1(cnt);
     if (QL == 4) cnt += quad_xor2(cnt);
     if (GL == 4) { const uint32_t o2 = quad_xor2(cnt); if (two) cnt += o2; }  // (the two lanes of a candidate: l and l ^ 2)

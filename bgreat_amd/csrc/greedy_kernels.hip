@@ -155,6 +155,8 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
 #define G4_ST_POS_MASK 0xFFFFFu
 
 // GL = lanes per read (kG4GroupLanes, align_kernels.h): 16 = four reads per wave, 8 = eight, 4 = sixteen.
+// The walk step is g4_step's lean form (no exception-plane code): the launch planner sends a graph with unitig bases outside ACGT
+// (BGR_GF_HAS_EXC) to bgr_align_greedy_kernel only (launch_plan.h, fast_pass).
 template <bool STAGE, int GL, bool ASCII>
 __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kernel(BgrDeviceGraph g, BatchIO io, KernelParams prm) {
     constexpr uint32_t RPW = 64 / GL;  // reads per wave
@@ -360,7 +362,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             if (!__any(on != 0)) break;
             uint32_t miss, ext;
             int32_t sid;
-            const uint32_t w1 = g4_step<GL>(g, F, L, K1, on, rec & G4_REC_MASK, (rec >> 28) & 1u, pos, budget, lane, &miss, &ext, &sid);
+            const uint32_t w1 = g4_step<GL, true>(g, F, L, K1, on, rec & G4_REC_MASK, (rec >> 28) & 1u, pos, budget, lane, &miss, &ext, &sid);
             if (on != 0) {
                 if (!(w1 & G4_FOUND)) {
                     st += 1u << G4_ST_TRIED_SHIFT;

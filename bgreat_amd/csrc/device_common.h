@@ -730,7 +730,7 @@ __device__ __forceinline__ bool greedy_from_anchor(const BgrDeviceGraph& g, cons
 }
 
 // ---- the extension step of the several-reads-per-wave kernels (greedy mode, anchors mode) ----------------------------------------
-// The compare loop of g4_step for graphs without exception bases: the mismatches between the unitig bases from base `ub` of seq word `fw` on
+// The compare loop of g2_step (graphs without exception bases): the mismatches between the unitig bases from base `ub` of seq word `fw` on
 // and the read bases from base `rb` of FW on, for `v` bases (<= 0: the lane compares nothing), in 32-base chunks `ql` chunks apart.  What
 // ham_chunk(g, FW, nullptr, false, ...) counts per chunk, summed, with what stays the same from chunk to chunk taken out of the loop:
 //  - both funnel shift amounts (a chunk lies 32 ql bases behind the one before it, at the same offsets inside its words) and the
@@ -768,10 +768,9 @@ __device__ __forceinline__ uint32_t g4_lean_compare(const u64* seq, const u64* F
 // One extension step for up to 64 / GL walks, one per GL-lane group (GL = 16, 8 or 4: four, two or one lane per candidate slot).  `phase` (uniform within a group): 0 = the group sits
 // out, 1 = left step (checkBeginGreedy / mapOnLeftEndGreedy), 2 = first right step (checkEndGreedy: the read slice starts
 // behind the k-1 overlap), 3 = later right step (mapOnRightEndGreedy: the slice includes the overlap).  alignerGreedy.cpp:167-364.
-// Result, uniform within a group: next record | next canonical << 28 | fits << 29 | found << 30; miss; ext; sid.
-// LEAN: the compare loop of g4_lean_compare instead of ham_chunk's -- for graphs without exception bases only (BGR_GF_HAS_EXC clear; the
-// launch planner never sends other graphs to the several-reads-per-wave kernels, launch_plan.h).
-template <int GL = 16, bool LEAN = false>
+// Result, uniform within a group: next record | next canonical << 28 | fits << 29 | found << 30; miss; ext; sid.  (The greedy multi
+// kernel walks through g2_step below, its two-lane form.)
+template <int GL = 16>
 __device__ __forceinline__ uint32_t g4_step(const BgrDeviceGraph& g, const u64* FW, uint32_t L, uint32_t K1, uint32_t phase, uint32_t rec, uint32_t canon,
                                             uint32_t pos, uint32_t budget, int lane, uint32_t* miss, uint32_t* ext_o, int32_t* sid_o) {
     constexpr uint32_t QL = GL / 4;  // lanes per candidate slot: each takes 32 bases per round of the compare
@@ -821,11 +820,8 @@ __device__ __forceinline__ uint32_t g4_step(const BgrDeviceGraph& g, const u64* 
     // instruction issue and the second compare path cost more than the load it saves -- chr1-scale 1 331 with, 1 359 Mreads/s without;
     // E. coli scale 1 206 / 1 286 -- so this step always reads the bases from `seq`)
     uint32_t cnt = 0;
-    if constexpr (LEAN) cnt = g4_lean_compare(g.seq, FW, fw, fo + ustart + q * 32, rstart + q * 32, (int32_t)n - (int32_t)(q * 32), ql);
-    else {
-        for (uint32_t b = q * 32; wave_any(b < n); b += 32 * ql)
-            if (b < n) cnt += ham_chunk(g, FW, nullptr, false, fw, fo + ustart + b, rstart + b, n - b);
-    }
+    for (uint32_t b = q * 32; wave_any(b < n); b += 32 * ql)
+        if (b < n) cnt += ham_chunk(g, FW, nullptr, false, fw, fo + ustart + b, rstart + b, n - b);
     if (QL >= 2) cnt += quad_xor1(cnt);
     if (QL == 4) cnt += quad_xor2(cnt);
     if (GL == 4) { const uint32_t o2 = quad_xor2(cnt); if (two) cnt += o2; }  // (the two lanes of a candidate: l and l ^ 2)
@@ -842,6 +838,86 @@ __device__ __forceinline__ uint32_t g4_step(const BgrDeviceGraph& g, const u64* 
     *sid_o = (int32_t)lane_get(fwd ? id : 0u - id, src);
     *miss = key >> 2;
     return (key >> 2) <= budget ? w1 | G4_FOUND : 0u;  // an empty record gives key 0xFFFFFFFF: not found
+}
+
+// One extension step for up to 32 walks, one per lane pair (lanes 2j, 2j + 1; `phase`, `rec`, `pos` and `budget` uniform within a pair), so
+// that the two halves of an anchor -- left walk, right walk -- can step at the same time on the two pairs of a read's quad.  Same phases,
+// same result, same choice ("first zero, else first strict minimum" = the smallest miss << 2 | slot) as g4_step on four lanes, with the
+// compare loop of g4_lean_compare: graphs without exception bases only (the launch planner sends no other graph to the several-reads-
+// per-wave kernels, launch_plan.h).  Lane c & 1 of a pair takes candidate c, 32 bases per compare round:
+//  - one candidate: both lanes take it, every other 32-base chunk each;
+//  - two candidates (nearly every other half of a graph of 2-allele sites): one lane each;
+//  - three or four (no BGR_SLOT_LAST on slots 0-1): a second round takes slots 2 and 3, loaded behind the first round's flags (a
+//    dependent load, but a rare one: the wave only runs it when one of its pairs needs it).
+// The pair's minimum is one quad_xor1 step, and the winner's pk / ext / sid come from the lane that holds it by DPP (no ds_bpermute).
+__device__ __forceinline__ uint32_t g2_step(const BgrDeviceGraph& g, const u64* FW, uint32_t L, uint32_t K1, uint32_t phase, uint32_t rec, uint32_t canon,
+                                            uint32_t pos, uint32_t budget, int lane, uint32_t* miss, uint32_t* ext_o, int32_t* sid_o) {
+    const uint32_t p = (uint32_t)lane & 1u;
+    const uint32_t on = (phase != 0 && rec != G4_REC_MASK) ? 1u : 0u;
+    const uint32_t left = phase == 1 ? 1u : 0u;
+    // left: `rl` bases of the read lie left of the overlap; right: behind it (first step) / from its start (later steps)
+    const uint32_t kk = phase == 2 ? K1 : 0u;
+    const uint32_t rl = left ? pos : L - pos - kk;
+    uint32_t c = p, n_cand = 0;
+    uint32_t best = 0xFFFFFFFFu, bpk = 0, bext = 0, bsid = 0;
+    for (uint32_t round = 0;; ++round) {
+        uint4 sl = make_uint4(0, 0, 0, BGR_SLOT_LAST), m0 = make_uint4(0, 0, 0, 0);
+        const uint32_t look = round == 0 ? on : (n_cand == 4 ? 1u : 0u);  // (4: slots 0-1 carry no flag, the count is not known yet)
+        if (look) {
+            const uint4* sp = reinterpret_cast<const uint4*>(g.recs) + (size_t)(rec + c) * 2;
+            sl = sp[0];
+            m0 = sp[1];
+        }
+        // candidates = the slots up to and including the first flagged one (none flagged among four: none, as in g4_step)
+        const uint32_t nb = (uint32_t)(__ballot((sl.w & BGR_SLOT_LAST) != 0) >> ((uint32_t)lane & 62u)) & 3u;
+        if (look) {
+            if (nb) n_cand = round * 2 + (nb & 1u ? 1u : 2u);
+            else if (round == 0) n_cand = 4;
+            else { n_cand = 0; best = 0xFFFFFFFFu; }
+        }
+        uint32_t nx = canon ? m0.y : m0.z;  // next half | canonical << 28 (graph_layout.h nx0 / nx1)
+        // a half with ONE candidate (on a graph of 2-allele sites: the long unitig behind an allele): the pair's second lane takes slot 0
+        // over (DPP) and the two lanes compare every other 32-base chunk, so the compare runs half the rounds
+        const uint32_t one = (round == 0 && n_cand == 1) ? 1u : 0u;
+        uint32_t q = 0, ql = 1;
+        {
+            const uint32_t t0 = quad_xor1(sl.x), t1 = quad_xor1(sl.y), t2 = quad_xor1(sl.z), t3 = quad_xor1(sl.w), t4 = quad_xor1(nx);
+            if (one && p) { sl = make_uint4(t0, t1, t2, t3); nx = t4; c = 0; }
+            if (one) { q = p; ql = 2; }
+        }
+        const uint32_t id = sl.x & BGR_SLOT_ID_MASK;
+        const uint32_t fwd = (sl.x & (canon ? BGR_SLOT_F0 : BGR_SLOT_F1)) ? 1u : 0u;
+        const uint32_t len = sl.y;
+        const uint32_t fw = sl.z, fo = (sl.w & BGR_SLOT_FO_MASK) + (fwd ? 0u : len);
+        const uint32_t ext = len - K1;
+        const uint32_t fits = ext >= rl ? 1u : 0u;
+        const uint32_t span = left ? ext : ext + K1 - kk;  // what is compared when the walk goes on: the unitig beyond the overlap, or all of it
+        uint32_t n = fits ? rl : (span < rl ? span : rl);  // (later right steps: read.substr(pos, |u|) is clipped at |read|)
+        const uint32_t ustart = left ? ext - n : kk;
+        const uint32_t rstart = left ? rl - n : pos + kk;
+        const uint32_t valid = (look && c < n_cand) ? 1u : 0u;
+        if (!valid) n = 0;
+        uint32_t cnt = g4_lean_compare(g.seq, FW, fw, fo + ustart + q * 32, rstart + q * 32, (int32_t)n - (int32_t)(q * 32), ql);
+        const uint32_t oc = quad_xor1(cnt);
+        if (one) cnt += oc;
+        const uint32_t key = valid ? ((cnt > 0x0FFFFFFFu ? 0x0FFFFFFFu : cnt) << 2) | c : 0xFFFFFFFFu;
+        if (key < best) {
+            best = key;
+            bpk = (nx & (G4_REC_MASK | G4_CANON)) | (fits ? G4_FITS : 0u);
+            bext = ext;
+            bsid = fwd ? id : 0u - id;
+        }
+        if (round == 1 || !wave_any(n_cand == 4)) break;
+        c += 2;
+    }
+    const uint32_t o = quad_xor1(best);
+    const uint32_t key = o < best ? o : best;
+    const uint32_t opk = quad_xor1(bpk), oext = quad_xor1(bext), osid = quad_xor1(bsid);
+    const uint32_t mine = (key & 1u) == p ? 1u : 0u;  // (candidate c sits on lane c & 1 of the pair)
+    *ext_o = mine ? bext : oext;
+    *sid_o = (int32_t)(mine ? bsid : osid);
+    *miss = key >> 2;
+    return (key >> 2) <= budget ? (mine ? bpk : opk) | G4_FOUND : 0u;  // an empty record gives key 0xFFFFFFFF: not found
 }
 
 // waves per SIMD the kernels are compiled for (__launch_bounds__)

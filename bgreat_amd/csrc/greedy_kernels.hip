@@ -1,6 +1,6 @@
 // greedy_kernels.hip -- greedy mode (alignReadGreedy, alignerGreedy.cpp:35-57,167-364) on gfx950.
 //   bgr_align_greedy_multi_kernel  sixteen reads per wavefront (lanes per read: a template parameter): the position scans one after the
-//                             other on all 64 lanes, the extensions side by side, 8 lanes each; settles the common shapes, lists the rest
+//                             other on all 64 lanes, the extensions side by side, 4 lanes each (both walks of an anchor at once); settles the common shapes, lists the rest
 //   bgr_align_greedy_kernel   the general kernel: one read per wavefront, every anchor, both strands, N planes, any path length
 #include "device_common.h"
 
@@ -128,9 +128,9 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
 // most 4 candidates x a few 32-base chunks, i.e. a handful of the 64 lanes, and per read there are ~3 such steps in a row.
 // Here a wave takes 64 / GL reads, GL lanes each (GL = 4: SIXTEEN reads; round 2 started with GL = 16, four reads, and ended with 8):
 // their position scans still run one after the other on all 64 lanes (a scan is lane-efficient: one (k-1)-mer per lane), then
-// the extensions run side by side, GL lanes each (4 candidate slots x GL/4 chunk lanes of 32 bases; at GL = 4 one lane per slot, two
-// when a half has at most two candidates), so sixteen slot/base load chains are in flight per wave and every wave instruction of a
-// walk step serves sixteen reads (a quad of reads needs max-over-4 = 3.4 steps, an octet 3.7: the instructions per read nearly halve
+// the extensions run side by side, GL lanes each (at GL = 4: the left walk on lanes 0-1, the right walk on lanes 2-3, one lane per
+// candidate slot; g2_step), so thirty-two slot/base load chains are in flight per wave and every wave instruction of a walk step serves
+// sixteen reads (a quad of reads needs max-over-4 = 3.4 steps, an octet 3.7: the instructions per read nearly halve
 // with every doubling).  Path ints go straight into the read's own row of the arena (kG4PathInts ints: left walk downwards from the
 // middle, right walk upwards), so there are no path registers, no per-wave arena chunks and no copy when a walk ends.
 //
@@ -155,10 +155,12 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
 #define G4_ST_POS_MASK 0xFFFFFu
 
 // GL = lanes per read (kG4GroupLanes, align_kernels.h): 16 = four reads per wave, 8 = eight, 4 = sixteen.
-// The walk step is g4_step's lean form (no exception-plane code): the launch planner sends a graph with unitig bases outside ACGT
-// (BGR_GF_HAS_EXC) to bgr_align_greedy_kernel only (launch_plan.h, fast_pass).
+// The walk step is g2_step: g4_step's lean form (no exception-plane code) on two lanes, the left and the right walk of a read on the two
+// pairs of its quad (so GL = 4 only).  The launch planner sends a graph with unitig bases outside ACGT (BGR_GF_HAS_EXC) to
+// bgr_align_greedy_kernel only (launch_plan.h, fast_pass).
 template <bool STAGE, int GL, bool ASCII>
 __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kernel(BgrDeviceGraph g, BatchIO io, KernelParams prm) {
+    static_assert(GL == 4, "the two-pair walk takes four lanes per read");
     constexpr uint32_t RPW = 64 / GL;  // reads per wave
     extern __shared__ u64 lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -331,62 +333,77 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         // starts over from the next one, if the scan has seen it, while the others go on ----
         // phase: 1 left walk, 2 first right step, 3 later right steps; 0 the walk is over (aligned, or there was no anchor),
         // 4 the path outgrew the registers, 5 every anchor seen failed.  `tried` counts on in the item's state word.
-        uint32_t nl = 0, nr = 0;
+        // The two walks of an anchor run at the same time on the two lane pairs of the group (g2_step): lanes 0-1 walk left, lanes 2-3
+        // walk right, each with its own phase, position, half, miss count and path ints, so the wave waits for the longest SIDE of its
+        // sixteen reads rather than for the longest left + right (E. coli scale, a CPU model that counts only the forward first items that align,
+        // tools/walk_sides.py: 2.9 instead of 3.9 loop iterations per sixteen reads).
+        // The right walk's steps do not depend on the left walk: a step's choice ignores the budget (which only decides whether the
+        // chosen candidate is accepted), and misses are >= 0, so "every step fits what is left of m" == "the running total stays <= m".
+        // Each pair stops once its own total passes m; the read is settled from both behind the loop, as the sequential walk would end.
         constexpr uint32_t PH = kG4PathInts / 2;
-        int32_t* PT = io.arena + (size_t)(r == BGR_NONE ? 0u : r) * kG4PathInts;  // the read's row; written by the group's first lane (only while the group walks)
-        uint32_t phase = (act && a_rec != BGR_NONE) ? 1u : 0u;
+        // the read's row in the arena, left ints from lane 0, right ints from lane 2 (an index, as `gbase` below: a 64-bit pointer costs a VGPR spill)
+        const uint32_t PT0 = (r == BGR_NONE ? 0u : r) * kG4PathInts;
+        const uint32_t side = (sub >> 1) & 1u;  // 0: the left walk, 1: the right walk
+        uint32_t phase = (act && a_rec != BGR_NONE) ? 1u + side : 0u;
 #ifdef BGR_PHASE_TIMING  /* diagnostic builds (tools/phase_cost.sh): knob DEBUG_STOP = 2 stops behind the anchor scan */
         if (prm.debug_stop == 2) phase = 0;
 #endif
         // rec: the half the next step reads (handle | canonical << 28).  An anchor is a key entry: its left walk starts from the half that
         // getEnd reads for it, its right walk from the one getBegin reads -- both handles sit in the key entry, fetched by ONE 8-byte load
-        // when the anchor is taken up (a_right waits for the left walk to end: a load at that point would stall all sixteen walks)
-        uint32_t a_right = G4_REC_MASK;
-        auto take_anchor = [&](uint32_t anchor) -> uint32_t {  // -> the left start; sets a_right
-            const uint32_t cn = (anchor >> 28) & 1u;
-            const uint2 h = *reinterpret_cast<const uint2*>(&g.keys[anchor & G4_REC_MASK].hL);
-            a_right = (cn ? h.x : h.y) | (cn ? G4_CANON : 0u);
-            return (cn ? h.y : h.x) | (cn ? G4_CANON : 0u);
-        };
-        uint32_t pos = a_pos, rec = phase ? take_anchor(a_rec) : G4_REC_MASK, budget = m;
+        uint32_t rec = G4_REC_MASK;
+        if (phase) {
+            const uint32_t cn = (a_rec >> 28) & 1u;
+            const uint2 h = *reinterpret_cast<const uint2*>(&g.keys[a_rec & G4_REC_MASK].hL);
+            rec = ((cn ^ side) ? h.y : h.x) | (cn ? G4_CANON : 0u);
+        }
+        uint32_t pos = a_pos, cum = 0, ni = 0;  // cum: the pair's misses so far; ni: the path ints it has pushed
         for (;;) {
-            if (phase == 1 && pos == 0) {  // the left walk reached the read's first base: push 0, then the right side of the anchor
-                if (sub == 0) PT[PH - 1 - nl] = 0;
-                ++nl;
-                phase = 2; pos = a_pos; rec = a_right;
+            if (phase == 1 && pos == 0) {  // the left walk reached the read's first base: push 0
+                if (sub == 0) io.arena[PT0 + PH - 1 - ni] = 0;
+                ++ni;
+                phase = 0;
             }
-            if (phase == 2 && L - pos - K1 == 0) phase = 0;  // nothing right of the anchor: aligned
-            if (phase == 3 && L - pos < K1 + 1) phase = 0;   // |readLeft| < k: aligned
-            if ((phase == 1 && nl > PH - 2) || ((phase == 2 || phase == 3) && nr > PH - 1)) phase = 4;  // path too long for the row (a left step may push two ints)
+            if (phase == 2 && L - pos - K1 == 0) phase = 0;  // nothing right of the anchor
+            if (phase == 3 && L - pos < K1 + 1) phase = 0;   // |readLeft| < k
+            if ((phase == 1 && ni > PH - 2) || ((phase == 2 || phase == 3) && ni > PH - 1)) phase = 4;  // path too long for the row (a left step may push two ints)
             const uint32_t on = (phase - 1u < 3u) ? phase : 0u;
             if (!__any(on != 0)) break;
             uint32_t miss, ext;
             int32_t sid;
-            const uint32_t w1 = g4_step<GL, true>(g, F, L, K1, on, rec & G4_REC_MASK, (rec >> 28) & 1u, pos, budget, lane, &miss, &ext, &sid);
+            const uint32_t w1 = g2_step(g, F, L, K1, on, rec & G4_REC_MASK, (rec >> 28) & 1u, pos, m - cum, lane, &miss, &ext, &sid);
             if (on != 0) {
-                if (!(w1 & G4_FOUND)) {
-                    st += 1u << G4_ST_TRIED_SHIFT;
-                    // (the next anchor of getNOverlap's list, when the scan saw it, is taken up by a follow-up item that resumes AT it -- rounds 3-4
-                    // restarted the walk in this loop, which kept all sixteen groups' loop going for one walk: profiles/r05_scan_schemes.txt)
-                    if (b_pos) { a_pos = b_pos - 1; b_pos = 0; }
-                    phase = 5;
-                } else if (phase == 1) {
-                    if (sub == 0) PT[PH - 1 - nl] = sid;
-                    ++nl;
-                    budget -= miss;
+                if (!(w1 & G4_FOUND)) phase = 5;
+                else {
+                    if ((sub & 1u) == 0) io.arena[PT0 + (phase == 1 ? PH - 1 - ni : PH + ni)] = sid;
+                    ++ni;
+                    cum += miss;
                     if (w1 & G4_FITS) {
-                        if (sub == 0) PT[PH - 1 - nl] = (int32_t)(ext - pos);
-                        ++nl;
-                        phase = 2; pos = a_pos; rec = a_right;
-                    } else { pos -= ext; rec = w1; }
-                } else {
-                    if (sub == 0) PT[PH + nr] = sid;
-                    ++nr;
-                    budget -= miss;
-                    if (w1 & G4_FITS) phase = 0;
+                        if (phase == 1) {
+                            if (sub == 0) io.arena[PT0 + PH - 1 - ni] = (int32_t)(ext - pos);
+                            ++ni;
+                        }
+                        phase = 0;
+                    } else if (phase == 1) { pos -= ext; rec = w1; }
                     else { pos += ext; rec = w1; phase = 3; }
                 }
             }
+        }
+        // Settle the read as the left-then-right walk would have ended (phase: 0 aligned, 4 general kernel, 5 failed): the left walk's
+        // overflow or failure decides alone; then a right overflow goes to the general kernel only if the steps done so far fit m
+        // together with the left walk's misses (else the sequential walk would have failed before it); then a right failure, or both
+        // totals together above m, fail the anchor.
+        const uint32_t o_phase = quad_xor2(phase), o_cum = quad_xor2(cum), o_ni = quad_xor2(ni);  // (the other pair: lanes l ^ 2)
+        const uint32_t lph = side ? o_phase : phase, rph = side ? phase : o_phase;
+        const uint32_t tot = cum + o_cum;
+        const uint32_t nl = side ? o_ni : ni, nr = side ? ni : o_ni;
+        if (lph == 4 || lph == 5) phase = lph;
+        else if (rph == 4) phase = tot <= m ? 4u : 5u;
+        else phase = (rph == 5 || tot > m) ? 5u : 0u;
+        if (phase == 5) {
+            st += 1u << G4_ST_TRIED_SHIFT;
+            // (the next anchor of getNOverlap's list, when the scan saw it, is taken up by a follow-up item that resumes AT it -- rounds 3-4
+            // restarted the walk in this loop, which kept all sixteen groups' loop going for one walk: profiles/r05_scan_schemes.txt)
+            if (b_pos) { a_pos = b_pos - 1; b_pos = 0; }
         }
 
         // ---- what became of each item (alignerGreedy.cpp:35-57) ---------------------------------------------------------------

@@ -758,7 +758,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         iof.gen_list = static_cast<uint32_t*>(a->ovf2.p);
         iof.gen_ctr = 8;
 #ifdef BGR_PHASE_TIMING
-        HIP_TRY(a->wave_times.ensure((uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block * 32));
+        HIP_TRY(a->wave_times.ensure((uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block * 64));  // time stamps, then scan counts
+        HIP_TRY(hipMemsetAsync(a->wave_times.p, 0, (uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block * 64, a->stream));  // (waves with no reads write nothing)
         iof.wave_times = static_cast<unsigned long long*>(a->wave_times.p);
         a->wave_times_n = (uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block;
 #endif
@@ -1604,6 +1605,16 @@ int bgr_debug_wave_times(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint
     *n_waves = a->wave_times_n;
     const uint64_t n = std::min(cap_waves, a->wave_times_n);
     if (n && out) HIP_TRY(hipMemcpy(out, a->wave_times.p, n * 32, hipMemcpyDeviceToHost));
+    return BGR_OK;
+}
+// the greedy multi kernel's anchor-scan counts per wave of the last launch: {scan steps, items scanned, groups of items, 0}
+int bgr_debug_scan_counts(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
+    if (!a || !n_waves) return BGR_E_ARG;
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    *n_waves = a->wave_times_n;
+    const uint64_t n = std::min(cap_waves, a->wave_times_n);
+    if (n && out) HIP_TRY(hipMemcpy(out, static_cast<const char*>(a->wave_times.p) + a->wave_times_n * 32, n * 32, hipMemcpyDeviceToHost));
     return BGR_OK;
 }
 #endif

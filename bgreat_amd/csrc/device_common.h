@@ -175,10 +175,19 @@ __device__ __forceinline__ uint32_t find_key(const BgrDeviceGraph& g, TP tab, u6
     return res;
 }
 
-// find_key for the anchor scan of bgr_align_greedy_multi_kernel with its key table staged in LDS: the 64 lanes hold 64 consecutive read
-// positions, lane order = position order, and the step only asks for the first key in lane order and -- need2 -- the second one.  The answer
-// is find_key's in every lane up to and including that hit (in all lanes when there are fewer hits); a lane behind it may say BGR_NONE
-// although it holds a key (it never names a slot that is not its key's).
+// scan_find_key's cut: the lanes of the lane's half (position order, lane & 31) up to and including its half's first hit -- need2: its
+// second -- so the number of lanes worth confirming; all 32 when there is no such hit.
+__device__ __forceinline__ uint32_t scan_hits_upto(u64 hits, bool need2, uint32_t lane) {
+    uint32_t h = (lane & 32u) ? (uint32_t)(hits >> 32) : (uint32_t)hits;
+    if (need2) h &= h - 1;
+    return (uint32_t)__builtin_popcount(h ^ (h - 1));
+}
+// find_key for the anchor scan of bgr_align_greedy_multi_kernel with its key table staged in LDS.  The wave scans two reads at once: lanes
+// 0-31 hold 32 consecutive positions of one read and lanes 32-63 of another, lane & 31 = position order within a half, and each half's
+// step only asks for its first key in lane order and -- need2, the lane's half's -- the second one.  The answer is find_key's in every lane
+// up to and including its half's needed hit (in all lanes of the half when it has fewer hits); a lane behind it may say BGR_NONE although
+// it holds a key (it never names a slot that is not its key's).  The cut is each half's own: a hit of one read must not cut the candidates
+// of the other.
 // The common step (no lane with two fingerprint candidates) costs one key load per candidate lane and no loop:
 //  - fingerprints: one broadcast, and per bucket word the short zero-byte test (x - 0x01..) & ~x & 0x80..: exact up to the lowest zero byte,
 //    above it a byte 0x01 can be flagged as well -- a candidate the key compare rejects, never a lost one;
@@ -202,14 +211,11 @@ __device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP ta
         ncand = (uint32_t)__builtin_popcount(c1) + (uint32_t)__builtin_popcount(c2);
         if (g.keys[slot].key == key) { res = slot; ncand = 0; }
     }
-    u64 hits;
     uint32_t upto;
     if (__ballot(ncand >= 2)) {  // rare: the rest of the candidates, as find_key does
         // lanes up to the step's first (need2: second) hit so far: what lies behind it cannot change the answer
-        hits = __ballot(res != BGR_NONE);
-        if (need2) hits &= hits - 1;
-        upto = (uint32_t)__builtin_popcountll(hits ^ (hits - 1));  // the lanes below this number (no such hit: all lanes)
-        if (ncand >= 2 && lane < upto) {
+        upto = scan_hits_upto(__ballot(res != BGR_NONE), need2, lane);  // the half's lanes below this number (no such hit: all 32)
+        if (ncand >= 2 && (lane & 31u) < upto) {
             if (first1) c1 &= c1 - 1;
             else c2 &= c2 - 1;
         } else {
@@ -228,10 +234,8 @@ __device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP ta
         }
     }
     if (g.flags & BGR_GF_HAS_FALLBACK) {
-        hits = __ballot(res != BGR_NONE);
-        if (need2) hits &= hits - 1;
-        upto = (uint32_t)__builtin_popcountll(hits ^ (hits - 1));
-        const bool look = active && res == BGR_NONE && lane < upto;
+        upto = scan_hits_upto(__ballot(res != BGR_NONE), need2, lane);
+        const bool look = active && res == BGR_NONE && (lane & 31u) < upto;
         if (wave_any(look) && look) {  // bisection in the sorted fallback list, as in find_key
             const uint32_t nfb = (uint32_t)g.hdr->n_fallback;
             const u64* fb = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(g.hdr) + g.hdr->off_fallback);

@@ -1,6 +1,7 @@
 // greedy_kernels.hip -- greedy mode (alignReadGreedy, alignerGreedy.cpp:35-57,167-364) on gfx950.
-//   bgr_align_greedy_multi_kernel  sixteen reads per wavefront (lanes per read: a template parameter): the position scans one after the
-//                             other on all 64 lanes, the extensions side by side, 4 lanes each (both walks of an anchor at once); settles the common shapes, lists the rest
+//   bgr_align_greedy_multi_kernel  sixteen reads per wavefront (lanes per read: a template parameter): the position scans two at a time on
+//                             32 lanes each (key table in LDS; else one at a time on all 64 lanes), the extensions side by side, 4 lanes each
+//                             (both walks of an anchor at once); settles the common shapes, lists the rest
 //   bgr_align_greedy_kernel   the general kernel: one read per wavefront, every anchor, both strands, N planes, any path length
 #include "device_common.h"
 
@@ -177,6 +178,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
 #ifdef BGR_PHASE_TIMING  /* tools/wave_times.sh: when does a wave start, have its table, finish its share of the batch, finish its queue */
     const unsigned long long wt0 = wall_clock64();
     unsigned long long wt2 = 0;
+    uint32_t dbg_steps = 0, dbg_items = 0, dbg_groups = 0;  // tools/scan_steps.py: scan steps, items scanned, groups of items taken
 #endif
     uint32_t ktab_words;
     const uint32_t* ktab = block_prologue<STAGE>(g, lds, &ktab_words);
@@ -289,42 +291,114 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         wave_sync();
 
         // ---- anchors (getNOverlap, aligner.cpp:345-378): the next overlap (k-1)-mer of each item from where its scan stands and,
-        // when it lies in the same 64 positions, the one after it; record | canonical << 28
+        // when it lies in the same step's positions, the one after it; record | canonical << 28
         uint32_t a_pos = 0, a_rec = BGR_NONE, b_pos = 0;  // (b_pos: the hit after a_pos when the scan's step saw one, else 0)
-        for (uint32_t q = 0; q < RPW; ++q) {
-            if (!rl32(act, (int)(GL * q))) continue;
+        if constexpr (STAGE) {
+            // Two scanners per wave: lanes 0-31 scan one item, lanes 32-63 another, 32 positions per step each.  A half is done with its
+            // item once it has seen the hit the item needs (and the next one, for b_pos, when that lies in the same 32 positions) or has
+            // passed npos; it then takes the next item in group order, so a step rarely spends lanes beyond the hit an item needs
+            // (E. coli scale: 22.7 -> 19.1 steps per sixteen reads, tools/scan_halves.py).  A step still looks up 64 (k-1)-mers.
+            // Per half, all uniform: the item's group hq, the step's first position hb, the item's npos hn (0: the half is idle) and
+            // whether it takes a second anchor (h2).  `pend`: bit GL q = group q's item is still to be scanned.
+            u64 pend = __ballot(act != 0 && sub == 0);
 #ifdef BGR_PHASE_TIMING
-            if (prm.debug_stop == 1) continue;  // 1 = stops behind the staging of the reads
+            if (prm.debug_stop == 1) pend = 0;  // 1 = stops behind the staging of the reads
+            dbg_items += (uint32_t)__popcll(pend);
+            ++dbg_groups;
 #endif
-            const uint32_t Lq = rl32(L, (int)(GL * q)), stq = rl32(st, (int)(GL * q));
-            const u64* A = RD + q * W;
-            const uint32_t left_q = eff - ((stq >> G4_ST_TRIED_SHIFT) & 0x7FFu);  // anchors this strand may still try (>= 1)
-            uint32_t npos = Lq >= K1 ? Lq - K1 + 1 : 0;
-            if (!prm.effort && npos > 1) npos = 1;
-            for (uint32_t base = stq & G4_ST_POS_MASK; base < npos; base += scan_step) {
-                const uint32_t i = base + (uint32_t)lane;
-                const bool valid = i < npos && (uint32_t)lane < scan_step;
-                u64 num = 0, win = 0;
-                if (valid || (mmx_w && i + BGR_MMX_BASES <= Lq)) win = lds_win32(A, i);
-                if (valid) num = win >> (64 - 2 * K1);
+            // The lane's own copy of its half's state, set when the half takes an item and stepped by 32 (no per-step selects between the
+            // halves' uniforms): position li, npos ln (0: idle), the item's first word lw, need2 l2.
+            const bool hi = lane >= 32;
+            uint32_t li = 0, ln = 0, lw = 0, l2 = 0;
+            auto take = [&](bool h, uint32_t& hq, uint32_t& hb, uint32_t& hn, uint32_t& h2) {
+                hn = 0;
+                while (pend) {
+                    const int at = __ffsll((long long)pend) - 1;
+                    pend &= pend - 1;
+                    const uint32_t Lq = rl32(L, at), stq = rl32(st, at);
+                    uint32_t npos = Lq >= K1 ? Lq - K1 + 1 : 0;
+                    if (!prm.effort && npos > 1) npos = 1;
+                    if ((stq & G4_ST_POS_MASK) < npos) {  // (else nothing left to scan: no anchor)
+                        hq = (uint32_t)at / GL;
+                        hb = stq & G4_ST_POS_MASK;
+                        hn = npos;
+                        h2 = eff - ((stq >> G4_ST_TRIED_SHIFT) & 0x7FFu) >= 2 ? 1u : 0u;  // anchors this strand may still try >= 2
+                        break;
+                    }
+                }
+                if (hi == h) { li = hb + ((uint32_t)lane & 31u); ln = hn; lw = hq * W; l2 = h2; }
+            };
+            uint32_t q0 = 0, b0 = 0, n0 = 0, s0 = 0, q1 = 0, b1 = 0, n1 = 0, s1 = 0;
+            take(false, q0, b0, n0, s0);
+            take(true, q1, b1, n1, s1);
+            while (n0 | n1) {
+#ifdef BGR_PHASE_TIMING
+                ++dbg_steps;
+#endif
+                const bool valid = li < ln;
+                u64 num = 0;
+                if (valid) num = lds_win32(RD + lw, li) >> (64 - 2 * K1);
                 const u64 rcn = rcb_fast(num, K1);  // no N in the read: the rolling reverse k-mer is rcb of the forward one
-                const uint32_t mblock = (STAGE || !mmx_w) ? 0u
-                                      : wide_scan ? scan_mblock_wide(g, win, i + BGR_MMX_BASES <= Lq, i + 2 * BGR_MMX_BASES <= Lq, mmx_w)
-                                                  : scan_mblock(g, win, i + BGR_MMX_BASES <= Lq, mmx_w);
-                // (table in LDS: the scan's own lookup, which confirms only the hits the step can use)
-                uint32_t idx;
-                if constexpr (STAGE) idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, left_q >= 2, (uint32_t)lane);
-                else idx = find_key<true>(g, ktab, num < rcn ? num : rcn, valid, mblock);
+                uint32_t idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, l2 != 0, (uint32_t)lane);
                 const u64 mask = __ballot(idx != BGR_NONE);
+                li += 32;
                 if (mask) {
                     if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;
-                    const int s1 = __ffsll((long long)mask) - 1;
-                    const u64 mask2 = mask & (mask - 1);
-                    const uint32_t h1 = rl32(idx, s1);
-                    uint32_t p2 = 0;
-                    if (mask2 && left_q >= 2) p2 = base + (uint32_t)(__ffsll((long long)mask2) - 1);  // a second anchor is tried when the first fails: where a follow-up item resumes
-                    if (grp == q) { a_pos = base + (uint32_t)s1; a_rec = h1; b_pos = p2; }
-                    break;
+                    // each half's first hit (and second) goes to its item's group: a readlane of the hit lane, a select on grp
+                    auto settle = [&](uint32_t mh, int off, uint32_t hq, uint32_t hb, uint32_t& hn, uint32_t h2) {
+                        if (mh) {
+                            const uint32_t f = (uint32_t)__builtin_ctz(mh), mh2 = mh & (mh - 1);
+                            const uint32_t h = rl32(idx, off + (int)f);
+                            // a second anchor is tried when the first fails: where a follow-up item resumes
+                            const uint32_t p2 = (mh2 && h2) ? hb + (uint32_t)__builtin_ctz(mh2) : 0u;
+                            if (grp == hq) { a_pos = hb + f; a_rec = h; b_pos = p2; }
+                            hn = 0;
+                        }
+                    };
+                    if (n0) settle((uint32_t)mask, 0, q0, b0, n0, s0);
+                    if (n1) settle((uint32_t)(mask >> 32), 32, q1, b1, n1, s1);
+                }
+                b0 += 32;
+                if (b0 >= n0) n0 = 0;
+                b1 += 32;
+                if (b1 >= n1) n1 = 0;
+                if (!n0) take(false, q0, b0, n0, s0);  // (both halves done: the low one takes first)
+                if (!n1) take(true, q1, b1, n1, s1);
+            }
+        } else {
+            // key table in L2 (minimizer filter: a window maximum across the whole wave): one item per step on all 64 lanes
+            for (uint32_t q = 0; q < RPW; ++q) {
+                if (!rl32(act, (int)(GL * q))) continue;
+#ifdef BGR_PHASE_TIMING
+                if (prm.debug_stop == 1) continue;  // 1 = stops behind the staging of the reads
+#endif
+                const uint32_t Lq = rl32(L, (int)(GL * q)), stq = rl32(st, (int)(GL * q));
+                const u64* A = RD + q * W;
+                const uint32_t left_q = eff - ((stq >> G4_ST_TRIED_SHIFT) & 0x7FFu);  // anchors this strand may still try (>= 1)
+                uint32_t npos = Lq >= K1 ? Lq - K1 + 1 : 0;
+                if (!prm.effort && npos > 1) npos = 1;
+                for (uint32_t base = stq & G4_ST_POS_MASK; base < npos; base += scan_step) {
+                    const uint32_t i = base + (uint32_t)lane;
+                    const bool valid = i < npos && (uint32_t)lane < scan_step;
+                    u64 num = 0, win = 0;
+                    if (valid || (mmx_w && i + BGR_MMX_BASES <= Lq)) win = lds_win32(A, i);
+                    if (valid) num = win >> (64 - 2 * K1);
+                    const u64 rcn = rcb_fast(num, K1);  // no N in the read: the rolling reverse k-mer is rcb of the forward one
+                    const uint32_t mblock = !mmx_w ? 0u
+                                          : wide_scan ? scan_mblock_wide(g, win, i + BGR_MMX_BASES <= Lq, i + 2 * BGR_MMX_BASES <= Lq, mmx_w)
+                                                      : scan_mblock(g, win, i + BGR_MMX_BASES <= Lq, mmx_w);
+                    uint32_t idx = find_key<true>(g, ktab, num < rcn ? num : rcn, valid, mblock);
+                    const u64 mask = __ballot(idx != BGR_NONE);
+                    if (mask) {
+                        if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;
+                        const int s1 = __ffsll((long long)mask) - 1;
+                        const u64 mask2 = mask & (mask - 1);
+                        const uint32_t h1 = rl32(idx, s1);
+                        uint32_t p2 = 0;
+                        if (mask2 && left_q >= 2) p2 = base + (uint32_t)(__ffsll((long long)mask2) - 1);  // a second anchor is tried when the first fails: where a follow-up item resumes
+                        if (grp == q) { a_pos = base + (uint32_t)s1; a_rec = h1; b_pos = p2; }
+                        break;
+                    }
                 }
             }
         }
@@ -465,6 +539,9 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
     if (io.wave_times && lane == 0) {
         unsigned long long* w = io.wave_times + 4ull * (blockIdx.x * waves + wave);
         w[0] = wt0; w[1] = wt1; w[2] = wt2; w[3] = wall_clock64();
+        // behind the time stamps of all waves: the wave's scan counts (two-scanner instances; 0 steps for the others)
+        unsigned long long* c = io.wave_times + 4ull * (gridDim.x * waves) + 4ull * (blockIdx.x * waves + wave);
+        c[0] = dbg_steps; c[1] = dbg_items; c[2] = dbg_groups; c[3] = 0;
     }
 #endif
     __syncthreads();

@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""How many anchor-scan steps does bgr_align_greedy_multi_kernel take?  Per-wave counts of the last launch (scan steps, items scanned, groups
+of items a wave took), summed over the launch: the measured counterpart of tools/scan_halves.py's model, every item included (follow-up
+items and reverse complements too).  Counted by the two-scanner scan of the table-in-LDS instances only.
+Needs the diagnostic build (make -C bgreat_amd BUILD=build_phase LIBDIR=lib_phase EXTRA=-DBGR_PHASE_TIMING lib_phase/libbgreat_gpu.so) loaded
+through BGR_LIB_PATH.  usage (GPU box): BGR_LIB_PATH=... python tools/scan_steps.py [--workload ecoli|small] [--reads N]"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bgreat_amd as B  # noqa: E402
+from tools.synth import Synth  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--workload", default="ecoli", choices=["ecoli", "small"])
+ap.add_argument("--reads", type=int, default=0)
+args = ap.parse_args()
+G, d, L, R = {"ecoli": (4_600_000, 140, 150, 5_000_000), "small": (250_000, 75, 100, 1_000_000)}[args.workload]
+R = args.reads or R
+s = Synth(G, d, 2, 31, 20261003)
+seqs, offs = s.unitigs()
+g = B.Graph.build(31, seqs, offs)
+al = B.Aligner(g, 0)
+reads, _ = s.reads(0, R, L, 2, 77, threads=16)
+db = B.DeviceBuffer(0, reads)
+do = B.DeviceBuffer(0, np.arange(R + 1, dtype=np.uint64) * np.uint64(L))
+al.align_device(db.data_ptr(), do.data_ptr(), R, R * L, L, m=2, effort=2, mode=0)
+al.sync()
+lib = B.lib()
+lib.bgr_debug_scan_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+n = C.c_uint64()
+B._check(lib.bgr_debug_scan_counts(al.h, None, 0, C.byref(n)))
+buf = np.zeros(4 * n.value, dtype=np.uint64)
+B._check(lib.bgr_debug_scan_counts(al.h, buf.ctypes.data, n.value, C.byref(n)))
+c = buf.reshape(-1, 4).astype(np.float64)
+steps, items, groups = c[:, 0].sum(), c[:, 1].sum(), c[:, 2].sum()
+print("workload %s, %d reads, %d waves (launch %s)" % (args.workload, R, n.value, al.launch_info()))
+print("scan steps %d, items scanned %d (%.3f per read), groups of items %d (%.2f items each)" % (steps, items, items / R, groups, items / max(groups, 1)))
+print("steps per read %.3f, per item %.3f, per sixteen items %.2f, per group %.2f" % (steps / R, steps / max(items, 1), 16 * steps / max(items, 1), steps / max(groups, 1)))

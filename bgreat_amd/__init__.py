@@ -30,7 +30,7 @@ SYMBOLS = [
     "bgr_aligner_reset_counters", "bgr_aligner_kernel_time", "bgr_aligner_reset_kernel_time", "bgr_aligner_launch_info",
     "bgr_aligner_configure", "bgr_readset_load", "bgr_readset_count", "bgr_readset_view", "bgr_readset_destroy",
     "bgr_write_records", "bgr_graph_unitigs", "bgr_readset_load_parallel", "bgr_align_all", "bgr_host_alloc", "bgr_host_free",
-    "bgr_set_build_threads", "bgr_graph_build_ex", "bgr_graph_build_from_fasta_ex", "bgr_graph_anchor_lookup", "bgr_graph_key_lookup",
+    "bgr_set_build_threads", "bgr_graph_build_ex", "bgr_graph_build_from_fasta_ex", "bgr_graph_anchor_lookup", "bgr_graph_key_lookup", "bgr_graph_key_lookup_wide",
     "bgr_aligner_set_knob", "bgr_aligner_pass_counts", "bgr_aligner_last_pass_runs", "bgr_set_option", "bgr_get_option", "bgr_option_name", "bgr_plan_launch", "bgr_aligner_kernel_times", "bgr_devices_init", "bgr_devices_method", "bgr_packed_plane_words", "bgr_pack_reads", "bgr_align_batch_packed",
     "bgr_align_fasta_text", "bgr_aligner_fetch_text", "bgr_host_cache_release", "bgr_device_local_cpus", "bgr_text_stage_create", "bgr_text_stage_destroy", "bgr_text_stage_upload",
     "bgr_align_batch_begin", "bgr_align_batch_test", "bgr_align_batch_wait", "bgr_text_stage_device", "bgr_text_stage_upload_parts",
@@ -51,7 +51,7 @@ class PlanInput(C.Structure):  # bgr_plan_input
                 ("num_cus", C.c_uint32), ("resident_waves", C.c_uint32 * 7), ("lds_per_cu", C.c_uint64),
                 ("cfg_waves", C.c_uint32), ("cfg_blocks_per_cu", C.c_uint32), ("cfg_lds_mphf", C.c_uint32),
                 ("mode", C.c_uint32), ("max_mismatch", C.c_uint32), ("partial", C.c_uint32), ("max_read_len", C.c_uint32),
-                ("n_reads", C.c_uint64), ("total_bases", C.c_uint64)]
+                ("n_reads", C.c_uint64), ("total_bases", C.c_uint64), ("wide_keys", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 class PlanPass(C.Structure):
@@ -146,6 +146,7 @@ def lib():
     L.bgr_graph_build_from_fasta_ex.argtypes = [C.c_char_p, u32, C.c_double, u32, C.POINTER(vp)]
     L.bgr_graph_anchor_lookup.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.bgr_graph_key_lookup.argtypes = [vp, u64, C.POINTER(C.c_uint32)]
+    L.bgr_graph_key_lookup_wide.argtypes = [vp, u64, u64, C.POINTER(C.c_uint32)]
     L.bgr_graph_blob.restype = vp
     L.bgr_graph_blob.argtypes = [vp, C.POINTER(u64)]
     L.bgr_graph_from_blob.argtypes = [vp, u64, C.POINTER(vp)]
@@ -364,9 +365,14 @@ class Graph:
         return cls(h)
 
     def key_lookup(self, key):
-        """slot of a canonical (k-1)-mer in the overlap key table, None for a non-member"""
+        """slot of a canonical (k-1)-mer (a non-negative int of up to 2(k-1) bits, any k) in the overlap key table, None for a non-member"""
+        key = int(key)
+        if key < 0:
+            raise ValueError("key_lookup: a (k-1)-mer is a non-negative integer")
+        if key >> 128:
+            return None
         slot = C.c_uint32()
-        _check(lib().bgr_graph_key_lookup(self.h, int(key), C.byref(slot)))
+        _check(lib().bgr_graph_key_lookup_wide(self.h, key >> 64, key & 0xFFFFFFFFFFFFFFFF, C.byref(slot)))
         return None if slot.value == 0xFFFFFFFF else int(slot.value)
 
     def anchor_lookup(self, kmer):

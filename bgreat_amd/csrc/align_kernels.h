@@ -81,6 +81,7 @@ struct LaunchCfg {
     uint32_t blocks;           // grid
     uint32_t lds_bytes;        // dynamic LDS
     uint32_t stage_mphf;       // 1: copy the MPHF cascade into LDS at block start
+    uint32_t wide_keys = 0;    // greedy mode: the graph's keys are two words (graph_layout.h): bgr_align_greedy_wide_kernel (host side only: no kernel argument)
 };
 
 // the last exhaustive pass (exh_memo, exhaustive_kernels.hip): u32 words of a frame of its explicit stack / of an entry of its table, both in HBM;

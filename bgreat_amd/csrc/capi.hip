@@ -266,7 +266,15 @@ int bgr_graph_anchor_lookup(const bgr_graph* g, uint64_t kmer, uint64_t* index_o
 int bgr_graph_key_lookup(const bgr_graph* g, uint64_t key, uint32_t* slot_out) {
     if (!g || !slot_out) return fail(BGR_E_ARG, "bgr_graph_key_lookup: null argument");
     if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_key_lookup: graph has no host blob");
+    if (g->header.wide_keys) return fail(BGR_E_ARG, "bgr_graph_key_lookup: the graph has two-word keys (k > 32): use bgr_graph_key_lookup_wide");
     *slot_out = bgr::host_lookup(g->host.header(), g->host.base(), key);
+    return BGR_OK;
+}
+
+int bgr_graph_key_lookup_wide(const bgr_graph* g, uint64_t key_hi, uint64_t key_lo, uint32_t* slot_out) {
+    if (!g || !slot_out) return fail(BGR_E_ARG, "bgr_graph_key_lookup_wide: null argument");
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_key_lookup_wide: graph has no host blob");
+    *slot_out = bgr::host_lookup_wide(g->host.header(), g->host.base(), key_hi, key_lo);
     return BGR_OK;
 }
 
@@ -553,7 +561,7 @@ static bgr::PlanGraph plan_graph_of(const BgrBlobHeader& h) {
     bgr::PlanGraph g;
     g.k = h.k; g.slot_fill_x100 = h.slot_fill_x100; g.table_bytes = (uint32_t)std::min<uint64_t>((uint64_t)h.n_buckets * 4, 0xFFFFFFFFull);
     g.total_bases = h.total_bases; g.n_unitigs = h.n_unitigs; g.n_buckets = h.n_buckets; g.max_unitig_len = h.max_unitig_len;
-    g.anc_n = h.anc_n; g.anc_active_levels = h.anc_active_levels; g.has_exc = h.has_exc != 0;
+    g.anc_n = h.anc_n; g.anc_active_levels = h.anc_active_levels; g.has_exc = h.has_exc != 0; g.wide_keys = h.wide_keys != 0;
     return g;
 }
 static bgr::PlanTuning plan_tuning_of(const bgr_aligner* a) {
@@ -570,6 +578,7 @@ extern "C" int bgr_plan_launch(const bgr_plan_input* in, bgr_plan_output* out) {
     bgr::PlanGraph g;
     g.k = in->k; g.slot_fill_x100 = in->slot_fill_x100; g.table_bytes = in->table_bytes; g.total_bases = in->graph_bases; g.n_unitigs = in->n_unitigs;
     g.n_buckets = in->table_bytes / 4; g.max_unitig_len = in->max_unitig_len; g.anc_n = in->anchors ? 1 : 0; g.anc_active_levels = in->anchor_levels; g.has_exc = in->has_exceptions != 0;
+    g.wide_keys = in->wide_keys != 0;
     bgr::PlanDevice d;
     if (in->num_cus) d.num_cus = in->num_cus;
     if (in->lds_per_cu) d.lds_per_cu = in->lds_per_cu;
@@ -605,6 +614,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     if (p->mode > BGR_MODE_ANCHORS) return fail(BGR_E_ARG, "bgr_align_device: unknown mode");
     if (p->mode == BGR_MODE_ANCHORS && !a->graph->header.anc_n)
         return fail(BGR_E_ARG, "bgr_align_device: BGR_MODE_ANCHORS needs a graph built with BGR_BUILD_ANCHORS");
+    if (p->mode != BGR_MODE_GREEDY && a->graph->header.wide_keys)
+        return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
     a->last_n = n_reads;
     a->deep.open = false;
     a->deep.runs = 0; a->deep.memo_cap = 0;
@@ -803,9 +814,11 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         io.subset = static_cast<uint32_t*>(a->lst.p);
         io.subset_ctr = 5;
     }
-    e = bgr::launch_align(dgl, io, kp, cfg, a->stream);
+    bgr::LaunchCfg cfg_gen = cfg;
+    cfg_gen.wide_keys = (p->mode == BGR_MODE_GREEDY && a->graph->header.wide_keys) ? 1u : 0u;  // two-word keys: bgr_align_greedy_wide_kernel
+    e = bgr::launch_align(dgl, io, kp, cfg_gen, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(mark(p->mode == BGR_MODE_GREEDY ? (fast_pass ? "bgr_align_greedy_kernel (listed reads)" : "bgr_align_greedy_kernel")
+    HIP_TRY(mark(p->mode == BGR_MODE_GREEDY ? (cfg_gen.wide_keys ? "bgr_align_greedy_wide_kernel" : fast_pass ? "bgr_align_greedy_kernel (listed reads)" : "bgr_align_greedy_kernel")
                  : p->mode == BGR_MODE_ANCHORS ? (a4_pass ? "bgr_align_anchors_kernel (listed reads)" : "bgr_align_anchors_kernel")
                  : deep_only ? "bgr_align_exhaustive_kernel (HBM state, remembered calls)" : level_search ? "bgr_align_exhaustive_dp_kernel" : "bgr_align_exhaustive_kernel"));
     bgr::BatchIO io2 = io;  // the last pass as enqueued (deep_only: the launch above)

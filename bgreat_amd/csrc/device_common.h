@@ -175,6 +175,62 @@ __device__ __forceinline__ uint32_t find_key(const BgrDeviceGraph& g, TP tab, u6
     return res;
 }
 
+// ---- two-word keys (graph_layout.h, wide graphs: k > 32, or test.wide_keys) -----------------------------------------------------------
+// The (k-1)-mer at base p of a per-wave LDS stream as the reference's integer split in two words: hi = its first K1 - 32 bases (0 when
+// K1 <= 32), lo = its last min(K1, 32).  Both windows end at or before p + K1, so a stream needs no padding beyond the one-word scan's.
+__device__ __forceinline__ void lds_key_wide(const u64* A, uint32_t p, uint32_t K1, u64* hi, u64* lo) {
+    const uint32_t nh = K1 > 32 ? K1 - 32 : 0, nl = K1 - nh;
+    *lo = lds_win32(A, p + nh) >> (64 - 2 * nl);
+    *hi = nh ? lds_win32(A, p) >> (64 - 2 * nh) : 0;
+}
+// rcb (utils.cpp:182-192) of a two-word (k-1)-mer: both words reversed and complemented (rcb_fast's four swap_pairs_not halves), the old low
+// word on top, then the 128-bit pair shifted right by 128 - 2 K1 (a funnel shift)
+__device__ __forceinline__ void rcb_wide(u64 hi, u64 lo, uint32_t K1, u64* rhi, u64* rlo) {
+    const u64 a = rcb_fast(lo, 32), b = rcb_fast(hi, 32);
+    const uint32_t s = 128 - 2 * K1;  // 2 .. 126
+    if (s >= 64) { *rhi = 0; *rlo = a >> (s - 64); }
+    else { *rhi = a >> s; *rlo = (b >> s) | (a << (64 - s)); }
+}
+__device__ __forceinline__ bool key_lt_wide(u64 ah, u64 al, u64 bh, u64 bl) { return ah < bh || (ah == bh && al < bl); }
+// find_key for a two-word key: the slot s of the wide entry (its handles: BgrKeyEntry index 2 s), or BGR_NONE.  A wide graph has no filter
+// in front of its table; LAZY2 as in find_key (table in L2: bucket 2 only when bucket 1 is full).
+template <bool LAZY2, typename TP>
+__device__ __forceinline__ uint32_t find_key_wide(const BgrDeviceGraph& g, TP tab, u64 hi, u64 lo, bool active) {
+    const u64 m = bgr_mix_wide(hi, lo);
+    const uint32_t b1 = __umulhi((uint32_t)m, g.n_buckets), b2 = __umulhi((uint32_t)(m >> 32), g.n_buckets);
+    const BgrKeyEntryWide* keys = reinterpret_cast<const BgrKeyEntryWide*>(g.keys);
+    uint32_t res = BGR_NONE, w1 = 0, w2 = 0;
+    if (active) {
+        w1 = tab[b1];
+        if (!LAZY2 || bgr_zero_bytes(w1) == 0) w2 = tab[b2];
+    }
+    const uint32_t f4 = bgr_tab_fp(m) * 0x01010101u;  // (an empty slot is 0 and the fingerprint is not: lanes that sit out match nothing)
+    uint32_t c1 = bgr_zero_bytes(w1 ^ f4), c2 = bgr_zero_bytes(w2 ^ f4);
+    while (wave_any((c1 | c2) != 0)) {
+        if (c1 | c2) {
+            const bool first = c1 != 0;
+            const uint32_t c = first ? c1 : c2;
+            const uint32_t idx = (first ? b1 : b2) * 4 + ((uint32_t)(__ffs((int)c) - 1) >> 3);
+            if (keys[idx].lo == lo && keys[idx].hi == hi) { res = idx; c1 = 0; c2 = 0; }
+            else if (first) c1 &= c1 - 1;
+            else c2 &= c2 - 1;
+        }
+    }
+    if ((g.flags & BGR_GF_HAS_FALLBACK) && wave_any(active && res == BGR_NONE)) {
+        if (active && res == BGR_NONE) {  // bisection in the sorted fallback list of {hi, lo} pairs
+            const uint32_t nfb = (uint32_t)g.hdr->n_fallback;
+            const u64* fb = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(g.hdr) + g.hdr->off_fallback);
+            uint32_t a = 0, z = nfb;
+            while (a < z) {
+                const uint32_t mid = (a + z) >> 1;
+                if (key_lt_wide(fb[2 * mid], fb[2 * mid + 1], hi, lo)) a = mid + 1; else z = mid;
+            }
+            if (a < nfb && fb[2 * a] == hi && fb[2 * a + 1] == lo) res = 4u * g.n_buckets + a;
+        }
+    }
+    return res;
+}
+
 // scan_find_key's cut: the lanes of the lane's half (position order, lane & 31) up to and including its half's first hit -- need2: its
 // second -- so the number of lanes worth confirming; all 32 when there is no such hit.
 __device__ __forceinline__ uint32_t scan_hits_upto(u64 hits, bool need2, uint32_t lane) {

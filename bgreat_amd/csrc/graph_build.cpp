@@ -56,10 +56,22 @@ inline uint64_t window(const uint64_t* seq, uint64_t pos, uint32_t n) {  // n in
 }
 inline uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
+// A (k-1)-mer as an integer (str2num, utils.cpp:117-129): one word for k <= 32, else two (graph_layout.h, wide graphs).  The builder is
+// written once over the key type; these are what differs.
+typedef unsigned __int128 u128;
+inline uint64_t key_mix(uint64_t x) { return bgr_mix64(x); }
+inline uint64_t key_mix(u128 x) { return bgr_mix_wide((uint64_t)(x >> 64), (uint64_t)x); }
+inline uint64_t key_rcb(uint64_t x, uint32_t n) { return bgr_rcb(x, n); }
+inline u128 key_rcb(u128 x, uint32_t n) {  // n <= 63 digits: the 64 digits of x reversed and complemented, then the top 64 - n of them dropped
+    const u128 r = ((u128)~bgr_rev2((uint64_t)x) << 64) | (u128)~bgr_rev2((uint64_t)(x >> 64));
+    return r >> (128 - 2 * n);
+}
+
+template <typename Key>
 struct KeyTable {
     std::vector<uint32_t> buckets;   // 4 one-byte fingerprints per dword, 0 = empty
     std::vector<uint32_t> who;       // per slot: which key (index into the sorted key list) lives there, BGR_NONE = empty
-    std::vector<uint64_t> fallback;  // keys that found no slot, sorted
+    std::vector<Key> fallback;       // keys that found no slot, sorted
     uint64_t n_placed = 0;
 };
 
@@ -67,13 +79,14 @@ struct KeyTable {
 // bucket 1 or bucket 2 of its hash; when both are full a resident is evicted to its other bucket (random walk, at most
 // kMaxKicks moves).  Keys are inserted in sorted order by one thread with a fixed pseudo-random sequence, so the table
 // -- and with it every index in the blob -- does not depend on the thread count.
-void build_key_table(const std::vector<uint64_t>& keys, double slots_per_key, unsigned T, bool evictions, KeyTable& t) {
+template <typename Key>
+void build_key_table(const std::vector<Key>& keys, double slots_per_key, unsigned T, bool evictions, KeyTable<Key>& t) {
     const uint64_t n = keys.size();
     const uint32_t nb = (uint32_t)std::max<uint64_t>(1, (uint64_t)std::ceil(slots_per_key * (double)n / 4.0));
     t.buckets.assign(nb, 0);
     std::vector<uint64_t> mix(n);
     parallel_ranges(T, n, [&](uint64_t b, uint64_t e, unsigned) {
-        for (uint64_t i = b; i < e; ++i) mix[i] = bgr_mix64(keys[i]);
+        for (uint64_t i = b; i < e; ++i) mix[i] = key_mix(keys[i]);
     });
     std::vector<uint32_t>& who = t.who;
     who.assign((size_t)nb * 4, BGR_NONE);
@@ -129,29 +142,47 @@ inline void fill_slot(BgrSlot* s, uint32_t idf, const BgrUnitigMeta& m, const ui
     s[j].near_lo = (uint32_t)near;
 }
 
-}  // namespace
+// the key stored in table slot / fallback entry `idx` of a blob (an empty slot of a wide table reads as hi = ~0)
+inline uint64_t entry_key(const BgrBlobHeader* h, const uint8_t* base, uint64_t idx, uint64_t*) {
+    return reinterpret_cast<const BgrKeyEntry*>(base + h->off_keys)[idx].key;
+}
+inline u128 entry_key(const BgrBlobHeader* h, const uint8_t* base, uint64_t idx, u128*) {
+    const BgrKeyEntryWide& e = reinterpret_cast<const BgrKeyEntryWide*>(base + h->off_keys)[idx];
+    return ((u128)e.hi << 64) | e.lo;
+}
 
-uint32_t host_lookup(const BgrBlobHeader* h, const uint8_t* base, uint64_t key) {
+// host_lookup over either key type (the device lookup's arithmetic): slot of `key`, or BGR_NONE
+template <typename Key>
+uint32_t lookup_key(const BgrBlobHeader* h, const uint8_t* base, Key key) {
     const uint32_t* table = reinterpret_cast<const uint32_t*>(base + h->off_table);
-    const BgrKeyEntry* keys = reinterpret_cast<const BgrKeyEntry*>(base + h->off_keys);
     const uint32_t nb = (uint32_t)h->n_buckets;
-    const uint64_t m = bgr_mix64(key);
+    const uint64_t m = key_mix(key);
     const uint32_t bk[2] = {bgr_tab_bucket((uint32_t)m, nb), bgr_tab_bucket((uint32_t)(m >> 32), nb)};
     const uint32_t f4 = bgr_tab_fp(m) * 0x01010101u;
     for (int c = 0; c < 2; ++c) {
         if (c == 1 && bk[1] == bk[0]) break;
         for (uint32_t z = bgr_zero_bytes(table[bk[c]] ^ f4); z; z &= z - 1) {
             const uint32_t idx = bk[c] * 4 + ((uint32_t)__builtin_ctz(z) >> 3);
-            if (keys[idx].key == key) return idx;
+            if (entry_key(h, base, idx, (Key*)nullptr) == key) return idx;
         }
     }
-    if (h->n_fallback) {
-        const uint64_t* fb = reinterpret_cast<const uint64_t*>(base + h->off_fallback);
-        const uint64_t* e = fb + h->n_fallback;
-        const uint64_t* it = std::lower_bound(fb, e, key);
-        if (it != e && *it == key) return (uint32_t)(4 * h->n_buckets + (it - fb));
+    if (h->n_fallback) {  // sorted; a wide list holds {hi, lo} pairs
+        uint64_t lo = 0, hi = h->n_fallback;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) / 2;
+            if (entry_key(h, base, 4 * h->n_buckets + mid, (Key*)nullptr) < key) lo = mid + 1; else hi = mid;
+        }
+        if (lo < h->n_fallback && entry_key(h, base, 4 * h->n_buckets + lo, (Key*)nullptr) == key) return (uint32_t)(4 * h->n_buckets + lo);
     }
     return BGR_NONE;
+}
+
+}  // namespace
+
+uint32_t host_lookup(const BgrBlobHeader* h, const uint8_t* base, uint64_t key) { return lookup_key<uint64_t>(h, base, key); }
+uint32_t host_lookup_wide(const BgrBlobHeader* h, const uint8_t* base, uint64_t key_hi, uint64_t key_lo) {
+    if (!h->wide_keys) return key_hi ? BGR_NONE : host_lookup(h, base, key_lo);
+    return lookup_key<u128>(h, base, ((u128)key_hi << 64) | key_lo);
 }
 
 void resolve_device_graph(const BgrBlobHeader* h, const void* basev, BgrDeviceGraph& dg) {
@@ -181,7 +212,10 @@ bool validate_blob_header(const BgrBlobHeader* h, uint64_t bytes, std::string& e
     if (bytes < sizeof(BgrBlobHeader)) { err = "blob smaller than its header"; return false; }
     if (h->magic != BGR_MAGIC || h->version != BGR_BLOB_VERSION) { err = "not a bgreat graph blob (magic/version)"; return false; }
     if (h->blob_bytes != bytes) { err = "blob size does not match its header"; return false; }
-    if (h->k < 2 || h->k > 32) { err = "corrupt blob header"; return false; }
+    if (h->k < 2 || h->k > BGR_MAX_K) { err = "corrupt blob header"; return false; }
+    // key layout: two words exactly when k > 32 (1), or at k <= 32 by the test option (2)
+    if (h->wide_keys > 2 || (h->k > BGR_NARROW_MAX_K) != (h->wide_keys == 1)) { err = "corrupt blob header (key layout)"; return false; }
+    const uint64_t key_bytes = h->wide_keys ? sizeof(BgrKeyEntryWide) : sizeof(BgrKeyEntry), fb_bytes = h->wide_keys ? 16 : 8;
     // off + count * size <= bytes without overflow; sections start behind the header, 256-byte aligned
     auto inside = [&](uint64_t off, uint64_t count, uint64_t size) {
         if (off < sizeof(BgrBlobHeader) || off > bytes || (off & 255u)) return false;
@@ -189,9 +223,10 @@ bool validate_blob_header(const BgrBlobHeader* h, uint64_t bytes, std::string& e
     };
     if (h->n_keys >= 0x0FFFFFFFull || h->n_unitigs > 0x40000000ull || h->n_buckets == 0 || h->n_buckets >= (1ull << 26)) { err = "corrupt blob header (counts)"; return false; }
     if (h->n_slots >= BGR_HNONE - 8) { err = "corrupt blob header (slots)"; return false; }
-    if (!inside(h->off_table, h->n_buckets, 4) || !inside(h->off_keys, h->n_keys, sizeof(BgrKeyEntry)) || !inside(h->off_recs, h->n_slots + 4, sizeof(BgrSlot)) ||
+    if (!inside(h->off_table, h->n_buckets, 4) || !inside(h->off_keys, h->n_keys, key_bytes) || !inside(h->off_recs, h->n_slots + 4, sizeof(BgrSlot)) ||
         !inside(h->off_meta, h->n_unitigs + 1, sizeof(BgrUnitigMeta)) || !inside(h->off_seq, h->seq_words, 8)) { err = "blob section outside the blob"; return false; }
-    if (h->n_fallback && !inside(h->off_fallback, h->n_fallback, 8)) { err = "blob section outside the blob"; return false; }
+    if (h->n_fallback && !inside(h->off_fallback, h->n_fallback, fb_bytes)) { err = "blob section outside the blob"; return false; }
+    if (h->wide_keys && (h->bloom_bits || h->anc_n)) { err = "corrupt blob header (wide keys: no filter, no anchors index)"; return false; }
     if (h->bloom_bits && ((h->bloom_bits & (h->bloom_bits - 1)) || h->bloom_bits < 64 || !inside(h->off_bloom, h->bloom_bits / 32, 4))) { err = "corrupt blob header (filter)"; return false; }
     if (h->bloom_bits && h->filter_kind == BGR_FILTER_FLAT && h->bloom_bits > (1ull << 32)) { err = "corrupt blob header (flat filter size)"; return false; }
     // (minimizer blocks: at least 2 of them, so that the block shift stays below 32; at most 2^27 = 8 GiB)
@@ -282,13 +317,21 @@ bool read_unitig_fasta(const std::string& path, uint32_t k, std::vector<char>& s
 // LDS a CU has for key table copies next to 16 waves of sixteen 150-bp reads each (160 KB - 64, 512 B fixed per workgroup, 768 B per wave)
 static const double kStageTwice = (163776.0 / 2 - 512 - 16 * 768), kStageOnce = (163776.0 - 512 - 16 * 768);
 
-bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* offs, double gamma, uint32_t flags, HostGraph& out, std::string& err) {
-    if (k < 2 || k > 32) { err = "k must be in [2,32] (kmer is uint64_t, utils.h:27)"; return false; }
+static void sort_keys(std::vector<uint64_t>& v, unsigned T) { parallel_sort(v, T); }
+static void sort_keys(std::vector<u128>& v, unsigned) { std::sort(v.begin(), v.end()); }
+
+// Key = uint64_t: the one-word layout (k <= 32); u128: the two-word one (wide_keys = 1 for k > 32, 2 under test.wide_keys)
+template <typename Key>
+static bool build_graph_t(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* offs, double gamma, uint32_t flags, uint32_t wide_keys, HostGraph& out, std::string& err) {
+    constexpr bool kWide = sizeof(Key) > 8;
     if (gamma != 0.0 && !(gamma >= 1.03 && gamma <= 64.0)) { err = "gamma (key table slots per key) must be in [1.03,64] (0 = choose)"; return false; }
     const uint32_t K1 = k - 1;
     // aligner.cpp:418-420: stop at the first sequence shorter than k
     uint64_t n = 0;
     while (n < n_in && offs[n + 1] - offs[n] >= k) ++n;
+    // (k > 32 is new ground -- the reference cannot load such a graph at all: a k under which not even the first unitig loads is taken
+    // for a wrong k rather than built into an empty graph)
+    if (wide_keys == 1 && n == 0) { err = "k > 32: the first unitig is shorter than k, so the graph would be empty (k must be in [2,64] and at most the unitig length)"; return false; }
     if (n >= BGR_SLOT_ID_MASK) { err = "too many unitigs (limit 2^30-1)"; return false; }
     uint64_t sum = 0, maxlen = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -314,8 +357,8 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
             F += 2ull * len;
         }
     }
-    std::vector<uint64_t> begs(n + 1), ends(n + 1);
-    std::vector<uint64_t> lr(2 * n);       // per unitig: its two canonical end keys
+    std::vector<Key> begs(n + 1), ends(n + 1);
+    std::vector<Key> lr(2 * n);            // per unitig: its two canonical end keys
     std::vector<uint8_t> side(2 * n);      // 0 = goes to the left key set, 1 = right
     std::atomic<bool> any_exc{false};
     parallel_ranges(T, n, [&](uint64_t b, uint64_t e, unsigned) {
@@ -323,12 +366,12 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
         for (uint64_t i = b + 1; i <= e; ++i) {
             const char* s = seqs + offs[i - 1];
             const uint32_t len = meta[i].len;
-            uint64_t beg = 0, end = 0;  // str2num of the first / last k-1 characters (utils.cpp:117-129)
+            Key beg = 0, end = 0;  // str2num of the first / last k-1 characters (utils.cpp:117-129)
             for (uint32_t j = 0; j < K1; ++j) {
                 beg = beg << 2 | code_of(s[j]);
                 end = end << 2 | code_of(s[len - K1 + j]);
             }
-            uint64_t rcBeg = bgr_rcb(beg, K1), rcEnd = bgr_rcb(end, K1);
+            Key rcBeg = key_rcb(beg, K1), rcEnd = key_rcb(end, K1);
             begs[i] = beg;
             ends[i] = end;
             if (beg <= rcBeg) { lr[2 * i - 2] = beg; side[2 * i - 2] = 0; } else { lr[2 * i - 2] = rcBeg; side[2 * i - 2] = 1; }
@@ -342,18 +385,18 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
         if (mine) any_exc.store(true);
     });
     const bool has_exc = any_exc.load();
-    std::vector<uint64_t> left, right;
+    std::vector<Key> left, right;
     left.reserve(n);
     right.reserve(n);
     for (uint64_t j = 0; j < 2 * n; ++j) (side[j] ? right : left).push_back(lr[j]);
     {
         unsigned Th = std::max(1u, T / 2);
-        std::thread tl([&] { parallel_sort(left, Th); left.erase(std::unique(left.begin(), left.end()), left.end()); });
-        parallel_sort(right, Th);
+        std::thread tl([&] { sort_keys(left, Th); left.erase(std::unique(left.begin(), left.end()), left.end()); });
+        sort_keys(right, Th);
         right.erase(std::unique(right.begin(), right.end()), right.end());
         tl.join();
     }
-    std::vector<uint64_t> keys(left.size() + right.size());
+    std::vector<Key> keys(left.size() + right.size());
     std::merge(left.begin(), left.end(), right.begin(), right.end(), keys.begin());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     if (keys.size() >= 0x0FFFFFFFull) { err = "too many overlap keys (limit 2^28-1)"; return false; }
@@ -376,7 +419,7 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
         else if (n * 1.03 <= kStageOnce) gamma = std::max(1.03, (kStageOnce - 64) / n);
         else gamma = 1.8;
     }
-    KeyTable tab;
+    KeyTable<Key> tab;
     build_key_table(keys, gamma, T, !(flags & BGR_BUILD_NO_EVICTIONS), tab);
     tm.lap("keytable");
 
@@ -414,6 +457,7 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
     h.magic = BGR_MAGIC;
     h.version = BGR_BLOB_VERSION;
     h.k = k;
+    h.wide_keys = wide_keys;
     h.n_unitigs = n;
     h.n_buckets = tab.buckets.size();
     h.n_placed = tab.n_placed;
@@ -430,19 +474,20 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
     uint64_t off = align256(4096);
     static_assert(sizeof(BgrBlobHeader) <= 4096, "header must fit its 4 KiB slot");
     h.off_table = off;    off = align256(off + h.n_buckets * 4 + 16);
-    h.off_keys = off;     off = align256(off + h.n_keys * sizeof(BgrKeyEntry) + 16);
+    h.off_keys = off;     off = align256(off + h.n_keys * (kWide ? sizeof(BgrKeyEntryWide) : sizeof(BgrKeyEntry)) + 16);
     h.off_meta = off;     off = align256(off + (n + 1) * sizeof(BgrUnitigMeta));
     h.off_seq = off;      off = align256(off + seq_words * 8);
     if (has_exc) {
         h.off_exc = off;  off = align256(off + exc_words * 8);
         h.off_excn = off; off = align256(off + exc_words * 8);
     }
-    h.off_fallback = off; off = align256(off + h.n_fallback * 8 + 8);
+    h.off_fallback = off; off = align256(off + h.n_fallback * sizeof(Key) + sizeof(Key));
     // a table too large for LDS staging gets a filter in front: minimizer-blocked when k-1 >= 20 (24-48 bits per key), else one hash
     // (4-8 bits per key).  BGREAT_BLOOM=0 builds without, =1 the one-hash kind, =2 the minimizer kind whatever the table size (tests)
     const int filter_env = (int)opt("build_filter");  // (bgr_set_option: tests force a filter kind onto small graphs)
     const bool large_table = (double)tab.buckets.size() * 4.0 > kStageTwice;  // (may be probed in memory: always beyond kStageOnce, below it with long reads)
-    if (filter_env != 0 && !keys.empty() && (large_table || filter_env == 2)) {
+    if (kWide && filter_env > 0) { err = "build_filter 1 / 2: a graph with two-word keys (k > 32, or test.wide_keys) is built without a filter"; return false; }
+    if (!kWide && filter_env != 0 && !keys.empty() && (large_table || filter_env == 2)) {
         const bool minimizer = k - 1 >= BGR_MMX_MIN_K1 && filter_env != 1;
         uint64_t bits = minimizer ? 1024 : 64;
         while (bits < (minimizer ? 24 : 4) * keys.size()) bits <<= 1;
@@ -476,8 +521,14 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
     uint8_t* base = reinterpret_cast<uint8_t*>(out.blob.data());
     memcpy(base, &h, sizeof(h));
     memcpy(base + h.off_table, tab.buckets.data(), tab.buckets.size() * 4);
-    if (h.n_fallback) memcpy(base + h.off_fallback, tab.fallback.data(), h.n_fallback * 8);
-    if (h.bloom_bits) {
+    if (h.n_fallback) {
+        uint64_t* fb = reinterpret_cast<uint64_t*>(base + h.off_fallback);
+        for (uint64_t j = 0; j < h.n_fallback; ++j) {
+            if (kWide) { fb[2 * j] = (uint64_t)(tab.fallback[j] >> 64); fb[2 * j + 1] = (uint64_t)tab.fallback[j]; }  // {hi, lo}
+            else fb[j] = (uint64_t)tab.fallback[j];
+        }
+    }
+    if constexpr (!kWide) if (h.bloom_bits) {
         uint32_t* bl = reinterpret_cast<uint32_t*>(base + h.off_bloom);
         const uint32_t mask = (uint32_t)(h.bloom_bits - 1);
         uint32_t lg = 0;
@@ -522,20 +573,32 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
     }
     tm.lap("pack");
 
-    // keys by table slot (~0 = empty slot), then the fallback list's; every key must now be found where it was put
+    // keys by table slot (~0 = empty slot; wide: hi = ~0), then the fallback list's; every key must now be found where it was put
     BgrKeyEntry* kout = reinterpret_cast<BgrKeyEntry*>(base + h.off_keys);
+    BgrKeyEntryWide* kwout = reinterpret_cast<BgrKeyEntryWide*>(base + h.off_keys);
+    auto put_key = [&](uint64_t j, bool empty, Key key) {
+        if (kWide) {
+            kwout[j].hi = empty ? BGR_EMPTY_KEY : (uint64_t)(key >> (kWide ? 64 : 0));
+            kwout[j].lo = empty ? BGR_EMPTY_KEY : (uint64_t)key;
+            kwout[j].pad = 0;
+            kwout[j].hL = kwout[j].hR = BGR_HNONE;
+        } else {
+            kout[j].key = empty ? BGR_EMPTY_KEY : (uint64_t)key;
+            kout[j].hL = kout[j].hR = BGR_HNONE;
+        }
+    };
     parallel_ranges(T, 4 * h.n_buckets, [&](uint64_t b, uint64_t e, unsigned) {
-        for (uint64_t j = b; j < e; ++j) { kout[j].key = tab.who[j] == BGR_NONE ? BGR_EMPTY_KEY : keys[tab.who[j]]; kout[j].hL = kout[j].hR = BGR_HNONE; }
+        for (uint64_t j = b; j < e; ++j) put_key(j, tab.who[j] == BGR_NONE, tab.who[j] == BGR_NONE ? Key(0) : keys[tab.who[j]]);
     });
-    for (uint64_t j = 0; j < h.n_fallback; ++j) { kout[4 * h.n_buckets + j].key = tab.fallback[j]; kout[4 * h.n_buckets + j].hL = kout[4 * h.n_buckets + j].hR = BGR_HNONE; }
+    for (uint64_t j = 0; j < h.n_fallback; ++j) put_key(4 * h.n_buckets + j, false, tab.fallback[j]);
     const BgrBlobHeader* hp = reinterpret_cast<const BgrBlobHeader*>(base);
     std::atomic<bool> bad{false};
     parallel_ranges(T, keys.size(), [&](uint64_t b, uint64_t e, unsigned) {
         for (uint64_t j = b; j < e; ++j) {
-            const uint32_t idx = host_lookup(hp, base, keys[j]);
-            if (idx == BGR_NONE || idx >= h.n_keys || kout[idx].key != keys[j]) { bad.store(true); return; }
+            const uint32_t idx = lookup_key<Key>(hp, base, keys[j]);
+            if (idx == BGR_NONE || idx >= h.n_keys || entry_key(hp, base, idx, (Key*)nullptr) != keys[j]) { bad.store(true); return; }
             if (idx < 4 * h.n_buckets) {  // what find_key<LAZY2> relies on: a key sits in its bucket 2 only when its bucket 1 is full
-                const uint32_t b1 = bgr_tab_bucket((uint32_t)bgr_mix64(keys[j]), (uint32_t)h.n_buckets);
+                const uint32_t b1 = bgr_tab_bucket((uint32_t)key_mix(keys[j]), (uint32_t)h.n_buckets);
                 if (idx / 4 != b1 && bgr_zero_bytes(tab.buckets[b1]) != 0) { bad.store(true); return; }
             }
         }
@@ -554,10 +617,10 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
     BgrUnitigMeta* mout = reinterpret_cast<BgrUnitigMeta*>(base + h.off_meta);
     parallel_ranges(T, n, [&](uint64_t b, uint64_t e, unsigned) {
         for (uint64_t i = b + 1; i <= e; ++i) {
-            uint64_t beg = begs[i], rcBeg = bgr_rcb(beg, K1), end = ends[i], rcEnd = bgr_rcb(end, K1);
+            Key beg = begs[i], rcBeg = key_rcb(beg, K1), end = ends[i], rcEnd = key_rcb(end, K1);
             BgrUnitigMeta m = meta[i];
-            m.rec_beg = host_lookup(hp, base, std::min(beg, rcBeg));
-            m.rec_end = host_lookup(hp, base, std::min(end, rcEnd));
+            m.rec_beg = lookup_key<Key>(hp, base, std::min(beg, rcBeg));
+            m.rec_end = lookup_key<Key>(hp, base, std::min(end, rcEnd));
             m.flags = (beg <= rcBeg ? BGR_META_CANON_BEG : 0) | (end <= rcEnd ? BGR_META_CANON_END : 0) |
                       (rcBeg <= beg ? BGR_META_CANON_RCBEG : 0) | (rcEnd <= end ? BGR_META_CANON_RCEND : 0);
             mout[i] = m;
@@ -571,7 +634,7 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
             const BgrUnitigMeta& m = mout[i];
             const bool mb = m.rec_beg >= lo && m.rec_beg < hi, me = m.rec_end >= lo && m.rec_end < hi;
             if (!mb && !me) continue;
-            uint64_t beg = begs[i], rcBeg = bgr_rcb(beg, K1), end = ends[i], rcEnd = bgr_rcb(end, K1);
+            Key beg = begs[i], rcBeg = key_rcb(beg, K1), end = ends[i], rcEnd = key_rcb(end, K1);
             uint32_t id = (uint32_t)i;
             uint32_t ib = m.rec_beg, ie = m.rec_end;
             // left-table slot of key x : F0 = (beg == x), F1 = (end == rc(x)); right-table slot of key y: F0 = (end == y), F1 = (beg == rc(y))
@@ -621,7 +684,10 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
         if (n_slots > slots_bound - 4) { err = "internal: more slots than unitig ends"; return false; }
         auto handle = [&](uint64_t half) { return hoff[half + 1] == hoff[half] ? (uint32_t)BGR_HNONE : hoff[half]; };
         parallel_ranges(T, nk, [&](uint64_t b, uint64_t e, unsigned) {
-            for (uint64_t j = b; j < e; ++j) { kout[j].hL = handle(2 * j); kout[j].hR = handle(2 * j + 1); }
+            for (uint64_t j = b; j < e; ++j) {
+                if (kWide) { kwout[j].hL = handle(2 * j); kwout[j].hR = handle(2 * j + 1); }
+                else { kout[j].hL = handle(2 * j); kout[j].hR = handle(2 * j + 1); }
+            }
         });
         BgrSlot* cs = reinterpret_cast<BgrSlot*>(base + h.off_recs);
         parallel_ranges(T, nh, [&](uint64_t b, uint64_t e, unsigned) {
@@ -693,6 +759,15 @@ bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* of
         tm.lap("anc_pos");
     }
     return true;
+}
+
+bool build_graph(uint32_t k, uint64_t n_in, const char* seqs, const uint64_t* offs, double gamma, uint32_t flags, HostGraph& out, std::string& err) {
+    // (the reference's kmer is a uint64_t, utils.h:27: k <= 32 there; beyond it a (k-1)-mer is kept as two words, graph_layout.h)
+    if (k < 2 || k > BGR_MAX_K) { err = "k must be in [2,64] (k > 32: two-word overlap keys, greedy mode only)"; return false; }
+    const uint32_t wide = k > BGR_NARROW_MAX_K ? 1u : opt("test.wide_keys") ? 2u : 0u;
+    if (wide && (flags & BGR_BUILD_ANCHORS)) { err = "BGR_BUILD_ANCHORS (-G) needs k <= 32 and one-word keys (anchor k-mers are 64-bit integers)"; return false; }
+    if (wide) return build_graph_t<u128>(k, n_in, seqs, offs, gamma, flags, wide, out, err);
+    return build_graph_t<uint64_t>(k, n_in, seqs, offs, gamma, flags, 0, out, err);
 }
 
 }  // namespace bgr

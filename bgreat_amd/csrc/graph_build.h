@@ -40,6 +40,7 @@ struct HostGraph {
 // than k, as aligner.cpp:418-420 does.  gamma: key table slots per key (0 = choose: 1.07 when the table fits LDS staging, else 1.8).
 // Returns false (and sets err) on invalid arguments / limits.
 // flags: BGR_BUILD_ANCHORS adds the anchors index of -G mode (graph_layout.h).
+// k in [2,64]: k > 32 (or the option test.wide_keys) builds the two-word key layout, without anchors index and without filter.
 #define BGR_BUILD_ANCHORS 1u
 #define BGR_BUILD_NO_EVICTIONS 2u  // test hook (include/bgreat_gpu.h)
 bool build_graph(uint32_t k, uint64_t n, const char* seqs, const uint64_t* offs, double gamma, uint32_t flags, HostGraph& out, std::string& err);
@@ -55,6 +56,9 @@ bool read_unitig_fasta(const std::string& path, uint32_t k, std::vector<char>& s
 // Host twin of the device lookup (same arithmetic): MPHF index of `key`, or BGR_NONE.  The caller still has
 // to compare keys[idx] with key for membership.
 uint32_t host_lookup(const BgrBlobHeader* h, const uint8_t* base, uint64_t key);
+// ... of a two-word key (hi, lo) on any graph: a graph with one-word keys holds only keys with hi == 0.  host_lookup itself
+// reads one-word keys only.
+uint32_t host_lookup_wide(const BgrBlobHeader* h, const uint8_t* base, uint64_t key_hi, uint64_t key_lo);
 
 // Fill a BgrDeviceGraph whose pointers are `base` + section offsets (base may be a device address).
 void resolve_device_graph(const BgrBlobHeader* h, const void* base, BgrDeviceGraph& dg);

@@ -24,6 +24,9 @@
 //          most read positions are not overlaps -- so the 8-byte key load is left to the members and a few false matches.
 //          About 8.6 bits per key at the default fill (0.935): the table of an E. coli-scale graph fits LDS twice per CU.
 //          Keys that found no slot after the eviction budget (in practice none) go to a sorted fallback list.
+//          WIDE graphs (k > 32, or any k under the test option test.wide_keys): a (k-1)-mer is a 2(k-1)-bit integer of up to 126 bits,
+//          kept as two words (BgrKeyEntryWide, 32 B per table slot; fallback list: sorted {hi, lo} pairs).  Hashing folds both words into
+//          one 64-bit mix (bgr_mix_wide) that picks buckets and fingerprint as above.  No filter is built in front of a wide table.
 //   keys   16 B per table slot: the u64 key (~0 for an empty slot: membership check, aligner.cpp:158,219,353,361) and the
 //          HANDLES of the key's two halves -- where its "left table" slots and its "right table" slots start in `slots`.
 //   slots  the neighbour records, COMPACT (round 3; round 2 kept 256 B per table slot, 8 x 32 B of which 1-3 were filled
@@ -49,7 +52,10 @@
 
 #define BGR_MAGIC 0x3130484752474742ULL /* "BGGRGH01" */
 #define BGR_BLOB_VERSION 13u /* 13: minimizer-blocked filter in front of large key tables; 12: one-hash Bloom filter there; 11: compact slots + half handles; 10: slots carry the 32 bases next to the overlap; 9: fingerprint key table instead of the MPHF cascade; 8: slot_fill_x100; 7: anchors levels with division magic */
-#define BGR_EMPTY_KEY 0xFFFFFFFFFFFFFFFFULL /* keys[] of an empty table slot: no (k-1)-mer, k <= 32, has bit 62 or 63 set */
+#define BGR_EMPTY_KEY 0xFFFFFFFFFFFFFFFFULL /* keys[] of an empty table slot: no (k-1)-mer, k <= 32, has bit 62 or 63 set.  Wide tables: hi = this
+                                               marks the empty slot (a key's high word holds at most 2(k-1) - 64 <= 62 bits; its low word can be ~0) */
+#define BGR_MAX_K 64u
+#define BGR_NARROW_MAX_K 32u  /* k of the one-word key layout; beyond it the graph is wide */
 #define BGR_NONE 0xFFFFFFFFu
 #define BGR_SLOT_ID_MASK 0x3FFFFFFFu
 #define BGR_HNONE 0x0FFFFFFFu      /* handle of a half without slots (28 bits; bit 28 of a handle word = "the query is canonical") */
@@ -100,6 +106,12 @@ typedef struct {
     uint64_t key;     // BGR_EMPTY_KEY for an empty table slot
     uint32_t hL, hR;  // handles of the key's left-table / right-table slots in `slots` (BGR_HNONE: none)
 } BgrKeyEntry;        // 16 B per table slot (and per fallback key)
+typedef struct {
+    uint64_t hi;      // the key's first k-1-32 bases (0 for k-1 <= 32), right aligned; BGR_EMPTY_KEY for an empty table slot
+    uint32_t hL, hR;  // as in BgrKeyEntry: read as BgrKeyEntry[], entry 2 s holds the handles of wide entry s (the walk's half_handle works unchanged)
+    uint64_t lo;      // the key's last min(k-1, 32) bases, right aligned
+    uint64_t pad;     // 0
+} BgrKeyEntryWide;    // 32 B per table slot of a wide graph
 BGR_HD uint64_t bgr_slot_near(uint32_t Fo_x, uint32_t mflags_x, uint32_t near_lo) {
     return ((uint64_t)((mflags_x & 0xFFFFFFF0u) | ((Fo_x >> 8) & 15u)) << 32) | near_lo;
 }
@@ -138,7 +150,8 @@ typedef struct {
     uint32_t filter_kind, has_exc;       // filter_kind: BGR_FILTER_* of the section at off_bloom
     uint64_t max_unitig_len;
     uint64_t n_left_keys, n_right_keys;  // sizes of the reference's two key sets (informational)
-    uint32_t slot_fill_x100, pad0;       // 100 x mean number of filled slots per non-empty half record (how branchy the graph is)
+    uint32_t slot_fill_x100;             // 100 x mean number of filled slots per non-empty half record (how branchy the graph is)
+    uint32_t wide_keys;                  // key layout: 0 one word (k <= 32), 1 two words because k > 32, 2 two words at k <= 32 (test.wide_keys)
     uint64_t n_slots;       // entries of `slots` (filled slots of all halves; 4 zero entries follow them)
     uint64_t off_bloom;     // large graphs (key table probed in L2/HBM, not staged in LDS): a filter over the keys in front of the table, so
     uint64_t bloom_bits;    //   that most read positions (no overlaps) are turned away before a table probe; bits = a power of two, 0 = none.
@@ -183,6 +196,8 @@ BGR_HD uint64_t bgr_mix64(uint64_t x) {
     x ^= x >> 32;
     return x * 0x9E3779B97F4A7C15ULL;
 }
+// a two-word key (hi, lo) -> 64 hash bits, used as bgr_mix64's are (hi == 0: bgr_mix64(lo))
+BGR_HD uint64_t bgr_mix_wide(uint64_t hi, uint64_t lo) { return bgr_mix64(lo ^ (hi * 0xC2B2AE3D27D4EB4FULL)); }
 BGR_HD uint32_t bgr_tab_bucket(uint32_t h, uint32_t n_buckets) { return (uint32_t)(((uint64_t)h * (uint64_t)n_buckets) >> 32); }
 BGR_HD uint32_t bgr_bloom_bit(uint64_t m, uint32_t mask) { return (uint32_t)(m >> 20) & mask; }  // (bits of both words of the hash)
 // ---- the minimizer-blocked filter (BGR_FILTER_MINIMIZER) ------------------------------------------------------------------

@@ -3,13 +3,17 @@
 //                             32 lanes each (key table in LDS; else one at a time on all 64 lanes), the extensions side by side, 4 lanes each
 //                             (both walks of an anchor at once); settles the common shapes, lists the rest
 //   bgr_align_greedy_kernel   the general kernel: one read per wavefront, every anchor, both strands, N planes, any path length
+//   bgr_align_greedy_wide_kernel  the same over two-word overlap keys (graphs with k > 32, or built under test.wide_keys); only the
+//                             position scan and the anchor's key differ, the walk is the same
 #include "device_common.h"
 
 namespace bgr {
 namespace {
 
-template <bool STAGE>
-__global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(BgrDeviceGraph g, BatchIO io, KernelParams prm) {
+// The general kernel's body.  WIDE: the graph's keys are two words (graph_layout.h BgrKeyEntryWide): the scan builds each window's
+// (k-1)-mer as (hi, lo), its reverse complement with rcb_wide, and looks it up with find_key_wide; no filter in front of the table.
+template <bool STAGE, bool WIDE>
+__device__ __forceinline__ void greedy_general(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& prm) {
     extern __shared__ u64 lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int waves = blockDim.x >> 6;
@@ -48,7 +52,7 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
         if (prm.debug_stop == 1) npos = 0;
 #endif
         // (minimizer filter in front of a key table that is not staged: a scan step covers 65 - w positions, device_common.h)
-        const uint32_t mmx_w = (!STAGE && g.bloom && g.filter_kind == BGR_FILTER_MINIMIZER) ? K1 + 1 - BGR_MMX_BASES : 0u;
+        const uint32_t mmx_w = (!WIDE && !STAGE && g.bloom && g.filter_kind == BGR_FILTER_MINIMIZER) ? K1 + 1 - BGR_MMX_BASES : 0u;
         const uint32_t scan_step = mmx_w ? 65 - mmx_w : 64;
         for (int pass = 0; pass < 2; ++pass) {
             if ((pass == 1 || hasN) && !derived) { derive_streams(L, W, K1, FW3, FWQ, RCW, NM, lane); derived = true; }
@@ -63,6 +67,17 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
             for (uint32_t base = 0; base < npos && !done && tried < effort; base += scan_step) {
                 const uint32_t i = base + lane;
                 const bool valid = i < npos && (uint32_t)lane < scan_step;
+                uint32_t idx;
+                if constexpr (WIDE) {  // the window's (k-1)-mer and the rolling reverse one as (hi, lo); the smaller is looked up
+                    u64 nh = 0, nl = 0, rh = 0, rl = 0;
+                    if (valid) {
+                        lds_key_wide(A, i, K1, &nh, &nl);
+                        if (plain) rcb_wide(nh, nl, K1, &rh, &rl);
+                        else lds_key_wide(B, L - K1 - i, K1, &rh, &rl);
+                    }
+                    const bool fw = key_lt_wide(nh, nl, rh, rl);
+                    idx = find_key_wide<!STAGE>(g, ktab, fw ? nh : rh, fw ? nl : rl, valid);
+                } else {
                 u64 num = 0, rcn = 0, win = 0;
                 if (valid || (mmx_w && i + BGR_MMX_BASES <= L)) win = lds_win32(A, i);
                 if (valid) {
@@ -74,7 +89,8 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
                 if (!STAGE && mmx_w) {  // (a read with an N: the key looked up need not be the canonical form of the window -- its own 16-mers then)
                     mblock = plain ? scan_mblock(g, win, i + BGR_MMX_BASES <= L, mmx_w) : bgr_mmx_block(bgr_mmx_of_key(rep, K1), g.bloom_mask);
                 }
-                const uint32_t idx = find_key<!STAGE>(g, ktab, rep, valid, mblock);
+                idx = find_key<!STAGE>(g, ktab, rep, valid, mblock);
+                }
                 u64 mask = __ballot(idx != BGR_NONE);
 #ifdef BGR_PHASE_TIMING
                 if (prm.debug_stop == 2) { if (mask) { ++tried; done = true; p_n = 0; } mask = 0; }
@@ -85,9 +101,26 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
                     ++tried;
                     // the anchor's k-mers are re-read from LDS (uniform) rather than kept in two 64-bit VGPRs across the walk
                     const uint32_t a_pos = base + (uint32_t)src;
+                    uint32_t a_rec;
+                    bool a_canon;
+                    if constexpr (WIDE) {
+                        u64 nh, nl, rh, rl, ch, cl;
+                        lds_key_wide(A, a_pos, K1, &nh, &nl);
+                        nh = rl64(nh, 0); nl = rl64(nl, 0);
+                        if (plain) rcb_wide(nh, nl, K1, &rh, &rl);
+                        else { lds_key_wide(B, L - K1 - a_pos, K1, &rh, &rl); rh = rl64(rh, 0); rl = rl64(rl, 0); }
+                        a_rec = rl32(idx, src);
+                        rcb_wide(nh, nl, K1, &ch, &cl);  // getBegin/getEnd's own rcb (aligner.cpp:149,211), as below
+                        if (ch != rh || cl != rl) {
+                            const bool fw = key_lt_wide(nh, nl, ch, cl);
+                            a_rec = find_key_wide<!STAGE>(g, ktab, fw ? nh : ch, fw ? nl : cl, true);
+                        }
+                        a_canon = !key_lt_wide(ch, cl, nh, nl);
+                        if (a_rec != BGR_NONE) a_rec *= 2;  // (wide entry s: its handles are BgrKeyEntry 2 s, what the walk's half_handle reads)
+                    } else {
                     const u64 a_num = rl64(lds_win32(A, a_pos) >> (64 - 2 * K1), 0);
                     const u64 a_rcn = plain ? rcb_fast(a_num, K1) : rl64(lds_win32(B, L - K1 - a_pos) >> (64 - 2 * K1), 0);
-                    uint32_t a_rec = rl32(idx, src);
+                    a_rec = rl32(idx, src);
                     // getBegin/getEnd recompute rc = rcb(num) (aligner.cpp:149,211); it differs from the
                     // rolling rcnum only when an N was rolled into the window.
                     const u64 rc2 = rcb_fast(a_num, K1);
@@ -95,7 +128,9 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
                         const u64 key2 = a_num < rc2 ? a_num : rc2;
                         a_rec = find_key<!STAGE>(g, ktab, key2, true, (!STAGE && mmx_w) ? bgr_mmx_block(bgr_mmx_of_key(key2, K1), g.bloom_mask) : 0u);
                     }
-                    if (greedy_from_anchor(g, CMP, NM, useN, L, K1, a_rec, a_num <= rc2, a_pos, prm.max_mismatch, PATH, &p_lo, &p_n, lane)) {
+                    a_canon = a_num <= rc2;
+                    }
+                    if (greedy_from_anchor(g, CMP, NM, useN, L, K1, a_rec, a_canon, a_pos, prm.max_mismatch, PATH, &p_lo, &p_n, lane)) {
                         done = true;
                         break;
                     }
@@ -122,6 +157,16 @@ __global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(
         if (lane == BGR_ST_ALIGNED && c_lane) atomicAdd(&counters[2], (unsigned long long)c_lane);
         if (lane == BGR_ST_FAILED && c_lane) atomicAdd(&counters[3], (unsigned long long)c_lane);
     }
+}
+
+template <bool STAGE>
+__global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_kernel(BgrDeviceGraph g, BatchIO io, KernelParams prm) {
+    greedy_general<STAGE, false>(g, io, prm);
+}
+// (its own name: the one-word kernel's mangled and profiler names stay as they were)
+template <bool STAGE>
+__global__ void __launch_bounds__(1024, BGR_GREEDY_OCC) bgr_align_greedy_wide_kernel(BgrDeviceGraph g, BatchIO io, KernelParams prm) {
+    greedy_general<STAGE, true>(g, io, prm);
 }
 
 // ================================= greedy, several reads per wavefront ====================================
@@ -566,6 +611,8 @@ hipError_t launch_greedy(const BgrDeviceGraph& g, const BatchIO& io, const Kerne
         return cfg.stage_mphf ? launch_one(bgr_align_greedy_multi_kernel<true, GL, false>, g, io, p, cfg, stream)
                               : launch_one(bgr_align_greedy_multi_kernel<false, GL, false>, g, io, p, cfg, stream);
     }
+    if (cfg.wide_keys) return cfg.stage_mphf ? launch_one(bgr_align_greedy_wide_kernel<true>, g, io, p, cfg, stream)
+                                             : launch_one(bgr_align_greedy_wide_kernel<false>, g, io, p, cfg, stream);
     return cfg.stage_mphf ? launch_one(bgr_align_greedy_kernel<true>, g, io, p, cfg, stream)
                           : launch_one(bgr_align_greedy_kernel<false>, g, io, p, cfg, stream);
 }

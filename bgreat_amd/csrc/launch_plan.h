@@ -21,6 +21,7 @@ struct PlanGraph {    // from BgrBlobHeader
     uint32_t k = 0, slot_fill_x100 = 100, table_bytes = 0;
     uint64_t total_bases = 0, n_unitigs = 0, n_buckets = 0, max_unitig_len = 0, anc_n = 0, anc_active_levels = 0;
     bool has_exc = false;
+    bool wide_keys = false;  // two-word keys (k > 32, graph_layout.h): the general greedy kernel's wide twin only
 };
 struct PlanDevice {
     uint32_t num_cus = 256;
@@ -196,7 +197,8 @@ inline LaunchPlan plan_launch(const PlanGraph& g, const PlanDevice& d, const Pla
     // when a read fits one lane per word and the graph has no exception planes; what it does not take (N reads, very long paths)
     // is listed and mapped by the general kernel (cfg) right behind.
     P.wfast = std::min<uint32_t>(P.words, 16);  // the many-reads-per-wave kernels take reads of < 16 words; longer ones of a mixed batch are listed
-    P.fast_pass = b.mode == BGR_MODE_GREEDY && !t.no_greedy_fast && !g.has_exc &&
+    // (a graph with two-word keys has no sixteen-reads-per-wave kernel: bgr_align_greedy_wide_kernel maps every read)
+    P.fast_pass = b.mode == BGR_MODE_GREEDY && !t.no_greedy_fast && !g.has_exc && !g.wide_keys &&
                   geometry(kG4ReadsPerWave * 8 * P.wfast, (n_reads + kG4ReadsPerWave - 1) / kG4ReadsPerWave, true, true, P.cfg_fast, std::max<uint32_t>(4, d.resident[4]),
                            50);  // sixteen reads per wave, E. coli-scale table (72 KB): 2 x 12 waves with the table in LDS 1 877 Mreads/s, 1 x 16: 1 543, 32 waves probing it in L2: 1 381
     // Exhaustive mode, first pass: eight reads per wave (bgr_align_exhaustive4_kernel) for the shape nearly every read has (one

@@ -1456,6 +1456,12 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     if (!graph || !prm || !opt || !reads_csv || !paths_file || !notaligned_file) return bgr::set_error(BGR_E_ARG, "bgr_align_all: null argument");
     if (opt->struct_size != sizeof(bgr_run_options))
         return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.struct_size is not this library's sizeof(bgr_run_options): the caller was built against another header (zero the struct, set struct_size)");
+    {   // (before any device work: a graph with k > 32 keeps two-word keys and maps in greedy mode only)
+        bgr_graph_info_t gi;
+        if (bgr_graph_info(graph, &gi) != BGR_OK) return BGR_E_ARG;
+        if (gi.k > 32 && prm->mode != BGR_MODE_GREEDY)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
+    }
     std::vector<std::string> files;  // aligner.cpp:552-586: comma-separated list
     {
         const std::string list(reads_csv);

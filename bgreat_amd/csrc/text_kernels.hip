@@ -786,6 +786,8 @@ __global__ void __launch_bounds__(kFmtThreads, 8) bgr_text_format_kernel(const u
 // failing that, reverse complemented -- else "bug compaction"; then walk.substr(path[0], read size), reverse complemented when the
 // path was found on the read's reverse complement (alignerGreedy.cpp:394-404).  Graphs without exception planes only (every unitig
 // character is one of ACGT, so the 2-bit store spells it); the caller formats such a batch on the host otherwise.
+// WIDE (k > 33: a (k-1)-mer is longer than one word): the overlap compare takes a second window for the bases behind the first 32.
+template <bool WIDE>
 struct WalkIter {   // the oriented unitigs of a path, one after the other
     const BgrDeviceGraph& g;
     const int32_t* path;
@@ -795,7 +797,8 @@ struct WalkIter {   // the oriented unitigs of a path, one after the other
     uint32_t len = 0, skip = 0;  // its length; bases of it that belong to the overlap with its predecessor (0 for the first, else k-1)
     bool bad = false;
     __device__ WalkIter(const BgrDeviceGraph& g_, const int32_t* p, uint32_t n) : g(g_), path(p), np(n), K1(g_.k - 1) {}
-    __device__ u64 kmer_at(u64 b) const { return win32(g.seq, b) >> (64 - 2 * K1); }
+    __device__ u64 kmer_at(u64 b) const { return win32(g.seq, b) >> (64 - 2 * (WIDE ? 32 : K1)); }
+    __device__ bool kmer_eq(u64 b, u64 t, u64 t2) const { return kmer_at(b) == t && (!WIDE || win32(g.seq, b + 32) >> (128 - 2 * K1) == t2); }
     __device__ bool load() {  // unitig i as its sign orients it; false when the id is out of range (getUnitig of a bad int)
         const int32_t s = path[i];
         const uint32_t id = (uint32_t)(s < 0 ? -(int64_t)s : (int64_t)s);
@@ -808,15 +811,15 @@ struct WalkIter {   // the oriented unitigs of a path, one after the other
     __device__ bool first() { skip = 0; i = 1; if (np < 2 || !load()) { bad = true; return false; } return true; }
     __device__ bool next() {   // false: no further unitig (or bad set: bug compaction)
         if (i + 1 >= np) return false;
-        const u64 tail = kmer_at(base + len - K1);
+        const u64 tail = kmer_at(base + len - K1), tail2 = WIDE ? win32(g.seq, base + len - K1 + 32) >> (128 - 2 * K1) : 0;
         ++i;
         if (!load()) { bad = true; return false; }
-        if (kmer_at(base) != tail) {  // compactionEnd's second try: the reverse complement (the other strand of the store)
+        if (!kmer_eq(base, tail, tail2)) {  // compactionEnd's second try: the reverse complement (the other strand of the store)
             const int32_t s = path[i];
             const uint32_t id = (uint32_t)(s < 0 ? -(int64_t)s : (int64_t)s);
             const BgrUnitigMeta m = g.meta[id];
             const u64 other = m.F + (s < 0 ? 0 : m.len);
-            if (kmer_at(other) != tail) { bad = true; return false; }
+            if (!kmer_eq(other, tail, tail2)) { bad = true; return false; }
             base = other;
         }
         skip = K1;
@@ -826,8 +829,9 @@ struct WalkIter {   // the oriented unitigs of a path, one after the other
 
 // sizes: mapped read -> header + '\n' + min(read size, walk size - offset) + '\n' in the paths stream; *bug (atomicMin) = the first
 // accepted read whose path does not spell a walk
-__global__ void __launch_bounds__(256) bgr_text_correct_sizes_kernel(BgrDeviceGraph g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                                                     uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
+template <bool WIDE>
+__device__ __forceinline__ void correct_sizes(const BgrDeviceGraph& g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
+                                              uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
     const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n_acc) return;
     const uint2 res = results[a];
@@ -835,7 +839,7 @@ __global__ void __launch_bounds__(256) bgr_text_correct_sizes_kernel(BgrDeviceGr
     const uint32_t np = res.y & 0xFFFFFFu, L = r.w & 0x7FFFFFFFu;
     uint32_t ps = 0, ns = 0, cl = 0;
     if (np) {
-        WalkIter w(g, arena + res.x, np);
+        WalkIter<WIDE> w(g, arena + res.x, np);
         u64 total = 0;
         if (w.first()) { total = w.len; while (w.next()) total += w.len - w.skip; }
         const int32_t off = arena[res.x];
@@ -852,13 +856,22 @@ __global__ void __launch_bounds__(256) bgr_text_correct_sizes_kernel(BgrDeviceGr
     nsz[a] = ns;
     clen[a] = cl;
 }
+__global__ void __launch_bounds__(256) bgr_text_correct_sizes_kernel(BgrDeviceGraph g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
+                                                                     uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
+    correct_sizes<false>(g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
+}
+__global__ void __launch_bounds__(256) bgr_text_correct_sizes_wide_kernel(BgrDeviceGraph g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
+                                                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
+    correct_sizes<true>(g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
+}
 
 __device__ __forceinline__ uint8_t base_char(uint32_t code) { return (uint8_t)((0x54474341u >> (8 * code)) & 0xFF); }  // "ACGT"
 
 // one 16-lane group per accepted read; a mapped read's record is header + '\n' + the corrected read + '\n'
-__global__ void __launch_bounds__(256) bgr_text_correct_write_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                     const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
-                                                                     uint8_t* pout, uint8_t* nout) {
+template <bool WIDE>
+__device__ __forceinline__ void correct_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                              const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
+                                              uint8_t* pout, uint8_t* nout) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n_acc) return;
     const uint2 res = results[a];
@@ -882,7 +895,7 @@ __global__ void __launch_bounds__(256) bgr_text_correct_write_kernel(BgrDeviceGr
     const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
     // every lane walks the path (a handful of unitigs) and spells the characters j = sub, sub + 16, ... of walk[off, off + cl)
     const uint32_t off = (uint32_t)arena[res.x];
-    WalkIter w(g, arena + res.x, np);
+    WalkIter<WIDE> w(g, arena + res.x, np);
     if (!w.first()) return;
     u64 start = 0;  // walk position of the current unitig's first NEW base (behind the overlap)
     for (;;) {
@@ -904,6 +917,16 @@ __global__ void __launch_bounds__(256) bgr_text_correct_write_kernel(BgrDeviceGr
         if (start >= (u64)off + cl) break;
         if (!w.next()) break;
     }
+}
+__global__ void __launch_bounds__(256) bgr_text_correct_write_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                     const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
+                                                                     uint8_t* pout, uint8_t* nout) {
+    correct_write<false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
+}
+__global__ void __launch_bounds__(256) bgr_text_correct_write_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                          const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
+                                                                          uint8_t* pout, uint8_t* nout) {
+    correct_write<true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
 }
 
 }  // namespace
@@ -963,14 +986,16 @@ hipError_t launch_text_write(const uint8_t* text, const uint2* results, const in
 hipError_t launch_text_correct_sizes(const BgrDeviceGraph& g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz,
                                      uint32_t* nsz, uint32_t* clen, uint32_t* bug, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
-    hipLaunchKernelGGL(bgr_text_correct_sizes_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, stream, g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
+    if (g.k > 33) hipLaunchKernelGGL(bgr_text_correct_sizes_wide_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, stream, g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
+    else hipLaunchKernelGGL(bgr_text_correct_sizes_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, stream, g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
     return hipGetLastError();
 }
 
 hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                      const uint32_t* poff, const uint32_t* noff, const uint32_t* clen, uint8_t* pout, uint8_t* nout, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
-    hipLaunchKernelGGL(bgr_text_correct_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
+    if (g.k > 33) hipLaunchKernelGGL(bgr_text_correct_write_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
+    else hipLaunchKernelGGL(bgr_text_correct_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
     return hipGetLastError();
 }
 

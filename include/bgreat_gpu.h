@@ -91,7 +91,9 @@ int bgr_device_count(void); /* number of HIP devices visible, 0 if none / no dri
  * staged in LDS, else 1.8).
  * The graph is built on the host; inputs are only read during the call.
  * Limits (narrower than the reference's int32 unitig ids, utils.h:26; a graph beyond them is refused with BGR_E_ARG and a message that
- * names the limit, never truncated): k <= 32 (as the reference); fewer than 2^30 unitigs (a slot's id field has 30 bits beside its two
+ * names the limit, never truncated): k <= 64.  k <= 32 as the reference (whose kmer is a uint64_t); 32 < k <= 64 keeps each (k-1)-mer as two
+ * words (the reference's arithmetic on a 2(k-1)-bit integer) and maps in greedy mode only -- with -c, -q, both text routes and
+ * several devices -- while exhaustive mode (-b) and the anchors index (-G, BGR_BUILD_ANCHORS) are refused with BGR_E_ARG; fewer than 2^30 unitigs (a slot's id field has 30 bits beside its two
  * orientation bits); fewer than 2^28 overlap keys and fewer than 2^27 - 8 filled neighbour slots (a handle is 28 bits, one of them the
  * "query is canonical" flag travelling with it); the packed sequence of both strands below 4 GiB = 2^34 bases (the kernels address it
  * with 32-bit byte offsets).  The BASELINE configs use 2 % / 0.4 % / 5 % of these (4 M unitigs, 2.6 M keys, 0.8 G bases at chr1 scale). */
@@ -117,7 +119,10 @@ int bgr_graph_anchor_lookup(const bgr_graph* g, uint64_t kmer, uint64_t* index_o
 /* The overlap key table, host side: the membership test of aligner.cpp:158,219,353,361 ("is this canonical (k-1)-mer an
  * overlap of the graph") as the kernels make it.  *slot_out = the key's slot (its index into the blob's keys / records)
  * or UINT32_MAX for a non-member.  Used by the CPU tests. */
-int bgr_graph_key_lookup(const bgr_graph* g, uint64_t canonical_k1mer, uint32_t* slot_out);
+int bgr_graph_key_lookup(const bgr_graph* g, uint64_t canonical_k1mer, uint32_t* slot_out);  /* BGR_E_ARG on a graph with k > 32 */
+/* The same for a (k-1)-mer of up to 126 bits given as two words: key_hi = its first k-1-32 bases, key_lo = its last min(k-1, 32)
+ * (the integer's high and low 64 bits).  Works on any graph; on one with k <= 32 only key_hi == 0 can be a member. */
+int bgr_graph_key_lookup_wide(const bgr_graph* g, uint64_t key_hi, uint64_t key_lo, uint32_t* slot_out);
 /* The graph as one position-independent byte blob (what is copied to HBM / broadcast between GPUs). */
 const void* bgr_graph_blob(const bgr_graph* g, uint64_t* bytes);
 int bgr_graph_from_blob(const void* blob, uint64_t bytes, bgr_graph** out); /* copies the blob */
@@ -334,6 +339,7 @@ typedef struct bgr_plan_input {
     uint32_t cfg_waves, cfg_blocks_per_cu, cfg_lds_mphf;                                /* bgr_aligner_configure */
     uint32_t mode, max_mismatch, partial, max_read_len;                                 /* batch */
     uint64_t n_reads, total_bases;
+    uint32_t wide_keys, reserved0;                                                      /* graph header: two-word keys (k > 32) */
 } bgr_plan_input;
 typedef struct bgr_plan_pass { uint32_t used, blocks, waves_per_block, lds_bytes, table_staged; } bgr_plan_pass;
 typedef struct bgr_plan_output {

@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(1024, BGR_ANC_OCC) bgr_align_anchors_kernel(Bg
         wave_sync();
     }
     if (lane == 0 && c_reads) {
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + 16);
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters);
         atomicAdd(&counters[0], (unsigned long long)c_reads);
         if (c_noov) atomicAdd(&counters[1], (unsigned long long)c_noov);
         if (c_al) atomicAdd(&counters[2], (unsigned long long)c_al);
@@ -514,13 +514,12 @@ __global__ void __launch_bounds__(1024, BGR_ANC4_OCC) bgr_align_anchors4_kernel(
 
 }  // namespace
 
-hipError_t launch_anchors(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
-    if (io.anc4 == 8) return launch_one(bgr_align_anchors4_kernel<8>, g, io, p, cfg, stream);  // (the value = lanes per read)
-    if (io.anc4) return launch_one(bgr_align_anchors4_kernel<16>, g, io, p, cfg, stream);
-    return launch_one(bgr_align_anchors_kernel, g, io, p, cfg, stream);
-}
-const void* anchors_kernel_fn(bool four_reads) {
-    return four_reads ? reinterpret_cast<const void*>(&bgr_align_anchors4_kernel<8>) : reinterpret_cast<const void*>(&bgr_align_anchors_kernel);
+const void* anchors_kernel(KernelId k, uint32_t lanes) {  // (neither stages the key table: the anchors index is probed where it lies)
+    switch (k) {
+        case KernelId::kAnchors4: return lanes == 8 ? kernel_ptr(bgr_align_anchors4_kernel<8>) : kernel_ptr(bgr_align_anchors4_kernel<16>);
+        case KernelId::kAnchors: return kernel_ptr(bgr_align_anchors_kernel);
+        default: return nullptr;
+    }
 }
 
 }  // namespace bgr

@@ -179,35 +179,46 @@ hipError_t launch_csr(const uint2* results, const int32_t* arena, uint32_t n, ui
     return hipGetLastError();
 }
 
-hipError_t launch_greedy(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream);
-hipError_t launch_exhaustive(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream);
-hipError_t launch_anchors(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream);
-const void* greedy_kernel_fn(bool four_reads);
-const void* exhaustive_kernel_fn(uint32_t which);
-const void* anchors_kernel_fn(bool four_reads);
+// the mapping kernels, by id and template choices (greedy_kernels.hip, exhaustive_kernels.hip, anchors_kernel.hip)
+const void* greedy_kernel(KernelId k, bool stage, bool ascii);
+const void* exhaustive_kernel(KernelId k, bool stage, uint32_t levels);
+const void* anchors_kernel(KernelId k, uint32_t lanes);
 
-uint32_t resident_waves_per_cu(uint32_t mode) {
+static const void* kernel_of(KernelId k, bool stage, bool ascii, uint32_t variant) {
+    switch (k) {
+        case KernelId::kGreedy: case KernelId::kGreedyMulti: case KernelId::kGreedyWide: return greedy_kernel(k, stage, ascii);
+        case KernelId::kAnchors: case KernelId::kAnchors4: return anchors_kernel(k, variant);
+        case KernelId::kExhaustive: case KernelId::kExhaustiveLevel: case KernelId::kExhaustive4: case KernelId::kExhaustiveLast: return exhaustive_kernel(k, stage, variant);
+    }
+    return nullptr;
+}
+
+uint32_t resident_waves_per_cu(KernelId k) {
+    // (measured on one instance of each kernel: staged for the greedy and the depth-first kernels, in L2 for the level search and the
+    // eight-reads-per-wave kernel, 16 levels per side, 8 lanes per read for the anchors kernel)
+    const bool stage = k == KernelId::kGreedy || k == KernelId::kGreedyMulti || k == KernelId::kExhaustive;
     hipFuncAttributes fa;
-    const void* fn = mode == 0 ? greedy_kernel_fn(false)
-                   : mode == 2 ? anchors_kernel_fn(false)
-                   : mode == 6 ? anchors_kernel_fn(true)
-                   : mode == 3 ? exhaustive_kernel_fn(1)
-                   : mode == 4 ? greedy_kernel_fn(true)
-                   : mode == 5 ? exhaustive_kernel_fn(2)
-                               : exhaustive_kernel_fn(0);
-    if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.numRegs <= 0) return 16;
+    if (hipFuncGetAttributes(&fa, kernel_of(k, stage, true, k == KernelId::kAnchors4 ? 8u : 16u)) != hipSuccess || fa.numRegs <= 0) return 16;
     // MI355X_MICROARCH.md "Register files": 512 VGPRs per SIMD lane, allocation granule 8, at most 8 waves per SIMD;
     // the one-read-per-wave kernels use ~106 SGPRs and are compiled for at most 6 waves per SIMD (compiling for 7: 72 VGPRs,
     // spills: 381 vs 532 Mreads/s greedy, 28 vs 37 exhaustive, round 1); the four-reads-per-wave greedy kernel runs 8.
     const uint32_t alloc = ((uint32_t)fa.numRegs + 7) / 8 * 8;
-    return 4 * std::min<uint32_t>(mode == 4 ? 8 : 6, 512 / alloc);
+    return 4 * std::min<uint32_t>(k == KernelId::kGreedyMulti ? 8 : 6, 512 / alloc);
 }
 
-hipError_t launch_align(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
+hipError_t launch_align(KernelId k, uint32_t variant, const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
     if (io.n_reads == 0) return hipSuccess;
-    if (p.mode == 0) return launch_greedy(g, io, p, cfg, stream);
-    if (p.mode == 2) return launch_anchors(g, io, p, cfg, stream);
-    return launch_exhaustive(g, io, p, cfg, stream);
+    const void* fn = kernel_of(k, cfg.stage_mphf != 0, io.ascii != nullptr, variant);
+    if (!fn) return hipErrorInvalidDeviceFunction;
+    if (cfg.lds_bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    BgrDeviceGraph ga = g;
+    BatchIO ia = io;
+    KernelParams pa = p;
+    void* args[] = {&ga, &ia, &pa};
+    return hipLaunchKernel(fn, dim3(cfg.blocks), dim3(cfg.waves_per_block * 64), args, cfg.lds_bytes, stream);
 }
 
 }  // namespace bgr

@@ -38,7 +38,6 @@ int fail(int code, const std::string& msg) { tl_err = msg; return code; }
         if (e_ != hipSuccess) return fail(BGR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-const uint32_t kRetryCtr = 6, kRetrySubsetCtr = 7;  // words of `cursor`: reads the last exhaustive pass hands back / reads of the list it maps when it runs again
 const int kTimerRing = 64;   // launches between two drains of the timers
 const int kTimerSlots = 8;   // kernels of one launch timed separately (pre-pass, passes)
 
@@ -109,14 +108,14 @@ struct bgr_aligner {
     uint32_t tx_want = 0;              // its want_output (2 = correction mode: mapped reads as spelled by their paths)
     double tx_phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
 
-    DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: cursor[16] u32 @0, counters[5] u64 @64
+    DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: kSmall* (align_kernels.h)
     struct DeepRun {  // the last pass of the exhaustive launch in flight, as enqueued: settle_launch runs it again for reads whose table filled up
         bool open = false;
+        bgr::Pass pass;
         bgr::BatchIO io;
         bgr::KernelParams kp;
         BgrDeviceGraph dg;
-        bgr::LaunchCfg cfg;
-        uint32_t per_wave_lds = 0, path_cap = 0, frames = 0, memo_cap = 0, runs = 0;
+        uint32_t per_wave_lds = 0, path_cap = 0, memo_cap = 0, runs = 0;
     } deep;
     bgr::PlanDevice plan_dev;     // CUs, LDS, resident waves per kernel: asked once
     bool plan_dev_known = false;
@@ -502,7 +501,7 @@ int bgr_aligner_create(bgr_graph* g, int device, bgr_aligner** out) {
     }
     if (a->blocking_sync && hipEventCreateWithFlags(&a->ev_wait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) a->blocking_sync = false;
     bgr::resolve_device_graph(&g->header, g->dev[device].ptr, a->dg);
-    e = a->small.ensure(256);
+    e = a->small.ensure(bgr::kSmallBytes);
     if (e == hipSuccess) e = hipMemset(a->small.p, 0, a->small.cap);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the fill runs on the null stream, which the aligner's non-blocking stream does not wait for)
     if (e != hipSuccess) { delete a; return fail(BGR_E_HIP, hipGetErrorString(e)); }
@@ -582,7 +581,7 @@ extern "C" int bgr_plan_launch(const bgr_plan_input* in, bgr_plan_output* out) {
     bgr::PlanDevice d;
     if (in->num_cus) d.num_cus = in->num_cus;
     if (in->lds_per_cu) d.lds_per_cu = in->lds_per_cu;
-    for (int i = 0; i < 7; ++i) if (in->resident_waves[i]) d.resident[i] = in->resident_waves[i];
+    for (uint32_t i = 0; i < bgr::kResidentKernels; ++i) if (in->resident_waves[i]) d.resident[i] = in->resident_waves[i];
     bgr::PlanTuning t;
     t.cfg_waves = in->cfg_waves; t.cfg_blocks_per_cu = in->cfg_blocks_per_cu; t.cfg_lds_mphf = in->cfg_lds_mphf;
     bgr::PlanBatch b;
@@ -590,20 +589,41 @@ extern "C" int bgr_plan_launch(const bgr_plan_input* in, bgr_plan_output* out) {
     const bgr::LaunchPlan P = bgr::plan_launch(g, d, t, b);
     memset(out, 0, sizeof(*out));
     if (P.error) return fail(BGR_E_ARG, P.error);
-    const bgr::LaunchCfg* cf[6] = {&P.cfg, &P.cfg_fast, &P.cfg_x4, &P.cfg_a4, &P.cfg_mid, &P.cfg_deep};
-    const bool used[6] = {true, P.fast_pass, P.x4_pass, P.a4_pass, P.mid_pass, P.two_pass};
-    for (int i = 0; i < 6; ++i) {
-        if (!used[i]) continue;
-        out->pass[i].used = 1; out->pass[i].blocks = cf[i]->blocks; out->pass[i].waves_per_block = cf[i]->waves_per_block;
-        out->pass[i].lds_bytes = cf[i]->lds_bytes; out->pass[i].table_staged = cf[i]->stage_mphf;
+    auto put = [out](int slot, const bgr::LaunchCfg& c) {
+        out->pass[slot] = bgr_plan_pass{1, c.blocks, c.waves_per_block, c.lds_bytes, c.stage_mphf};
+    };
+    // slot 0: the mode's general kernel, the first pass that maps one read per wave (in a launch that sends every read to the last pass: that pass)
+    const uint32_t general = bgr::many_reads_per_wave(P.pass[0].kernel) ? 1 : 0;
+    for (uint32_t i = 0; i < P.n_passes; ++i) {
+        const bgr::Pass& ps = P.pass[i];
+        if (i == general) put(0, ps.cfg);
+        switch (ps.kernel) {
+            case bgr::KernelId::kGreedyMulti: put(1, ps.cfg); break;
+            case bgr::KernelId::kExhaustive4: put(2, ps.cfg); break;
+            case bgr::KernelId::kAnchors4: put(3, ps.cfg); break;
+            case bgr::KernelId::kExhaustive: if (i != general) put(4, ps.cfg); break;  // (behind the level search)
+            case bgr::KernelId::kExhaustiveLast: put(5, ps.cfg); break;
+            default: break;
+        }
     }
-    out->level_search = P.level_search; out->deep_only = P.deep_only; out->x4_levels = P.x4_levels; out->memo_cap = P.memo_cap;
-    out->deep_scratch_bytes = P.two_pass ? (uint64_t)P.cfg_deep.blocks * P.cfg_deep.waves_per_block * P.deep_stride * 4 : 0;
+    out->level_search = P.level_search; out->deep_only = P.pass[0].kernel == bgr::KernelId::kExhaustiveLast; out->x4_levels = P.x4_levels; out->memo_cap = P.memo_cap;
+    out->deep_scratch_bytes = P.deep_scratch_bytes;
     out->arena_ints = P.arena_cap;
     return BGR_OK;
 }
 
-// The mapping launch of one batch: the geometry comes from plan_launch (launch_plan.h, a pure function of numbers), this function sizes the
+// The buffer of each list of reads a pass leaves to a later one (bgr::List; greedy mode keeps the follow-up items' rings in `ovf`)
+static DevBuf* list_buf(bgr_aligner* a, bgr::List l) {
+    switch (l) {
+        case bgr::List::kSearch: return &a->ovf;
+        case bgr::List::kDepthFirst: case bgr::List::kGeneral: return &a->ovf2;
+        case bgr::List::kFirst: return &a->lst;
+        case bgr::List::kRetry: return &a->retry;
+        default: return nullptr;
+    }
+}
+
+// The mapping launch of one batch: the passes come from plan_launch (launch_plan.h, a pure function of numbers), this function sizes the
 // buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
 // (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
 // d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
@@ -630,7 +650,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     if (!a->plan_dev_known) {
         a->plan_dev.num_cus = (uint32_t)a->num_cus;
         a->plan_dev.lds_per_cu = a->lds_per_cu;
-        for (uint32_t m = 0; m < 7; ++m) a->plan_dev.resident[m] = bgr::resident_waves_per_cu(m);
+        for (uint32_t k = 0; k < bgr::kResidentKernels; ++k) a->plan_dev.resident[k] = bgr::resident_waves_per_cu(static_cast<bgr::KernelId>(k));
         a->plan_dev_known = true;
     }
     bgr::PlanBatch pb;
@@ -638,15 +658,17 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     pb.n_reads = n_reads; pb.total_bases = total_bases;
     const bgr::LaunchPlan P = bgr::plan_launch(plan_graph_of(a->graph->header), a->plan_dev, plan_tuning_of(a), pb);
     if (P.error) return fail(BGR_E_ARG, P.error);
-    const bgr::LaunchCfg &cfg = P.cfg, &cfg_deep = P.cfg_deep, &cfg_mid = P.cfg_mid, &cfg_fast = P.cfg_fast, &cfg_x4 = P.cfg_x4, &cfg_a4 = P.cfg_a4;
-    const bool level_search = P.level_search, two_pass = P.two_pass, deep_only = P.deep_only, mid_pass = P.mid_pass, fast_pass = P.fast_pass, x4_pass = P.x4_pass, a4_pass = P.a4_pass;
-    const uint32_t waves = cfg.waves_per_block, wfast = P.wfast;
-    if (two_pass) HIP_TRY(a->deepbuf.ensure((uint64_t)cfg_deep.blocks * cfg_deep.waves_per_block * P.deep_stride * 4));
+    const bgr::Pass& first = P.pass[0];
+    if (P.deep_scratch_bytes) HIP_TRY(a->deepbuf.ensure(P.deep_scratch_bytes));
     HIP_TRY(a->arena.ensure(P.arena_cap * 4));
-    a->last_launch[0] = cfg.blocks; a->last_launch[1] = waves * 64; a->last_launch[2] = cfg.lds_bytes; a->last_launch[3] = cfg.stage_mphf | (level_search && !deep_only ? 2u : 0u) | (fast_pass ? 4u : 0u);
-    if (a4_pass) { a->last_launch[0] = cfg_a4.blocks; a->last_launch[1] = cfg_a4.waves_per_block * 64; a->last_launch[2] = cfg_a4.lds_bytes; a->last_launch[3] = 4u; }
-    if (x4_pass) { a->last_launch[0] = cfg_x4.blocks; a->last_launch[1] = cfg_x4.waves_per_block * 64; a->last_launch[2] = cfg_x4.lds_bytes; a->last_launch[3] = cfg_x4.stage_mphf | (level_search ? 2u : 0u) | 4u; }
-    if (fast_pass) { a->last_launch[0] = cfg_fast.blocks; a->last_launch[1] = cfg_fast.waves_per_block * 64; a->last_launch[2] = cfg_fast.lds_bytes; a->last_launch[3] = cfg_fast.stage_mphf | 4u; }
+    for (uint32_t i = 0; i < P.n_passes; ++i) {  // the lists the passes leave each other, and the rings of follow-up items of the sixteen-reads-per-wave kernel
+        const bgr::Pass& ps = P.pass[i];
+        if (ps.appends != bgr::List::kNone) HIP_TRY(list_buf(a, ps.appends)->ensure(n_reads * 4));
+        if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(a->ovf.ensure((uint64_t)ps.cfg.blocks * ps.cfg.waves_per_block * P.q_cap * 8));
+    }
+    // (bgr_aligner_launch_info: the first pass; the level search ran unless every read went to the last pass)
+    a->last_launch[0] = first.cfg.blocks; a->last_launch[1] = first.cfg.waves_per_block * 64; a->last_launch[2] = first.cfg.lds_bytes;
+    a->last_launch[3] = first.cfg.stage_mphf | (P.level_search && first.kernel != bgr::KernelId::kExhaustiveLast ? 2u : 0u) | (bgr::many_reads_per_wave(first.kernel) ? 4u : 0u);
 
     // A launch handed ASCII reads maps them straight from the characters: the mapping kernels stage each read's 2-bit words themselves (round 5:
     // the pre-pass was 4-11 % of a launch and existed only to write 40 B per read that the next kernel read back).  BGR_KNOB_GREEDY_PREPASS 1 = the
@@ -655,14 +677,14 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     // mode keeps the pre-pass: its four-reads-per-wave kernel -- BooPHF arithmetic at 96 VGPRs -- lost more inside than the pre-pass cost: 934 vs 965-1 000 Mreads/s)
     // ... and so do launches without a several-reads-per-wave pass (-i, budgets beyond 254, exception planes, the knobs): the one-read-per-wave kernels alone are
     // faster from planes (depth-first 11.8 vs 12.8 ms per 5 M reads, level search 14.0 vs 14.3 per 2 M)
-    const bool inline_pack = (fast_pass || x4_pass) && !planes_ready && d_reads && !a->knob_prepass;
+    const bool inline_pack = (first.kernel == bgr::KernelId::kGreedyMulti || first.kernel == bgr::KernelId::kExhaustive4) && !planes_ready && d_reads && !a->knob_prepass;
     if (!reads_bytes) reads_bytes = total_bases;  // (reads end to end: the buffer holds exactly their bases)
     if (!inline_pack) {
         HIP_TRY(a->pk_fw3.ensure(P.plane_words * 8));
         HIP_TRY(a->pk_nm.ensure(P.plane_words * 8));
         HIP_TRY(a->pk_hasn.ensure((n_reads + 31) / 32 * 4 + 4));
     }
-    bgr::BatchIO io;
+    bgr::BatchIO io{};  // what every pass shares; the loop below sets the rest
     io.ascii = inline_pack ? static_cast<const uint8_t*>(d_reads) : nullptr;
     io.ascii_src = inline_pack ? static_cast<const uint32_t*>(d_src_off) : nullptr;
     io.ascii_bytes = reads_bytes;
@@ -670,54 +692,19 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     io.nmw = static_cast<const uint64_t*>(a->pk_nm.p);
     io.hasn = static_cast<const uint32_t*>(a->pk_hasn.p);
     io.read_offs = static_cast<const uint64_t*>(d_read_offsets);
-    io.n_reads = (uint32_t)n_reads;
-    io.words_per_read = P.words;
-    io.path_cap = P.path_cap;
-    io.arena_cap = (uint32_t)P.arena_cap;
-    io.arena_chunk = P.arena_chunk;
-    io.frames_per_wave = P.frames;
-    io.ovf_list = nullptr;
-    io.subset = nullptr;
-    io.deep_scratch = nullptr;
-    io.deep_stride = (uint32_t)P.deep_stride;
-    io.level_search = level_search ? 1u : 0u;
-    io.search_iters = P.search_iters;
-    io.deep_memo_cap = P.memo_cap;
-    io.wide_scan = P.wide_scan ? 1u : 0u;
-    io.greedy_multi = 0;
-    io.queue = nullptr;
-    io.q_cap = 0;
-    io.gen_list = nullptr;
-    io.gen_ctr = 8;
-    io.exh4 = 0;
-    io.anc4 = 0;
-    io.subset_ctr = 2;
-    io.ovf_ctr = 2;
-    io.wave_times = nullptr;
-    io.task_ctr = 10;  // (cursor[0..15] are zeroed in front of every launch; 10 is used by nothing else)
-    if (fast_pass) {
-        const uint64_t grid_waves = (uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block;
-        HIP_TRY(a->ovf.ensure(grid_waves * P.q_cap * 8));
-        HIP_TRY(a->ovf2.ensure(n_reads * 4));
-    }
-    if (two_pass) {
-        HIP_TRY(a->retry.ensure(n_reads * 4));  // what the last pass hands back for another run (a table that filled up)
-        if (!deep_only) {
-            HIP_TRY(a->ovf.ensure(n_reads * 4));
-            io.ovf_list = static_cast<uint32_t*>(a->ovf.p);
-            if (mid_pass) HIP_TRY(a->ovf2.ensure(n_reads * 4));
-        }
-    }
-    if (deep_only) {
-        io.level_search = 0;
-        io.frames_per_wave = P.frames_deep;
-        io.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
-        io.ovf_list = static_cast<uint32_t*>(a->retry.p);
-        io.ovf_ctr = kRetryCtr;
-    }
     io.results = static_cast<uint2*>(a->results.p);
     io.arena = static_cast<int32_t*>(a->arena.p);
     io.cursor = static_cast<uint32_t*>(a->small.p);
+    io.n_reads = (uint32_t)n_reads;
+    io.path_cap = P.path_cap;
+    io.arena_cap = (uint32_t)P.arena_cap;
+    io.arena_chunk = P.arena_chunk;
+    io.arena_own = (uint32_t)P.arena_own;  // (< 2^32: plan_launch refuses a launch whose arena is larger)
+    io.deep_stride = (uint32_t)P.deep_stride;
+    io.deep_memo_cap = P.memo_cap;
+    io.search_iters = P.search_iters;
+    io.wide_scan = P.wide_scan ? 1u : 0u;
+    io.task_ctr = bgr::kCurTasks;
     bgr::KernelParams kp = {p->max_mismatch, p->effort, p->partial, p->mode, a->knob_debug_stop};
     // the filter in front of a large key table pays where many read positions are probed per anchor (greedy scans: chr1-scale graph
     // 1 020 -> 1 184 Mreads/s, L2 requests per read 135 -> 28).  The exhaustive scan meets its first hit within a few positions; with
@@ -727,13 +714,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     BgrDeviceGraph dgl = a->dg;
     if (p->mode == BGR_MODE_EXHAUSTIVE && !(dgl.filter_kind == BGR_FILTER_MINIMIZER && a->exh_filter)) dgl.bloom = nullptr;
 
-    if (!cursor_is_zero) HIP_TRY(hipMemsetAsync(a->small.p, 0, 64, a->stream));  // cursor[0..15]: arena cursor, overflow flag, list counters (the text form: the parse launch cleared them)
-    {   // the waves of a several-reads-per-wave kernel own the first grid x chunk ints of the arena by their number: what the cursor hands out lies behind
-        const uint64_t own = fast_pass ? P.fast_rows
-                           : x4_pass   ? (uint64_t)cfg_x4.blocks * cfg_x4.waves_per_block * P.arena_chunk
-                           : a4_pass   ? n_reads * bgr::kA4PathInts : 0;
-        io.arena_own = (uint32_t)own;   // (< 2^32: plan_launch refuses a launch whose arena is larger)
-    }
+    // the cursor block: arena cursor, overflow flag, list counts (the text form: the parse launch cleared it)
+    if (!cursor_is_zero) HIP_TRY(hipMemsetAsync(a->small.p, 0, bgr::kCurWords * 4, a->stream));
     // HIP events on the aligner's stream: one in front of the launch, one behind every kernel of it (bgr_aligner_kernel_times)
     int marks = 0;
     // (timing a kernel is not free: the events make the runtime dispatch with completion stamps and keep the kernels of a launch apart -- three events around two
@@ -756,106 +738,46 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("pre-pass launch: ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_pack_reads_kernel"));
     }
-    if (fast_pass) {
-        // ONE launch of the sixteen-reads-per-wave kernel: every wave maps its share of the batch and then works off its own queue of
-        // follow-up items (the next anchors of a read whose first ones failed, then its reverse complement: alignerGreedy.cpp:41-56).
-        // Reads the kernel does not take (N, very long paths) are mapped from scratch by the general kernel right behind: with an
-        // empty list its workgroups exit at once.
-        bgr::BatchIO iof = io;
-        iof.greedy_multi = 1;
-        iof.words_per_read = wfast;
-        iof.queue = static_cast<uint2*>(a->ovf.p);
-        iof.q_cap = P.q_cap;
-        iof.gen_list = static_cast<uint32_t*>(a->ovf2.p);
-        iof.gen_ctr = 8;
-#ifdef BGR_PHASE_TIMING
-        HIP_TRY(a->wave_times.ensure((uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block * 64));  // time stamps, then scan counts
-        HIP_TRY(hipMemsetAsync(a->wave_times.p, 0, (uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block * 64, a->stream));  // (waves with no reads write nothing)
-        iof.wave_times = static_cast<unsigned long long*>(a->wave_times.p);
-        a->wave_times_n = (uint64_t)cfg_fast.blocks * cfg_fast.waves_per_block;
-#endif
-        e = bgr::launch_align(dgl, iof, kp, cfg_fast, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (sixteen-reads-per-wave kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_align_greedy_multi_kernel (all reads, retries in the launch)"));
-        io.subset = static_cast<uint32_t*>(a->ovf2.p);
-        io.subset_ctr = 8;
-    }
-    if (a4_pass) {
-        HIP_TRY(a->lst.ensure(n_reads * 4));
-        bgr::BatchIO ioa = io;
-        ioa.anc4 = P.a4_lanes;
-        ioa.words_per_read = wfast;
-        ioa.subset = nullptr;
-        ioa.ovf_list = static_cast<uint32_t*>(a->lst.p);
-        ioa.ovf_ctr = 5;
-        e = bgr::launch_align(dgl, ioa, kp, cfg_a4, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (anchors, four reads per wave): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_align_anchors4_kernel (all reads)"));
-        io.subset = static_cast<uint32_t*>(a->lst.p);
-        io.subset_ctr = 5;
-    }
-    if (x4_pass) {
-        HIP_TRY(a->lst.ensure(n_reads * 4));
-        bgr::BatchIO iox = io;
-        iox.exh4 = P.x4_levels;
-        iox.words_per_read = wfast;
-        iox.level_search = 0;
-        iox.subset = nullptr;
-        iox.ovf_list = static_cast<uint32_t*>(a->lst.p);
-        iox.ovf_ctr = 5;
-#ifdef BGR_PHASE_TIMING
-        HIP_TRY(a->wave_times.ensure((uint64_t)cfg_x4.blocks * cfg_x4.waves_per_block * 32));
-        iox.wave_times = static_cast<unsigned long long*>(a->wave_times.p);
-        a->wave_times_n = (uint64_t)cfg_x4.blocks * cfg_x4.waves_per_block;
-#endif
-        e = bgr::launch_align(dgl, iox, kp, cfg_x4, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (exhaustive, four reads per wave): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_align_exhaustive4_kernel (all reads)"));
-        io.subset = static_cast<uint32_t*>(a->lst.p);
-        io.subset_ctr = 5;
-    }
-    bgr::LaunchCfg cfg_gen = cfg;
-    cfg_gen.wide_keys = (p->mode == BGR_MODE_GREEDY && a->graph->header.wide_keys) ? 1u : 0u;  // two-word keys: bgr_align_greedy_wide_kernel
-    e = bgr::launch_align(dgl, io, kp, cfg_gen, a->stream);
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(mark(p->mode == BGR_MODE_GREEDY ? (cfg_gen.wide_keys ? "bgr_align_greedy_wide_kernel" : fast_pass ? "bgr_align_greedy_kernel (listed reads)" : "bgr_align_greedy_kernel")
-                 : p->mode == BGR_MODE_ANCHORS ? (a4_pass ? "bgr_align_anchors_kernel (listed reads)" : "bgr_align_anchors_kernel")
-                 : deep_only ? "bgr_align_exhaustive_kernel (HBM state, remembered calls)" : level_search ? "bgr_align_exhaustive_dp_kernel" : "bgr_align_exhaustive_kernel"));
-    bgr::BatchIO io2 = io;  // the last pass as enqueued (deep_only: the launch above)
-    if (two_pass && !deep_only) {  // always enqueued: with an empty list its waves exit at once (no host round trip in between)
-        const uint32_t* pending = io.ovf_list;
-        uint32_t pending_ctr = 2;
-        if (mid_pass) {  // depth-first search, LDS stack, over what the level search listed; its own overflow goes to list 2
-            bgr::BatchIO iom = io;
-            iom.level_search = 0;
-            iom.frames_per_wave = P.frames_mid;
-            iom.subset = io.ovf_list;
-            iom.subset_ctr = 2;
-            iom.ovf_list = static_cast<uint32_t*>(a->ovf2.p);
-            iom.ovf_ctr = 3;
-            e = bgr::launch_align(dgl, iom, kp, cfg_mid, a->stream);
-            if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (depth-first pass): ") + hipGetErrorString(e));
-            HIP_TRY(mark("bgr_align_exhaustive_kernel (listed reads)"));
-            pending = iom.ovf_list;
-            pending_ctr = 3;
+    // The passes, back to back on the stream.  A pass behind a list maps what an earlier pass listed; with an empty list its waves exit at once
+    // (no host round trip in between).  The sixteen-reads-per-wave kernel works off the follow-up items of its reads (the next anchors of a read whose
+    // first ones failed, then its reverse complement: alignerGreedy.cpp:41-56) in its own per-wave queues, inside the launch.
+    for (uint32_t i = 0; i < P.n_passes; ++i) {
+        const bgr::Pass& ps = P.pass[i];
+        bgr::BatchIO pio = io;
+        pio.words_per_read = ps.words;
+        pio.frames_per_wave = ps.frames;
+        pio.subset = ps.maps == bgr::List::kNone ? nullptr : static_cast<const uint32_t*>(list_buf(a, ps.maps)->p);
+        pio.subset_ctr = bgr::list_word(ps.maps);
+        uint32_t* appends = ps.appends == bgr::List::kNone ? nullptr : static_cast<uint32_t*>(list_buf(a, ps.appends)->p);
+        if (ps.kernel == bgr::KernelId::kGreedyMulti) {
+            pio.queue = static_cast<uint2*>(a->ovf.p);
+            pio.q_cap = P.q_cap;
+            pio.gen_list = appends;
+            pio.gen_ctr = bgr::list_word(ps.appends);
+        } else {
+            pio.ovf_list = appends;
+            pio.ovf_ctr = bgr::list_word(ps.appends);
         }
-        io2.frames_per_wave = P.frames_deep;
-        io2.subset = pending;
-        io2.subset_ctr = pending_ctr;
-        io2.ovf_list = static_cast<uint32_t*>(a->retry.p);
-        io2.ovf_ctr = kRetryCtr;
-        io2.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
-        io2.level_search = 0;
-        e = bgr::launch_align(dgl, io2, kp, cfg_deep, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (last pass): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_align_exhaustive_kernel (HBM state, remembered calls; listed reads)"));
-    }
-    if (two_pass) {  // what settle_launch needs to run the last pass again for the reads it handed back
-        a->deep.open = true;
-        a->deep.io = io2; a->deep.kp = kp; a->deep.dg = dgl; a->deep.cfg = cfg_deep;
-        a->deep.per_wave_lds = bgr::deep_lds_bytes_per_wave(max_read_len);
-        a->deep.path_cap = P.path_cap; a->deep.frames = P.frames_deep; a->deep.memo_cap = P.memo_cap;
-        a->deep.runs = 1;
+        if (ps.kernel == bgr::KernelId::kExhaustiveLast) pio.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
+#ifdef BGR_PHASE_TIMING
+        if (ps.kernel == bgr::KernelId::kGreedyMulti || ps.kernel == bgr::KernelId::kExhaustive4) {  // time stamps per wave (the greedy kernel: then its scan counts)
+            const uint64_t waves = (uint64_t)ps.cfg.blocks * ps.cfg.waves_per_block, bytes = waves * (ps.kernel == bgr::KernelId::kGreedyMulti ? 64 : 32);
+            HIP_TRY(a->wave_times.ensure(bytes));
+            if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(hipMemsetAsync(a->wave_times.p, 0, bytes, a->stream));  // (waves with no reads write nothing)
+            pio.wave_times = static_cast<unsigned long long*>(a->wave_times.p);
+            a->wave_times_n = waves;
+        }
+#endif
+        e = bgr::launch_align(ps.kernel, ps.variant, dgl, pio, kp, ps.cfg, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (") + ps.name + "): " + hipGetErrorString(e));
+        HIP_TRY(mark(ps.name));
+        if (ps.kernel == bgr::KernelId::kExhaustiveLast) {  // what settle_launch needs to run the last pass again for the reads it handed back
+            a->deep.open = true;
+            a->deep.pass = ps; a->deep.io = pio; a->deep.kp = kp; a->deep.dg = dgl;
+            a->deep.per_wave_lds = bgr::deep_lds_bytes_per_wave(max_read_len);
+            a->deep.path_cap = P.path_cap; a->deep.memo_cap = P.memo_cap;
+            a->deep.runs = 1;
+        }
     }
     if (timed) {
         a->ev_marks[a->ev_used] = marks;
@@ -864,25 +786,26 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     return BGR_OK;
 }
 
-// Behind a mapping launch, with its stream waited for and cursor[0 .. 15] on the host (`cur`): the arena must not have overflowed, and in
+// Behind a mapping launch, with its stream waited for and the cursor block on the host (`cur`): the arena must not have overflowed, and in
 // exhaustive mode the last pass may have handed reads back whose table of remembered calls filled up (exh_memo, exhaustive_kernels.hip):
 // those run again -- the last pass only, over that list -- with a table sixteen times as large and as few waves as the list has reads, until
 // none is left.  A search visits at most positions x halves x 2 nodes, so this ends; what can end it early is the device's memory.
 static int settle_launch(bgr_aligner* a, uint32_t* cur) {
-    if (cur[1]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
+    if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
     if (!a->deep.open) return BGR_OK;
-    while (cur[kRetryCtr]) {
-        const uint32_t n_retry = cur[kRetryCtr];
+    const uint32_t kRetry = bgr::list_word(bgr::List::kRetry);
+    while (cur[kRetry]) {
+        const uint32_t n_retry = cur[kRetry];
         auto& D = a->deep;
         if (D.runs >= bgr::kDeepRuns || D.memo_cap >= (1u << 28))
             return fail(BGR_E_NOMEM, "exhaustive search: a read's table of remembered calls outgrew 2^28 entries per wave (8 GiB)");
         D.memo_cap *= 16;
-        const uint64_t stride = bgr::deep_scratch_words(D.path_cap, D.frames, D.memo_cap);
+        const uint64_t stride = bgr::deep_scratch_words(D.path_cap, D.pass.frames, D.memo_cap);
         if (stride > 0xFFFFFFFFull) return fail(BGR_E_NOMEM, "exhaustive search: a read's table of remembered calls outgrew the 16 GiB a wave can address");
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         const uint64_t room = (uint64_t)free_b + a->deepbuf.cap;
-        uint64_t waves = std::min<uint64_t>(n_retry, (uint64_t)D.cfg.blocks * D.cfg.waves_per_block);
+        uint64_t waves = std::min<uint64_t>(n_retry, (uint64_t)D.pass.cfg.blocks * D.pass.cfg.waves_per_block);
         waves = std::min<uint64_t>(waves, std::max<uint64_t>(1, room / 2 / (stride * 4)));
         if (stride * 4 > room - room / 8) return fail(BGR_E_NOMEM, "exhaustive search: not enough device memory for a read's table of remembered calls");
         HIP_TRY(a->deepbuf.ensure(waves * stride * 4));
@@ -891,24 +814,23 @@ static int settle_launch(bgr_aligner* a, uint32_t* cur) {
         HIP_TRY(other.ensure((uint64_t)n_retry * 4));
         bgr::BatchIO io = D.io;
         io.subset = io.ovf_list;
-        io.subset_ctr = kRetrySubsetCtr;
+        io.subset_ctr = bgr::kCurRetrySubset;
         io.ovf_list = static_cast<uint32_t*>(other.p);
-        io.ovf_ctr = kRetryCtr;
+        io.ovf_ctr = kRetry;
         io.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
         io.deep_stride = (uint32_t)stride;
         io.deep_memo_cap = D.memo_cap;
-        uint32_t ctr[2] = {0, n_retry};  // cursor[kRetryCtr] = 0, cursor[kRetrySubsetCtr] = n
-        static_assert(kRetrySubsetCtr == kRetryCtr + 1, "the two counters are written with one copy");
-        HIP_TRY(hipMemcpyAsync(static_cast<uint32_t*>(a->small.p) + kRetryCtr, ctr, 8, hipMemcpyHostToDevice, a->stream));
-        bgr::LaunchCfg cfg = D.cfg;
+        uint32_t ctr[2] = {0, n_retry};  // the count of the list handed back = 0, the count of the list to map (kCurRetrySubset, the word behind it) = n
+        HIP_TRY(hipMemcpyAsync(static_cast<uint32_t*>(a->small.p) + kRetry, ctr, 8, hipMemcpyHostToDevice, a->stream));
+        bgr::LaunchCfg cfg = D.pass.cfg;
         cfg.waves_per_block = (uint32_t)std::min<uint64_t>(cfg.waves_per_block, waves);
         cfg.blocks = (uint32_t)std::max<uint64_t>(1, waves / cfg.waves_per_block);
         cfg.lds_bytes = bgr::kLdsFixed + cfg.waves_per_block * D.per_wave_lds;
-        hipError_t e = bgr::launch_align(D.dg, io, D.kp, cfg, a->stream);
+        hipError_t e = bgr::launch_align(D.pass.kernel, D.pass.variant, D.dg, io, D.kp, cfg, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (last pass, run again): ") + hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(cur, a->small.p, 64, hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipMemcpyAsync(cur, a->small.p, bgr::kCurWords * 4, hipMemcpyDeviceToHost, a->stream));
         HIP_TRY(wait_stream(a));
-        if (cur[1]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
+        if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
         std::swap(a->retry, a->retry2);  // (D.io.ovf_list names the list the next round maps)
         D.io.ovf_list = io.ovf_list;
         ++D.runs;
@@ -919,7 +841,7 @@ static int settle_launch(bgr_aligner* a, uint32_t* cur) {
 // ... for callers that have not looked at the cursor yet (exhaustive launches only: nothing to settle otherwise but the arena flag, which every fetch checks)
 static int settle_launch_sync(bgr_aligner* a) {
     if (!a->deep.open) return BGR_OK;
-    uint32_t cur[16];
+    uint32_t cur[bgr::kCurWords];
     HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return settle_launch(a, cur);
@@ -1164,12 +1086,12 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     // TXT_INFO_WORDS u32 behind cursor / counters / CSR total -- two such blocks, taken in turn: a piece's parse launch clears the block of the NEXT piece (and the
     // mapping launch's cursor), so that no fill stands in front of either (the blocks start zero: bgr_aligner_create)
     a->tx_flip ^= 1u;   // (here, behind everything that can fail before the launch: a block is cleared by the launch in front of the one that uses it)
-    uint32_t* info = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + 192 + 32 * a->tx_flip);
-    uint32_t* info_next = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + 192 + 32 * (a->tx_flip ^ 1u));
-    static_assert(TXT_INFO_WORDS * 4 == 32, "two info blocks of 32 bytes at small + 192");
+    uint32_t* info = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * a->tx_flip);
+    uint32_t* info_next = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * (a->tx_flip ^ 1u));
+    static_assert(TXT_INFO_WORDS * 4 == bgr::kSmallTextInfoBytes, "two info blocks at small + kSmallTextInfo");
     hipError_t e = bgr::launch_text_parse(text, nbytes, rec_lines, a->dg.k, tickets, a->tx_ticket[0], ++a->tx_epoch, chains, static_cast<uint4*>(a->tx_rec.p),
                                           static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint32_t*>(a->tx_accrec.p), static_cast<uint32_t*>(a->tx_accsrc.p),
-                                          static_cast<uint64_t*>(a->tx_offs.p), info, R_cap, static_cast<uint32_t*>(a->small.p), 16, info_next, TXT_INFO_WORDS, a->stream);
+                                          static_cast<uint64_t*>(a->tx_offs.p), info, R_cap, static_cast<uint32_t*>(a->small.p), bgr::kCurWords, info_next, TXT_INFO_WORDS, a->stream);
     if (e == hipSuccess) a->tx_ticket[0] += bgr::text_tiles(nbytes);   // (as many tickets as workgroups will take)
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text record launches: ") + hipGetErrorString(e));
     uint32_t h[TXT_INFO_WORDS];
@@ -1207,10 +1129,10 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
         HIP_TRY(hipMemcpyAsync(b->record_info_out, a->tx_info.p, (size_t)R * 4, hipMemcpyDeviceToHost, a->stream));
     }
     if (!b->want_output) {  // counters only: the launch still has to be settled (arena flag; exhaustive mode: reads the last pass handed back)
-        uint32_t cur[16];
+        uint32_t cur[bgr::kCurWords];
         HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
         HIP_TRY(wait_stream(a));
-        const bool handed_back = a->deep.open && cur[kRetryCtr] != 0;
+        const bool handed_back = a->deep.open && cur[bgr::list_word(bgr::List::kRetry)] != 0;
         rc = settle_launch(a, cur);
         if (rc != BGR_OK || !handed_back || !b->record_info_out) return rc;
         continue;  // (the record info was made from results that were not final)
@@ -1236,15 +1158,15 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     if (e == hipSuccess && b->want_output == 2) e = bgr::launch_scan2_u32(static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_nsz.p), static_cast<uint32_t*>(a->tx_poff.p),
                                                    static_cast<uint32_t*>(a->tx_noff.p), n_acc, nullptr, sums2, info + TXT_INFO_PBYTES, info + TXT_INFO_NBYTES, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text size launches: ") + hipGetErrorString(e));
-    uint32_t all[64], h2[16];   // the cursor words (cursor[1]: arena overflow flag) and the info block lie in the same 256 bytes: one copy
+    uint32_t all[bgr::kSmallBytes / 4], h2[bgr::kCurWords];   // the cursor block and the info block lie in the same `small` buffer: one copy
     HIP_TRY(hipMemcpyAsync(all, a->small.p, sizeof(all), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     memcpy(h2, all, sizeof(h2));
     memcpy(h, all + (info - static_cast<const uint32_t*>(a->small.p)), sizeof(h));
     lap(2);
-    if (h2[1]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
+    if (h2[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
     if (a->deep.open) {
-        const bool handed_back = h2[kRetryCtr] != 0;
+        const bool handed_back = h2[bgr::list_word(bgr::List::kRetry)] != 0;
         rc = settle_launch(a, h2);
         if (rc != BGR_OK) return rc;
         if (handed_back) continue;  // sizes and offsets once more, from the final results
@@ -1290,20 +1212,20 @@ static int fetch_total(bgr_aligner* a, uint64_t n, uint64_t* total_out) {
     HIP_TRY(a->csr_sums.ensure(nb * 4 + 64));
     HIP_TRY(a->csr_poffs.ensure((n + 1) * 8));
     HIP_TRY(a->csr_status.ensure(n));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + 128);
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallCsrTotal);
     hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
                                    static_cast<uint32_t*>(a->csr_sums.p), d_total, nullptr, nullptr, nullptr, 0, 0, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("csr launch: ") + hipGetErrorString(e));
-    uint64_t hs[17];  // cursor[0..1] @0, path-int total @128
+    uint64_t hs[bgr::kSmallCsrTotal / 8 + 1];  // the cursor block at the start, the path-int total at the end
     HIP_TRY(hipMemcpyAsync(hs, a->small.p, sizeof(hs), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     const uint32_t* cur = reinterpret_cast<const uint32_t*>(hs);
-    if (cur[1]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
-    *total_out = hs[16];
+    if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
+    *total_out = hs[bgr::kSmallCsrTotal / 8];
     return BGR_OK;
 }
 static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths_out, uint64_t* path_offsets, uint8_t* status, bool with_end = true) {
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + 128);
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallCsrTotal);
     HIP_TRY(a->csr_paths.ensure(total * 4 + 16));
     hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
                                    static_cast<uint32_t*>(a->csr_sums.p), d_total, static_cast<unsigned long long*>(a->csr_poffs.p),
@@ -1527,13 +1449,13 @@ int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]) {
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     { const int src = settle_launch_sync(a); if (src != BGR_OK) return src; }  // (exhaustive mode: reads the last pass handed back are mapped -- and counted -- first)
-    HIP_TRY(hipMemcpy(out, static_cast<char*>(a->small.p) + 64, 40, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, static_cast<char*>(a->small.p) + bgr::kSmallCounters, bgr::kCounters * 8, hipMemcpyDeviceToHost));
     for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
-        uint64_t t[5];
+        uint64_t t[bgr::kCounters];
         HIP_TRY(hipStreamSynchronize(tw->stream));
         { const int src = settle_launch_sync(tw); if (src != BGR_OK) return src; }
-        HIP_TRY(hipMemcpy(t, static_cast<char*>(tw->small.p) + 64, 40, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 5; ++i) out[i] += t[i];
+        HIP_TRY(hipMemcpy(t, static_cast<char*>(tw->small.p) + bgr::kSmallCounters, sizeof(t), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < bgr::kCounters; ++i) out[i] += t[i];
     }
     return BGR_OK;
 }
@@ -1542,10 +1464,10 @@ int bgr_aligner_reset_counters(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_counters: null aligner");
     HIP_TRY(hipSetDevice(a->device));
     // (on the aligner's own stream: a fill on the null stream is not ordered with a non-blocking stream's kernels)
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(a->small.p) + 64, 0, 40, a->stream));
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(a->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(tw->small.p) + 64, 0, 40, tw->stream));
+        HIP_TRY(hipMemsetAsync(static_cast<char*>(tw->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8, tw->stream));
         HIP_TRY(hipStreamSynchronize(tw->stream));
     }
     return BGR_OK;
@@ -1643,9 +1565,11 @@ int bgr_aligner_pass_counts(bgr_aligner* a, uint32_t out[4]) {
     if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_pass_counts: null argument");
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
-    uint32_t cur[16];
+    uint32_t cur[bgr::kCurWords];
     HIP_TRY(hipMemcpy(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost));
-    out[0] = cur[2]; out[1] = cur[3]; out[2] = cur[5]; out[3] = cur[8];
+    static_assert(bgr::kCurFollowUps == bgr::list_word(bgr::List::kSearch), "out[0]: greedy mode's follow-up items, exhaustive mode's first list");
+    out[0] = cur[bgr::kCurFollowUps]; out[1] = cur[bgr::list_word(bgr::List::kDepthFirst)];
+    out[2] = cur[bgr::list_word(bgr::List::kFirst)]; out[3] = cur[bgr::list_word(bgr::List::kGeneral)];
     return BGR_OK;
 }
 

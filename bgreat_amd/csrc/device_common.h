@@ -1033,7 +1033,7 @@ __device__ __forceinline__ void wg_counts_flush(const BatchIO& io, unsigned long
         if (ov) atomicAdd(&c[4], ov);
     }
     __syncthreads();
-    if (threadIdx.x < 5 && c[threadIdx.x]) atomicAdd(reinterpret_cast<unsigned long long*>(io.cursor + 16) + threadIdx.x, c[threadIdx.x]);
+    if (threadIdx.x < kCounters && c[threadIdx.x]) atomicAdd(reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters) + threadIdx.x, c[threadIdx.x]);
 }
 
 // ---- which reads a wave maps next: claimed at run time, not dealt out beforehand ------------------------------------------------
@@ -1102,7 +1102,7 @@ __device__ __forceinline__ uint32_t publish_path(const BatchIO& io, const int32_
     if (p_n > *chunk_end - *chunk_pos) {
         const uint32_t want = p_n > io.arena_chunk ? p_n : io.arena_chunk;
         uint32_t got = 0;
-        if (lane == 0) got = io.arena_own + atomicAdd(io.cursor, want);
+        if (lane == 0) got = io.arena_own + atomicAdd(io.cursor + kCurArena, want);
         *chunk_pos = rl32(got, 0);
         *chunk_end = *chunk_pos + want;
     }
@@ -1111,20 +1111,13 @@ __device__ __forceinline__ uint32_t publish_path(const BatchIO& io, const int32_
     if (abase + p_n <= io.arena_cap) {
         for (uint32_t j = lane; j < p_n; j += 64) io.arena[abase + j] = PATH[p_lo + j];
     } else if (lane == 0) {
-        io.cursor[1] = 1;  // overflow: reported by the host as an error
+        io.cursor[kCurOverflow] = 1;  // overflow: reported by the host as an error
     }
     return abase;
 }
 
-template <typename K>
-hipError_t launch_one(K kernel, const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
-    if (cfg.lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, dim3(cfg.blocks), dim3(cfg.waves_per_block * 64), cfg.lds_bytes, stream, g, io, p);
-    return hipGetLastError();
-}
+// a mapping kernel as launch_align takes it: every one has the arguments (BgrDeviceGraph, BatchIO, KernelParams)
+inline const void* kernel_ptr(void (*kernel)(BgrDeviceGraph, BatchIO, KernelParams)) { return reinterpret_cast<const void*>(kernel); }
 
 }  // namespace
 }  // namespace bgr

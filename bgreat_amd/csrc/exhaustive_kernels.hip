@@ -639,7 +639,7 @@ __global__ void __launch_bounds__(1024, DEEP ? BGR_EXH_DEEP_OCC : BGR_EXH_OCC) b
         wave_sync();
     }
     if (lane == 0 && c_reads) {
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + 16);
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters);
         atomicAdd(&counters[0], (unsigned long long)c_reads);
         if (c_al) atomicAdd(&counters[2], (unsigned long long)c_al);
         if (c_na) atomicAdd(&counters[3], (unsigned long long)c_na);
@@ -990,7 +990,7 @@ __global__ void __launch_bounds__(1024, BGR_X4_OCC) bgr_align_exhaustive4_kernel
         if (tot > chunk_end - chunk_pos) {
             const uint32_t want = tot > io.arena_chunk ? tot : io.arena_chunk;
             uint32_t got = 0;
-            if (lane == 0) got = io.arena_own + atomicAdd(io.cursor, want);
+            if (lane == 0) got = io.arena_own + atomicAdd(io.cursor + kCurArena, want);
             chunk_pos = rl32(got, 0);
             chunk_end = chunk_pos + want;
         }
@@ -999,7 +999,7 @@ __global__ void __launch_bounds__(1024, BGR_X4_OCC) bgr_align_exhaustive4_kernel
         chunk_pos += tot;
         for (uint32_t j = sub; j < p_n; j += GL)
             if (room) io.arena[gbase + j] = OUTG[j];
-        if (!room && lane == 0 && tot) io.cursor[1] = 1;
+        if (!room && lane == 0 && tot) io.cursor[kCurOverflow] = 1;
         if (sub == 0 && have) {
             if (outcome == 0) io.results[r] = make_uint2(gbase, p_n | ((uint32_t)BGR_ST_ALIGNED << 24));
             else if (outcome == 2) io.results[r] = make_uint2(0u, (uint32_t)BGR_ST_FAILED << 24);
@@ -1119,7 +1119,7 @@ __global__ void __launch_bounds__(1024, BGR_DP_OCC) bgr_align_exhaustive_dp_kern
         wave_sync();
     }
     if (lane == 0 && c_reads) {
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + 16);
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters);
         atomicAdd(&counters[0], (unsigned long long)c_reads);
         if (c_al) atomicAdd(&counters[2], (unsigned long long)c_al);
         if (c_na) atomicAdd(&counters[3], (unsigned long long)c_na);
@@ -1129,24 +1129,17 @@ __global__ void __launch_bounds__(1024, BGR_DP_OCC) bgr_align_exhaustive_dp_kern
 
 }  // namespace
 
-hipError_t launch_exhaustive(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
-    if (io.exh4) {
-        constexpr int GL = (int)kX4GroupLanes;
-        if (io.exh4 == 8) return cfg.stage_mphf ? launch_one(bgr_align_exhaustive4_kernel<true, GL, 8>, g, io, p, cfg, stream)
-                                                : launch_one(bgr_align_exhaustive4_kernel<false, GL, 8>, g, io, p, cfg, stream);
-        return cfg.stage_mphf ? launch_one(bgr_align_exhaustive4_kernel<true, GL, 16>, g, io, p, cfg, stream)
-                              : launch_one(bgr_align_exhaustive4_kernel<false, GL, 16>, g, io, p, cfg, stream);
+const void* exhaustive_kernel(KernelId k, bool stage, uint32_t levels) {
+    constexpr int GL = (int)kX4GroupLanes;
+    switch (k) {
+        case KernelId::kExhaustive4:
+            if (levels == 8) return stage ? kernel_ptr(bgr_align_exhaustive4_kernel<true, GL, 8>) : kernel_ptr(bgr_align_exhaustive4_kernel<false, GL, 8>);
+            return stage ? kernel_ptr(bgr_align_exhaustive4_kernel<true, GL, 16>) : kernel_ptr(bgr_align_exhaustive4_kernel<false, GL, 16>);
+        case KernelId::kExhaustiveLast: return kernel_ptr(bgr_align_exhaustive_kernel<false, true>);  // (never staged)
+        case KernelId::kExhaustiveLevel: return stage ? kernel_ptr(bgr_align_exhaustive_dp_kernel<true>) : kernel_ptr(bgr_align_exhaustive_dp_kernel<false>);
+        case KernelId::kExhaustive: return stage ? kernel_ptr(bgr_align_exhaustive_kernel<true, false>) : kernel_ptr(bgr_align_exhaustive_kernel<false, false>);
+        default: return nullptr;
     }
-    if (io.deep_scratch) return launch_one(bgr_align_exhaustive_kernel<false, true>, g, io, p, cfg, stream);
-    if (io.level_search) return cfg.stage_mphf ? launch_one(bgr_align_exhaustive_dp_kernel<true>, g, io, p, cfg, stream)
-                                               : launch_one(bgr_align_exhaustive_dp_kernel<false>, g, io, p, cfg, stream);
-    return cfg.stage_mphf ? launch_one(bgr_align_exhaustive_kernel<true, false>, g, io, p, cfg, stream)
-                          : launch_one(bgr_align_exhaustive_kernel<false, false>, g, io, p, cfg, stream);
-}
-const void* exhaustive_kernel_fn(uint32_t which) {  // 0 depth-first, 1 level search, 2 several reads per wave
-    return which == 1 ? reinterpret_cast<const void*>(&bgr_align_exhaustive_dp_kernel<false>)
-         : which == 2 ? reinterpret_cast<const void*>(&bgr_align_exhaustive4_kernel<false, (int)kX4GroupLanes, 16>)
-                      : reinterpret_cast<const void*>(&bgr_align_exhaustive_kernel<true, false>);
 }
 
 }  // namespace bgr

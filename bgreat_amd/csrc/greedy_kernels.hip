@@ -150,7 +150,7 @@ __device__ __forceinline__ void greedy_general(const BgrDeviceGraph& g, const Ba
         wave_sync();
     }
     {   // aligner.h:68 counters: [0] readNumber [1] noOverlapRead [2] alignedRead [3] notAligned
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + 16);
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters);
         const uint32_t total = rl32(c_lane, BGR_ST_NOANCHOR) + rl32(c_lane, BGR_ST_FAILED) + rl32(c_lane, BGR_ST_ALIGNED);
         if (lane == 0 && total) atomicAdd(&counters[0], (unsigned long long)total);
         if (lane == BGR_ST_NOANCHOR && c_lane) atomicAdd(&counters[1], (unsigned long long)c_lane);
@@ -591,33 +591,28 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
 #endif
     __syncthreads();
     if (threadIdx.x == 0) {  // aligner.h:68 counters: [0] readNumber [1] noOverlapRead [2] alignedRead [3] notAligned
-        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + 16);
+        unsigned long long* counters = reinterpret_cast<unsigned long long*>(io.cursor + kCurCounters);
         const uint32_t al = wg_counts[0], noov = wg_counts[1], na = wg_counts[2], qa = wg_counts[3];  // (indexed by `outcome`)
         if (al | noov | na) atomicAdd(&counters[0], (unsigned long long)(al + noov + na));
         if (noov) atomicAdd(&counters[1], (unsigned long long)noov);
         if (al) atomicAdd(&counters[2], (unsigned long long)al);
         if (na) atomicAdd(&counters[3], (unsigned long long)na);
-        if (qa) atomicAdd(io.cursor + 2, qa);  // follow-up items of the launch (bgr_aligner_pass_counts)
+        if (qa) atomicAdd(io.cursor + kCurFollowUps, qa);  // follow-up items of the launch (bgr_aligner_pass_counts)
     }
 }
 
 }  // namespace
 
-hipError_t launch_greedy(const BgrDeviceGraph& g, const BatchIO& io, const KernelParams& p, const LaunchCfg& cfg, hipStream_t stream) {
+const void* greedy_kernel(KernelId k, bool stage, bool ascii) {
     constexpr int GL = (int)kG4GroupLanes;
-    if (io.greedy_multi) {
-        if (io.ascii) return cfg.stage_mphf ? launch_one(bgr_align_greedy_multi_kernel<true, GL, true>, g, io, p, cfg, stream)
-                                            : launch_one(bgr_align_greedy_multi_kernel<false, GL, true>, g, io, p, cfg, stream);
-        return cfg.stage_mphf ? launch_one(bgr_align_greedy_multi_kernel<true, GL, false>, g, io, p, cfg, stream)
-                              : launch_one(bgr_align_greedy_multi_kernel<false, GL, false>, g, io, p, cfg, stream);
+    switch (k) {
+        case KernelId::kGreedyMulti:
+            if (ascii) return stage ? kernel_ptr(bgr_align_greedy_multi_kernel<true, GL, true>) : kernel_ptr(bgr_align_greedy_multi_kernel<false, GL, true>);
+            return stage ? kernel_ptr(bgr_align_greedy_multi_kernel<true, GL, false>) : kernel_ptr(bgr_align_greedy_multi_kernel<false, GL, false>);
+        case KernelId::kGreedyWide: return stage ? kernel_ptr(bgr_align_greedy_wide_kernel<true>) : kernel_ptr(bgr_align_greedy_wide_kernel<false>);
+        case KernelId::kGreedy: return stage ? kernel_ptr(bgr_align_greedy_kernel<true>) : kernel_ptr(bgr_align_greedy_kernel<false>);
+        default: return nullptr;
     }
-    if (cfg.wide_keys) return cfg.stage_mphf ? launch_one(bgr_align_greedy_wide_kernel<true>, g, io, p, cfg, stream)
-                                             : launch_one(bgr_align_greedy_wide_kernel<false>, g, io, p, cfg, stream);
-    return cfg.stage_mphf ? launch_one(bgr_align_greedy_kernel<true>, g, io, p, cfg, stream)
-                          : launch_one(bgr_align_greedy_kernel<false>, g, io, p, cfg, stream);
-}
-const void* greedy_kernel_fn(bool many_reads) {
-    return many_reads ? reinterpret_cast<const void*>(&bgr_align_greedy_multi_kernel<true, (int)kG4GroupLanes, true>) : reinterpret_cast<const void*>(&bgr_align_greedy_kernel<true>);
 }
 
 }  // namespace bgr

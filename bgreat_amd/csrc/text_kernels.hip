@@ -530,22 +530,6 @@ __global__ void __launch_bounds__(256) bgr_text_record_info_kernel(const uint4* 
     out[j] = v;
 }
 
-// accepted records, compacted in input order: which record, where its sequence starts in the text, base offsets of the batch
-__global__ void __launch_bounds__(256) bgr_text_compact_kernel(const uint4* rec, const uint32_t* n_rec_p, const uint32_t* acc_idx, const uint32_t* base_off,
-                                                               uint32_t* acc_rec, uint32_t* acc_src, u64* read_offs, const uint32_t* n_acc_p, const uint32_t* bases_p, uint32_t rec_cap) {
-    const uint32_t R = *n_rec_p;
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (R > rec_cap) return;  // (rec[] was not written: the piece goes to the host parser)
-    if (j == 0) read_offs[*n_acc_p] = *bases_p;
-    if (j >= R) return;
-    const uint4 r = rec[j];
-    if (!(r.w >> 31)) return;
-    const uint32_t a = acc_idx[j];
-    acc_rec[a] = j;
-    acc_src[a] = r.z;
-    read_offs[a] = base_off[j];
-}
-
 // ---- out: sizes of the formatted records -----------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t dec_len(int32_t v) {  // characters of to_string(v) + '.'
     uint32_t u = (uint32_t)v, len = 1;

@@ -271,7 +271,8 @@ int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, c
  * that reads the device results below by itself calls this first. */
 int bgr_aligner_sync(bgr_aligner* a);
 /* Device pointers of the last bgr_align_device results: results uint32[n][2] = {path offset in the arena,
- * path length | status << 24}, arena int32[], cursor u32[1] (ints used in the arena).
+ * path length | status << 24}, arena int32[], cursor u32[2]: [0] = path ints handed out from the part of the arena behind the rows
+ * the launch's several-reads-per-wave first pass owns by read or wave number (so not all the ints in use), [1] = 1 if the arena overflowed.
  * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)]. */
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor);
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
@@ -295,11 +296,11 @@ int bgr_aligner_kernel_times(bgr_aligner* a, uint64_t* launches, double slot_ms[
  * bit 2 = the mode ran its several-reads-per-wave first pass (sixteen in greedy mode, eight or four in the others; the numbers then
  * describe that launch). */
 int bgr_aligner_launch_info(bgr_aligner* a, uint32_t out[4]);
-/* How the last mapping launch went through its passes.  Greedy mode: out[0..2] = reads the first / second / third launch of
- * the sixteen-reads-per-wave kernel handed on to the next one, counted in list entries (lists are written in per-wave slices,
- * so the figure includes a few unused entries; out[2] is 0: the third launch hands everything to the general kernel),
- * out[3] = reads mapped by the general kernel.  Exhaustive mode: out[2] = reads the four-reads-per-wave pass left to the level
- * / depth-first search, out[0] = reads that search listed for its second pass, out[1] = for its third.  Synchronises the stream. */
+/* How the last mapping launch went through its passes.  Greedy mode: out[0] = follow-up items (the next anchors of a read, its
+ * reverse complement) the sixteen-reads-per-wave kernel queued and worked off inside its launch, out[1] = out[2] = 0,
+ * out[3] = reads it left to the general kernel.  Anchors mode: out[2] = reads the several-reads-per-wave pass left to the general
+ * kernel.  Exhaustive mode: out[2] = reads the four-reads-per-wave pass left to the level / depth-first search, out[0] = reads that
+ * search listed for its second pass, out[1] = for its third.  Synchronises the stream. */
 int bgr_aligner_pass_counts(bgr_aligner* a, uint32_t out[4]);
 /* Tuning knobs (0 keeps the default): waves per workgroup, workgroups per CU, LDS staging of the overlap
  * key table (0 auto, 1 off: probed in L2, 2 on -- where it can be had: anchors mode stages nothing, a table beyond a CU's LDS is probed in L2;

@@ -25,7 +25,7 @@ BUILD_NO_EVICTIONS = 2  # test hook: keys whose two buckets are full go to the f
 SYMBOLS = [
     "bgr_last_error", "bgr_device_count", "bgr_graph_build", "bgr_graph_build_from_fasta", "bgr_graph_blob",
     "bgr_graph_from_blob", "bgr_graph_info", "bgr_graph_destroy", "bgr_graph_upload", "bgr_graph_device_blob",
-    "bgr_graph_adopt_device_blob", "bgr_aligner_create", "bgr_aligner_destroy", "bgr_align_batch", "bgr_align_device",
+    "bgr_graph_adopt_device_blob", "bgr_aligner_create", "bgr_aligner_destroy", "bgr_align_batch", "bgr_align_device", "bgr_aligner_path_stats",
     "bgr_aligner_sync", "bgr_aligner_device_results", "bgr_aligner_fetch", "bgr_aligner_counters",
     "bgr_aligner_reset_counters", "bgr_aligner_kernel_time", "bgr_aligner_reset_kernel_time", "bgr_aligner_launch_info",
     "bgr_aligner_configure", "bgr_readset_load", "bgr_readset_count", "bgr_readset_view", "bgr_readset_destroy",
@@ -74,7 +74,14 @@ class Params(C.Structure):
 class RunOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint64), ("n_gpus", C.c_uint32), ("threads", C.c_uint32), ("batch_reads", C.c_uint64), ("chunk_bytes", C.c_uint64),
                 ("fastq", C.c_uint32), ("write_exhaustive", C.c_uint32), ("echo_files", C.c_uint32), ("correction", C.c_uint32),
-                ("no_overlap_file", C.c_char_p), ("first_device", C.c_uint32), ("route", C.c_uint32), ("numa", C.c_uint32), ("split_output", C.c_uint32)]
+                ("no_overlap_file", C.c_char_p), ("first_device", C.c_uint32), ("route", C.c_uint32), ("numa", C.c_uint32), ("split_output", C.c_uint32), ("gaf", C.c_uint32)]
+
+
+class PathStat(C.Structure):  # bgr_path_stat
+    _fields_ = [("path_len", C.c_uint64), ("path_start", C.c_uint64), ("aligned", C.c_uint32), ("mismatches", C.c_uint32)]
+
+
+PATH_STAT_NO_WALK = 0x80000000
 
 
 class Ticket(C.Structure):
@@ -182,6 +189,7 @@ def lib():
     L.bgr_aligner_sync.argtypes = [vp]
     L.bgr_aligner_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.bgr_aligner_fetch.argtypes = [vp, u64, vp, u64, vp, vp]
+    L.bgr_aligner_path_stats.argtypes = [vp, vp, vp, u64, vp]
     L.bgr_aligner_counters.argtypes = [vp, vp]
     L.bgr_aligner_reset_counters.argtypes = [vp]
     L.bgr_aligner_kernel_time.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_double)]
@@ -504,7 +512,8 @@ class Aligner:
 
     def align_fasta_text(self, text, m=2, effort=2, mode=MODE_GREEDY, partial=False, want_output=True, paths_cap=None, staged=False, fastq=False, parts=None, record_info=False):
         """bgr_align_fasta_text: a piece of a FASTA file (bytes) -> (paths bytes, notAligned bytes, info dict); info["irregular"] = the
-        device left the piece to the host parser (nothing mapped).  fastq: True / 1 = the piece is whole four-line FASTQ records instead, 2 = their
+        device left the piece to the host parser (nothing mapped).  want_output: 1 / True = the reference's records, 2 = corrected reads (-c), 3 = GAF
+        lines (--gaf); info["no_walk"] is there (and "irregular" set) when a path of the piece spells no walk (2 and 3).  fastq: True / 1 = the piece is whole four-line FASTQ records instead, 2 = their
         header and read lines only.  A too small `paths_cap` is grown through bgr_aligner_fetch_text.  parts (with staged): byte offsets at which
         the piece is cut into host ranges sent with bgr_text_stage_upload_parts (the call itself then gets no host pointer)."""
         text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else _as_u8(text)
@@ -543,6 +552,8 @@ class Aligner:
                 lib().bgr_text_stage_destroy(stage)
         _check(rc)
         info = {"irregular": bool(b.irregular), "n_records": int(b.n_records), "n_accepted": int(b.n_accepted)}
+        if b.irregular == 2:
+            info["no_walk"] = True
         if rinfo is not None:  # one word per record: kept << 31 | mapped << 30 | read length
             info["records"] = rinfo[: int(b.n_records)].copy()
         return pout[: int(b.paths_bytes)].tobytes(), nout[: int(b.notaligned_bytes)].tobytes(), info
@@ -557,6 +568,14 @@ class Aligner:
         status = np.empty(max(n, 1), dtype=np.uint8)
         _check(lib().bgr_aligner_fetch(self.h, n, paths.ctypes.data, cap, poffs.ctypes.data, status.ctypes.data))
         return paths[: int(poffs[n])].copy(), poffs, status[:n]
+
+    def path_stats(self, d_reads_ptr, d_offsets_ptr, n):
+        """bgr_aligner_path_stats over the last align_device launch (the same device reads again) -> structured array of n rows with the fields
+        path_len, path_start, aligned, mismatches (PATH_STAT_NO_WALK set there for a path that spells no walk; zeros for an unmapped read)."""
+        out = np.zeros(n, dtype=np.dtype([("path_len", np.uint64), ("path_start", np.uint64), ("aligned", np.uint32), ("mismatches", np.uint32)]))
+        assert out.dtype.itemsize == C.sizeof(PathStat)
+        _check(lib().bgr_aligner_path_stats(self.h, d_reads_ptr, d_offsets_ptr, n, out.ctypes.data))
+        return out
 
     def sync(self):
         _check(lib().bgr_aligner_sync(self.h))
@@ -616,13 +635,15 @@ class Aligner:
 
 
 def align_all(graph, reads_csv, paths_file, notaligned_file, m=2, effort=2, mode=MODE_GREEDY, partial=False, n_gpus=1, threads=1,
-              batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False):
+              batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False,
+              gaf=False):
     """Aligner::alignAll (aligner.cpp:550-597) as one call -> (counters dict, mapping seconds).  route: 0 = FASTA goes through the device as
     text when it can (bgr_align_fasta_text), 1 = host parser + host formatter always.  split_output: one pipeline per device, device d
-    writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes)."""
+    writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes).  gaf: the paths file holds one GAF line per
+    mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction)."""
     p = Params(mode, m, effort, int(partial))
     o = RunOptions(C.sizeof(RunOptions), n_gpus, threads, batch_reads, chunk_bytes, int(fastq), int(write_exhaustive), 0, int(correction),
-                   no_overlap_file.encode() if no_overlap_file else None, first_device, route, numa, int(split_output))
+                   no_overlap_file.encode() if no_overlap_file else None, first_device, route, numa, int(split_output), int(gaf))
     out = np.zeros(5, dtype=np.uint64)
     secs = C.c_double()
     _check(lib().bgr_align_all(graph.h, C.byref(p), C.byref(o), reads_csv.encode(), paths_file.encode(), notaligned_file.encode(),

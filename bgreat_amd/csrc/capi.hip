@@ -97,7 +97,7 @@ struct bgr_aligner {
     hipStream_t stream = nullptr;
     BgrDeviceGraph dg;
     // the text route (bgr_align_fasta_text): the piece, its records, the formatted streams
-    DevBuf tx_in, tx_sums, tx_state, tx_rec, tx_idx, tx_accrec, tx_accsrc, tx_offs, tx_psz, tx_nsz, tx_poff, tx_noff, tx_pout, tx_nout, tx_info;
+    DevBuf tx_in, tx_sums, tx_state, tx_rec, tx_idx, tx_accrec, tx_accsrc, tx_offs, tx_psz, tx_nsz, tx_poff, tx_noff, tx_pout, tx_nout, tx_info, tx_gaf, path_stats;
     uint64_t tx_n_acc = 0, tx_pbytes = 0, tx_nbytes = 0;
     bool blocking_sync = bgr::opt("blocking_sync") != 0;
     hipEvent_t ev_wait = nullptr;
@@ -105,7 +105,7 @@ struct bgr_aligner {
     uint32_t tx_flip = 0;              // which of the two info blocks the current piece uses
     uint32_t tx_epoch = 0, tx_ticket[2] = {0, 0};   // the one-launch kernels' chains: epoch of the last launch; tickets earlier launches took (parse, format)
     bool tx_written = false;           // the streams lie in tx_pout / tx_nout (the format launch wrote them: every stretch ended below the capacities)
-    uint32_t tx_want = 0;              // its want_output (2 = correction mode: mapped reads as spelled by their paths)
+    uint32_t tx_want = 0;              // its want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
     double tx_phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
 
     DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: kSmall* (align_kernels.h)
@@ -120,6 +120,7 @@ struct bgr_aligner {
     bgr::PlanDevice plan_dev;     // CUs, LDS, resident waves per kernel: asked once
     bool plan_dev_known = false;
     uint64_t last_n = 0;
+    uint32_t last_mode = 0;       // mode of the last mapping launch (bgr_aligner_path_stats)
     DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
     uint64_t wave_times_n = 0;
     uint64_t ticket_serial = 0;       // bgr_align_batch_begin: tickets handed out; the batch of the last one is in flight until its wait
@@ -520,7 +521,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
         a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
-                          &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info}) b->release();
+                          &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
         if (a->ev_wait) (void)hipEventDestroy(a->ev_wait);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -637,6 +638,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     if (p->mode != BGR_MODE_GREEDY && a->graph->header.wide_keys)
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
     a->last_n = n_reads;
+    a->last_mode = p->mode;
     a->deep.open = false;
     a->deep.runs = 0; a->deep.memo_cap = 0;
     if (n_reads == 0) return BGR_OK;
@@ -930,7 +932,12 @@ static int fetch_text_impl(bgr_aligner* a, bgr_text_batch* b) {
     if (!a->tx_written) {   // (correction mode; streams larger than the buffers the format launch wrote into; a second fetch)
     HIP_TRY(a->tx_pout.ensure(a->tx_pbytes + 64));
     HIP_TRY(a->tx_nout.ensure(a->tx_nbytes + 64));
-    hipError_t e = a->tx_want == 2
+    hipError_t e = a->tx_want == 3
+        ? bgr::launch_text_gaf_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
+                                     static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
+                                     static_cast<const uint32_t*>(a->tx_noff.p), static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_idx.p),
+                                     static_cast<const uint4*>(a->tx_gaf.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p), a->stream)
+        : a->tx_want == 2
         ? bgr::launch_text_correct_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
                                          static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
                                          static_cast<const uint32_t*>(a->tx_noff.p), static_cast<const uint32_t*>(a->tx_idx.p), static_cast<uint8_t*>(a->tx_pout.p),
@@ -1029,15 +1036,17 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     double tw = wall_now();
     auto lap = [&](int i) { const double t = wall_now(); a->tx_phase_s[i] += t - tw; tw = t; };
     if (b->text_bytes >= (1ull << 31)) return fail(BGR_E_ARG, "bgr_align_fasta_text: piece of 2 GiB or more; cut it");
-    if (b->want_output > 2) return fail(BGR_E_ARG, "bgr_align_fasta_text: want_output must be 0, 1 or 2");
+    if (b->want_output > 3) return fail(BGR_E_ARG, "bgr_align_fasta_text: want_output must be 0, 1, 2 or 3");
     if (b->fastq > 2) return fail(BGR_E_ARG, "bgr_align_fasta_text: fastq must be 0, 1 (four-line records) or 2 (header and read lines only)");
     const uint32_t rec_lines = b->fastq == 2 ? 2u : b->fastq ? 4u : 0u;  // lines per record of a FASTQ piece (0: FASTA, records start at '>' lines)
     if (b->fastq && b->text_bytes && b->text && b->text[b->text_bytes - 1] != '\n' && !b->stage)
         return fail(BGR_E_ARG, "bgr_align_fasta_text: a FASTQ piece holds whole four-line records and ends with a newline");
     if (b->want_output == 2 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
         return fail(BGR_E_ARG, "bgr_align_fasta_text: correction on the device needs a graph of ACGT-only unitigs and greedy mode (format such a run on the host)");
-    if (b->record_info_out && (b->want_output == 2 || b->record_info_cap < b->text_bytes / 24 + 1024))
-        return fail(BGR_E_ARG, "bgr_align_fasta_text: record_info_out needs room for text_bytes / 24 + 1024 words and is not available in correction mode");
+    if (b->want_output == 3 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
+        return fail(BGR_E_ARG, "bgr_align_fasta_text: GAF output needs a graph of ACGT-only unitigs (a path read backwards does not spell the reverse complement on one with other characters) and a greedy mode");
+    if (b->record_info_out && (b->want_output >= 2 || b->record_info_cap < b->text_bytes / 24 + 1024))
+        return fail(BGR_E_ARG, "bgr_align_fasta_text: record_info_out needs room for text_bytes / 24 + 1024 words and is not available in correction mode or with GAF output");
     a->tx_want = b->want_output;
     b->irregular = 0;
     b->n_records = b->n_accepted = b->paths_bytes = b->notaligned_bytes = 0;
@@ -1138,7 +1147,13 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
         continue;  // (the record info was made from results that were not final)
     }
     // 4. sizes of the records, stream offsets, the bytes
-    if (b->want_output == 2) {  // (tx_idx is free again behind the compaction: it takes the corrected reads' lengths)
+    if (b->want_output == 3) {  // (tx_idx is free again behind the compaction: it takes the lengths of the names)
+        HIP_TRY(a->tx_gaf.ensure(((uint64_t)n_acc + 1) * 16));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
+        e = bgr::launch_text_gaf_sizes(a->dg, text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
+                                       static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, static_cast<uint32_t*>(a->tx_psz.p), static_cast<uint32_t*>(a->tx_nsz.p),
+                                       static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint4*>(a->tx_gaf.p), info + TXT_INFO_BUG, a->stream);
+    } else if (b->want_output == 2) {  // (tx_idx is free again behind the compaction: it takes the corrected reads' lengths)
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
         e = bgr::launch_text_correct_sizes(a->dg, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
                                            static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, static_cast<uint32_t*>(a->tx_psz.p), static_cast<uint32_t*>(a->tx_nsz.p),
@@ -1155,7 +1170,7 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
                                     static_cast<uint32_t*>(a->tx_noff.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p), pcap_dev, ncap_dev, info, a->stream);
         if (n_acc && e == hipSuccess) a->tx_ticket[1] += bgr::format_tiles(n_acc);   // (as many tickets as workgroups ran: launch_text_format launches nothing for zero reads)
     }
-    if (e == hipSuccess && b->want_output == 2) e = bgr::launch_scan2_u32(static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_nsz.p), static_cast<uint32_t*>(a->tx_poff.p),
+    if (e == hipSuccess && b->want_output >= 2) e = bgr::launch_scan2_u32(static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_nsz.p), static_cast<uint32_t*>(a->tx_poff.p),
                                                    static_cast<uint32_t*>(a->tx_noff.p), n_acc, nullptr, sums2, info + TXT_INFO_PBYTES, info + TXT_INFO_NBYTES, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text size launches: ") + hipGetErrorString(e));
     uint32_t all[bgr::kSmallBytes / 4], h2[bgr::kCurWords];   // the cursor block and the info block lie in the same `small` buffer: one copy
@@ -1173,7 +1188,7 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     }
     break;
     }
-    if (b->want_output == 2 && h[TXT_INFO_BUG] != 0xFFFFFFFFu) {  // a path that does not spell a walk: the reference prints "bug compaction" and exits
+    if (b->want_output >= 2 && h[TXT_INFO_BUG] != 0xFFFFFFFFu) {  // a path that does not spell a walk: the reference prints "bug compaction" and exits
         b->irregular = 2;                                          // (aligner.cpp:280-283); the caller reproduces that on the host
         a->tx_n_acc = 0;
         return BGR_OK;
@@ -1235,6 +1250,24 @@ static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths
     HIP_TRY(hipMemcpyAsync(path_offsets, a->csr_poffs.p, (n + (with_end ? 1 : 0)) * 8, hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(hipMemcpyAsync(status, a->csr_status.p, n, hipMemcpyDeviceToHost, a->stream));
     if (total) HIP_TRY(hipMemcpyAsync(paths_out, a->csr_paths.p, total * 4, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(wait_stream(a));
+    return BGR_OK;
+}
+
+int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n, bgr_path_stat* out) {
+    if (!a || (n && (!d_reads || !d_read_offsets || !out))) return fail(BGR_E_ARG, "bgr_aligner_path_stats: null argument");
+    if (a->graph->header.has_exc)
+        return fail(BGR_E_ARG, "bgr_aligner_path_stats: needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
+    if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_path_stats: n_reads differs from the last bgr_align_device call");
+    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_path_stats: the last launch was exhaustive; paths of the greedy modes only");
+    if (n == 0) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    static_assert(sizeof(bgr_path_stat) == 24, "six words per read, as the kernel writes them");
+    HIP_TRY(a->path_stats.ensure(n * sizeof(bgr_path_stat)));
+    hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->results.p),
+                                          static_cast<const int32_t*>(a->arena.p), (uint32_t)n, static_cast<uint32_t*>(a->path_stats.p), a->stream);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path stats launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(out, a->path_stats.p, n * sizeof(bgr_path_stat), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return BGR_OK;
 }

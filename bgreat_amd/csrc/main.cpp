@@ -12,6 +12,9 @@
 //                                                                   <notAligned>.<d>; `cat` in device order = the reference's files)
 //                                                   --host-route (parse and format on the host always; default: FASTA goes through the
 //                                                                 device as text when the run writes the reference's two files)
+//                                                   --gaf (the paths file holds one GAF line per mapped read -- name, query interval, strand, the path's
+//                                                          segments with their orientations, path interval, matches, NM:i -- instead of
+//                                                          header + path ints; greedy modes, ACGT-only unitigs, not with -c: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -36,11 +39,11 @@ int main(int argc, char** argv) {
     std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
-    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false;
+    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
-                                {"set", required_argument, nullptr, 1007},
+                                {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -71,6 +74,7 @@ int main(int argc, char** argv) {
                 if (eq == std::string::npos || bgr_set_option(kv.substr(0, eq).c_str(), std::stoll(kv.substr(eq + 1))) != BGR_OK) die("--set name=value");
                 break;
             }
+            case 1008: gaf = true; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -112,6 +116,7 @@ int main(int argc, char** argv) {
     opt.no_overlap_file = noOverlapFile.empty() ? nullptr : noOverlapFile.c_str();
     opt.route = host_route ? 1u : 0u;
     opt.split_output = split_out ? 1u : 0u;
+    opt.gaf = gaf ? 1u : 0u;
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;

@@ -347,6 +347,63 @@ bool recover_path(const Unitigs& u, const int32_t* path, uint64_t n, uint32_t re
     return true;
 }
 
+// ---- GAF output (--gaf, bgr_run_options.gaf): one line per mapped read; the definition is in include/bgreat_gpu.h ------
+inline void put_u64(std::string& o, uint64_t v) {
+    char b[24];
+    char* e = b + sizeof(b);
+    char* w = e;
+    do { *--w = (char)('0' + v % 10); v /= 10; } while (v);
+    o.append(w, (size_t)(e - w));
+}
+// Appends the line of one mapped read (path of n >= 2 ints) to `out`.  The walk is recover_path's, with the orientation each unitig was glued
+// on in kept in `fwd`; false = the path spells no walk (walk / tmp then hold what the reference prints behind "bug compaction").
+bool gaf_line(const Unitigs& u, const int32_t* path, uint64_t n, const char* h, uint32_t hl, const char* read, uint32_t L, bool on_rc, std::string& out,
+              std::string& walk, std::string& tmp, std::string& rc, std::vector<uint8_t>& fwd) {
+    const uint32_t K1 = u.k - 1;
+    oriented_unitig(u, path[1], walk);
+    tmp.clear();
+    if (walk.empty()) return false;
+    fwd.assign(1, path[1] > 0 ? 1 : 0);
+    for (uint64_t i = 2; i < n; ++i) {
+        oriented_unitig(u, path[i], tmp);
+        if (tmp.empty() || walk.size() < K1 || tmp.size() < K1) return false;
+        if (walk.compare(walk.size() - K1, K1, tmp, 0, K1) == 0) { walk.append(tmp, K1, std::string::npos); fwd.push_back(path[i] > 0 ? 1 : 0); continue; }
+        rc.resize(tmp.size());
+        for (size_t j = 0; j < tmp.size(); ++j) rc[j] = rc_char(tmp[tmp.size() - 1 - j]);
+        if (walk.compare(walk.size() - K1, K1, rc, 0, K1) == 0) { walk.append(rc, K1, std::string::npos); fwd.push_back(path[i] > 0 ? 0 : 1); continue; }
+        return false;
+    }
+    if (path[0] < 0 || (uint64_t)path[0] > walk.size()) return false;
+    const uint64_t off = (uint64_t)path[0], plen = walk.size();
+    const uint32_t cl = (uint32_t)std::min<uint64_t>(L, plen - off);
+    uint32_t nm = 0;   // characters of the read that differ from what the path spells under them
+    if (!on_rc) { for (uint32_t j = 0; j < cl; ++j) nm += walk[off + j] != read[j]; }
+    else for (uint32_t j = 0; j < cl; ++j) nm += rc_char(walk[off + j]) != read[L - 1 - j];
+    const uint32_t qs = on_rc ? L - cl : 0u, qe = on_rc ? L : cl;
+    const uint64_t pstart = on_rc ? plen - (off + cl) : off;
+    size_t nl = 0;   // the name: behind the header's first character up to the first space or tab
+    while (1 + nl < hl && h[1 + nl] != ' ' && h[1 + nl] != '\t') ++nl;
+    if (nl) out.append(h + 1, nl); else out.push_back('*');
+    out.push_back('\t'); put_u64(out, L);
+    out.push_back('\t'); put_u64(out, qs);
+    out.push_back('\t'); put_u64(out, qe);
+    out.append("\t+\t");
+    for (uint64_t s = 0; s + 1 < n; ++s) {   // a read mapped on its reverse complement: the path from its end, every orientation flipped
+        const uint64_t i = on_rc ? n - 1 - s : 1 + s;
+        const int64_t id = path[i] < 0 ? -(int64_t)path[i] : (int64_t)path[i];
+        out.push_back((fwd[i - 1] != 0) != on_rc ? '>' : '<');
+        put_u64(out, (uint64_t)id);
+    }
+    out.push_back('\t'); put_u64(out, plen);
+    out.push_back('\t'); put_u64(out, pstart);
+    out.push_back('\t'); put_u64(out, pstart + cl);
+    out.push_back('\t'); put_u64(out, cl - nm);
+    out.push_back('\t'); put_u64(out, cl);
+    out.append("\t255\tNM:i:"); put_u64(out, nm);
+    out.push_back('\n');
+    return true;
+}
+
 // Records lo..hi of a batch as the reference writes them: mapped -> "header\n" + "int." * n + "\n" into pbuf
 // (alignerGreedy.cpp:406-411), the others -> "header\nread\n" into nbuf (alignerGreedy.cpp:421-427).
 void format_range(const Batch& b, uint64_t lo, uint64_t hi, std::string& pbuf, std::string& nbuf) {
@@ -380,22 +437,29 @@ void format_range(const Batch& b, uint64_t lo, uint64_t hi, std::string& pbuf, s
     pbuf.resize(pmax ? (size_t)(po - p0) : 0);
 }
 
-// The same with the two opt-in output variants: correction mode (mapped reads are written as header + corrected read,
+// The same with the opt-in output variants: GAF lines in the place of the path records (`gaf`; needs `correct`, the unitigs), correction mode (mapped reads are written as header + corrected read,
 // alignerGreedy.cpp:394-404) and the no-overlap split (reads without any anchor go to a third buffer).
 // Returns false on the reference's "bug compaction" condition (aligner.cpp:280-283: it prints "bug compaction", the walk
 // so far and the unitig that does not continue it, and exits); the buffers then hold the records BEFORE that read and
 // `bug` the two strings the reference prints.
-bool format_range_ext(const Batch& b, uint64_t lo, uint64_t hi, const Unitigs* correct, bool split_no_overlap, std::string& pbuf,
+bool format_range_ext(const Batch& b, uint64_t lo, uint64_t hi, const Unitigs* correct, bool gaf, bool split_no_overlap, std::string& pbuf,
                       std::string& nbuf, std::string& obuf, std::string& bug) {
     const int32_t* paths = static_cast<const int32_t*>(b.pin->paths.p);
     const uint64_t* poffs = static_cast<const uint64_t*>(b.pin->poffs.p);
     const uint8_t* status = static_cast<const uint8_t*>(b.pin->status.p);
     pbuf.clear(); nbuf.clear(); obuf.clear();
     std::string walk, tmp, rc;
+    std::vector<uint8_t> fwd;
     for (uint64_t i = lo; i < hi; ++i) {
         const RecSlice& r = b.recs[i];
         const uint64_t np = poffs[i + 1] - poffs[i];
-        if (np) {
+        if (np && gaf) {
+            if (np < 2) { walk.clear(); tmp.clear(); }
+            if (np < 2 || !gaf_line(*correct, paths + poffs[i], np, r.h, r.hl, r.s, r.sl, (status[i] & BGR_ST_RC) != 0, pbuf, walk, tmp, rc, fwd)) {
+                bug = walk + " " + tmp;
+                return false;
+            }
+        } else if (np) {
             if (correct && (np < 2 || !recover_path(*correct, paths + poffs[i], np, r.sl, walk, tmp, rc))) {
                 bug = walk + " " + tmp;
                 return false;
@@ -488,6 +552,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     // (one launch addresses its path arena with 32 bits: a batch stays below 4 M reads and ~1 G bases)
     const bool writes = prm->mode != BGR_MODE_EXHAUSTIVE || opt->write_exhaustive;
     const bool correction = opt->correction && prm->mode != BGR_MODE_EXHAUSTIVE;  // alignPartExhaustive ignores -c
+    const bool gaf = opt->gaf != 0;  // (bgr_align_all has refused it in exhaustive mode, with -c and on a graph with exception planes)
     const bool progress_blocks = opt->echo_files && prm->mode == BGR_MODE_EXHAUSTIVE;
     // Text route: the device parses, packs, maps and formats (bgr_align_fasta_text); the host only moves bytes.  FASTA, the
     // reference's two output files and no -b progress blocks (those count getReads() calls, which only the host parser tracks).
@@ -508,7 +573,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     const uint64_t chunk_bytes = opt->chunk_bytes ? opt->chunk_bytes
                                                   : std::min<uint64_t>(8ull << 20, std::max<uint64_t>(256ull << 10, batch_reads * 170 / threads));
     Unitigs unitigs;
-    if (correction) {
+    if (correction || gaf) {
         if (bgr_graph_unitigs(graph, &unitigs.seqs, &unitigs.offs, &unitigs.n) != BGR_OK) return BGR_E_ARG;
         bgr_graph_info_t gi0;
         if (bgr_graph_info(graph, &gi0) != BGR_OK) return BGR_E_ARG;
@@ -519,7 +584,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
         ovlF = fopen(opt->no_overlap_file, "wb");
         if (!ovlF) return bgr::set_error(BGR_E_IO, "bgr_align_all: cannot open the no-overlap file");
     }
-    const bool extended = correction || ovlF != nullptr;
+    const bool extended = correction || gaf || ovlF != nullptr;
     bgr_graph_info_t gi;
     if (bgr_graph_info(graph, &gi) != BGR_OK) return BGR_E_ARG;
 
@@ -574,7 +639,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     // of them in the other file: a quarter of the piece each to start with (page-locked memory costs ~0.2 s per GB: less of it, and a fresh
     // process reaches its rate sooner); a stream that does not fit comes back as BGR_E_CAPACITY and the set's buffer grows once (-c, whose
     // paths stream is header + read, starts at the full size)
-    const uint64_t out_div = correction ? 1 : 4;
+    const uint64_t out_div = correction ? 1 : gaf ? 2 : 4;   // (a GAF line is about half a 150 bp record)
     // FASTQ on the text route: only the header and read lines of a piece go to the device (option fastq_gather = 0: the four-line records as they are)
     const bool fastq_gather = bgr::opt("fastq_gather") != 0;
     std::atomic<uint64_t> us_parse{0}, us_gather{0}, us_gpu{0}, us_format{0}, us_write{0}, us_alloc{0};
@@ -1070,7 +1135,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
                         tb.text_bytes = b->t_gathered;
                         tb.fastq = 2u;
                     }
-                    tb.want_output = writes ? (correction ? 2u : 1u) : 0u;
+                    tb.want_output = writes ? (gaf ? 3u : correction ? 2u : 1u) : 0u;
                     tb.paths_out = static_cast<char*>(b->pin->ptext.p);
                     tb.paths_cap = b->pin->ptext.cap;
                     tb.notaligned_out = static_cast<char*>(b->pin->ntext.p);
@@ -1292,7 +1357,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
                     uint64_t lo = t * per, hi = std::min<uint64_t>(cp->n, lo + per);
                     if (lo >= hi) return;
                     if (!extended) format_range(*cp, lo, hi, pb[t], nb[t]);
-                    else okv[t] = format_range_ext(*cp, lo, hi, correction ? &unitigs : nullptr, ovlF != nullptr, pb[t], nb[t], ob[t], bugv[t]) ? 1 : 0;
+                    else okv[t] = format_range_ext(*cp, lo, hi, (correction || gaf) ? &unitigs : nullptr, gaf, ovlF != nullptr, pb[t], nb[t], ob[t], bugv[t]) ? 1 : 0;
                 }, 3);
                 // "bug compaction": like the reference, everything before the offending read is written, nothing after it
                 unsigned t_stop = threads;
@@ -1474,7 +1539,17 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     const bool progress_blocks = opt->echo_files && prm->mode == BGR_MODE_EXHAUSTIVE;
     const bool correction = opt->correction && prm->mode != BGR_MODE_EXHAUSTIVE;
-    if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->no_overlap_file)
+    if (opt->gaf) {   // GAF output: what it cannot describe is refused before any device work
+        bgr_graph_info_t gi;
+        if (bgr_graph_info(graph, &gi) != BGR_OK) return BGR_E_ARG;
+        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) is for the greedy modes; exhaustive mode (-b) writes no paths");
+        if (opt->correction)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) and correction (-c) both claim the paths file; choose one");
+        if (gi.has_exceptions)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
+    }
+    if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)
         return align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
     std::vector<InputSpan> inputs(files.size());
     for (size_t i = 0; i < files.size(); ++i) inputs[i].file = files[i];

@@ -224,8 +224,10 @@ typedef struct {
     uint64_t text_bytes;          /*     < 2^31 */
     uint32_t want_output;         /*     0 = map and count only (-b without --write-exhaustive writes nothing), 1 = the reference's records,
                                          2 = correction mode (-c, alignerGreedy.cpp:394-404): a mapped read's record is header + the read as
-                                         spelled by its path (recoverPath, aligner.cpp:270-290); greedy modes, ACGT-only unitigs */
-    uint32_t irregular;           /* out: 1 = piece left to the host parser; 2 = (want_output 2) a path of this piece does not spell a walk --
+                                         spelled by its path (recoverPath, aligner.cpp:270-290); greedy modes, ACGT-only unitigs,
+                                         3 = GAF (--gaf): a mapped read's record is one GAF line (below, bgr_run_options.gaf); greedy modes,
+                                         ACGT-only unitigs; capacities, BGR_E_CAPACITY and bgr_aligner_fetch_text as with 2 */
+    uint32_t irregular;           /* out: 1 = piece left to the host parser; 2 = (want_output 2, 3) a path of this piece does not spell a walk --
                                          the reference's "bug compaction" exit, which the caller reproduces on the host */
     char* paths_out;              /* in: where the records of mapped reads go */
     uint64_t paths_cap;
@@ -243,7 +245,7 @@ typedef struct {
     uint32_t* record_info_out;    /* in, optional: one word per RECORD of the piece, in the piece's order -- bit 31: getReads keeps it, bit 30: it was mapped,
                                      bits 0..29: its read's length (0 unless kept) -- what the reference's -b progress blocks count between two getReads()
                                      calls (alignerExhaustive.cpp:306-316: a record, kept or dropped, is one iteration of the call).  Needs room for
-                                     text_bytes / 24 + 1024 words (record_info_cap); n_records of them are written.  Not with want_output = 2. */
+                                     text_bytes / 24 + 1024 words (record_info_cap); n_records of them are written.  Not with want_output = 2 or 3. */
     uint64_t record_info_cap;
 } bgr_text_batch;
 /* A stage = a device buffer for one piece + a copy stream: bgr_text_stage_upload starts the host -> device copy and returns; the
@@ -275,6 +277,18 @@ int bgr_aligner_sync(bgr_aligner* a);
  * the launch's several-reads-per-wave first pass owns by read or wave number (so not all the ints in use), [1] = 1 if the arena overflowed.
  * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)]. */
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor);
+/* What bgr_run_options.gaf writes per read, for a caller that keeps its own reads: over the results of the last bgr_align_device launch of this
+ * aligner (greedy or anchors mode; the caller hands the same device reads again, the aligner keeps nothing alive), out[i] for read i: the size of the
+ * walk its path spells, where the read starts on the path as GAF counts it (from the other end for a read mapped on its reverse complement), the
+ * characters covered and how many of them differ from the read.  Zeros for an unmapped read; mismatches = BGR_PATH_STAT_NO_WALK for a path that
+ * spells no walk (no error: the caller decides).  Blocking: one kernel on the aligner's stream and one copy.  BGR_E_ARG on a graph with non-ACGT
+ * unitig characters, after an exhaustive launch, or when n_reads is not the launch's. */
+typedef struct {
+    uint64_t path_len, path_start;
+    uint32_t aligned, mismatches;
+} bgr_path_stat;
+#define BGR_PATH_STAT_NO_WALK 0x80000000u
+int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n_reads, bgr_path_stat* out);
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n_reads, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status);
 
@@ -410,6 +424,21 @@ typedef struct {
                                   file system (~6-13 GB/s: 125-250 Mreads/s at ~50 bytes per read) whatever the number of GPUs; this form has
                                   no stage shared between devices.  FASTA input without -c, --no-overlap and -b progress blocks; any
                                   other run ignores the flag.                                                                  */
+    uint32_t gaf;              /* --gaf: the paths file holds one GAF line per mapped read, in input order, instead of header + path ints (0 = the
+                                  reference's records).  Tab separated: name (the header line without its first character, up to the first space
+                                  or tab; '*' if empty), read size L, query start, query end, '+', the path's segments ('>' id for a unitig read
+                                  forward, '<' id for its reverse complement; ids are the 1-based ordinals of the paths file), walk size, path
+                                  start, path end, matches, block size, 255, NM:i:mismatches.  The walk is the one -c spells (recoverPath,
+                                  aligner.cpp:270-290), the orientations the ones compactionEnd glued on; cl = min(L, walk size - path[0])
+                                  characters are covered.  A read mapped on its reverse complement (BGR_ST_RC) is described as it stands in
+                                  the input: its path reversed with every orientation flipped, query [L - cl, L), path start = walk size -
+                                  (path[0] + cl); a forward read: query [0, cl), path start = path[0].  The segments spelled and cut to
+                                  [path start, path end) are the read -c writes; NM = the positions where it differs from the read's
+                                  characters (an N always differs), matches = cl - NM, block size = cl.  Greedy modes (also -G, -q,
+                                  --no-overlap, several devices, the host route, k up to 64); refused with BGR_E_ARG on a graph with non-ACGT
+                                  unitig characters (has_exceptions: reversing a path does not reverse what it spells there), in exhaustive
+                                  mode and together with `correction`.  A path that spells no walk ends the run as -c's does
+                                  (BGR_E_COMPACTION).  split_output is ignored, as with -c.                                          */
 } bgr_run_options;
 /* bgr_align_all keeps its page-locked staging buffers for the next call of the process (they cost ~0.2 s per GB to allocate);
  * this frees them. */

@@ -35,8 +35,11 @@ SYMBOLS = [
     "bgr_align_fasta_text", "bgr_aligner_fetch_text", "bgr_host_cache_release", "bgr_device_local_cpus", "bgr_text_stage_create", "bgr_text_stage_destroy", "bgr_text_stage_upload",
     "bgr_align_batch_begin", "bgr_align_batch_test", "bgr_align_batch_wait", "bgr_text_stage_device", "bgr_text_stage_upload_parts",
     "bgr_device_alloc", "bgr_device_free", "bgr_device_upload", "bgr_device_download",
+    "bgr_aligner_abundance_enable", "bgr_aligner_abundance", "bgr_aligner_reset_abundance", "bgr_aligner_abundance_plan", "bgr_plan_abundance", "bgr_graph_abundance", "bgr_write_abundance",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+KNOB_ABUNDANCE_FORM = 12
+ABUNDANCE_AUTO, ABUNDANCE_GLOBAL, ABUNDANCE_LDS = 0, 1, 2
 SEARCH_AUTO, SEARCH_DEPTH_FIRST, SEARCH_BY_LEVEL = 0, 1, 2
 
 
@@ -74,7 +77,12 @@ class Params(C.Structure):
 class RunOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint64), ("n_gpus", C.c_uint32), ("threads", C.c_uint32), ("batch_reads", C.c_uint64), ("chunk_bytes", C.c_uint64),
                 ("fastq", C.c_uint32), ("write_exhaustive", C.c_uint32), ("echo_files", C.c_uint32), ("correction", C.c_uint32),
-                ("no_overlap_file", C.c_char_p), ("first_device", C.c_uint32), ("route", C.c_uint32), ("numa", C.c_uint32), ("split_output", C.c_uint32), ("gaf", C.c_uint32)]
+                ("no_overlap_file", C.c_char_p), ("first_device", C.c_uint32), ("route", C.c_uint32), ("numa", C.c_uint32), ("split_output", C.c_uint32), ("gaf", C.c_uint32),
+                ("abundance", C.c_uint32)]
+
+
+class UnitigAbundance(C.Structure):  # bgr_unitig_abundance
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64)]
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -222,6 +230,13 @@ def lib():
     L.bgr_readset_destroy.argtypes = [vp]
     L.bgr_readset_destroy.restype = None
     L.bgr_write_records.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    L.bgr_aligner_abundance_enable.argtypes = [vp, u32]
+    L.bgr_aligner_abundance.argtypes = [vp, vp, u64]
+    L.bgr_aligner_reset_abundance.argtypes = [vp]
+    L.bgr_aligner_abundance_plan.argtypes = [vp, u64, u64, vp]
+    L.bgr_plan_abundance.argtypes = [u64, u32, u64, u64, u32, u64, u32, vp]
+    L.bgr_graph_abundance.argtypes = [vp, vp, u64]
+    L.bgr_write_abundance.argtypes = [C.c_char_p, vp, vp, u64]
     _lib = L
     return L
 
@@ -429,6 +444,14 @@ class Graph:
     def device_blob(self, device=0):
         return lib().bgr_graph_device_blob(self.h, device)
 
+    def abundance(self):
+        """bgr_graph_abundance: the per-unitig totals of the last align_all(..., abundance=True) on this graph -> uint64 (n_unitigs, 3) =
+        (reads, bases, kmers), row i = unitig id i + 1.  Raises BgrError when there are none."""
+        n = self.info()["n_unitigs"]
+        out = np.zeros((n, 3), dtype=np.uint64)
+        _check(lib().bgr_graph_abundance(self.h, out.ctypes.data, n))
+        return out
+
     def close(self):
         if self.h:
             lib().bgr_graph_destroy(self.h)
@@ -577,6 +600,27 @@ class Aligner:
         _check(lib().bgr_aligner_path_stats(self.h, d_reads_ptr, d_offsets_ptr, n, out.ctypes.data))
         return out
 
+    def abundance_enable(self, on=True):
+        """bgr_aligner_abundance_enable: every greedy / anchors launch from now on adds its rows to the aligner's per-unitig table."""
+        _check(lib().bgr_aligner_abundance_enable(self.h, int(bool(on))))
+
+    def abundance(self):
+        """bgr_aligner_abundance -> uint64 (n_unitigs, 3) = (reads, bases, kmers) since enable / reset, row i = unitig id i + 1."""
+        n = self.graph.info()["n_unitigs"]
+        out = np.zeros((n, 3), dtype=np.uint64)
+        assert C.sizeof(UnitigAbundance) == 24
+        _check(lib().bgr_aligner_abundance(self.h, out.ctypes.data, n))
+        return out
+
+    def abundance_plan(self, n_reads, total_bases):
+        """bgr_aligner_abundance_plan: the abundance kernel behind a launch of this size -> dict(form (1 = A, 2 = B), blocks, threads, lds_bytes)."""
+        out = (C.c_uint32 * 4)()
+        _check(lib().bgr_aligner_abundance_plan(self.h, int(n_reads), int(total_bases), out))
+        return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+    def reset_abundance(self):
+        _check(lib().bgr_aligner_reset_abundance(self.h))
+
     def sync(self):
         _check(lib().bgr_aligner_sync(self.h))
 
@@ -636,19 +680,35 @@ class Aligner:
 
 def align_all(graph, reads_csv, paths_file, notaligned_file, m=2, effort=2, mode=MODE_GREEDY, partial=False, n_gpus=1, threads=1,
               batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False,
-              gaf=False):
+              gaf=False, abundance=False):
     """Aligner::alignAll (aligner.cpp:550-597) as one call -> (counters dict, mapping seconds).  route: 0 = FASTA goes through the device as
     text when it can (bgr_align_fasta_text), 1 = host parser + host formatter always.  split_output: one pipeline per device, device d
     writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes).  gaf: the paths file holds one GAF line per
-    mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction)."""
+    mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction).  abundance: count per unitig the reads, bases and k-mers mapped onto it
+    (bgr_run_options.abundance; greedy modes); Graph.abundance() then has the run's totals."""
     p = Params(mode, m, effort, int(partial))
     o = RunOptions(C.sizeof(RunOptions), n_gpus, threads, batch_reads, chunk_bytes, int(fastq), int(write_exhaustive), 0, int(correction),
-                   no_overlap_file.encode() if no_overlap_file else None, first_device, route, numa, int(split_output), int(gaf))
+                   no_overlap_file.encode() if no_overlap_file else None, first_device, route, numa, int(split_output), int(gaf), int(abundance))
     out = np.zeros(5, dtype=np.uint64)
     secs = C.c_double()
     _check(lib().bgr_align_all(graph.h, C.byref(p), C.byref(o), reads_csv.encode(), paths_file.encode(), notaligned_file.encode(),
                                out.ctypes.data, C.byref(secs)))
     return dict(zip(["reads", "no_overlap", "aligned", "not_aligned", "overlaps"], (int(x) for x in out))), secs.value
+
+
+def plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus=0, lds_per_cu=0, form=0):
+    """bgr_plan_abundance: the choice between the abundance kernel's forms from plain numbers (no device) -> dict as Aligner.abundance_plan."""
+    out = (C.c_uint32 * 4)()
+    _check(lib().bgr_plan_abundance(int(n_unitigs), int(k), int(n_reads), int(total_bases), int(num_cus), int(lds_per_cu), int(form), out))
+    return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+
+def write_abundance(path, graph, rows):
+    """bgr_write_abundance: `rows` (n_unitigs, 3) as text -- "#unitig length reads bases kmers", one tab-separated line per unitig."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[1] != 3:
+        raise ValueError("write_abundance: rows must be (n_unitigs, 3)")
+    _check(lib().bgr_write_abundance(path.encode(), graph.h, rows.ctypes.data, rows.shape[0]))
 
 
 def load_reads(path, k, fastq=False, threads=1, chunk_bytes=0):

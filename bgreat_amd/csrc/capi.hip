@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/bgreat_gpu.h"
+#include "abundance_kernels.h"
 #include "align_kernels.h"
 #include "fanout.h"
 #include "fastx.h"
@@ -25,6 +26,7 @@
 #include "graph_build.h"
 #include "launch_plan.h"
 #include "read_pack.h"
+#include "run_abundance.h"
 #include "text_kernels.h"
 #include "options.h"
 
@@ -55,7 +57,28 @@ struct bgr_graph {
     struct Dev { void* ptr; bool owned; };
     std::map<int, Dev> dev;
     uint32_t fanout_method = 0;  // how bgr_devices_init moved the blob between devices last time
+    // per-unitig totals of the last bgr_align_all with bgr_run_options.abundance (row i = unitig id i + 1); the run's aligners add theirs as they finish
+    std::vector<bgr_unitig_abundance> abundance;
+    bool abundance_valid = false;
+    std::mutex abundance_m;   // (the lanes of a split run end side by side)
 };
+
+namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
+void graph_abundance_begin(bgr_graph* g) {  // a new run: the totals of the one before are gone, whatever becomes of this one
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->abundance.assign(g->header.n_unitigs, bgr_unitig_abundance{0, 0, 0});
+    g->abundance_valid = false;
+}
+void graph_abundance_add(bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n) {  // one aligner's table
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    for (uint64_t i = 0; i < n && i < g->abundance.size(); ++i) { g->abundance[i].reads += rows[i].reads; g->abundance[i].bases += rows[i].bases; g->abundance[i].kmers += rows[i].kmers; }
+}
+void graph_abundance_end(bgr_graph* g, bool ok) {  // totals only of a run that ended well
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    if (!ok) g->abundance.clear();
+    g->abundance_valid = ok;
+}
+}  // namespace
 
 struct DevBuf {
     void* p = nullptr;
@@ -133,6 +156,9 @@ struct bgr_aligner {
     uint32_t knob_frame_cap = 0, knob_search = 0, knob_debug_stop = 0, knob_greedy_fast = 0, knob_exh_fast = 0, knob_anc_fast = 0, knob_memo_cap = 0, knob_prepass = 0, knob_no_events = 0;
     uint64_t knob_split_limit = 0;
     uint32_t knob_overlap = 0;      // BGR_KNOB_BATCH_OVERLAP
+    uint32_t knob_abundance_form = 0;  // BGR_KNOB_ABUNDANCE_FORM
+    bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel
+    DevBuf abundance;               // u64[n_unitigs + 1][3], allocated and zeroed on the first enable
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
     bool is_twin = false;
     int num_cus = 0;
@@ -519,7 +545,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -550,6 +576,7 @@ int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value) {
         case BGR_KNOB_ANCHORS_FAST: if (value > 1) break; a->knob_anc_fast = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_GREEDY_PREPASS: if (value > 1) break; a->knob_prepass = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_KERNEL_EVENTS: if (value > 1) break; a->knob_no_events = value ? 0u : 1u; return BGR_OK;
+        case BGR_KNOB_ABUNDANCE_FORM: if (value > 2) break; a->knob_abundance_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_abundance_form = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_EXH_MEMO_CAP: a->knob_memo_cap = (uint32_t)std::min<uint64_t>(value, 1u << 24); return BGR_OK;
         default: break;
     }
@@ -628,6 +655,11 @@ static DevBuf* list_buf(bgr_aligner* a, bgr::List l) {
 // buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
 // (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
 // d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
+// the geometry and form of the abundance kernel behind a launch of this size (bgr_aligner_abundance_plan reports what this returns)
+static bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases) {
+    return bgr::plan_abundance(a->graph->header.n_unitigs, a->dg.k, n_reads, total_bases, (uint32_t)a->num_cus, a->lds_per_cu, a->knob_abundance_form);
+}
+
 static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
                              uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
                              bool cursor_is_zero = false) {
@@ -637,6 +669,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: BGR_MODE_ANCHORS needs a graph built with BGR_BUILD_ANCHORS");
     if (p->mode != BGR_MODE_GREEDY && a->graph->header.wide_keys)
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
+    if (a->abundance_on && p->mode == BGR_MODE_EXHAUSTIVE)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     a->last_n = n_reads;
     a->last_mode = p->mode;
     a->deep.open = false;
@@ -781,6 +815,18 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
             a->deep.runs = 1;
         }
     }
+    // Unitig abundance (bgr_aligner_abundance_enable): one kernel behind the last pass adds this launch's rows to the aligner's table.  Every route
+    // comes through here once per batch (a fetch into larger buffers after BGR_E_CAPACITY launches nothing), so nothing is counted twice.
+    // (The kernel is queued before anybody knows how the launch ends: one that fails later -- an arena overflow, found when its cursors are read -- has
+    // added the rows it did write.  include/bgreat_gpu.h says so: after a failed launch the table is undefined until bgr_aligner_reset_abundance.)
+    if (a->abundance_on) {
+        const uint64_t nu = a->graph->header.n_unitigs;
+        const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
+        e = bgr::launch_abundance(a->dg, nu, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), P.arena_cap, io.read_offs, io.n_reads,
+                                  static_cast<unsigned long long*>(a->abundance.p), ap, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_abundance_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_abundance_kernel"));
+    }
     if (timed) {
         a->ev_marks[a->ev_used] = marks;
         ++a->ev_used;
@@ -847,6 +893,111 @@ static int settle_launch_sync(bgr_aligner* a) {
     HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return settle_launch(a, cur);
+}
+
+// ---- unitig abundance (bgr_run_options.abundance has the definition) ------------------------------------------------------------------
+static int abundance_set(bgr_aligner* a, bool on) {
+    if (on && !a->abundance.p) {
+        HIP_TRY(hipSetDevice(a->device));
+        HIP_TRY(a->abundance.ensure((a->graph->header.n_unitigs + 1) * sizeof(bgr_unitig_abundance)));
+        HIP_TRY(hipMemsetAsync(a->abundance.p, 0, a->abundance.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        HIP_TRY(bgr::prepare_abundance(a->lds_per_cu));   // (once per aligner, not per launch: form B's tables beyond 48 KB)
+    }
+    a->abundance_on = on;
+    return BGR_OK;
+}
+
+int bgr_aligner_abundance_enable(bgr_aligner* a, uint32_t on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_abundance_enable: null aligner");
+    for (bgr_aligner* x = a; x; x = x->twin) { const int rc = abundance_set(x, on != 0); if (rc != BGR_OK) return rc; }
+    return BGR_OK;
+}
+
+int bgr_aligner_abundance(bgr_aligner* a, bgr_unitig_abundance* out, uint64_t n_rows) {
+    static_assert(sizeof(bgr_unitig_abundance) == 24, "three u64 per unitig, as the kernel adds them");
+    if (!a || (n_rows && !out)) return fail(BGR_E_ARG, "bgr_aligner_abundance: null argument");
+    if (n_rows != a->graph->header.n_unitigs) return fail(BGR_E_ARG, "bgr_aligner_abundance: n_rows is not the graph's number of unitigs");
+    if (!a->abundance.p) return fail(BGR_E_ARG, "bgr_aligner_abundance: abundance was never enabled on this aligner (bgr_aligner_abundance_enable)");
+    if (n_rows == 0) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    HIP_TRY(hipMemcpy(out, static_cast<const bgr_unitig_abundance*>(a->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
+    std::vector<bgr_unitig_abundance> t;
+    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
+        if (!tw->abundance.p) continue;
+        t.resize(n_rows);
+        HIP_TRY(hipStreamSynchronize(tw->stream));
+        HIP_TRY(hipMemcpy(t.data(), static_cast<const bgr_unitig_abundance*>(tw->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n_rows; ++i) { out[i].reads += t[i].reads; out[i].bases += t[i].bases; out[i].kmers += t[i].kmers; }
+    }
+    return BGR_OK;
+}
+
+int bgr_aligner_abundance_plan(bgr_aligner* a, uint64_t n_reads, uint64_t total_bases, uint32_t out[4]) {
+    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_abundance_plan: null argument");
+    const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
+    out[0] = ap.form; out[1] = ap.blocks; out[2] = ap.threads; out[3] = ap.lds_bytes;
+    return BGR_OK;
+}
+
+int bgr_plan_abundance(uint64_t n_unitigs, uint32_t k, uint64_t n_reads, uint64_t total_bases, uint32_t num_cus, uint64_t lds_per_cu, uint32_t form_knob, uint32_t out[4]) {
+    if (!out || form_knob > 2) return fail(BGR_E_ARG, "bgr_plan_abundance: null argument or a form beyond 2");
+    const bgr::AbundancePlan ap = bgr::plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus, lds_per_cu, form_knob);
+    out[0] = ap.form; out[1] = ap.blocks; out[2] = ap.threads; out[3] = ap.lds_bytes;
+    return BGR_OK;
+}
+
+int bgr_aligner_reset_abundance(bgr_aligner* a) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_abundance: null aligner");
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) {
+        if (!x->abundance.p) continue;
+        HIP_TRY(hipMemsetAsync(x->abundance.p, 0, x->abundance.cap, x->stream));
+        HIP_TRY(hipStreamSynchronize(x->stream));
+    }
+    return BGR_OK;
+}
+
+// what a whole run calls (run_abundance.h)
+static int run_abundance_enable(bgr_aligner* a) { return bgr_aligner_abundance_enable(a, 1); }
+static int run_abundance_collect(bgr_graph* g, bgr_aligner* a) {
+    std::vector<bgr_unitig_abundance> rows(g->header.n_unitigs);
+    const int rc = bgr_aligner_abundance(a, rows.data(), rows.size());
+    if (rc == BGR_OK) graph_abundance_add(g, rows.data(), rows.size());
+    return rc;
+}
+static const bool g_run_abundance_registered = (bgr::g_run_abundance = bgr::RunAbundance{graph_abundance_begin, run_abundance_enable, run_abundance_collect, graph_abundance_end}, true);
+
+int bgr_graph_abundance(const bgr_graph* g, bgr_unitig_abundance* out, uint64_t n_rows) {
+    if (!g || (n_rows && !out)) return fail(BGR_E_ARG, "bgr_graph_abundance: null argument");
+    if (!g->abundance_valid) return fail(BGR_E_ARG, "bgr_graph_abundance: no totals -- they are those of the last successful bgr_align_all with bgr_run_options.abundance = 1");
+    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_graph_abundance: n_rows is not the graph's number of unitigs");
+    if (n_rows) memcpy(out, g->abundance.data(), n_rows * sizeof(bgr_unitig_abundance));
+    return BGR_OK;
+}
+
+int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows) {
+    if (!path || !g || (n_rows && !rows)) return fail(BGR_E_ARG, "bgr_write_abundance: null argument");
+    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_write_abundance: n_rows is not the graph's number of unitigs");
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_abundance: the graph has no host blob (the unitig lengths are read from it)");
+    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string("bgr_write_abundance: cannot open ") + path);
+    std::string buf = "#unitig\tlength\treads\tbases\tkmers\n";
+    bool ok = true;
+    for (uint64_t i = 0; i < n_rows && ok; ++i) {
+        buf += std::to_string(i + 1); buf += '\t';
+        buf += std::to_string(meta[i + 1].len); buf += '\t';
+        buf += std::to_string(rows[i].reads); buf += '\t';
+        buf += std::to_string(rows[i].bases); buf += '\t';
+        buf += std::to_string(rows[i].kmers); buf += '\n';
+        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
+    }
+    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_abundance: write to ") + path + " failed");
+    return BGR_OK;
 }
 
 int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
@@ -1332,6 +1483,8 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
         tw->cfg_waves = a->cfg_waves; tw->cfg_blocks_per_cu = a->cfg_blocks_per_cu; tw->cfg_lds_mphf = a->cfg_lds_mphf;
         tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
         tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
+        tw->knob_abundance_form = a->knob_abundance_form;
+        if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         al[t] = tw;
     }
     uint64_t cut[kOverlapMaxPieces + 1];

@@ -15,6 +15,8 @@
 //                                                   --gaf (the paths file holds one GAF line per mapped read -- name, query interval, strand, the path's
 //                                                          segments with their orientations, path interval, matches, NM:i -- instead of
 //                                                          header + path ints; greedy modes, ACGT-only unitigs, not with -c: include/bgreat_gpu.h)
+//                                                   --abundance FILE (per unitig: the reads, bases and k-mers mapped onto it, counted on the device while mapping; one
+//                                                                     tab-separated line per unitig; greedy modes; the other outputs stay as they are)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -36,14 +38,14 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
-                                {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008},
+                                {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -75,6 +77,7 @@ int main(int argc, char** argv) {
                 break;
             }
             case 1008: gaf = true; break;
+            case 1009: abundanceFile = optarg; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -117,6 +120,7 @@ int main(int argc, char** argv) {
     opt.route = host_route ? 1u : 0u;
     opt.split_output = split_out ? 1u : 0u;
     opt.gaf = gaf ? 1u : 0u;
+    opt.abundance = abundanceFile.empty() ? 0u : 1u;
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;
@@ -127,6 +131,12 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (arc != BGR_OK) die("mapping");
+    if (!abundanceFile.empty()) {  // (behind a run that ended well: a run that stops with "bug compaction" leaves no totals)
+        bgr_graph_info_t gi;
+        if (bgr_graph_info(graph, &gi) != BGR_OK) die("abundance");
+        std::vector<bgr_unitig_abundance> rows(gi.n_unitigs);
+        if (bgr_graph_abundance(graph, rows.data(), gi.n_unitigs) != BGR_OK || bgr_write_abundance(abundanceFile.c_str(), graph, rows.data(), gi.n_unitigs) != BGR_OK) die("abundance");
+    }
     const uint64_t rn = tot[0], no = tot[1], ali = tot[2], na = tot[3];
     std::cout << "The End" << std::endl;  // aligner.cpp:588-596
     std::cout << "Reads : " << rn << std::endl;

@@ -38,9 +38,11 @@
 #include "file_image.h"
 #include "read_pack.h"
 #include "options.h"
+#include "run_abundance.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip
+RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abundance.h: registered by capi.hip
 }
 
 namespace {
@@ -512,6 +514,9 @@ struct InputSpan {
 int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt, const std::vector<InputSpan>& inputs,
                    const char* paths_file, const char* notaligned_file, uint64_t counters_out[5], double* mapping_seconds, std::atomic<bool>* cancel) {
     const unsigned n_gpus = std::max<uint32_t>(1, opt->n_gpus);
+    // (option test.lanes_on_one_device, a test hook: every device of the run is the first one -- the N-device code path on a one-GPU box)
+    const bool one_device = bgr::opt("test.lanes_on_one_device") != 0;
+    auto device_of = [&](unsigned g) { return (int)(one_device ? opt->first_device : opt->first_device + g); };
     unsigned threads = std::max<uint32_t>(1, opt->threads);
     // The threads of this run (and the page-locked memory they allocate) on the NUMA node of the devices they feed: a copy engine
     // reading staging buffers across the socket link runs at about half its rate.  Only when all devices of the run share a node;
@@ -525,7 +530,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
         std::string first_list;
         for (unsigned g = 0; g < n_gpus && same; ++g) {
             char list[512];
-            if (bgr_device_local_cpus((int)(opt->first_device + g), list, sizeof(list)) != BGR_OK) { same = false; break; }
+            if (bgr_device_local_cpus(device_of(g), list, sizeof(list)) != BGR_OK) { same = false; break; }
             if (g == 0) first_list = list; else if (first_list != list) same = false;
         }
         if (same && !first_list.empty() && sched_getaffinity(0, sizeof(old_aff), &old_aff) == 0) {
@@ -604,7 +609,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     for (unsigned g = 0; g < n_gpus; ++g) {
         for (unsigned j = 0; j < per_dev; ++j) {
             bgr_aligner* a = nullptr;
-            int rc = bgr_aligner_create(graph, (int)(opt->first_device + g), &a);
+            int rc = bgr_aligner_create(graph, device_of(g), &a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);
                 fclose(pathF); fclose(notF);
@@ -612,7 +617,13 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             }
             // (nobody reads bgr_aligner_kernel_times here: no events around the kernels -- they cost a 262 144-read piece's mapping launch a tenth of its time)
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
+            if (opt->abundance) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
             aligners.push_back(a);
+            if (rc != BGR_OK) {
+                for (auto* x : aligners) bgr_aligner_destroy(x);
+                fclose(pathF); fclose(notF);
+                return rc;
+            }
         }
     }
 
@@ -1022,8 +1033,8 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
         if (b.pin->stages.size() < n_gpus) b.pin->stages.resize(n_gpus, nullptr);
         bgr_text_stage*& st = b.pin->stages[b.dev];
         // (a set cached by an earlier run of the process may carry the stage of another device in this place: the index is relative to the run)
-        if (st && bgr_text_stage_device(st) != (int)(opt->first_device + b.dev)) { bgr_text_stage_destroy(st); st = nullptr; }
-        if (!st && bgr_text_stage_create((int)(opt->first_device + b.dev), &st) != BGR_OK) { fail(BGR_E_HIP, bgr_last_error()); return false; }
+        if (st && bgr_text_stage_device(st) != device_of(b.dev)) { bgr_text_stage_destroy(st); st = nullptr; }
+        if (!st && bgr_text_stage_create(device_of(b.dev), &st) != BGR_OK) { fail(BGR_E_HIP, bgr_last_error()); return false; }
         if (b.fastq_piece && !b.fq_parts.empty()) {
             // FASTQ: the header and read lines of every part, gathered where the part's bytes would have gone (never more than they are);
             // the parts travel one after the other and lie back to back on the device
@@ -1400,6 +1411,10 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     for (auto* a : aligners) {
         uint64_t c5[5];
         if (!failed && bgr_aligner_counters(a, c5) == BGR_OK) for (int j = 0; j < 5; ++j) tot[j] += c5[j];
+        if (!failed && opt->abundance) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
+            const int arc = bgr::g_run_abundance.collect(graph, a);
+            if (arc != BGR_OK) fail(arc, bgr_last_error());
+        }
         bgr_aligner_destroy(a);
     }
     if (counters_out) memcpy(counters_out, tot, sizeof(tot));
@@ -1549,9 +1564,21 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
         if (gi.has_exceptions)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
     }
+    if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
+    if (opt->abundance) {   // unitig abundance: defined on the rows of the greedy modes; refused before any device work
+        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
+        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+        bgr::g_run_abundance.begin(graph);
+    }
+    int run_rc;
     if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)
-        return align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
-    std::vector<InputSpan> inputs(files.size());
-    for (size_t i = 0; i < files.size(); ++i) inputs[i].file = files[i];
-    return align_all_impl(graph, prm, opt, inputs, paths_file, notaligned_file, counters_out, mapping_seconds, nullptr);
+        run_rc = align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
+    else {
+        std::vector<InputSpan> inputs(files.size());
+        for (size_t i = 0; i < files.size(); ++i) inputs[i].file = files[i];
+        run_rc = align_all_impl(graph, prm, opt, inputs, paths_file, notaligned_file, counters_out, mapping_seconds, nullptr);
+    }
+    if (opt->abundance) bgr::g_run_abundance.end(graph, run_rc == BGR_OK);   // (the message of a failed run stays: this sets none)
+    return run_rc;
 }

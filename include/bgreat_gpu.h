@@ -292,6 +292,26 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n_reads, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status);
 
+/* Per-unitig abundance, counted on the device behind every mapping launch (the definition: bgr_run_options.abundance below).  Off unless enabled;
+ * while enabled every greedy / anchors launch of the aligner -- through bgr_align_device, bgr_align_batch and its split and overlapped forms, the
+ * packed form, begin / wait, the text form -- is followed on its stream by one kernel ("bgr_abundance_kernel" in bgr_aligner_kernel_times) that adds
+ * the launch's rows to a table in the aligner: exact 64-bit sums, whatever the batching.  An exhaustive launch on an enabled aligner is refused
+ * (BGR_E_ARG: its rows end in an end offset, alignerExhaustive.cpp:96-104, 249-257).  Fetching the same results again (after BGR_E_CAPACITY)
+ * counts nothing.  enable allocates and zeroes the table the first time; disabling keeps it.  bgr_aligner_abundance synchronises and delivers the
+ * table (n_rows must be the graph's n_unitigs; row i = unitig id i + 1), with what the other streams of overlapped batches counted added in.
+ * The kernel is queued with the launch: a launch that fails afterwards (BGR_E_INTERNAL, BGR_E_HIP) may have added part of its rows, and the table is
+ * undefined until bgr_aligner_reset_abundance.
+ * bgr_aligner_abundance_plan: the kernel a launch of n_reads reads and total_bases bases on this aligner is followed by, with its knob as it stands --
+ * out = {form (1 = A, 2 = B), workgroups, threads per workgroup, bytes of LDS per workgroup}.  bgr_plan_abundance is the same choice from plain
+ * numbers, without a device (num_cus / lds_per_cu 0 = the MI355X's); form B needs 12 x (n_unitigs + 1) bytes of LDS and k x total_bases < 2^32
+ * (no 32-bit counter of the launch can wrap then), and a launch that misses either takes form A whatever BGR_KNOB_ABUNDANCE_FORM says. */
+typedef struct { uint64_t reads, bases, kmers; } bgr_unitig_abundance;
+int bgr_aligner_abundance_enable(bgr_aligner* a, uint32_t on);
+int bgr_aligner_abundance(bgr_aligner* a, bgr_unitig_abundance* out, uint64_t n_rows);
+int bgr_aligner_reset_abundance(bgr_aligner* a);
+int bgr_aligner_abundance_plan(bgr_aligner* a, uint64_t n_reads, uint64_t total_bases, uint32_t out[4]);
+int bgr_plan_abundance(uint64_t n_unitigs, uint32_t k, uint64_t n_reads, uint64_t total_bases, uint32_t num_cus, uint64_t lds_per_cu, uint32_t form_knob, uint32_t out[4]);
+
 /* aligner.h:68 counters since creation/reset: out[0]=readNumber, [1]=noOverlapRead, [2]=alignedRead,
  * [3]=notAligned, [4]=overlaps (exhaustive only).  Synchronises the stream. */
 int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]);
@@ -339,6 +359,8 @@ int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blo
                                    16 times as large, until it fits (bgr_aligner_last_pass_runs); tests set 8 to walk that path with small inputs */
 #define BGR_KNOB_GREEDY_PREPASS 10u /* a launch handed ASCII reads, greedy / exhaustive mode: 0 = the mapping kernels stage their reads straight from the characters (default), 1 = a pre-pass writes 2-bit planes first (rounds 2-4; what anchors mode does) */
 #define BGR_KNOB_KERNEL_EVENTS 11u /* 1 = a HIP event in front of a mapping launch and behind each of its kernels (default: bgr_aligner_kernel_times reports them), 0 = none (a caller that never asks for the times: bgr_align_all without its timing option) */
+#define BGR_KNOB_ABUNDANCE_FORM 12u /* the abundance kernel (bgr_aligner_abundance_enable): 0 = choose per graph and batch, 1 = form A (64-bit atomics on the table in HBM), 2 = form B where its table fits and no counter can wrap
+                                      (32-bit counters in each workgroup's LDS, flushed once); same table either way */
 #define BGR_KNOB_GREEDY_FAST 5u /* greedy mode: 0 = sixteen-reads-per-wave pass + general kernel for the rest (default), 1 = general kernel only */
 int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value);
 /* The launch geometry by itself (bgreat_amd/csrc/launch_plan.h: a pure function of these numbers; no device, no graph object needed -- CPU tests sweep
@@ -439,12 +461,33 @@ typedef struct {
                                   unitig characters (has_exceptions: reversing a path does not reverse what it spells there), in exhaustive
                                   mode and together with `correction`.  A path that spells no walk ends the run as -c's does
                                   (BGR_E_COMPACTION).  split_output is ignored, as with -c.                                          */
+    uint32_t abundance;        /* --abundance: every aligner of the run counts, per unitig, the reads, bases and k-mers mapped onto it; the tables of all
+                                  aligners and devices are summed when the run ends and kept in the graph (bgr_graph_abundance) until the next such run.
+                                  Greedy modes, where a mapped read's row is [off, id_1 .. id_n] (the offset in the walk, then signed 1-based unitig ids).
+                                  With K1 = k - 1, len_j = the length of unitig |id_j| and L the read's length, the walk's extents are s_1 = 0,
+                                  e_j = s_j + len_j, s_(j+1) = e_j - K1, plen = e_n; cl = max(0, min(L, plen - off)) and the read covers the walk
+                                  positions [off, off + cl).  For every occurrence j, with o_j = max(0, min(off + cl, e_j) - max(off, s_j)):
+                                  reads[|id_j|] += 1 (every occurrence, whatever o_j: what counting the ids of the paths file gives),
+                                  bases[|id_j|] += o_j (the k-1 characters two neighbours share count for both), kmers[|id_j|] += max(0, o_j - K1).
+                                  Neither a unitig's orientation nor the read's strand enters; unmapped reads add nothing; integer adds commute, so
+                                  the totals do not depend on batches, routes, streams or devices.  Any graph greedy mode maps (k up to 64, exception
+                                  planes), together with fastq, correction, gaf, no_overlap_file, several devices, split_output, both routes; the
+                                  run's files and counters are what they are without it.  Refused with BGR_E_ARG in exhaustive mode (other rows).
+                                  A run that fails (BGR_E_COMPACTION too) leaves no totals.  (The field took the struct's four bytes of tail padding:
+                                  sizeof is unchanged.) */
 } bgr_run_options;
 /* bgr_align_all keeps its page-locked staging buffers for the next call of the process (they cost ~0.2 s per GB to allocate);
  * this frees them. */
 void bgr_host_cache_release(void);
 int bgr_align_all(bgr_graph* g, const bgr_params* p, const bgr_run_options* o, const char* reads_csv, const char* paths_file,
                   const char* notaligned_file, uint64_t counters_out[5], double* mapping_seconds);
+
+/* The totals of the last bgr_align_all with bgr_run_options.abundance = 1 on this graph (n_rows must be its n_unitigs; row i = unitig id i + 1);
+ * BGR_E_ARG if there are none.  bgr_write_abundance (host code, deterministic bytes) writes such a table as text: the line
+ * "#unitig<TAB>length<TAB>reads<TAB>bases<TAB>kmers", then one line per unitig 1 .. n in order, zero rows included, decimal, tab separated;
+ * the lengths come from the graph (one with a host blob). */
+int bgr_graph_abundance(const bgr_graph* g, bgr_unitig_abundance* out, uint64_t n_rows);
+int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows);
 
 /* The CPUs next to a device (the `local_cpulist` of its PCI function in sysfs, e.g. "0-63,128-191"): threads that feed a GPU and the
  * page-locked memory they allocate belong on its NUMA node.  BGR_E_IO when the platform does not say. */

@@ -43,6 +43,21 @@ __device__ __forceinline__ u64 lds_win32(const u64* A, uint32_t p) {
     const u64 hi = A[p >> 5], lo = A[(p >> 5) + 1];
     return (hi << s) | ((lo >> 1) >> (63 - s));
 }
+// The same window for a lane whose position p keeps p & 15 from call to call (the two-scanner anchor scan: a half's lane j holds a position
+// = j mod 16, and a step adds 32), so that nothing but the loads and three shifts is left per call.  In base order a stream is a row of
+// dwords, dword d = bases [16 d, 16 d + 16) = the HIGH half of word d / 2 for an even d, the low half for an odd one: dword index d ^ 1 in
+// memory.  The window starts at bit t = 2 (p & 15) of dword d = p >> 4 and ends inside dword d + 2.  The caller keeps the LDS byte address
+// `a` of dword d (d + 2 lies 8 bytes further up in memory whatever d's parity) and `b` of dword d + 1, adds 8 to both per 32 positions,
+// and passes sh = 32 - t (2 .. 32; only its low six bits are looked at).  Dwords d .. d + 2 lie in words p >> 5 and (p >> 5) + 1: nothing
+// is read that lds_win32(A, p) does not read -- also for the last group of the last wave (what lds_win32 needed readable behind it is all this needs).
+typedef const __attribute__((address_space(3))) uint32_t* lds_dword_ptr;
+__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
+__device__ __forceinline__ u64 lds_win32_fixed(uint32_t a, uint32_t b, uint32_t sh) {
+    typedef const volatile __attribute__((address_space(3))) uint32_t* vp;  // (volatile: four plain loads, each straight into its place)
+    const uint32_t e0 = *(vp)(uintptr_t)a, e1 = *(vp)(uintptr_t)b, e2 = *(vp)(uintptr_t)(a + 8), e1b = *(vp)(uintptr_t)b;
+    const uint32_t hi = (uint32_t)((((u64)e0 << 32) | e1) >> (sh & 63)), lo = (uint32_t)((((u64)e1b << 32) | e2) >> (sh & 63));
+    return ((u64)hi << 32) | lo;
+}
 // 32 BITS starting at bit q of a 1-bit-per-base plane, most significant first
 __device__ __forceinline__ uint32_t plane32(const u64* P, u64 q) {
     u64 w = q >> 6;

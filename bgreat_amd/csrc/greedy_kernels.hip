@@ -343,55 +343,89 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             // item once it has seen the hit the item needs (and the next one, for b_pos, when that lies in the same 32 positions) or has
             // passed npos; it then takes the next item in group order, so a step rarely spends lanes beyond the hit an item needs
             // (E. coli scale: 22.7 -> 19.1 steps per sixteen reads, tools/scan_halves.py).  A step still looks up 64 (k-1)-mers.
-            // Per half, all uniform: the item's group hq, the step's first position hb, the item's npos hn (0: the half is idle) and
-            // whether it takes a second anchor (h2).  `pend`: bit GL q = group q's item is still to be scanned.
-            u64 pend = __ballot(act != 0 && sub == 0);
+            // Per half, all uniform: the item's group hq, the step's first position hb and the item's npos hn (0: the half is idle).
+            // `pend`: bit GL q = group q's item is still to be scanned (an item with nothing left to scan never gets there: no anchor).
+            const uint32_t g_from = st & G4_ST_POS_MASK;  // where the group's item resumes: the first position it may report
+            uint32_t Ls = L;  // (an opaque copy: npos is worked out again behind the walks, and kept across them it would cost them a register)
+            asm volatile("" : "+v"(Ls));
+            uint32_t g_npos = Ls >= K1 ? Ls - K1 + 1 : 0;
+            if (!prm.effort && g_npos > 1) g_npos = 1;
+            u64 pend = __ballot(act != 0 && sub == 0 && g_from < g_npos);
 #ifdef BGR_PHASE_TIMING
             if (prm.debug_stop == 1) pend = 0;  // 1 = stops behind the staging of the reads
             dbg_items += (uint32_t)__popcll(pend);
             ++dbg_groups;
 #endif
-            // The lane's own copy of its half's state, set when the half takes an item and stepped by 32 (no per-step selects between the
-            // halves' uniforms): position li, npos ln (0: idle), the item's first word lw, need2 l2.
+            // The lane's own copy of its half's state, set when the half takes an item and stepped per 32 positions (no per-step selects
+            // between the halves' uniforms).  A half starts at a multiple of 16 -- the item's resume position rounded down -- so lane j
+            // always holds a position = j mod 16: the bit its window starts at inside a dword is the lane's constant, and the window is
+            // three dwords and three shifts (lds_win32_fixed).  The lane keeps
+            //   li = (its position - the resume position) << 6 | the window's shift, ln = (npos - the resume position) << 6 (0: idle):
+            //        li < ln, unsigned, says that the position is one of the item's AND not below where the item resumes (the lanes below
+            //        wrap around; they are off in the item's first step only, so an anchor that has failed is never seen again);
+            //   wa, wb = the LDS byte addresses of the dword its window starts in and of the next one; l2 = need2.
+            // What a half needs of an item is worked out for all sixteen groups at once, here, and fetched by readlane when the half takes
+            // the item: g_ln -> ln, g_wa = where the item's dword (resume position / 16) lies, were the dwords in base order, | need2.
             const bool hi = lane >= 32;
-            uint32_t li = 0, ln = 0, lw = 0, l2 = 0;
-            auto take = [&](bool h, uint32_t& hq, uint32_t& hb, uint32_t& hn, uint32_t& h2) {
+            const uint32_t g_ln = (g_npos - g_from) << 6;
+            // (the lane's two constants are worked out here, once per sixteen items, behind an empty asm that keeps the compiler from
+            // hoisting them out of the kernel's loop: they would cost the extension below two registers it does not have)
+            uint32_t sl = threadIdx.x;
+            asm volatile("" : "+v"(sl));
+            const uint32_t lc = ((sl & 31u) << 6) | (32u - 2u * (sl & 15u));
+            const uint32_t c4 = 4u * ((sl >> 4) & 1u);  // lanes 16-31 of a half start one dword further on
+            // (the address of the group's words, F, worked out again from the lane number: as lds_addr(F) it would be hoisted as well)
+            const uint32_t g_wa = (lds_addr(lds + 64 + ktab_words) + (sl / GL) * (W * 8u) + ((g_from >> 4) << 2))
+                                | (eff - ((st >> G4_ST_TRIED_SHIFT) & 0x7FFu) >= 2 ? 1u : 0u);  // (bit 0: anchors this strand may still try >= 2)
+            uint32_t li = 0, ln = 0, wa = 0, wb = 0, l2 = 0;
+            auto take = [&](bool h, uint32_t& hq, uint32_t& hb, uint32_t& hn) {
+                uint32_t s_li = 0, s_ln = 0, s_l2 = 0, s_wa = 0;
                 hn = 0;
-                while (pend) {
+                if (pend) {
                     const int at = __ffsll((long long)pend) - 1;
                     pend &= pend - 1;
-                    const uint32_t Lq = rl32(L, at), stq = rl32(st, at);
-                    uint32_t npos = Lq >= K1 ? Lq - K1 + 1 : 0;
-                    if (!prm.effort && npos > 1) npos = 1;
-                    if ((stq & G4_ST_POS_MASK) < npos) {  // (else nothing left to scan: no anchor)
-                        hq = (uint32_t)at / GL;
-                        hb = stq & G4_ST_POS_MASK;
-                        hn = npos;
-                        h2 = eff - ((stq >> G4_ST_TRIED_SHIFT) & 0x7FFu) >= 2 ? 1u : 0u;  // anchors this strand may still try >= 2
-                        break;
-                    }
+                    const uint32_t from = rl32(st, at) & G4_ST_POS_MASK;
+                    s_ln = rl32(g_ln, at);
+                    s_wa = rl32(g_wa, at);
+                    s_l2 = s_wa & 1u;
+                    s_wa &= ~1u;
+                    s_li = (from & 15u) << 6;
+                    hq = (uint32_t)at / GL;
+                    hb = from & ~15u;
+                    hn = from + (s_ln >> 6);
                 }
-                if (hi == h) { li = hb + ((uint32_t)lane & 31u); ln = hn; lw = hq * W; l2 = h2; }
+                if (hi == h) {
+                    li = lc - s_li;
+                    ln = s_ln;
+                    l2 = s_l2;
+                    // dword d of an item's words, in base order, is dword d ^ 1 in memory: the words start at a multiple of 8 bytes
+                    const uint32_t t = s_wa + c4;
+                    wa = t ^ 4u;
+                    wb = (t + 4u) ^ 4u;
+                }
             };
-            uint32_t q0 = 0, b0 = 0, n0 = 0, s0 = 0, q1 = 0, b1 = 0, n1 = 0, s1 = 0;
-            take(false, q0, b0, n0, s0);
-            take(true, q1, b1, n1, s1);
+            uint32_t q0 = 0, b0 = 0, n0 = 0, q1 = 0, b1 = 0, n1 = 0;
+            take(false, q0, b0, n0);
+            take(true, q1, b1, n1);
             while (n0 | n1) {
 #ifdef BGR_PHASE_TIMING
                 ++dbg_steps;
 #endif
                 const bool valid = li < ln;
                 u64 num = 0;
-                if (valid) num = lds_win32(RD + lw, li) >> (64 - 2 * K1);
+                if (valid) num = lds_win32_fixed(wa, wb, li) >> (64 - 2 * K1);
                 const u64 rcn = rcb_fast(num, K1);  // no N in the read: the rolling reverse k-mer is rcb of the forward one
                 uint32_t idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, l2 != 0, (uint32_t)lane);
                 const u64 mask = __ballot(idx != BGR_NONE);
-                li += 32;
+                li += 32u << 6;
+                wa += 8;
+                wb += 8;
                 if (mask) {
                     if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;
                     // each half's first hit (and second) goes to its item's group: a readlane of the hit lane, a select on grp
-                    auto settle = [&](uint32_t mh, int off, uint32_t hq, uint32_t hb, uint32_t& hn, uint32_t h2) {
+                    auto settle = [&](uint32_t mh, int off, uint32_t hq, uint32_t hb, uint32_t& hn) {
                         if (mh) {
+                            const uint32_t h2 = rl32(l2, off);  // the half's need2, from its first lane
                             const uint32_t f = (uint32_t)__builtin_ctz(mh), mh2 = mh & (mh - 1);
                             const uint32_t h = rl32(idx, off + (int)f);
                             // a second anchor is tried when the first fails: where a follow-up item resumes
@@ -400,15 +434,15 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                             hn = 0;
                         }
                     };
-                    if (n0) settle((uint32_t)mask, 0, q0, b0, n0, s0);
-                    if (n1) settle((uint32_t)(mask >> 32), 32, q1, b1, n1, s1);
+                    if (n0) settle((uint32_t)mask, 0, q0, b0, n0);
+                    if (n1) settle((uint32_t)(mask >> 32), 32, q1, b1, n1);
                 }
                 b0 += 32;
                 if (b0 >= n0) n0 = 0;
                 b1 += 32;
                 if (b1 >= n1) n1 = 0;
-                if (!n0) take(false, q0, b0, n0, s0);  // (both halves done: the low one takes first)
-                if (!n1) take(true, q1, b1, n1, s1);
+                if (!n0) take(false, q0, b0, n0);  // (both halves done: the low one takes first)
+                if (!n1) take(true, q1, b1, n1);
             }
         } else {
             // key table in L2 (minimizer filter: a window maximum across the whole wave): one item per step on all 64 lanes

@@ -36,10 +36,14 @@ SYMBOLS = [
     "bgr_align_batch_begin", "bgr_align_batch_test", "bgr_align_batch_wait", "bgr_text_stage_device", "bgr_text_stage_upload_parts",
     "bgr_device_alloc", "bgr_device_free", "bgr_device_upload", "bgr_device_download",
     "bgr_aligner_abundance_enable", "bgr_aligner_abundance", "bgr_aligner_reset_abundance", "bgr_aligner_abundance_plan", "bgr_plan_abundance", "bgr_graph_abundance", "bgr_write_abundance",
+    "bgr_aligner_links_enable", "bgr_aligner_links", "bgr_aligner_reset_links", "bgr_aligner_links_info", "bgr_aligner_links_plan", "bgr_plan_links", "bgr_graph_links_bound",
+    "bgr_graph_links_enable", "bgr_graph_links", "bgr_write_gfa", "bgr_link_canonical", "bgr_graph_links_enabled",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
 ABUNDANCE_AUTO, ABUNDANCE_GLOBAL, ABUNDANCE_LDS = 0, 1, 2
+KNOB_LINKS_FORM = 13
+LINKS_AUTO, LINKS_GLOBAL, LINKS_LDS = 0, 1, 2
 SEARCH_AUTO, SEARCH_DEPTH_FIRST, SEARCH_BY_LEVEL = 0, 1, 2
 
 
@@ -83,6 +87,13 @@ class RunOptions(C.Structure):
 
 class UnitigAbundance(C.Structure):  # bgr_unitig_abundance
     _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64)]
+
+
+class Link(C.Structure):  # bgr_link
+    _fields_ = [("from_", C.c_int32), ("to", C.c_int32), ("count", C.c_uint64)]
+
+
+LINK_DTYPE = np.dtype([("from", np.int32), ("to", np.int32), ("count", np.uint64)])   # an array of bgr_link
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -237,6 +248,18 @@ def lib():
     L.bgr_plan_abundance.argtypes = [u64, u32, u64, u64, u32, u64, u32, vp]
     L.bgr_graph_abundance.argtypes = [vp, vp, u64]
     L.bgr_write_abundance.argtypes = [C.c_char_p, vp, vp, u64]
+    L.bgr_aligner_links_enable.argtypes = [vp, u32]
+    L.bgr_aligner_links.argtypes = [vp, vp, u64, vp]
+    L.bgr_aligner_reset_links.argtypes = [vp]
+    L.bgr_aligner_links_info.argtypes = [vp, vp]
+    L.bgr_aligner_links_plan.argtypes = [vp, u64, vp]
+    L.bgr_plan_links.argtypes = [u64, u64, u32, u32, vp]
+    L.bgr_graph_links_bound.argtypes = [vp, vp]
+    L.bgr_graph_links_enable.argtypes = [vp, u32]
+    L.bgr_graph_links.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_gfa.argtypes = [C.c_char_p, vp, vp, u64, vp, u64]
+    L.bgr_graph_links_enabled.argtypes = [vp]
+    L.bgr_link_canonical.argtypes = [C.c_int32, C.c_int32, vp, vp]
     _lib = L
     return L
 
@@ -452,6 +475,25 @@ class Graph:
         _check(lib().bgr_graph_abundance(self.h, out.ctypes.data, n))
         return out
 
+    def links_enable(self, on=True):
+        """bgr_graph_links_enable: sticky -- every later align_all on this graph counts unitig abundance and links."""
+        _check(lib().bgr_graph_links_enable(self.h, int(bool(on))))
+
+    def links_enabled(self):
+        """bgr_graph_links_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_links_enabled(self.h))
+
+    def links(self):
+        """bgr_graph_links: the links of the last align_all with the switch on -> array of LINK_DTYPE (from, to, count), canonical, sorted by key.
+        Raises BgrError when there are none."""
+        return _fetch_links(lib().bgr_graph_links, self.h)
+
+    def links_bound(self):
+        """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
+        b = C.c_uint64(0)
+        _check(lib().bgr_graph_links_bound(self.h, C.byref(b)))
+        return int(b.value)
+
     def close(self):
         if self.h:
             lib().bgr_graph_destroy(self.h)
@@ -621,6 +663,29 @@ class Aligner:
     def reset_abundance(self):
         _check(lib().bgr_aligner_reset_abundance(self.h))
 
+    def links_enable(self, on=True):
+        """bgr_aligner_links_enable: every greedy / anchors launch from now on adds the consecutive pairs of its rows to the aligner's table of links."""
+        _check(lib().bgr_aligner_links_enable(self.h, int(bool(on))))
+
+    def links(self):
+        """bgr_aligner_links -> array of LINK_DTYPE (from, to, count) since enable / reset: canonical links, sorted by key."""
+        return _fetch_links(lib().bgr_aligner_links, self.h)
+
+    def links_info(self):
+        """bgr_aligner_links_info -> dict(capacity, bound, overflow, lds_fell_through)."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().bgr_aligner_links_info(self.h, out))
+        return dict(zip(("capacity", "bound", "overflow", "lds_fell_through"), (int(x) for x in out)))
+
+    def links_plan(self, n_reads):
+        """bgr_aligner_links_plan: the links kernel behind a launch of this size -> dict(form (1 = A, 2 = B), blocks, threads, lds_bytes)."""
+        out = (C.c_uint32 * 4)()
+        _check(lib().bgr_aligner_links_plan(self.h, int(n_reads), out))
+        return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+    def reset_links(self):
+        _check(lib().bgr_aligner_reset_links(self.h))
+
     def sync(self):
         _check(lib().bgr_aligner_sync(self.h))
 
@@ -680,12 +745,21 @@ class Aligner:
 
 def align_all(graph, reads_csv, paths_file, notaligned_file, m=2, effort=2, mode=MODE_GREEDY, partial=False, n_gpus=1, threads=1,
               batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False,
-              gaf=False, abundance=False):
+              gaf=False, abundance=False, links=None):
     """Aligner::alignAll (aligner.cpp:550-597) as one call -> (counters dict, mapping seconds).  route: 0 = FASTA goes through the device as
     text when it can (bgr_align_fasta_text), 1 = host parser + host formatter always.  split_output: one pipeline per device, device d
     writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes).  gaf: the paths file holds one GAF line per
     mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction).  abundance: count per unitig the reads, bases and k-mers mapped onto it
-    (bgr_run_options.abundance; greedy modes); Graph.abundance() then has the run's totals."""
+    (bgr_run_options.abundance; greedy modes); Graph.abundance() then has the run's totals.  links: True / False sets the graph's switch (Graph.links_enable) for this call and puts it back
+    afterwards -- the run counts unitig abundance and links, Graph.abundance() and Graph.links() then have its totals; None leaves the switch as it is."""
+    if links is not None:
+        before = graph.links_enabled()
+        graph.links_enable(links)
+        try:
+            return align_all(graph, reads_csv, paths_file, notaligned_file, m, effort, mode, partial, n_gpus, threads, batch_reads, chunk_bytes, fastq, write_exhaustive,
+                             correction, no_overlap_file, first_device, route, numa, split_output, gaf, abundance)
+        finally:
+            graph.links_enable(before)
     p = Params(mode, m, effort, int(partial))
     o = RunOptions(C.sizeof(RunOptions), n_gpus, threads, batch_reads, chunk_bytes, int(fastq), int(write_exhaustive), 0, int(correction),
                    no_overlap_file.encode() if no_overlap_file else None, first_device, route, numa, int(split_output), int(gaf), int(abundance))
@@ -701,6 +775,47 @@ def plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus=0, lds_per_cu=0, 
     out = (C.c_uint32 * 4)()
     _check(lib().bgr_plan_abundance(int(n_unitigs), int(k), int(n_reads), int(total_bases), int(num_cus), int(lds_per_cu), int(form), out))
     return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+
+def _fetch_links(fn, handle):
+    """the two-call form of bgr_aligner_links / bgr_graph_links: the number first (BGR_E_CAPACITY), then the links"""
+    n = C.c_uint64(0)
+    rc = fn(handle, None, 0, C.byref(n))
+    if rc != -4:   # (BGR_E_CAPACITY with n set: there are links)
+        _check(rc)
+        return np.zeros(0, dtype=LINK_DTYPE)
+    if n.value == 0:   # (the table overflowed: the message says so)
+        _check(rc)
+    out = np.zeros(n.value, dtype=LINK_DTYPE)
+    assert LINK_DTYPE.itemsize == C.sizeof(Link) == 16
+    _check(fn(handle, out.ctypes.data, n.value, C.byref(n)))
+    return out[: n.value]
+
+
+def link_canonical(a, b):
+    """bgr_link_canonical: the canonical form of the link (a, b) and its 64-bit table key, by the code the kernel runs -> ((from, to), key)."""
+    out, key = Link(), C.c_uint64(0)
+    _check(lib().bgr_link_canonical(int(a), int(b), C.byref(out), C.byref(key)))
+    return (int(out.from_), int(out.to)), int(key.value)
+
+
+def plan_links(links_bound, n_reads, num_cus=0, form=0):
+    """bgr_plan_links: the choice between the links kernel's forms from plain numbers (no device) -> dict as Aligner.links_plan."""
+    out = (C.c_uint32 * 4)()
+    _check(lib().bgr_plan_links(int(links_bound), int(n_reads), int(num_cus), int(form), out))
+    return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+
+def write_gfa(path, graph, abundance_rows, links):
+    """bgr_write_gfa: GFA 1.0 -- an S line per unitig with RC / KC from `abundance_rows` (n_unitigs, 3), an L line per link of `links` (an array
+    of LINK_DTYPE, or (from, to, count) triples), which must be sorted by key as Graph.links() delivers them."""
+    rows = np.ascontiguousarray(abundance_rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[1] != 3:
+        raise ValueError("write_gfa: abundance_rows must be (n_unitigs, 3)")
+    if not (isinstance(links, np.ndarray) and links.dtype == LINK_DTYPE):
+        links = np.array([(int(a), int(b), int(c)) for a, b, c in links], dtype=LINK_DTYPE)
+    links = np.ascontiguousarray(links)
+    _check(lib().bgr_write_gfa(path.encode(), graph.h, rows.ctypes.data, rows.shape[0], links.ctypes.data, links.shape[0]))
 
 
 def write_abundance(path, graph, rows):

@@ -25,8 +25,10 @@
 #include "anchor_index.h"
 #include "graph_build.h"
 #include "launch_plan.h"
+#include "links_kernels.h"
 #include "read_pack.h"
 #include "run_abundance.h"
+#include "run_links.h"
 #include "text_kernels.h"
 #include "options.h"
 
@@ -61,6 +63,11 @@ struct bgr_graph {
     std::vector<bgr_unitig_abundance> abundance;
     bool abundance_valid = false;
     std::mutex abundance_m;   // (the lanes of a split run end side by side)
+    // links (bgr_graph_links_enable): the sticky switch, the bound of distinct links (computed from the host blob the first time it is asked for),
+    // and the totals of the last bgr_align_all with the switch on: {key, count} as the aligners delivered them until the run ends, then merged and sorted
+    bool links_on = false, links_valid = false, links_bound_known = false;
+    uint64_t links_bound = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> links;
 };
 
 namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
@@ -159,6 +166,11 @@ struct bgr_aligner {
     uint32_t knob_abundance_form = 0;  // BGR_KNOB_ABUNDANCE_FORM
     bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel
     DevBuf abundance;               // u64[n_unitigs + 1][3], allocated and zeroed on the first enable
+    uint32_t knob_links_form = 0;   // BGR_KNOB_LINKS_FORM
+    bool links_on = false;          // bgr_aligner_links_enable: every greedy / anchors launch is followed by the links kernel
+    DevBuf links;                   // {u64 key, u64 count}[links_cap] + the tail words (links_kernels.h), allocated and zeroed on the first enable
+    unsigned long long* links_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
+    uint64_t links_cap = 0, links_bound = 0;
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
     bool is_twin = false;
     int num_cus = 0;
@@ -545,7 +557,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -577,6 +589,7 @@ int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value) {
         case BGR_KNOB_GREEDY_PREPASS: if (value > 1) break; a->knob_prepass = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_KERNEL_EVENTS: if (value > 1) break; a->knob_no_events = value ? 0u : 1u; return BGR_OK;
         case BGR_KNOB_ABUNDANCE_FORM: if (value > 2) break; a->knob_abundance_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_abundance_form = (uint32_t)value; return BGR_OK;
+        case BGR_KNOB_LINKS_FORM: if (value > 2) break; a->knob_links_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_links_form = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_EXH_MEMO_CAP: a->knob_memo_cap = (uint32_t)std::min<uint64_t>(value, 1u << 24); return BGR_OK;
         default: break;
     }
@@ -671,6 +684,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
     if (a->abundance_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->links_on && p->mode == BGR_MODE_EXHAUSTIVE)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts links (bgr_aligner_links_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     a->last_n = n_reads;
     a->last_mode = p->mode;
     a->deep.open = false;
@@ -826,6 +841,14 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
                                   static_cast<unsigned long long*>(a->abundance.p), ap, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_abundance_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_abundance_kernel"));
+    }
+    // Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
+    if (a->links_on) {
+        const bgr::LinksPlan lp = bgr::plan_links(a->links_bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
+        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), P.arena_cap, io.n_reads, a->links_tab,
+                              a->links_cap, lp, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_links_kernel"));
     }
     if (timed) {
         a->ev_marks[a->ev_used] = marks;
@@ -997,6 +1020,227 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
     if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
     if (fclose(f) != 0) ok = false;
     if (!ok) return fail(BGR_E_IO, std::string("bgr_write_abundance: write to ") + path + " failed");
+    return BGR_OK;
+}
+
+
+// ---- links (bgr_link in include/bgreat_gpu.h has the definition) ---------------------------------------------------------------------------
+static int graph_links_bound(bgr_graph* g, uint64_t* bound) {
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_links_bound: the graph has no host blob (the bound is counted over its slots)");
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    if (!g->links_bound_known) { g->links_bound = bgr::links_bound_of_blob(g->host.header(), g->host.base()); g->links_bound_known = true; }
+    *bound = g->links_bound;
+    return BGR_OK;
+}
+int bgr_graph_links_bound(bgr_graph* g, uint64_t* bound) {
+    if (!g || !bound) return fail(BGR_E_ARG, "bgr_graph_links_bound: null argument");
+    return graph_links_bound(g, bound);
+}
+
+int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key) {
+    if (!out || a == 0 || b == 0 || a == INT32_MIN || b == INT32_MIN || std::abs((int64_t)a) >= 0x40000000 || std::abs((int64_t)b) >= 0x40000000)
+        return fail(BGR_E_ARG, "bgr_link_canonical: null argument or an id that is 0 or beyond 2^30");
+    const uint64_t c = bgr::links_canonical(a, b);   // (the function the kernel calls)
+    *out = bgr_link{bgr::links_key_from(c), bgr::links_key_to(c), 0};
+    if (key) *key = c;
+    return BGR_OK;
+}
+
+static void links_share(bgr_aligner* a) {   // the twins add to the aligner's table
+    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) { tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on; }
+}
+
+int bgr_aligner_links_enable(bgr_aligner* a, uint32_t on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_links_enable: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_links_enable: an internal stream of another aligner");
+    if (on && !a->links_tab) {
+        uint64_t bound = 0;
+        const int rc = graph_links_bound(a->graph, &bound);
+        if (rc != BGR_OK) return rc;
+        uint64_t cap = bgr::links_capacity(bound);
+        if (const int64_t c = bgr::opt("test.links_capacity")) { cap = 2; while (cap < (uint64_t)c) cap <<= 1; }
+        HIP_TRY(hipSetDevice(a->device));
+        const hipError_t e = a->links.ensure(bgr::links_table_bytes(cap));
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_links_enable: " + std::to_string(bgr::links_table_bytes(cap)) + " bytes for the table of links: " + hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(a->links.p, 0, a->links.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        a->links_tab = static_cast<unsigned long long*>(a->links.p);
+        a->links_cap = cap;
+        a->links_bound = bound;
+    }
+    a->links_on = on != 0;
+    links_share(a);
+    return BGR_OK;
+}
+
+// the words behind the aligner's table (links_kernels.h), every stream that adds to it waited for; BGR_E_CAPACITY when the overflow word is set
+static int links_tail(bgr_aligner* a, const char* who, uint64_t tail[bgr::kLinksTailWords]) {
+    if (!a->links_tab) return fail(BGR_E_ARG, std::string(who) + ": links were never enabled on this aligner (bgr_aligner_links_enable)");
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemcpy(tail, a->links_tab + 2 * a->links_cap, bgr::kLinksTailWords * 8, hipMemcpyDeviceToHost));
+    if (tail[0])
+        return fail(BGR_E_CAPACITY, std::string(who) + ": the table of links (" + std::to_string(a->links_cap) + " slots) was full: " + std::to_string(tail[0]) +
+                                        " traversals found no place; the counts are incomplete until bgr_aligner_reset_links");
+    return BGR_OK;
+}
+// ... and the table as it stands: the used slots as {key, count}, sorted by key.  Only if there are at most `room` of them (the kernel counts the
+// slots it claims): a caller that asks for the number first does not pay for the table's way to the host twice
+static int links_snapshot(bgr_aligner* a, const char* who, uint64_t room, std::vector<std::pair<uint64_t, uint64_t>>& kv, uint64_t tail[bgr::kLinksTailWords]) {
+    const int rc = links_tail(a, who, tail);
+    if (rc != BGR_OK) return rc;
+    kv.clear();
+    if (tail[2] > room || tail[2] == 0) return BGR_OK;
+    std::vector<uint64_t> t(2 * a->links_cap);
+    HIP_TRY(hipMemcpy(t.data(), a->links_tab, t.size() * 8, hipMemcpyDeviceToHost));
+    for (uint64_t s = 0; s < a->links_cap; ++s)
+        if (t[2 * s]) kv.emplace_back(t[2 * s], t[2 * s + 1]);
+    std::sort(kv.begin(), kv.end());
+    return BGR_OK;
+}
+static void links_deliver(const std::vector<std::pair<uint64_t, uint64_t>>& kv, bgr_link* out) {
+    for (size_t i = 0; i < kv.size(); ++i) out[i] = bgr_link{bgr::links_key_from(kv[i].first), bgr::links_key_to(kv[i].first), kv[i].second};
+}
+
+int bgr_aligner_links(bgr_aligner* a, bgr_link* out, uint64_t cap, uint64_t* n) {
+    static_assert(sizeof(bgr_link) == 16, "two ids and a 64-bit count");
+    if (n) *n = 0;
+    if (!a || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_links: null argument");
+    std::vector<std::pair<uint64_t, uint64_t>> kv;
+    uint64_t tail[bgr::kLinksTailWords];
+    const int rc = links_snapshot(a, "bgr_aligner_links", cap, kv, tail);
+    if (rc != BGR_OK) return rc;
+    *n = tail[2];
+    if (tail[2] > cap) return fail(BGR_E_CAPACITY, "bgr_aligner_links: " + std::to_string(tail[2]) + " links, room for " + std::to_string(cap));
+    if (kv.size() != tail[2]) return fail(BGR_E_INTERNAL, "bgr_aligner_links: the table's used slots and their counter disagree");
+    links_deliver(kv, out);
+    return BGR_OK;
+}
+
+int bgr_aligner_links_info(bgr_aligner* a, uint64_t out[4]) {
+    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_links_info: null argument");
+    uint64_t tail[bgr::kLinksTailWords] = {0, 0, 0};
+    const int rc = links_tail(a, "bgr_aligner_links_info", tail);
+    if (rc != BGR_OK && rc != BGR_E_CAPACITY) return rc;   // (an overflow is what this call reports)
+    out[0] = a->links_cap; out[1] = a->links_bound; out[2] = tail[0]; out[3] = tail[1];
+    return BGR_OK;
+}
+
+int bgr_aligner_links_plan(bgr_aligner* a, uint64_t n_reads, uint32_t out[4]) {
+    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_links_plan: null argument");
+    uint64_t bound = a->links_bound;
+    if (!a->links_tab) { const int rc = graph_links_bound(a->graph, &bound); if (rc != BGR_OK) return rc; }
+    const bgr::LinksPlan lp = bgr::plan_links(bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
+    out[0] = lp.form; out[1] = lp.blocks; out[2] = lp.threads; out[3] = lp.lds_bytes;
+    return BGR_OK;
+}
+
+int bgr_plan_links(uint64_t links_bound, uint64_t n_reads, uint32_t num_cus, uint32_t form_knob, uint32_t out[4]) {
+    if (!out || form_knob > 2) return fail(BGR_E_ARG, "bgr_plan_links: null argument or a form beyond 2");
+    const bgr::LinksPlan lp = bgr::plan_links(links_bound, n_reads, num_cus, form_knob);
+    out[0] = lp.form; out[1] = lp.blocks; out[2] = lp.threads; out[3] = lp.lds_bytes;
+    return BGR_OK;
+}
+
+int bgr_aligner_reset_links(bgr_aligner* a) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_links: null aligner");
+    if (!a->links.p) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));   // (the twins add to the same table)
+    HIP_TRY(hipMemsetAsync(a->links.p, 0, a->links.cap, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    return BGR_OK;
+}
+
+// what a whole run calls (run_links.h)
+static bool run_links_wanted(const bgr_graph* g) { return g && g->links_on; }
+static void run_links_begin(bgr_graph* g) {
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->links.clear();
+    g->links_valid = false;
+}
+static int run_links_enable(bgr_aligner* a) { return bgr_aligner_links_enable(a, 1); }
+static int run_links_collect(bgr_graph* g, bgr_aligner* a) {
+    std::vector<std::pair<uint64_t, uint64_t>> kv;
+    uint64_t tail[bgr::kLinksTailWords];
+    const int rc = links_snapshot(a, "bgr_align_all", ~0ull, kv, tail);
+    if (rc != BGR_OK) return rc;
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->links.insert(g->links.end(), kv.begin(), kv.end());
+    return BGR_OK;
+}
+static void run_links_end(bgr_graph* g, bool ok) {   // the aligners' tables, one behind the other: sorted, equal keys summed
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    if (!ok) g->links.clear();
+    else {
+        std::sort(g->links.begin(), g->links.end());
+        size_t w = 0;
+        for (size_t i = 0; i < g->links.size(); ++i) {
+            if (w && g->links[w - 1].first == g->links[i].first) g->links[w - 1].second += g->links[i].second;
+            else g->links[w++] = g->links[i];
+        }
+        g->links.resize(w);
+    }
+    g->links_valid = ok;
+}
+static const bool g_run_links_registered = (bgr::g_run_links = bgr::RunLinks{run_links_wanted, run_links_begin, run_links_enable, run_links_collect, run_links_end}, true);
+
+int bgr_graph_links_enable(bgr_graph* g, uint32_t on) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_links_enable: null graph");
+    if (on && g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_links_enable: the graph has no host blob (the table of links is sized from it)");
+    g->links_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_links_enabled(const bgr_graph* g) { return g && g->links_on ? 1 : 0; }
+
+int bgr_graph_links(const bgr_graph* g, bgr_link* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_links: null argument");
+    if (!g->links_valid) return fail(BGR_E_ARG, "bgr_graph_links: no totals -- they are those of the last successful bgr_align_all with bgr_graph_links_enable on");
+    *n = g->links.size();
+    if (g->links.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_links: " + std::to_string(g->links.size()) + " links, room for " + std::to_string(cap));
+    links_deliver(g->links, out);
+    return BGR_OK;
+}
+
+int bgr_write_gfa(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows, const bgr_link* links, uint64_t n_links) {
+    if (!path || !g || (n_rows && !rows) || (n_links && !links)) return fail(BGR_E_ARG, "bgr_write_gfa: null argument");
+    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_write_gfa: n_rows is not the graph's number of unitigs");
+    if (g->ascii_offs.empty() && n_rows) return fail(BGR_E_ARG, "bgr_write_gfa: this graph was created from a blob and carries no unitig characters");
+    for (uint64_t i = 0; i < n_links; ++i) {
+        const bgr_link& l = links[i];
+        if (l.from == 0 || l.to == 0 || l.from == INT32_MIN || l.to == INT32_MIN || (uint64_t)std::abs((int64_t)l.from) > n_rows || (uint64_t)std::abs((int64_t)l.to) > n_rows)
+            return fail(BGR_E_ARG, "bgr_write_gfa: a link names a unitig the graph does not have");
+        if (i && bgr::links_pack(links[i - 1].from, links[i - 1].to) >= bgr::links_pack(l.from, l.to)) return fail(BGR_E_ARG, "bgr_write_gfa: the links are not sorted by key");
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string("bgr_write_gfa: cannot open ") + path);
+    std::string buf = "H\tVN:Z:1.0\n";
+    bool ok = true;
+    auto drain = [&](bool all) { if (ok && (all ? !buf.empty() : buf.size() > (1u << 20))) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); } };
+    for (uint64_t i = 0; i < n_rows && ok; ++i) {
+        const uint64_t b = g->ascii_offs[i], e = g->ascii_offs[i + 1];
+        buf += "S\t"; buf += std::to_string(i + 1); buf += '\t';
+        buf.append(g->ascii.data() + b, e - b);
+        buf += "\tLN:i:"; buf += std::to_string(e - b);
+        buf += "\tRC:i:"; buf += std::to_string(rows[i].reads);
+        buf += "\tKC:i:"; buf += std::to_string(rows[i].kmers); buf += '\n';
+        drain(false);
+    }
+    const std::string overlap = std::to_string(g->header.k - 1) + "M";
+    for (uint64_t i = 0; i < n_links && ok; ++i) {
+        const bgr_link& l = links[i];
+        if (!l.count) continue;
+        buf += "L\t"; buf += std::to_string(std::abs((int64_t)l.from)); buf += l.from < 0 ? "\t-\t" : "\t+\t";
+        buf += std::to_string(std::abs((int64_t)l.to)); buf += l.to < 0 ? "\t-\t" : "\t+\t";
+        buf += overlap; buf += "\tRC:i:"; buf += std::to_string(l.count); buf += '\n';
+        drain(false);
+    }
+    drain(true);
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_gfa: write to ") + path + " failed");
     return BGR_OK;
 }
 
@@ -1484,6 +1728,8 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
         tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
         tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
         tw->knob_abundance_form = a->knob_abundance_form;
+        tw->knob_links_form = a->knob_links_form;
+        tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on;   // (one table for the aligner and its twins: the atomics are device-scope)
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         al[t] = tw;
     }

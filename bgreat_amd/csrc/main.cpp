@@ -17,6 +17,9 @@
 //                                                          header + path ints; greedy modes, ACGT-only unitigs, not with -c: include/bgreat_gpu.h)
 //                                                   --abundance FILE (per unitig: the reads, bases and k-mers mapped onto it, counted on the device while mapping; one
 //                                                                     tab-separated line per unitig; greedy modes; the other outputs stay as they are)
+//                                                   --gfa FILE (the graph the run's reads support, as GFA 1.0: every unitig as an S line under the 1-based ordinal the paths
+//                                                               file and --gaf use, with its read and k-mer counts, and every link that a mapped read's path crosses
+//                                                               as an L line with its count, counted on the device while mapping; greedy modes: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -38,14 +41,14 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
-                                {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009},
+                                {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009}, {"gfa", required_argument, nullptr, 1010},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -78,6 +81,7 @@ int main(int argc, char** argv) {
             }
             case 1008: gaf = true; break;
             case 1009: abundanceFile = optarg; break;
+            case 1010: gfaFile = optarg; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -121,6 +125,7 @@ int main(int argc, char** argv) {
     opt.split_output = split_out ? 1u : 0u;
     opt.gaf = gaf ? 1u : 0u;
     opt.abundance = abundanceFile.empty() ? 0u : 1u;
+    if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;
@@ -136,6 +141,17 @@ int main(int argc, char** argv) {
         if (bgr_graph_info(graph, &gi) != BGR_OK) die("abundance");
         std::vector<bgr_unitig_abundance> rows(gi.n_unitigs);
         if (bgr_graph_abundance(graph, rows.data(), gi.n_unitigs) != BGR_OK || bgr_write_abundance(abundanceFile.c_str(), graph, rows.data(), gi.n_unitigs) != BGR_OK) die("abundance");
+    }
+    if (!gfaFile.empty()) {  // (likewise)
+        bgr_graph_info_t gi;
+        if (bgr_graph_info(graph, &gi) != BGR_OK) die("gfa");
+        std::vector<bgr_unitig_abundance> rows(gi.n_unitigs);
+        uint64_t n_links = 0;
+        if (bgr_graph_abundance(graph, rows.data(), gi.n_unitigs) != BGR_OK) die("gfa");
+        if (bgr_graph_links(graph, nullptr, 0, &n_links) != BGR_OK && n_links == 0) die("gfa");   // (BGR_E_CAPACITY with the number of links)
+        std::vector<bgr_link> links(n_links);
+        if (n_links && bgr_graph_links(graph, links.data(), n_links, &n_links) != BGR_OK) die("gfa");
+        if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), n_links) != BGR_OK) die("gfa");
     }
     const uint64_t rn = tot[0], no = tot[1], ali = tot[2], na = tot[3];
     std::cout << "The End" << std::endl;  // aligner.cpp:588-596

@@ -39,10 +39,14 @@
 #include "read_pack.h"
 #include "options.h"
 #include "run_abundance.h"
+#include "run_links.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip
 RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abundance.h: registered by capi.hip
+RunLinks g_run_links = {nullptr, nullptr, nullptr, nullptr, nullptr};    // run_links.h: likewise
+// the graph's switch (bgr_graph_links_enable): the run counts links, and unitig abundance with them, whatever bgr_run_options.abundance says
+static bool run_links(const bgr_graph* g) { return g_run_links.wanted && g_run_links.wanted(g); }
 }
 
 namespace {
@@ -617,7 +621,8 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             }
             // (nobody reads bgr_aligner_kernel_times here: no events around the kernels -- they cost a 262 144-read piece's mapping launch a tenth of its time)
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
-            if (opt->abundance) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
+            if (opt->abundance || bgr::run_links(graph)) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
+            if (rc == BGR_OK && bgr::run_links(graph)) rc = bgr::g_run_links.enable(a);   // ... and by the links kernel
             aligners.push_back(a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);
@@ -1411,7 +1416,11 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     for (auto* a : aligners) {
         uint64_t c5[5];
         if (!failed && bgr_aligner_counters(a, c5) == BGR_OK) for (int j = 0; j < 5; ++j) tot[j] += c5[j];
-        if (!failed && opt->abundance) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
+        if (!failed && bgr::run_links(graph)) {  // likewise its table of links
+            const int lrc = bgr::g_run_links.collect(graph, a);
+            if (lrc != BGR_OK) fail(lrc, bgr_last_error());
+        }
+        if (!failed && (opt->abundance || bgr::run_links(graph))) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
             const int arc = bgr::g_run_abundance.collect(graph, a);
             if (arc != BGR_OK) fail(arc, bgr_last_error());
         }
@@ -1565,12 +1574,19 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
     }
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
+    const bool links = bgr::run_links(graph), abundance = opt->abundance || links;
+    if (links) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
+        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
+        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+    }
     if (opt->abundance) {   // unitig abundance: defined on the rows of the greedy modes; refused before any device work
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
         if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
-        bgr::g_run_abundance.begin(graph);
     }
+    if (abundance) bgr::g_run_abundance.begin(graph);
+    if (links) bgr::g_run_links.begin(graph);
     int run_rc;
     if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)
         run_rc = align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
@@ -1579,6 +1595,7 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
         for (size_t i = 0; i < files.size(); ++i) inputs[i].file = files[i];
         run_rc = align_all_impl(graph, prm, opt, inputs, paths_file, notaligned_file, counters_out, mapping_seconds, nullptr);
     }
-    if (opt->abundance) bgr::g_run_abundance.end(graph, run_rc == BGR_OK);   // (the message of a failed run stays: this sets none)
+    if (abundance) bgr::g_run_abundance.end(graph, run_rc == BGR_OK);   // (the message of a failed run stays: this sets none)
+    if (links) bgr::g_run_links.end(graph, run_rc == BGR_OK);
     return run_rc;
 }

@@ -312,6 +312,42 @@ int bgr_aligner_reset_abundance(bgr_aligner* a);
 int bgr_aligner_abundance_plan(bgr_aligner* a, uint64_t n_reads, uint64_t total_bases, uint32_t out[4]);
 int bgr_plan_abundance(uint64_t n_unitigs, uint32_t k, uint64_t n_reads, uint64_t total_bases, uint32_t num_cus, uint64_t lds_per_cu, uint32_t form_knob, uint32_t out[4]);
 
+/* Links: which unitigs the mapped reads join, and how often.  A mapped read's row in the greedy modes is [off, id_1 .. id_n] with signed 1-based ids;
+ * every consecutive pair (a, b) = (id_j, id_j+1), j = 1 .. n-1, is one traversal of a link.  (a, b) and (-b, -a) are the same link -- the same
+ * junction read from the other strand: with key(x, y) = the tuple (|x|, x < 0, |y|, y < 0), the canonical form is whichever of (a, b) and (-b, -a)
+ * has the smaller key, compared lexicographically ((a, -a) is its own mate), and count[canonical link] += 1 per traversal.  Neither the read's strand
+ * (BGR_ST_RC) nor off enters; unmapped reads and one-unitig paths add nothing; ids that are 0 or beyond n_unitigs are skipped, as the abundance kernel
+ * skips them.  The counts are exact 64-bit integers and do not depend on batching, routes, streams or devices.
+ * Counted on the device as unitig abundance is: off unless enabled; while enabled every greedy / anchors launch of the aligner, through every entry
+ * point, is followed on its stream by one kernel ("bgr_links_kernel" in bgr_aligner_kernel_times while a slot is free) that adds the launch's pairs to
+ * an open-addressed hash table {u64 key, u64 count} in device memory.  The table is sized when counting is first enabled, from the graph (one with a
+ * host blob): bgr_graph_links_bound counts, over the unitig ends and the slots of the half record each end's walk reads, how many distinct links any
+ * rows on this graph can hold (bgreat_amd/csrc/links_kernels.h has the argument), and the capacity is the power of two that is at least twice that,
+ * 16 bytes per slot -- so the table cannot fill.  Should an insert find no place all the same, it is counted in an overflow word, and
+ * bgr_aligner_links / the run return BGR_E_CAPACITY with a message until bgr_aligner_reset_links.  The internal streams of overlapped batches add to
+ * the same table.  An exhaustive launch on an enabled aligner is refused (BGR_E_ARG) and adds nothing; launches of an aligner that is not counting
+ * add nothing; disabling keeps the table; a launch that fails afterwards may have added part of its rows.
+ * bgr_aligner_links synchronises and delivers the canonical links with a count, sorted by key; *n = their number, BGR_E_CAPACITY (with *n set) when
+ * cap is smaller -- the kernel counts the slots it claims, so the call that only asks for the number (cap 0) moves three words, not the table.
+ * A delivery copies the whole table to the host (16 bytes per slot: 512 MiB on a chr1-scale graph) and picks and sorts the used slots on the calling
+ * thread: a call per run or per batch of launches, not per launch.
+ * bgr_aligner_links_info (diagnostic: tests and tools/links_rate.py read it): out = {slots of the table, the graph's bound, traversals that found no place, workgroups of form B whose
+ * LDS table handed at least one traversal straight to the table in device memory}.
+ * bgr_aligner_links_plan: the kernel behind a launch of n_reads reads on this aligner, with its knob as it stands -- out = {form (1 = A, 2 = B),
+ * workgroups, threads per workgroup, bytes of LDS per workgroup}; bgr_plan_links is the same choice from plain numbers, without a device
+ * (num_cus 0 = the MI355X's): form B by default exactly where links_bound is at most half of its LDS table's 2048 slots. */
+typedef struct { int32_t from, to; uint64_t count; } bgr_link;
+int bgr_aligner_links_enable(bgr_aligner* a, uint32_t on);
+int bgr_aligner_links(bgr_aligner* a, bgr_link* out, uint64_t cap, uint64_t* n);
+int bgr_aligner_reset_links(bgr_aligner* a);
+int bgr_aligner_links_info(bgr_aligner* a, uint64_t out[4]);
+int bgr_aligner_links_plan(bgr_aligner* a, uint64_t n_reads, uint32_t out[4]);
+int bgr_plan_links(uint64_t links_bound, uint64_t n_reads, uint32_t num_cus, uint32_t form_knob, uint32_t out[4]);
+int bgr_graph_links_bound(bgr_graph* g, uint64_t* bound);
+/* Diagnostic (the host tests pin the kernel's canonicalisation through it): the canonical form of the link (a, b) as the kernel computes it (the same inline code, compiled for the host): out = {from, to, 0}, and, if key is
+ * not NULL, the 64-bit integer the tables hold for it -- (|from| << 33) | (from < 0) << 32 | (|to| << 1) | (to < 0), whose order is the order of the keys. */
+int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key);
+
 /* aligner.h:68 counters since creation/reset: out[0]=readNumber, [1]=noOverlapRead, [2]=alignedRead,
  * [3]=notAligned, [4]=overlaps (exhaustive only).  Synchronises the stream. */
 int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]);
@@ -361,6 +397,8 @@ int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blo
 #define BGR_KNOB_KERNEL_EVENTS 11u /* 1 = a HIP event in front of a mapping launch and behind each of its kernels (default: bgr_aligner_kernel_times reports them), 0 = none (a caller that never asks for the times: bgr_align_all without its timing option) */
 #define BGR_KNOB_ABUNDANCE_FORM 12u /* the abundance kernel (bgr_aligner_abundance_enable): 0 = choose per graph and batch, 1 = form A (64-bit atomics on the table in HBM), 2 = form B where its table fits and no counter can wrap
                                       (32-bit counters in each workgroup's LDS, flushed once); same table either way */
+#define BGR_KNOB_LINKS_FORM 13u /* the links kernel (bgr_aligner_links_enable): 0 = choose per graph, 1 = form A (every traversal is an insert into the table in device memory), 2 = form B (a table of 2048 links per
+                                  workgroup in LDS, flushed once; what finds no place in it goes the way of form A); same counts either way */
 #define BGR_KNOB_GREEDY_FAST 5u /* greedy mode: 0 = sixteen-reads-per-wave pass + general kernel for the rest (default), 1 = general kernel only */
 int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value);
 /* The launch geometry by itself (bgreat_amd/csrc/launch_plan.h: a pure function of these numbers; no device, no graph object needed -- CPU tests sweep
@@ -488,6 +526,24 @@ int bgr_align_all(bgr_graph* g, const bgr_params* p, const bgr_run_options* o, c
  * the lengths come from the graph (one with a host blob). */
 int bgr_graph_abundance(const bgr_graph* g, bgr_unitig_abundance* out, uint64_t n_rows);
 int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows);
+
+/* The read-supported graph of a whole run.  bgr_run_options has no room left (its size is part of the ABI), so the switch is the graph's:
+ * bgr_graph_links_enable(g, 1) is sticky, and every later bgr_align_all on the graph counts unitig abundance (as with bgr_run_options.abundance) and
+ * links (bgr_link above) in every aligner of the run; the tables of all aligners and devices are summed when the run ends and kept in the graph:
+ * bgr_graph_abundance has the unitigs' totals, bgr_graph_links the links (canonical, sorted by key, counts > 0; *n = their number, BGR_E_CAPACITY
+ * with *n set when cap is smaller; BGR_E_ARG if there are none).  With the switch on, exhaustive mode is refused before any device work (BGR_E_ARG;
+ * the message names -b and --gfa); a run that fails (BGR_E_COMPACTION too) leaves no totals; a run with the switch off leaves the last totals alone.
+ * The run's files, counters and stdout are what they are without it.
+ * bgr_write_gfa (host code, deterministic bytes) writes GFA 1.0: the line "H<TAB>VN:Z:1.0"; for every unitig i = 1 .. n in order
+ * "S<TAB>i<TAB>sequence<TAB>LN:i:length<TAB>RC:i:reads<TAB>KC:i:kmers" (zero rows included; the sequence as bgr_graph_unitigs holds it, non-ACGT
+ * characters kept; reads and kmers from abundance_rows); for every link with count > 0, in the order given -- which must be ascending by key, as
+ * bgr_graph_links delivers -- "L<TAB>|from|<TAB>+ or -<TAB>|to|<TAB>+ or -<TAB>(k-1)M<TAB>RC:i:count".  Every line ends with a newline.  The ids are the
+ * 1-based ordinals of the paths file and of --gaf: every GAF line of the same run walks L lines of this file.  BGR_E_ARG on a wrong n_rows, a link
+ * beyond the graph or out of order, or a graph without unitig characters; BGR_E_IO on a path it cannot write. */
+int bgr_graph_links_enable(bgr_graph* g, uint32_t on);
+int bgr_graph_links_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_links(const bgr_graph* g, bgr_link* out, uint64_t cap, uint64_t* n);
+int bgr_write_gfa(const char* path, const bgr_graph* g, const bgr_unitig_abundance* abundance_rows, uint64_t n_rows, const bgr_link* links, uint64_t n_links);
 
 /* The CPUs next to a device (the `local_cpulist` of its PCI function in sysfs, e.g. "0-63,128-191"): threads that feed a GPU and the
  * page-locked memory they allocate belong on its NUMA node.  BGR_E_IO when the platform does not say. */

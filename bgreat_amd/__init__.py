@@ -38,6 +38,8 @@ SYMBOLS = [
     "bgr_aligner_abundance_enable", "bgr_aligner_abundance", "bgr_aligner_reset_abundance", "bgr_aligner_abundance_plan", "bgr_plan_abundance", "bgr_graph_abundance", "bgr_write_abundance",
     "bgr_aligner_links_enable", "bgr_aligner_links", "bgr_aligner_reset_links", "bgr_aligner_links_info", "bgr_aligner_links_plan", "bgr_plan_links", "bgr_graph_links_bound",
     "bgr_graph_links_enable", "bgr_graph_links", "bgr_write_gfa", "bgr_link_canonical", "bgr_graph_links_enabled",
+    "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
+    "bgr_write_pileup", "bgr_write_depth",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
@@ -259,6 +261,14 @@ def lib():
     L.bgr_graph_links.argtypes = [vp, vp, u64, vp]
     L.bgr_write_gfa.argtypes = [C.c_char_p, vp, vp, u64, vp, u64]
     L.bgr_graph_links_enabled.argtypes = [vp]
+    L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
+    L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
+    L.bgr_aligner_reset_pileup.argtypes = [vp]
+    L.bgr_graph_pileup_enable.argtypes = [vp, u32]
+    L.bgr_graph_pileup_enabled.argtypes = [vp]
+    L.bgr_graph_pileup.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_pileup.argtypes = [C.c_char_p, vp]
+    L.bgr_write_depth.argtypes = [C.c_char_p, vp]
     L.bgr_link_canonical.argtypes = [C.c_int32, C.c_int32, vp, vp]
     _lib = L
     return L
@@ -488,6 +498,27 @@ class Graph:
         Raises BgrError when there are none."""
         return _fetch_links(lib().bgr_graph_links, self.h)
 
+    def pileup_enable(self, on=True):
+        """bgr_graph_pileup_enable: sticky -- every later align_all on this graph counts unitig abundance and the per-base pileup."""
+        _check(lib().bgr_graph_pileup_enable(self.h, int(bool(on))))
+
+    def pileup_enabled(self):
+        """bgr_graph_pileup_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_pileup_enabled(self.h))
+
+    def pileup(self):
+        """bgr_graph_pileup: the totals of the last align_all with the switch on -> (array of PILEUP_DTYPE (depth, a, c, g, t, n), one row per
+        base, flat in unitig order; rows that spelled no walk).  Raises BgrError when there are none."""
+        return _fetch_pileup(lib().bgr_graph_pileup, self)
+
+    def write_pileup(self, path):
+        """bgr_write_pileup: one line per position with a count."""
+        _check(lib().bgr_write_pileup(path.encode(), self.h))
+
+    def write_depth(self, path):
+        """bgr_write_depth: one bedGraph-like line per run of equal non-zero depth."""
+        _check(lib().bgr_write_depth(path.encode(), self.h))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -686,6 +717,19 @@ class Aligner:
     def reset_links(self):
         _check(lib().bgr_aligner_reset_links(self.h))
 
+    def pileup_enable(self, on=True):
+        """bgr_aligner_pileup_enable: every greedy / anchors launch from now on adds per-base depth and mismatches to the aligner's table
+        (and its rows to the abundance table, which guards the depths)."""
+        _check(lib().bgr_aligner_pileup_enable(self.h, int(bool(on))))
+
+    def pileup(self):
+        """bgr_aligner_pileup -> (array of PILEUP_DTYPE (depth, a, c, g, t, n) since enable / reset, one row per base, flat in unitig order;
+        rows that spelled no walk)."""
+        return _fetch_pileup(lib().bgr_aligner_pileup, self)
+
+    def reset_pileup(self):
+        _check(lib().bgr_aligner_reset_pileup(self.h))
+
     def sync(self):
         _check(lib().bgr_aligner_sync(self.h))
 
@@ -745,13 +789,22 @@ class Aligner:
 
 def align_all(graph, reads_csv, paths_file, notaligned_file, m=2, effort=2, mode=MODE_GREEDY, partial=False, n_gpus=1, threads=1,
               batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False,
-              gaf=False, abundance=False, links=None):
+              gaf=False, abundance=False, links=None, pileup=None):
     """Aligner::alignAll (aligner.cpp:550-597) as one call -> (counters dict, mapping seconds).  route: 0 = FASTA goes through the device as
     text when it can (bgr_align_fasta_text), 1 = host parser + host formatter always.  split_output: one pipeline per device, device d
     writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes).  gaf: the paths file holds one GAF line per
     mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction).  abundance: count per unitig the reads, bases and k-mers mapped onto it
     (bgr_run_options.abundance; greedy modes); Graph.abundance() then has the run's totals.  links: True / False sets the graph's switch (Graph.links_enable) for this call and puts it back
-    afterwards -- the run counts unitig abundance and links, Graph.abundance() and Graph.links() then have its totals; None leaves the switch as it is."""
+    afterwards -- the run counts unitig abundance and links, Graph.abundance() and Graph.links() then have its totals; None leaves the switch as it is.
+    pileup: likewise the graph's pileup switch (Graph.pileup_enable); Graph.pileup() then has the run's per-base totals."""
+    if pileup is not None:
+        before = graph.pileup_enabled()
+        graph.pileup_enable(pileup)
+        try:
+            return align_all(graph, reads_csv, paths_file, notaligned_file, m, effort, mode, partial, n_gpus, threads, batch_reads, chunk_bytes, fastq, write_exhaustive,
+                             correction, no_overlap_file, first_device, route, numa, split_output, gaf, abundance, links)
+        finally:
+            graph.pileup_enable(before)
     if links is not None:
         before = graph.links_enabled()
         graph.links_enable(links)
@@ -775,6 +828,18 @@ def plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus=0, lds_per_cu=0, 
     out = (C.c_uint32 * 4)()
     _check(lib().bgr_plan_abundance(int(n_unitigs), int(k), int(n_reads), int(total_bases), int(num_cus), int(lds_per_cu), int(form), out))
     return dict(zip(("form", "blocks", "threads", "lds_bytes"), (int(x) for x in out)))
+
+
+PILEUP_DTYPE = np.dtype([("depth", np.uint32), ("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("n", np.uint32)])
+
+
+def _fetch_pileup(fn, obj):
+    g = obj if isinstance(obj, Graph) else obj.graph
+    n = g.info()["total_bases"] // 2
+    out = np.zeros(n, dtype=PILEUP_DTYPE)
+    skipped = C.c_uint64(0)
+    _check(fn(obj.h, out.ctypes.data, n, C.byref(skipped)))
+    return out, int(skipped.value)
 
 
 def _fetch_links(fn, handle):

@@ -26,9 +26,11 @@
 #include "graph_build.h"
 #include "launch_plan.h"
 #include "links_kernels.h"
+#include "pileup_kernels.h"
 #include "read_pack.h"
 #include "run_abundance.h"
 #include "run_links.h"
+#include "run_pileup.h"
 #include "text_kernels.h"
 #include "options.h"
 
@@ -68,6 +70,12 @@ struct bgr_graph {
     bool links_on = false, links_valid = false, links_bound_known = false;
     uint64_t links_bound = 0;
     std::vector<std::pair<uint64_t, uint64_t>> links;
+    // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
+    // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
+    bool pileup_on = false, pileup_valid = false;
+    std::vector<uint64_t> base_offs;          // [n_unitigs + 2]: base_offs[id] = sum of len of the unitigs 1 .. id - 1
+    std::vector<uint32_t> pileup_words;       // alt[4 T] then delta[T + n] (pileup_kernels.h)
+    uint64_t pileup_skipped = 0;
 };
 
 namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
@@ -171,6 +179,10 @@ struct bgr_aligner {
     DevBuf links;                   // {u64 key, u64 count}[links_cap] + the tail words (links_kernels.h), allocated and zeroed on the first enable
     unsigned long long* links_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
     uint64_t links_cap = 0, links_bound = 0;
+    bool pileup_on = false;         // bgr_aligner_pileup_enable: every greedy / anchors launch is followed by the pileup kernel
+    DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
+    uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
+    const uint64_t* pileup_base_offs = nullptr;
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
     bool is_twin = false;
     int num_cus = 0;
@@ -557,7 +569,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -686,6 +698,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->links_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts links (bgr_aligner_links_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     a->last_n = n_reads;
     a->last_mode = p->mode;
     a->deep.open = false;
@@ -849,6 +863,17 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
                               a->links_cap, lp, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_links_kernel"));
+    }
+    // Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches.  It reads the read characters where this launch
+    // has them: the ASCII bytes when the mapping kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
+    if (a->pileup_on) {
+        bgr::PileupReads pr;
+        if (inline_pack) { pr.ascii = static_cast<const uint8_t*>(d_reads); pr.src_off = static_cast<const uint32_t*>(d_src_off); pr.ascii_bytes = reads_bytes; }
+        else { pr.fw3 = io.fw3; pr.nmw = io.nmw; pr.hasn = io.hasn; }
+        e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
+                               P.arena_cap, io.read_offs, io.n_reads, pr, a->pileup_base_offs, a->pileup_tab, (uint32_t)a->num_cus, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_pileup_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_pileup_kernel"));
     }
     if (timed) {
         a->ev_marks[a->ev_used] = marks;
@@ -1022,6 +1047,238 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
     if (!ok) return fail(BGR_E_IO, std::string("bgr_write_abundance: write to ") + path + " failed");
     return BGR_OK;
 }
+
+
+// ---- pileup (bgr_pileup_base in include/bgreat_gpu.h has the definition) -------------------------------------------------------------------
+static int graph_base_offs(bgr_graph* g, const char* who) {   // prefix sums of the unitig lengths, once per graph
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, std::string(who) + ": the graph has no host blob (the unitig lengths and characters are read from it)");
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    if (g->base_offs.empty()) {
+        const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+        std::vector<uint64_t> o(g->header.n_unitigs + 2, 0);
+        for (uint64_t i = 1; i <= g->header.n_unitigs; ++i) o[i + 1] = o[i] + meta[i].len;
+        g->base_offs.swap(o);
+    }
+    return BGR_OK;
+}
+static int pileup_refusal(const bgr_graph* g, const char* who) {
+    if (g->header.has_exc)
+        return fail(BGR_E_ARG, std::string(who) + ": the pileup (--pileup, --depth) needs a graph of ACGT-only unitigs: on one with other characters the 2-bit store does not spell them and a path read backwards does not spell the reverse complement");
+    return BGR_OK;
+}
+static void pileup_share(bgr_aligner* a) {   // the twins add to the aligner's table
+    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) { tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on; }
+}
+
+int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_pileup_enable: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_enable: an internal stream of another aligner");
+    if (on) {
+        int rc = pileup_refusal(a->graph, "bgr_aligner_pileup_enable");
+        if (rc == BGR_OK) rc = graph_base_offs(a->graph, "bgr_aligner_pileup_enable");
+        if (rc == BGR_OK) rc = bgr_aligner_abundance_enable(a, 1);   // (its reads column bounds every depth: bgr_aligner_pileup checks it)
+        if (rc != BGR_OK) return rc;
+    }
+    if (on && !a->pileup_tab) {
+        const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2, bytes = bgr::pileup_table_bytes(T, n);
+        HIP_TRY(hipSetDevice(a->device));
+        hipError_t e = a->pileup.ensure(bytes);
+        if (e == hipSuccess) e = a->pileup_offs.ensure((n + 2) * 8);
+        if (e != hipSuccess) {
+            a->pileup.release(); a->pileup_offs.release();
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_pileup_enable: " + std::to_string(bytes) + " bytes for the pileup table (20 per base of the graph): " + hipGetErrorString(e));
+        }
+        HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bytes, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
+        HIP_TRY(hipMemcpyAsync(a->pileup_offs.p, a->graph->base_offs.data(), (n + 2) * 8, hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        a->pileup_tab = static_cast<uint32_t*>(a->pileup.p);
+        a->pileup_base_offs = static_cast<const uint64_t*>(a->pileup_offs.p);
+    }
+    a->pileup_on = on != 0;
+    pileup_share(a);
+    return BGR_OK;
+}
+
+// alt / delta words -> rows: the depth is the running sum of a unitig's delta words, N lies in the alt word of the unitig's own base
+static void pileup_unitig_rows(const bgr_graph* g, const uint32_t* words, uint64_t id, bgr_pileup_base* out) {   // the len rows of one unitig
+    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
+    const uint32_t* alt = words;
+    const uint32_t* delta = words + bgr::pileup_alt_words(g->header.total_bases / 2);
+    const uint64_t b0 = g->base_offs[id], d0 = b0 + id - 1, F = meta[id].F;
+    uint32_t depth = 0;
+    for (uint64_t pos = 0; pos < meta[id].len; ++pos) {
+        depth += delta[d0 + pos];   // (mod 2^32)
+        const uint64_t p = F + pos;
+        const uint32_t ref = (uint32_t)(seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u;
+        const uint32_t* w = alt + 4 * (b0 + pos);
+        uint32_t c[4] = {w[0], w[1], w[2], w[3]};
+        c[ref] = 0;   // (nothing that differs from the base has the base's code: that word counted the Ns)
+        out[pos] = bgr_pileup_base{depth, c[0], c[1], c[2], c[3], w[ref]};
+    }
+}
+static void pileup_rows(const bgr_graph* g, const uint32_t* words, bgr_pileup_base* out) {
+    for (uint64_t id = 1; id <= g->header.n_unitigs; ++id) pileup_unitig_rows(g, words, id, out + g->base_offs[id]);
+}
+// this aligner's reads column may not have reached 2^32 anywhere: it bounds every depth on the unitig, and a depth is kept mod 2^32
+static int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (rows[i].reads >> 32)
+            return fail(BGR_E_CAPACITY, std::string(who) + ": unitig " + std::to_string(i + 1) + " lies on " + std::to_string(rows[i].reads) + " reads' paths: a per-base depth (32 bits) may have wrapped; no pileup is delivered");
+    return BGR_OK;
+}
+// the aligner's table on the host (every stream that adds to it waited for), behind the guard
+static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t>& words, uint64_t* skipped) {
+    if (!a->pileup_tab) return fail(BGR_E_ARG, std::string(who) + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
+    const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2;
+    std::vector<bgr_unitig_abundance> ab(n);
+    int rc = bgr_aligner_abundance(a, ab.data(), n);   // (synchronises the aligner's stream and its twins')
+    if (rc == BGR_OK) rc = pileup_guard(ab.data(), n, who);
+    if (rc != BGR_OK) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    words.resize(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n));
+    if (!words.empty()) HIP_TRY(hipMemcpy(words.data(), a->pileup_tab, words.size() * 4, hipMemcpyDeviceToHost));
+    unsigned long long sk = 0;
+    HIP_TRY(hipMemcpy(&sk, reinterpret_cast<const char*>(a->pileup_tab) + bgr::pileup_tail_byte(T, n), 8, hipMemcpyDeviceToHost));
+    *skipped = sk;
+    return BGR_OK;
+}
+
+int bgr_aligner_pileup(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) {
+    static_assert(sizeof(bgr_pileup_base) == 24, "six u32 per base");
+    if (!a || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup: null argument");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup: an internal stream of another aligner");
+    if (n_bases != a->graph->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_aligner_pileup: n_bases is not the sum of the graph's unitig lengths");
+    std::vector<uint32_t> words;
+    uint64_t sk = 0;
+    const int rc = pileup_snapshot(a, "bgr_aligner_pileup", words, &sk);
+    if (rc != BGR_OK) return rc;
+    pileup_rows(a->graph, words.data(), out);
+    if (skipped) *skipped = sk;
+    return BGR_OK;
+}
+
+int bgr_aligner_reset_pileup(bgr_aligner* a) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: an internal stream of another aligner");
+    if (!a->pileup.p) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    return BGR_OK;   // (the abundance table stays: the guard's column then counts more launches than the pileup holds, which errs on the safe side)
+}
+
+// what a whole run calls (run_pileup.h)
+static bool run_pileup_wanted(const bgr_graph* g) { return g && g->pileup_on; }
+static void run_pileup_begin(bgr_graph* g) {
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->pileup_words.clear();
+    g->pileup_skipped = 0;
+    g->pileup_valid = false;
+}
+static int run_pileup_enable(bgr_aligner* a) { return bgr_aligner_pileup_enable(a, 1); }
+static int run_pileup_collect(bgr_graph* g, bgr_aligner* a) {
+    std::vector<uint32_t> words;
+    uint64_t sk = 0;
+    const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk);
+    if (rc != BGR_OK) return rc;
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    if (g->pileup_words.empty()) g->pileup_words.swap(words);
+    else for (size_t i = 0; i < words.size(); ++i) g->pileup_words[i] += words[i];   // (mod 2^32: the delta sums commute)
+    g->pileup_skipped += sk;
+    return BGR_OK;
+}
+static int run_pileup_end(bgr_graph* g, bool ok) {   // behind the abundance's end: the summed reads column guards the summed table
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    int rc = BGR_OK;
+    if (ok) {
+        const uint64_t T = g->header.total_bases / 2, n = g->header.n_unitigs;
+        if (g->pileup_words.empty()) g->pileup_words.assign(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n), 0u);   // (a run without aligners' tables: nothing mapped)
+        rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: a pileup without the abundance totals that guard it");
+    }
+    if (!ok || rc != BGR_OK) { g->pileup_words.clear(); g->pileup_words.shrink_to_fit(); }
+    g->pileup_valid = ok && rc == BGR_OK;
+    return rc;
+}
+static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end}, true);
+
+int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_enable: null graph");
+    if (on) {
+        int rc = pileup_refusal(g, "bgr_graph_pileup_enable");
+        if (rc == BGR_OK) rc = graph_base_offs(g, "bgr_graph_pileup_enable");
+        if (rc != BGR_OK) return rc;
+    }
+    g->pileup_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_pileup_enabled(const bgr_graph* g) { return g && g->pileup_on ? 1 : 0; }
+
+static int graph_pileup_check(const bgr_graph* g, const char* who) {
+    if (!g->pileup_valid) return fail(BGR_E_ARG, std::string(who) + ": no totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_enable on");
+    return BGR_OK;
+}
+
+int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) {
+    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup: null argument");
+    const int rc = graph_pileup_check(g, "bgr_graph_pileup");
+    if (rc != BGR_OK) return rc;
+    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup: n_bases is not the sum of the graph's unitig lengths");
+    pileup_rows(g, g->pileup_words.data(), out);
+    if (skipped) *skipped = g->pileup_skipped;
+    return BGR_OK;
+}
+
+// the two writers: host code, deterministic bytes, straight from the graph's totals
+static int pileup_write(const char* path, const bgr_graph* g, bool sites, const char* who) {
+    if (!path || !g) return fail(BGR_E_ARG, std::string(who) + ": null argument");
+    const int rc = graph_pileup_check(g, who);
+    if (rc != BGR_OK) return rc;
+    const uint64_t n = g->header.n_unitigs;
+    std::vector<bgr_pileup_base> rows(g->header.max_unitig_len + 1);   // (converted unitig by unitig: no second table on the host)
+    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string(who) + ": cannot open " + path);
+    std::string buf = sites ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\n" : "";
+    bool ok = true;
+    auto flush = [&](bool all) { if (ok && !buf.empty() && (all || buf.size() > (1u << 20))) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); } };
+    for (uint64_t id = 1; id <= n && ok; ++id) {
+        const uint64_t len = meta[id].len;
+        if (len > rows.size()) rows.resize(len);
+        pileup_unitig_rows(g, g->pileup_words.data(), id, rows.data());
+        const bgr_pileup_base* r = rows.data();
+        if (sites) {
+            for (uint64_t pos = 0; pos < len; ++pos) {
+                const bgr_pileup_base& b = r[pos];
+                if (!(b.depth | b.a | b.c | b.g | b.t | b.n)) continue;
+                const uint64_t p = meta[id].F + pos;
+                buf += std::to_string(id); buf += '\t'; buf += std::to_string(pos); buf += '\t';
+                buf += "ACGT"[(seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u];
+                for (const uint32_t v : {b.depth, b.a, b.c, b.g, b.t, b.n}) { buf += '\t'; buf += std::to_string(v); }
+                buf += '\n';
+            }
+        } else {
+            for (uint64_t pos = 0; pos < len;) {   // maximal runs of equal non-zero depth
+                uint64_t e = pos + 1;
+                while (e < len && r[e].depth == r[pos].depth) ++e;
+                if (r[pos].depth) { buf += std::to_string(id); buf += '\t'; buf += std::to_string(pos); buf += '\t'; buf += std::to_string(e); buf += '\t'; buf += std::to_string(r[pos].depth); buf += '\n'; }
+                pos = e;
+            }
+        }
+        flush(false);
+    }
+    flush(true);
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string(who) + ": write to " + path + " failed");
+    return BGR_OK;
+}
+int bgr_write_pileup(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup"); }
+int bgr_write_depth(const char* path, const bgr_graph* g) { return pileup_write(path, g, false, "bgr_write_depth"); }
 
 
 // ---- links (bgr_link in include/bgreat_gpu.h has the definition) ---------------------------------------------------------------------------
@@ -1729,6 +1986,7 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
         tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
         tw->knob_abundance_form = a->knob_abundance_form;
         tw->knob_links_form = a->knob_links_form;
+        tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;   // (likewise)
         tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on;   // (one table for the aligner and its twins: the atomics are device-scope)
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         al[t] = tw;

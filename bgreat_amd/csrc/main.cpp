@@ -20,6 +20,9 @@
 //                                                   --gfa FILE (the graph the run's reads support, as GFA 1.0: every unitig as an S line under the 1-based ordinal the paths
 //                                                               file and --gaf use, with its read and k-mer counts, and every link that a mapped read's path crosses
 //                                                               as an L line with its count, counted on the device while mapping; greedy modes: include/bgreat_gpu.h)
+//                                                   --pileup FILE, --depth FILE (per base of every unitig: how many reads cover it and, by read character, how many differ from it,
+//                                                               counted on the device while mapping; --pileup writes one line per position with a count, --depth one
+//                                                               bedGraph-like line per run of equal depth; greedy modes, ACGT-only unitigs: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -41,7 +44,7 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
@@ -49,6 +52,7 @@ int main(int argc, char** argv) {
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
                                 {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009}, {"gfa", required_argument, nullptr, 1010},
+                                {"pileup", required_argument, nullptr, 1011}, {"depth", required_argument, nullptr, 1012},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -82,6 +86,8 @@ int main(int argc, char** argv) {
             case 1008: gaf = true; break;
             case 1009: abundanceFile = optarg; break;
             case 1010: gfaFile = optarg; break;
+            case 1011: pileupFile = optarg; break;
+            case 1012: depthFile = optarg; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -126,6 +132,8 @@ int main(int argc, char** argv) {
     opt.gaf = gaf ? 1u : 0u;
     opt.abundance = abundanceFile.empty() ? 0u : 1u;
     if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
+    const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
+    if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;
@@ -153,6 +161,8 @@ int main(int argc, char** argv) {
         if (n_links && bgr_graph_links(graph, links.data(), n_links, &n_links) != BGR_OK) die("gfa");
         if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), n_links) != BGR_OK) die("gfa");
     }
+    if (!pileupFile.empty() && bgr_write_pileup(pileupFile.c_str(), graph) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
+    if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");
     const uint64_t rn = tot[0], no = tot[1], ali = tot[2], na = tot[3];
     std::cout << "The End" << std::endl;  // aligner.cpp:588-596
     std::cout << "Reads : " << rn << std::endl;

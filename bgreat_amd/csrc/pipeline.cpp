@@ -40,6 +40,7 @@
 #include "options.h"
 #include "run_abundance.h"
 #include "run_links.h"
+#include "run_pileup.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip
@@ -47,6 +48,9 @@ RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abu
 RunLinks g_run_links = {nullptr, nullptr, nullptr, nullptr, nullptr};    // run_links.h: likewise
 // the graph's switch (bgr_graph_links_enable): the run counts links, and unitig abundance with them, whatever bgr_run_options.abundance says
 static bool run_links(const bgr_graph* g) { return g_run_links.wanted && g_run_links.wanted(g); }
+RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
+// the graph's switch (bgr_graph_pileup_enable): the run counts per-base depth and mismatches, and unitig abundance with them
+static bool run_pileup(const bgr_graph* g) { return g_run_pileup.wanted && g_run_pileup.wanted(g); }
 }
 
 namespace {
@@ -621,8 +625,9 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             }
             // (nobody reads bgr_aligner_kernel_times here: no events around the kernels -- they cost a 262 144-read piece's mapping launch a tenth of its time)
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
-            if (opt->abundance || bgr::run_links(graph)) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
+            if (opt->abundance || bgr::run_links(graph) || bgr::run_pileup(graph)) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
             if (rc == BGR_OK && bgr::run_links(graph)) rc = bgr::g_run_links.enable(a);   // ... and by the links kernel
+            if (rc == BGR_OK && bgr::run_pileup(graph)) rc = bgr::g_run_pileup.enable(a);   // ... and by the pileup kernel
             aligners.push_back(a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);
@@ -1420,7 +1425,11 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             const int lrc = bgr::g_run_links.collect(graph, a);
             if (lrc != BGR_OK) fail(lrc, bgr_last_error());
         }
-        if (!failed && (opt->abundance || bgr::run_links(graph))) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
+        if (!failed && bgr::run_pileup(graph)) {  // likewise its pileup table
+            const int prc = bgr::g_run_pileup.collect(graph, a);
+            if (prc != BGR_OK) fail(prc, bgr_last_error());
+        }
+        if (!failed && (opt->abundance || bgr::run_links(graph) || bgr::run_pileup(graph))) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
             const int arc = bgr::g_run_abundance.collect(graph, a);
             if (arc != BGR_OK) fail(arc, bgr_last_error());
         }
@@ -1574,7 +1583,12 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
     }
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
-    const bool links = bgr::run_links(graph), abundance = opt->abundance || links;
+    const bool links = bgr::run_links(graph), pileup = bgr::run_pileup(graph), abundance = opt->abundance || links || pileup;
+    if (pileup) {   // the graph's switch (bgr_graph_pileup_enable): per-base counts, defined on the rows of the greedy modes
+        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
+        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+    }
     if (links) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
@@ -1587,6 +1601,7 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     if (abundance) bgr::g_run_abundance.begin(graph);
     if (links) bgr::g_run_links.begin(graph);
+    if (pileup) bgr::g_run_pileup.begin(graph);
     int run_rc;
     if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)
         run_rc = align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
@@ -1597,5 +1612,9 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     if (abundance) bgr::g_run_abundance.end(graph, run_rc == BGR_OK);   // (the message of a failed run stays: this sets none)
     if (links) bgr::g_run_links.end(graph, run_rc == BGR_OK);
+    if (pileup) {   // (behind the abundance totals: their reads column bounds every depth, and the end refuses totals that may have wrapped)
+        const int prc = bgr::g_run_pileup.end(graph, run_rc == BGR_OK);
+        if (run_rc == BGR_OK) run_rc = prc;
+    }
     return run_rc;
 }

@@ -10,6 +10,7 @@
 // Streaming byte work: HBM-bound by design, no MFMA.
 #include "device_common.h"
 #include "text_kernels.h"
+#include "walk_lanes.h"
 
 #ifdef BGR_X_TIMES
 __device__ unsigned long long bgr_x_times[4 * 16];
@@ -21,8 +22,6 @@ extern "C" int bgr_x_times_read(unsigned long long* out) { return (int)hipMemcpy
 
 namespace bgr {
 namespace {
-
-typedef uint32_t __attribute__((ext_vector_type(4), aligned(1))) u32x4_unaligned;
 
 constexpr uint32_t kTxtThreads = 1024;
 
@@ -119,8 +118,6 @@ __global__ void __launch_bounds__(kTxtThreads) bgr_scan2_apply(const uint32_t* i
 
 // bit 7 of every byte of x that equals the byte replicated in `pat`
 __device__ __forceinline__ uint32_t eq_bytes(uint32_t x, uint32_t pat) { return bgr_zero_bytes(x ^ pat); }
-// bits 7, 15, 23, 31 of h -> bits 0..3 (one multiply: the four shifted copies do not meet)
-__device__ __forceinline__ uint32_t nibble_of(uint32_t h) { return (((h >> 7) * 0x00204081u) >> 21) & 0xFu; }
 
 // min over the 16 lanes of a row, result in every lane
 __device__ __forceinline__ uint32_t row16_min(uint32_t x) {
@@ -936,17 +933,6 @@ __device__ __forceinline__ void put_dec(uint8_t* e, u64 u) {
     if (u <= 0xFFFFFFFFull) { uint32_t v = (uint32_t)u; do { const uint32_t q = v / 10; *--e = (uint8_t)('0' + (v - q * 10)); v = q; } while (v); }
     else do { const u64 q = u / 10; *--e = (uint8_t)('0' + (uint32_t)(u - q * 10)); u = q; } while (u);
 }
-// 16 bytes at p of which `valid` (>= 1) belong to the buffer; PADDED: the buffer may be read 15 bytes past its end (the text is)
-template <bool PADDED>
-__device__ __forceinline__ void load16p(const uint8_t* p, uint32_t valid, uint32_t w[4]) {
-    if (PADDED || valid >= 16) {
-        const u32x4_unaligned v = *reinterpret_cast<const u32x4_unaligned*>(p);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-        w[0] = w[1] = w[2] = w[3] = 0;
-        for (uint32_t i = 0; i < valid; ++i) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
-    }
-}
 // the header's name: its characters behind the first one ('>' or '@') up to the first space or tab -> their number (0: the line gets '*')
 __device__ __forceinline__ uint32_t gaf_name_len(const uint8_t* text, uint32_t p, uint32_t hl, uint32_t sub) {
     if (hl < 2) return 0;
@@ -961,18 +947,8 @@ __device__ __forceinline__ uint32_t gaf_name_len(const uint8_t* text, uint32_t p
     }
     return e - s;
 }
-// shuffles inside a 16-lane group (64-bit by halves)
-__device__ __forceinline__ u64 grp_get64(u64 x, uint32_t l) {
-    return ((u64)(uint32_t)__shfl((int)(uint32_t)(x >> 32), (int)l, 16) << 32) | (uint32_t)__shfl((int)(uint32_t)x, (int)l, 16);
-}
-__device__ __forceinline__ u64 grp_up64(u64 x, uint32_t d) {
-    return ((u64)(uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 16) << 32) | (uint32_t)__shfl_up((int)(uint32_t)x, d, 16);
-}
 // The walk of one mapped read's path (np >= 1 ints) and the compare of the read with it, by the 16 lanes of a group; the results in every lane.
-// read: its L characters as they stand in the input.  A serial walk costs three dependent loads per unitig (path int -> meta -> bases) in every lane;
-// here lane i takes unitig i of a pass of sixteen: all path ints, metas and the (k-1)-mers at both ends of both strands are in flight together, and what
-// compactionEnd decides -- which strand of each unitig continues the walk, given the strand its predecessor was glued on in -- runs down the lanes by
-// shuffles (state 0: forward strand at F, 1: reverse complement at F + len, 2: no walk).  A prefix sum of the new bases places every unitig in the walk;
+// read: its L characters as they stand in the input.  The walk itself -- lane i takes unitig i of a pass of sixteen -- is walk_pass (walk_lanes.h);
 // then lane c takes the read's characters [16 c, 16 c + 16) and compares them with the one or two unitigs that lie under them.
 template <bool WIDE, bool PADDED>
 __device__ __forceinline__ GafStat gaf_stat(const BgrDeviceGraph& g, const int32_t* path, uint32_t np, const uint8_t* read, uint32_t L, bool rc, uint32_t sub) {
@@ -980,57 +956,17 @@ __device__ __forceinline__ GafStat gaf_stat(const BgrDeviceGraph& g, const int32
     const int32_t off_s = path[0];
     if (np < 2 || off_s < 0) { s.bad = true; return s; }
     const u64 off = (u64)off_s;
-    const uint32_t nu = np - 1, K1 = g.k - 1, n_unitigs = (uint32_t)g.hdr->n_unitigs;
-    const uint32_t sh1 = 64 - 2 * (WIDE ? 32 : K1), sh2 = WIDE ? 128 - 2 * K1 : 0;
-    u64 total = 0, cT = 0, cT2 = 0;   // the walk so far: its size, the (k-1)-mer at its end
+    const uint32_t nu = np - 1, K1 = g.k - 1;
+    WalkCarry carry;
     uint32_t nm = 0;
     for (uint32_t u0 = 0; u0 < nu; u0 += 16) {
-        const uint32_t u = u0 + sub;
-        const bool on = u < nu;
-        const int32_t sid = on ? path[1 + u] : 0;
-        const uint32_t id = (uint32_t)(sid < 0 ? -(int64_t)sid : (int64_t)sid);
-        const bool ok = on && id != 0 && id <= n_unitigs;
-        uint32_t len = 0;
-        u64 F = 0, hA = 0, hB = 0, tA = 0, tB = 0, hA2 = 0, hB2 = 0, tA2 = 0, tB2 = 0;
-        if (ok) {
-            const BgrUnitigMeta m = g.meta[id];
-            len = m.len; F = m.F;
-            hA = win32(g.seq, F) >> sh1; hB = win32(g.seq, F + len) >> sh1;
-            tA = win32(g.seq, F + len - K1) >> sh1; tB = win32(g.seq, F + 2ull * len - K1) >> sh1;
-            if (WIDE) {
-                hA2 = win32(g.seq, F + 32) >> sh2; hB2 = win32(g.seq, F + len + 32) >> sh2;
-                tA2 = win32(g.seq, F + len - K1 + 32) >> sh2; tB2 = win32(g.seq, F + 2ull * len - K1 + 32) >> sh2;
-            }
-        }
-        // the strand this unitig is glued on in when its predecessor lies on its strand A (rA) / B (rB)
-        u64 pA = grp_up64(tA, 1), pB = grp_up64(tB, 1), pA2 = WIDE ? grp_up64(tA2, 1) : 0, pB2 = WIDE ? grp_up64(tB2, 1) : 0;
-        if (sub == 0) { pA = pB = cT; pA2 = pB2 = cT2; }
-        const uint32_t sS = sid > 0 ? 0u : 1u;   // the strand its sign names: compactionEnd's first try
-        const u64 hS = sS ? hB : hA, hR = sS ? hA : hB, hS2 = sS ? hB2 : hA2, hR2 = sS ? hA2 : hB2;
-        uint32_t rA = 2, rB = 2;
-        if (ok) {
-            rA = (hS == pA && hS2 == pA2) ? sS : (hR == pA && hR2 == pA2) ? sS ^ 1u : 2u;
-            rB = (hS == pB && hS2 == pB2) ? sS : (hR == pB && hR2 == pB2) ? sS ^ 1u : 2u;
-        }
-        uint32_t st = sub == 0 ? (u0 == 0 ? (ok ? sS : 2u) : rA) : 2u;
-#pragma unroll
-        for (uint32_t j = 1; j < 16; ++j) {
-            const uint32_t p = (uint32_t)__shfl_up((int)st, 1, 16);
-            if (sub == j) st = p == 0 ? rA : p == 1 ? rB : 2u;
-        }
-        if (row16_sum(on && st == 2 ? 1u : 0u)) { s.bad = true; return s; }
-        // where it lies in the walk
-        const u64 new_len = on ? (u64)len - (u == 0 ? 0u : K1) : 0ull;
-        u64 inc = new_len;
-#pragma unroll
-        for (uint32_t d = 1; d < 16; d <<= 1) { const u64 up = grp_up64(inc, d); if (sub >= d) inc += up; }
-        const u64 start = total + inc - new_len, end = total + inc;
-        const u64 pass_end = grp_get64(end, 15);
+        WalkLane w;
+        if (!walk_pass<WIDE>(g, path, nu, u0, sub, carry, w)) { s.bad = true; return s; }
+        const uint32_t u = u0 + sub, id = w.id, len = w.len, st = w.st, last = w.last;
+        const bool on = w.on;
+        const u64 F = w.F, start = w.start, end = w.end, total = w.pass_start, pass_end = w.pass_end;
         s.segbytes += row16_sum(on ? 1u + dec_digits(id) : 0u);
         s.obits |= row16_sum(on && u < 32 && st == 0 ? 1u << u : 0u);
-        const uint32_t last = nu - u0 < 16 ? nu - u0 - 1 : 15u;
-        cT = grp_get64(st ? tB : tA, last);
-        if (WIDE) cT2 = grp_get64(st ? tB2 : tA2, last);
         // read position t faces base t + cst of the store: forward the strand it was glued on in; on the rc the read runs against the walk, i.e. along
         // the unitig's OTHER strand (the store holds both)
         const u64 skip = u == 0 ? 0u : K1;
@@ -1056,20 +992,14 @@ __device__ __forceinline__ GafStat gaf_stat(const BgrDeviceGraph& g, const int32
                     if (mine && xa < xb) {
                         const uint32_t a = (uint32_t)xa - t0, b = (uint32_t)xb - t0;
                         const uint32_t codes = (uint32_t)(win32(g.seq, (u64)(xa + cv)) >> 32) >> (2 * a);   // base of character i at bits 31 - 2 i, 30 - 2 i
-                        uint32_t eq = 0;
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            const uint32_t x = codes >> (24 - 8 * d);
-                            const uint32_t sel = ((x >> 6) & 3u) | (((x >> 4) & 3u) << 8) | (((x >> 2) & 3u) << 16) | ((x & 3u) << 24);
-                            eq |= nibble_of(bgr_zero_bytes(ch[d] ^ __builtin_amdgcn_perm(0u, 0x54474341u, sel))) << (4 * d);   // "ACGT" by code
-                        }
+                        const uint32_t eq = eq16_acgt(ch, codes);
                         nm += (uint32_t)__popc(~eq & ((1u << b) - 1u) & ~((1u << a) - 1u));
                     }
                 }
             }
         }
-        total = pass_end;
     }
+    const u64 total = carry.total;
     if (off > total) { s.bad = true; return s; }
     s.plen = total;
     s.cl = total - off < L ? (uint32_t)(total - off) : L;

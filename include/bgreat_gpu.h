@@ -344,6 +344,38 @@ int bgr_aligner_links_info(bgr_aligner* a, uint64_t out[4]);
 int bgr_aligner_links_plan(bgr_aligner* a, uint64_t n_reads, uint32_t out[4]);
 int bgr_plan_links(uint64_t links_bound, uint64_t n_reads, uint32_t num_cus, uint32_t form_knob, uint32_t out[4]);
 int bgr_graph_links_bound(bgr_graph* g, uint64_t* bound);
+/* Pileup: per base of every unitig, how many mapped reads cover it and how many of them differ from it, by read character.  Take a mapped row
+ * (status, path = [off, id_1 .. id_n]) of a read R of L characters in the greedy modes; the path spells a walk in which unitig occurrence j is glued on
+ * in its forward strand or its reverse complement (recoverPath / compactionEnd: the strand its sign names, or failing that the other) and has the
+ * extent [s_j, e_j): s_1 = 0, e_j = s_j + len_j, s_(j+1) = e_j - (k-1) -- the k-1 characters two neighbours share belong to BOTH.  With
+ * cl = min(L, walk size - off) and Q = R, or its reverse complement when status has BGR_ST_RC: for every i in [0, cl) and every occurrence j whose
+ * extent holds p = off + i, x = p - s_j, pos = x on a forward occurrence and len - 1 - x on a reversed one, c = Q[i] resp. its complement (any character
+ * outside ACGT is N, and stays N): depth[unitig][pos] += 1 and, if c is not the unitig's character there, the count of c at [unitig][pos] += 1.
+ * Positions are 0-based on the strand the unitig file spells; a, c, g, t count only reads that DIFFER from the unitig's base (the word of the base's
+ * own letter is always 0).  Unmapped reads add nothing; a path that spells no walk (bgr_path_stat's BGR_PATH_STAT_NO_WALK condition) adds nothing and is
+ * counted in *skipped.  For every unitig the sum of its depths equals its `bases` of bgr_unitig_abundance.  Rows are flat in unitig order: base pos of
+ * unitig i (1-based) has index sum(len_j, j < i) + pos; n_bases must be the sum of the unitig lengths (bgr_graph_info's total_bases / 2).
+ * Counted on the device as unitig abundance is: off unless enabled; while enabled every greedy / anchors launch of the aligner, through every entry
+ * point, is followed on its stream by one kernel ("bgr_pileup_kernel" in bgr_aligner_kernel_times while a slot is free) that walks each path with
+ * sixteen lanes, adds +1 / -1 at the two ends of each occurrence's covered stretch to a difference array (the depth is its running sum, taken mod 2^32
+ * when the table is read) and one 32-bit atomic per differing character.  The internal streams of overlapped batches add to the same table.  The table
+ * takes 20 bytes per base of the graph and 4 per unitig in device memory, per aligner, allocated (with the buffers' usual slack of one eighth) when
+ * counting is first enabled: 164 MiB on bench.py's default graph (8 587 555 bases in 98 866 unitigs), 7.3 GiB on the chr1-scale graph (389 965 388
+ * bases in 3 966 085 unitigs); BGR_E_NOMEM, with nothing allocated, when the device does not have it.  A character outside ACGTN is an N where the kernel reads the read's
+ * characters (bgr_align_batch, bgr_align_device and the text form in greedy mode); where it reads the 2-bit planes (bgr_align_batch_packed, and launches
+ * that pack the reads in a pre-pass: anchors mode, BGR_KNOB_GREEDY_PREPASS) it sees what the packing made of it -- its str2num code, as the mapping
+ * kernels do -- so such a character counts like the letter it packs to there.  The file parsers admit only ACGTN, so whole runs never meet one.
+ * Enabling the pileup also enables unitig
+ * abundance (as links do): its `reads` column is an exact upper bound on every depth on the unitig, and when any unitig's reads reach 2^32
+ * bgr_aligner_pileup and the run return BGR_E_CAPACITY with a message instead of wrapped numbers.  Refused with BGR_E_ARG: an exhaustive launch on an
+ * enabled aligner, and enabling on a graph with non-ACGT unitig characters (as GAF output) or without a host blob.  Disabling keeps the table; a launch
+ * that fails afterwards may have added part of its rows, and the table is undefined until bgr_aligner_reset_pileup (which leaves the abundance table
+ * alone).  bgr_aligner_pileup synchronises, copies the table to the host (20 bytes per base) and converts it on the calling thread: a call per run or
+ * per batch of launches, not per launch. */
+typedef struct { uint32_t depth, a, c, g, t, n; } bgr_pileup_base;
+int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on);
+int bgr_aligner_pileup(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped);
+int bgr_aligner_reset_pileup(bgr_aligner* a);
 /* Diagnostic (the host tests pin the kernel's canonicalisation through it): the canonical form of the link (a, b) as the kernel computes it (the same inline code, compiled for the host): out = {from, to, 0}, and, if key is
  * not NULL, the 64-bit integer the tables hold for it -- (|from| << 33) | (from < 0) << 32 | (|to| << 1) | (to < 0), whose order is the order of the keys. */
 int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key);
@@ -544,6 +576,26 @@ int bgr_graph_links_enable(bgr_graph* g, uint32_t on);
 int bgr_graph_links_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
 int bgr_graph_links(const bgr_graph* g, bgr_link* out, uint64_t cap, uint64_t* n);
 int bgr_write_gfa(const char* path, const bgr_graph* g, const bgr_unitig_abundance* abundance_rows, uint64_t n_rows, const bgr_link* links, uint64_t n_links);
+
+/* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
+ * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig
+ * abundance and the pileup in every aligner of the run; the tables of all aligners and devices are summed (mod 2^32: the differences commute) when
+ * the run ends and kept in the graph, guarded by the summed abundance: BGR_E_CAPACITY from the run when a unitig's reads reach 2^32.  With the switch
+ * on, exhaustive mode is refused before any device work (BGR_E_ARG; the message names -b, --pileup and --depth); a run that fails (BGR_E_COMPACTION
+ * too) leaves no totals; a run with the switch off leaves the last totals alone.  The run's files, counters and stdout are what they are without it.
+ * bgr_graph_pileup delivers the totals (n_bases as above; *skipped, if not NULL, the rows that spelled no walk); BGR_E_ARG if there are none.
+ * The writers (host code, deterministic bytes) write the graph's totals as text: bgr_write_pileup the line
+ * "#unitig<TAB>pos<TAB>ref<TAB>depth<TAB>A<TAB>C<TAB>G<TAB>T<TAB>N", then one line per position where at least one of the six numbers is not zero,
+ * in (unitig, pos) order, ids the 1-based ordinals of the paths file, pos 0-based, ref the unitig's character; bgr_write_depth, bedGraph-like,
+ * "unitig<TAB>start<TAB>end<TAB>depth" per maximal run of equal non-zero depth inside a unitig, 0-based and half-open.  BGR_E_IO on a path they
+ * cannot write.  Host memory: the graph keeps the summed table, 20 bytes per base (7.3 GiB on the chr1-scale graph), until the next run with the
+ * switch on or bgr_graph_destroy; while a run ends, each further aligner's table passes through a second buffer of that size before it is added, so the
+ * peak is 40 bytes per base; the writers convert unitig by unitig and add nothing to that, bgr_graph_pileup fills the caller's 24 bytes per base. */
+int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on);
+int bgr_graph_pileup_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped);
+int bgr_write_pileup(const char* path, const bgr_graph* g);
+int bgr_write_depth(const char* path, const bgr_graph* g);
 
 /* The CPUs next to a device (the `local_cpulist` of its PCI function in sysfs, e.g. "0-63,128-191"): threads that feed a GPU and the
  * page-locked memory they allocate belong on its NUMA node.  BGR_E_IO when the platform does not say. */

@@ -40,6 +40,8 @@ SYMBOLS = [
     "bgr_graph_links_enable", "bgr_graph_links", "bgr_write_gfa", "bgr_link_canonical", "bgr_graph_links_enabled",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
+    "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
+    "bgr_graph_variants_params", "bgr_write_vcf", "bgr_parse_af_ppm",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
@@ -268,6 +270,15 @@ def lib():
     L.bgr_graph_pileup_enabled.argtypes = [vp]
     L.bgr_graph_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_write_pileup.argtypes = [C.c_char_p, vp]
+    L.bgr_aligner_pileup_sites.argtypes = [vp, vp, vp, u64, vp]
+    L.bgr_aligner_pileup_sites_times.argtypes = [vp, vp]
+    L.bgr_aligner_pileup_add.argtypes = [vp, vp]
+    L.bgr_graph_variants_enable.argtypes = [vp, vp]
+    L.bgr_graph_variants_enabled.argtypes = [vp]
+    L.bgr_graph_variants.argtypes = [vp, vp, u64, vp]
+    L.bgr_graph_variants_params.argtypes = [vp, vp]
+    L.bgr_write_vcf.argtypes = [C.c_char_p, vp, vp, vp, u64]
+    L.bgr_parse_af_ppm.argtypes = [C.c_char_p, vp]
     L.bgr_write_depth.argtypes = [C.c_char_p, vp]
     L.bgr_link_canonical.argtypes = [C.c_int32, C.c_int32, vp, vp]
     _lib = L
@@ -519,6 +530,35 @@ class Graph:
         """bgr_write_depth: one bedGraph-like line per run of equal non-zero depth."""
         _check(lib().bgr_write_depth(path.encode(), self.h))
 
+    def variants_enable(self, min_depth=2, min_alt=2, min_af_ppm=200000, on=True):
+        """bgr_graph_variants_enable: sticky -- every later align_all on this graph counts the pileup and calls SNV sites from it on the device
+        (a base with depth >= min_depth where an allele has count >= min_alt and count * 1e6 >= min_af_ppm * depth).  on=False switches it off."""
+        prm = VariantParams(int(min_depth), int(min_alt), int(min_af_ppm))
+        _check(lib().bgr_graph_variants_enable(self.h, C.byref(prm) if on else None))
+
+    def variants_enabled(self):
+        """bgr_graph_variants_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_variants_enabled(self.h))
+
+    def variants(self):
+        """bgr_graph_variants: the sites of the last align_all with the switch on -> array of VARIANT_DTYPE (unitig, pos, depth, a, c, g, t, n) in
+        (unitig, pos) order.  Raises BgrError when there are none."""
+        return _fetch_sites(lambda out, cap, n: lib().bgr_graph_variants(self.h, out, cap, n))
+
+    def variants_params(self):
+        """bgr_graph_variants_params: (min_depth, min_alt, min_af_ppm) the sites of Graph.variants() were called with."""
+        prm = VariantParams()
+        _check(lib().bgr_graph_variants_params(self.h, C.byref(prm)))
+        return int(prm.min_depth), int(prm.min_alt), int(prm.min_af_ppm)
+
+    def write_vcf(self, path, sites=None, params=None):
+        """bgr_write_vcf: `sites` (default: Graph.variants()) called with `params` (default: Graph.variants_params()) as VCF 4.2."""
+        if sites is None:
+            sites = self.variants()
+        prm = VariantParams(*(self.variants_params() if params is None else params))
+        sites = np.ascontiguousarray(sites, dtype=VARIANT_DTYPE)
+        _check(lib().bgr_write_vcf(path.encode(), self.h, C.byref(prm), sites.ctypes.data if len(sites) else None, len(sites)))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -730,6 +770,22 @@ class Aligner:
     def reset_pileup(self):
         _check(lib().bgr_aligner_reset_pileup(self.h))
 
+    def pileup_sites(self, min_depth=2, min_alt=2, min_af_ppm=200000):
+        """bgr_aligner_pileup_sites -> array of VARIANT_DTYPE: the SNV sites of this aligner's pileup table, called on the device (five launches
+        on the aligner's stream); only the records cross to the host."""
+        prm = VariantParams(int(min_depth), int(min_alt), int(min_af_ppm))
+        return _fetch_sites(lambda out, cap, n: lib().bgr_aligner_pileup_sites(self.h, C.byref(prm), out, cap, n))
+
+    def pileup_sites_times(self):
+        """bgr_aligner_pileup_sites_times -> the milliseconds of the last pileup_sites' five launches (tile sums, scan, classify, scan, emit)."""
+        ms = (C.c_double * 5)()
+        _check(lib().bgr_aligner_pileup_sites_times(self.h, ms))
+        return [float(x) for x in ms]
+
+    def pileup_add(self, other):
+        """bgr_aligner_pileup_add: other's pileup table is added into this aligner's, on the device(s); the abundance tables are not touched."""
+        _check(lib().bgr_aligner_pileup_add(self.h, other.h))
+
     def sync(self):
         _check(lib().bgr_aligner_sync(self.h))
 
@@ -831,6 +887,33 @@ def plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus=0, lds_per_cu=0, 
 
 
 PILEUP_DTYPE = np.dtype([("depth", np.uint32), ("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("n", np.uint32)])
+
+
+VARIANT_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "pos", "depth", "a", "c", "g", "t", "n")])   # an array of bgr_variant_site
+VARIANTS_TILE = 2048   # BGR_VARIANTS_TILE: words of the difference array per tile of the passes
+
+
+class VariantParams(C.Structure):  # bgr_variant_params
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_af_ppm", C.c_uint32)]
+
+
+def _fetch_sites(fn):
+    """the two-call form of bgr_aligner_pileup_sites / bgr_graph_variants: the number first (BGR_E_CAPACITY), then the records"""
+    n = C.c_uint64(0)
+    rc = fn(None, 0, C.byref(n))
+    if rc != -4 or n.value == 0:
+        _check(rc)
+        return np.zeros(0, dtype=VARIANT_DTYPE)
+    out = np.zeros(n.value, dtype=VARIANT_DTYPE)
+    _check(fn(out.ctypes.data, n.value, C.byref(n)))
+    return out[: n.value]
+
+
+def parse_af_ppm(text):
+    """bgr_parse_af_ppm: the CLI's --min-af parser -> parts per million; BgrError for anything but a decimal in 0 .. 1 with at most six places."""
+    ppm = C.c_uint32(0)
+    _check(lib().bgr_parse_af_ppm(text.encode(), C.byref(ppm)))
+    return int(ppm.value)
 
 
 def _fetch_pileup(fn, obj):

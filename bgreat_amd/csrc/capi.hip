@@ -32,6 +32,7 @@
 #include "run_links.h"
 #include "run_pileup.h"
 #include "text_kernels.h"
+#include "variants_kernels.h"
 #include "options.h"
 
 namespace {
@@ -76,6 +77,12 @@ struct bgr_graph {
     std::vector<uint64_t> base_offs;          // [n_unitigs + 2]: base_offs[id] = sum of len of the unitigs 1 .. id - 1
     std::vector<uint32_t> pileup_words;       // alt[4 T] then delta[T + n] (pileup_kernels.h)
     uint64_t pileup_skipped = 0;
+    // SNV sites (bgr_graph_variants_enable): the sticky switch and its thresholds; while a run collects its aligners, the run's pileup table on a device
+    // (the first aligner's, adopted; the others' added into it); then the sites of the last successful run and the thresholds they were called with
+    bool variants_on = false, variants_valid = false;
+    bgr_variant_params variants_prm = {2, 2, 200000}, variants_called = {0, 0, 0};
+    struct VariantsRun* variants_run = nullptr;
+    std::vector<bgr_variant_site> variants_sites;
 };
 
 namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
@@ -112,6 +119,22 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+struct VariantsRun {   // the pileup table of a run with bgr_graph_variants_enable while its aligners are collected (bgr_graph has the rest)
+    int device = 0, num_cus = 0;
+    hipStream_t stream = nullptr;
+    BgrDeviceGraph dg;
+    DevBuf table, offs, stage;
+};
+static void variants_run_free(bgr_graph* g) {
+    if (!g->variants_run) return;
+    if (hipSetDevice(g->variants_run->device) == hipSuccess) {
+        if (g->variants_run->stream) (void)hipStreamDestroy(g->variants_run->stream);
+        g->variants_run->table.release(); g->variants_run->offs.release(); g->variants_run->stage.release();
+    }
+    delete g->variants_run;
+    g->variants_run = nullptr;
+}
 
 struct bgr_text_stage {  // one piece of text on its way to / resident in a device: buffer, copy stream, "it has arrived" event
     int device = 0;
@@ -183,6 +206,8 @@ struct bgr_aligner {
     DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
     uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
     const uint64_t* pileup_base_offs = nullptr;
+    DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
+    double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
     bool is_twin = false;
     int num_cus = 0;
@@ -364,6 +389,7 @@ void bgr_graph_destroy(bgr_graph* g) {
             if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second.ptr);
         }
     }
+    variants_run_free(g);
     delete g;
 }
 
@@ -569,7 +595,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -1171,39 +1197,57 @@ int bgr_aligner_reset_pileup(bgr_aligner* a) {
     return BGR_OK;   // (the abundance table stays: the guard's column then counts more launches than the pileup holds, which errs on the safe side)
 }
 
-// what a whole run calls (run_pileup.h)
-static bool run_pileup_wanted(const bgr_graph* g) { return g && g->pileup_on; }
+// what a whole run calls (run_pileup.h): the graph's pileup switch gathers the tables on the host, its variants switch (further down) on a device
+static int variants_collect(bgr_graph* g, bgr_aligner* a);
+static int variants_end(bgr_graph* g, bool ok);
+static bool run_pileup_wanted(const bgr_graph* g) { return g && (g->pileup_on || g->variants_on); }
+static bool run_pileup_variants(const bgr_graph* g) { return g && g->variants_on; }
 static void run_pileup_begin(bgr_graph* g) {
     std::lock_guard<std::mutex> l(g->abundance_m);
-    g->pileup_words.clear();
-    g->pileup_skipped = 0;
-    g->pileup_valid = false;
+    if (g->pileup_on) {
+        g->pileup_words.clear();
+        g->pileup_skipped = 0;
+        g->pileup_valid = false;
+    }
+    if (g->variants_on) {
+        variants_run_free(g);
+        g->variants_sites.clear();
+        g->variants_valid = false;
+    }
 }
 static int run_pileup_enable(bgr_aligner* a) { return bgr_aligner_pileup_enable(a, 1); }
 static int run_pileup_collect(bgr_graph* g, bgr_aligner* a) {
-    std::vector<uint32_t> words;
-    uint64_t sk = 0;
-    const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk);
-    if (rc != BGR_OK) return rc;
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (g->pileup_words.empty()) g->pileup_words.swap(words);
-    else for (size_t i = 0; i < words.size(); ++i) g->pileup_words[i] += words[i];   // (mod 2^32: the delta sums commute)
-    g->pileup_skipped += sk;
-    return BGR_OK;
+    if (g->pileup_on) {
+        std::vector<uint32_t> words;
+        uint64_t sk = 0;
+        const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk);
+        if (rc != BGR_OK) return rc;
+        std::lock_guard<std::mutex> l(g->abundance_m);
+        if (g->pileup_words.empty()) g->pileup_words.swap(words);
+        else for (size_t i = 0; i < words.size(); ++i) g->pileup_words[i] += words[i];   // (mod 2^32: the delta sums commute)
+        g->pileup_skipped += sk;
+    }
+    return g->variants_on ? variants_collect(g, a) : BGR_OK;   // (behind the snapshot: the first aligner's table leaves it here)
 }
 static int run_pileup_end(bgr_graph* g, bool ok) {   // behind the abundance's end: the summed reads column guards the summed table
-    std::lock_guard<std::mutex> l(g->abundance_m);
     int rc = BGR_OK;
-    if (ok) {
-        const uint64_t T = g->header.total_bases / 2, n = g->header.n_unitigs;
-        if (g->pileup_words.empty()) g->pileup_words.assign(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n), 0u);   // (a run without aligners' tables: nothing mapped)
-        rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: a pileup without the abundance totals that guard it");
+    if (g->pileup_on) {
+        std::lock_guard<std::mutex> l(g->abundance_m);
+        if (ok) {
+            const uint64_t T = g->header.total_bases / 2, n = g->header.n_unitigs;
+            if (g->pileup_words.empty()) g->pileup_words.assign(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n), 0u);   // (a run without aligners' tables: nothing mapped)
+            rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: a pileup without the abundance totals that guard it");
+        }
+        if (!ok || rc != BGR_OK) { g->pileup_words.clear(); g->pileup_words.shrink_to_fit(); }
+        g->pileup_valid = ok && rc == BGR_OK;
     }
-    if (!ok || rc != BGR_OK) { g->pileup_words.clear(); g->pileup_words.shrink_to_fit(); }
-    g->pileup_valid = ok && rc == BGR_OK;
+    if (g->variants_on) {
+        const int vrc = variants_end(g, ok && rc == BGR_OK);
+        if (rc == BGR_OK) rc = vrc;
+    }
     return rc;
 }
-static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end}, true);
+static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end, run_pileup_variants}, true);
 
 int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on) {
     if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_enable: null graph");
@@ -1279,6 +1323,210 @@ static int pileup_write(const char* path, const bgr_graph* g, bool sites, const 
 }
 int bgr_write_pileup(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup"); }
 int bgr_write_depth(const char* path, const bgr_graph* g) { return pileup_write(path, g, false, "bgr_write_depth"); }
+
+
+// ---- SNV sites (bgr_variant_site in include/bgreat_gpu.h has the definition; variants_kernels.h the passes) -------------------------------------
+// the five launches over one table on `stream` of the current device, then the records' way to the host: into `vec` (as many as there are), or into
+// `out` when they are at most `cap`.  *n = their number in any case.  ms: null, or the five launches' milliseconds
+static int variants_call(const BgrDeviceGraph& dg, const bgr_graph* g, const uint32_t* table, const uint64_t* base_offs, const bgr_variant_params& prm, DevBuf& scratch,
+                         DevBuf& outbuf, hipStream_t stream, const char* who, std::vector<bgr_variant_site>* vec, bgr_variant_site* out, uint64_t cap, uint64_t* n, double* ms) {
+    static_assert(sizeof(bgr_variant_site) == 32, "eight u32 per site");
+    const uint64_t nu = g->header.n_unitigs, T = g->header.total_bases / 2, tiles = bgr::variants_tiles(T, nu);
+    *n = 0;
+    if (ms) for (int i = 0; i < 5; ++i) ms[i] = 0;
+    if (vec) vec->clear();
+    if (tiles == 0 || nu == 0) return BGR_OK;
+    hipError_t e = scratch.ensure(bgr::variants_scratch_bytes(tiles));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the passes' tile arrays: " + hipGetErrorString(e)); }
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 6; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+    if (ms) {
+        for (int i = 0; i < 6; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+        HIP_TRY(hipEventRecord(ev[0], stream));
+    }
+    e = bgr::launch_variants_count(dg, nu, T, table, base_offs, prm, scratch.p, stream, ms ? ev + 1 : nullptr);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_*_kernel): " + hipGetErrorString(e));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, bgr::variants_total_word(scratch.p, tiles), 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n = total;
+    if (total > T) return fail(BGR_E_INTERNAL, std::string(who) + ": more sites than bases");
+    if (!vec && total > cap) return fail(BGR_E_CAPACITY, std::string(who) + ": " + std::to_string(total) + " sites, room for " + std::to_string(cap));
+    if (total) {
+        e = outbuf.ensure(total * sizeof(bgr_variant_site));
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": " + std::to_string(total) + " site records on the device: " + hipGetErrorString(e)); }
+        e = bgr::launch_variants_emit(dg, nu, T, table, base_offs, prm, scratch.p, static_cast<bgr_variant_site*>(outbuf.p), stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_classify_kernel, emit): " + hipGetErrorString(e));
+        if (ms) HIP_TRY(hipEventRecord(ev[5], stream));
+        if (vec) { vec->resize(total); out = vec->data(); }
+        HIP_TRY(hipMemcpyAsync(out, outbuf.p, total * sizeof(bgr_variant_site), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (ms)
+        for (int i = 0; i < (total ? 5 : 4); ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, ev[i], ev[i + 1])); ms[i] = f; }
+    return BGR_OK;
+}
+
+// dst += src, two whole pileup tables of `bytes` bytes; the current device is dst's, `stream` one of its streams, waited for before the return.
+// On one device one kernel; across devices -- or whenever the test hook names a piece size -- through `stage`, a piece of at most 64 MiB at a time
+static int variants_table_add(uint32_t* dst, int dst_device, const uint32_t* src, int src_device, uint64_t bytes, DevBuf& stage, uint32_t num_cus, hipStream_t stream, const char* who) {
+    const int64_t hook = bgr::opt("test.variants_stage_bytes");
+    hipError_t e;
+    if (dst_device == src_device && hook == 0) {
+        e = bgr::launch_pileup_add(dst, src, bytes / 4, true, num_cus, stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_pileup_add_kernel): " + hipGetErrorString(e));
+    } else {
+        uint64_t piece = hook > 0 ? ((uint64_t)hook + 15) / 16 * 16 : (64ull << 20);
+        if (piece > (64ull << 20)) piece = 64ull << 20;
+        if (piece > bytes) piece = (bytes + 15) / 16 * 16;
+        e = stage.ensure(piece);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the staging piece of a table from another device: " + hipGetErrorString(e)); }
+        for (uint64_t off = 0; off < bytes; off += piece) {   // (the pieces follow each other on one stream: the copy of the next waits for the add of this one)
+            const uint64_t len = bytes - off < piece ? bytes - off : piece;
+            if (dst_device == src_device) HIP_TRY(hipMemcpyAsync(stage.p, reinterpret_cast<const char*>(src) + off, len, hipMemcpyDeviceToDevice, stream));
+            else HIP_TRY(hipMemcpyPeerAsync(stage.p, dst_device, reinterpret_cast<const char*>(src) + off, src_device, len, stream));
+            e = bgr::launch_pileup_add(dst + off / 4, static_cast<const uint32_t*>(stage.p), len / 4, off + len == bytes, num_cus, stream);
+            if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_pileup_add_kernel): " + hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return BGR_OK;
+}
+
+int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, bgr_variant_site* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!a || !params || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: null argument");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: an internal stream of another aligner");
+    if (!bgr::variants_params_ok(*params)) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
+    if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
+    const uint64_t nu = a->graph->header.n_unitigs;
+    std::vector<bgr_unitig_abundance> ab(nu);
+    int rc = bgr_aligner_abundance(a, ab.data(), nu);   // (synchronises the aligner's stream and its twins')
+    if (rc == BGR_OK) rc = pileup_guard(ab.data(), nu, "bgr_aligner_pileup_sites");
+    if (rc != BGR_OK) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    return variants_call(a->dg, a->graph, a->pileup_tab, a->pileup_base_offs, *params, a->var_scratch, a->var_out, a->stream, "bgr_aligner_pileup_sites", nullptr, out, cap, n,
+                         a->knob_no_events ? nullptr : a->var_ms);
+}
+
+int bgr_aligner_pileup_sites_times(bgr_aligner* a, double ms[5]) {
+    if (!a || !ms) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites_times: null argument");
+    for (int i = 0; i < 5; ++i) ms[i] = a->var_ms[i];
+    return BGR_OK;
+}
+
+int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src) {
+    if (!dst || !src) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: null aligner");
+    if (dst->is_twin || src->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: an internal stream of another aligner");
+    if (dst == src || dst->graph != src->graph) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: two different aligners of one graph are needed");
+    if (!dst->pileup_tab || !src->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: the pileup was never enabled on one of the aligners (bgr_aligner_pileup_enable)");
+    HIP_TRY(hipSetDevice(src->device));
+    for (bgr_aligner* x = src; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    HIP_TRY(hipSetDevice(dst->device));
+    for (bgr_aligner* x = dst; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    const uint64_t bytes = bgr::pileup_table_bytes(dst->graph->header.total_bases / 2, dst->graph->header.n_unitigs);
+    return variants_table_add(dst->pileup_tab, dst->device, src->pileup_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
+}
+
+// a run's aligner, its streams idle from here on: the first one's table becomes the run's (the buffers move: nothing is allocated), the others' are added
+static int variants_collect(bgr_graph* g, bgr_aligner* a) {
+    if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_align_all: the pileup was never enabled on an aligner of the run");
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    std::lock_guard<std::mutex> l(g->abundance_m);   // (the lanes of a split run end side by side: one at a time here)
+    if (!g->variants_run) {
+        VariantsRun* r = new VariantsRun();
+        r->device = a->device; r->num_cus = a->num_cus; r->dg = a->dg;
+        if (hipStreamCreate(&r->stream) != hipSuccess) { delete r; (void)hipGetLastError(); return fail(BGR_E_HIP, "bgr_align_all: a stream for the run's pileup table"); }
+        std::swap(r->table, a->pileup);
+        std::swap(r->offs, a->pileup_offs);
+        a->pileup_tab = nullptr; a->pileup_base_offs = nullptr; a->pileup_on = false;
+        pileup_share(a);
+        g->variants_run = r;
+        return BGR_OK;
+    }
+    VariantsRun* r = g->variants_run;
+    HIP_TRY(hipSetDevice(r->device));
+    return variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->pileup_tab, a->device, bgr::pileup_table_bytes(g->header.total_bases / 2, g->header.n_unitigs),
+                              r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
+}
+// the run's end: behind the guard of the summed abundance the passes run once on the run's table; the table is freed whatever happens
+static int variants_end(bgr_graph* g, bool ok) {
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    int rc = BGR_OK;
+    if (ok) {
+        rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: sites without the abundance totals that guard them");
+        if (rc == BGR_OK && g->variants_run) {
+            VariantsRun* r = g->variants_run;
+            DevBuf scratch, outbuf;
+            uint64_t n = 0;
+            rc = hipSetDevice(r->device) == hipSuccess ? variants_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint64_t*>(r->offs.p), g->variants_prm, scratch, outbuf,
+                                                                       r->stream, "bgr_align_all", &g->variants_sites, nullptr, 0, &n, nullptr)
+                                                       : fail(BGR_E_HIP, "bgr_align_all: hipSetDevice for the run's pileup table");
+            scratch.release(); outbuf.release();
+        }
+    }
+    variants_run_free(g);
+    if (!ok || rc != BGR_OK) { g->variants_sites.clear(); g->variants_sites.shrink_to_fit(); }
+    g->variants_called = g->variants_prm;
+    g->variants_valid = ok && rc == BGR_OK;
+    return rc;
+}
+
+int bgr_graph_variants_enable(bgr_graph* g, const bgr_variant_params* params) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_variants_enable: null graph");
+    if (params) {
+        if (!bgr::variants_params_ok(*params)) return fail(BGR_E_ARG, "bgr_graph_variants_enable: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
+        int rc = pileup_refusal(g, "bgr_graph_variants_enable");
+        if (rc == BGR_OK) rc = graph_base_offs(g, "bgr_graph_variants_enable");
+        if (rc != BGR_OK) return rc;
+        g->variants_prm = *params;
+    }
+    g->variants_on = params != nullptr;
+    return BGR_OK;
+}
+
+int bgr_graph_variants_enabled(const bgr_graph* g) { return g && g->variants_on ? 1 : 0; }
+
+int bgr_graph_variants(const bgr_graph* g, bgr_variant_site* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_variants: null argument");
+    if (!g->variants_valid) return fail(BGR_E_ARG, "bgr_graph_variants: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_enable on");
+    *n = g->variants_sites.size();
+    if (g->variants_sites.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_variants: " + std::to_string(g->variants_sites.size()) + " sites, room for " + std::to_string(cap));
+    if (!g->variants_sites.empty()) memcpy(out, g->variants_sites.data(), g->variants_sites.size() * sizeof(bgr_variant_site));
+    return BGR_OK;
+}
+
+int bgr_graph_variants_params(const bgr_graph* g, bgr_variant_params* out) {
+    if (!g || !out) return fail(BGR_E_ARG, "bgr_graph_variants_params: null argument");
+    if (!g->variants_valid) return fail(BGR_E_ARG, "bgr_graph_variants_params: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_enable on");
+    *out = g->variants_called;
+    return BGR_OK;
+}
+
+int bgr_write_vcf(const char* path, const bgr_graph* g, const bgr_variant_params* params, const bgr_variant_site* sites, uint64_t n) {
+    if (!path || !g || !params || (n && !sites)) return fail(BGR_E_ARG, "bgr_write_vcf: null argument");
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_vcf: the graph has no host blob (the reference letters are read from it)");
+    if (g->header.has_exc) return fail(BGR_E_ARG, "bgr_write_vcf: a graph of ACGT-only unitigs is needed (--vcf): the 2-bit store does not spell other characters");
+    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
+    std::string err;
+    if (!bgr::vcf_write(nullptr, meta, seq, g->header.n_unitigs, *params, sites, n, &err)) return fail(BGR_E_ARG, "bgr_write_vcf: " + err);   // (the checks alone: no file for sites that are none)
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string("bgr_write_vcf: cannot open ") + path);
+    bool ok = bgr::vcf_write(f, meta, seq, g->header.n_unitigs, *params, sites, n, &err);
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_vcf: write to ") + path + " failed");
+    return BGR_OK;
+}
+
+int bgr_parse_af_ppm(const char* text, uint32_t* ppm) {
+    if (!text || !ppm) return fail(BGR_E_ARG, "bgr_parse_af_ppm: null argument");
+    if (!bgr::parse_af_ppm(text, ppm)) return fail(BGR_E_ARG, std::string("bgr_parse_af_ppm: '") + text + "' is no fraction between 0 and 1 with at most six decimals");
+    return BGR_OK;
+}
 
 
 // ---- links (bgr_link in include/bgreat_gpu.h has the definition) ---------------------------------------------------------------------------

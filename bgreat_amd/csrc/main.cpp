@@ -23,6 +23,11 @@
 //                                                   --pileup FILE, --depth FILE (per base of every unitig: how many reads cover it and, by read character, how many differ from it,
 //                                                               counted on the device while mapping; --pileup writes one line per position with a count, --depth one
 //                                                               bedGraph-like line per run of equal depth; greedy modes, ACGT-only unitigs: include/bgreat_gpu.h)
+//                                                   --vcf FILE [--min-depth N] [--min-alt N] [--min-af F] (the SNV sites on the unitigs as VCF 4.2, CHROM the 1-based ordinal of the paths file: a base
+//                                                               covered by at least N reads (2) where a letter other than the unitig's is read at least N times (2) and in
+//                                                               at least the fraction F of the covering reads (0.2: a decimal with at most six places); called on the
+//                                                               device from the pileup counted while mapping -- the table never crosses to the host; greedy modes, ACGT-only
+//                                                               unitigs: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -44,8 +49,10 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
+    bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
+    bool vprm_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
@@ -53,6 +60,8 @@ int main(int argc, char** argv) {
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
                                 {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009}, {"gfa", required_argument, nullptr, 1010},
                                 {"pileup", required_argument, nullptr, 1011}, {"depth", required_argument, nullptr, 1012},
+                                {"vcf", required_argument, nullptr, 1013}, {"min-depth", required_argument, nullptr, 1014}, {"min-alt", required_argument, nullptr, 1015},
+                                {"min-af", required_argument, nullptr, 1016},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -88,6 +97,22 @@ int main(int argc, char** argv) {
             case 1010: gfaFile = optarg; break;
             case 1011: pileupFile = optarg; break;
             case 1012: depthFile = optarg; break;
+            case 1013: vcfFile = optarg; break;
+            case 1014:
+            case 1015: {   // a positive integer, digits only
+                const std::string v = optarg;
+                if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stol(v) < 1) {
+                    fprintf(stderr, "bgreat: %s takes a positive integer, not '%s'\n", c == 1014 ? "--min-depth" : "--min-alt", optarg);
+                    return 2;
+                }
+                (c == 1014 ? vprm.min_depth : vprm.min_alt) = (uint32_t)std::stol(v);
+                vprm_given = true;
+                break;
+            }
+            case 1016:
+                if (bgr_parse_af_ppm(optarg, &vprm.min_af_ppm) != BGR_OK) die("--min-af");
+                vprm_given = true;
+                break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -99,6 +124,7 @@ int main(int argc, char** argv) {
                   << "-c to output corrected reads" << std::endl;
         return 0;
     }
+    if (vprm_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-depth, --min-alt and --min-af are thresholds of --vcf FILE\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -134,6 +160,7 @@ int main(int argc, char** argv) {
     if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
+    if (!vcfFile.empty() && bgr_graph_variants_enable(graph, &vprm) != BGR_OK) die("--vcf");   // (likewise; it implies the counting of the pileup, whose tables then stay on the devices)
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;
@@ -143,7 +170,7 @@ int main(int argc, char** argv) {
         bgr_host_cache_release();
         return 0;
     }
-    if (arc != BGR_OK) die("mapping");
+    if (arc != BGR_OK) die(vcfFile.empty() ? "mapping" : "mapping (--vcf)");
     if (!abundanceFile.empty()) {  // (behind a run that ended well: a run that stops with "bug compaction" leaves no totals)
         bgr_graph_info_t gi;
         if (bgr_graph_info(graph, &gi) != BGR_OK) die("abundance");
@@ -163,6 +190,13 @@ int main(int argc, char** argv) {
     }
     if (!pileupFile.empty() && bgr_write_pileup(pileupFile.c_str(), graph) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");
+    if (!vcfFile.empty()) {   // (the run has called the sites: they, not the table, are what the graph keeps)
+        uint64_t n_sites = 0;
+        if (bgr_graph_variants(graph, nullptr, 0, &n_sites) != BGR_OK && n_sites == 0) die("--vcf");   // (BGR_E_CAPACITY with the number of sites)
+        std::vector<bgr_variant_site> sites(n_sites);
+        if (n_sites && bgr_graph_variants(graph, sites.data(), n_sites, &n_sites) != BGR_OK) die("--vcf");
+        if (bgr_write_vcf(vcfFile.c_str(), graph, &vprm, sites.data(), n_sites) != BGR_OK) die("--vcf");
+    }
     const uint64_t rn = tot[0], no = tot[1], ali = tot[2], na = tot[3];
     std::cout << "The End" << std::endl;  // aligner.cpp:588-596
     std::cout << "Reads : " << rn << std::endl;

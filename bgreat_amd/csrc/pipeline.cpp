@@ -48,8 +48,8 @@ RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abu
 RunLinks g_run_links = {nullptr, nullptr, nullptr, nullptr, nullptr};    // run_links.h: likewise
 // the graph's switch (bgr_graph_links_enable): the run counts links, and unitig abundance with them, whatever bgr_run_options.abundance says
 static bool run_links(const bgr_graph* g) { return g_run_links.wanted && g_run_links.wanted(g); }
-RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
-// the graph's switch (bgr_graph_pileup_enable): the run counts per-base depth and mismatches, and unitig abundance with them
+RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
+// the graph's switches (bgr_graph_pileup_enable, bgr_graph_variants_enable): the run counts per-base depth and mismatches, and unitig abundance with them
 static bool run_pileup(const bgr_graph* g) { return g_run_pileup.wanted && g_run_pileup.wanted(g); }
 }
 
@@ -1586,7 +1586,9 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     const bool links = bgr::run_links(graph), pileup = bgr::run_pileup(graph), abundance = opt->abundance || links || pileup;
     if (pileup) {   // the graph's switch (bgr_graph_pileup_enable): per-base counts, defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
+            return bgr::set_error(BGR_E_ARG, bgr::g_run_pileup.variants && bgr::g_run_pileup.variants(graph)
+                                                  ? "bgr_align_all: SNV sites (--vcf, bgr_graph_variants_enable) are called from the pileup, which is for the greedy modes; the rows of exhaustive mode (-b) have another layout"
+                                                  : "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
         if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     }
     if (links) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes

@@ -11,11 +11,12 @@
 namespace bgr {
 
 struct RunPileup {
-    bool (*wanted)(const bgr_graph* g);           // the graph's switch: this run counts unitig abundance and the pileup
+    bool (*wanted)(const bgr_graph* g);           // the graph's switches (pileup, variants): this run counts unitig abundance and the pileup
     void (*begin)(bgr_graph* g);                  // a new run: the totals of the one before are gone, whatever becomes of this one
     int (*enable)(bgr_aligner* a);                // every launch of this aligner counts
     int (*collect)(bgr_graph* g, bgr_aligner* a); // the aligner's table (its stream waited for) joins the run's totals in the graph
     int (*end)(bgr_graph* g, bool ok);            // totals only of a run that ended well; BGR_E_CAPACITY when a depth may have wrapped (behind the abundance's end)
+    bool (*variants)(const bgr_graph* g);         // the graph's variants switch (bgr_graph_variants_enable) is among what `wanted` answers for: the run calls SNV sites (--vcf)
 };
 extern RunPileup g_run_pileup;  // pipeline.cpp; all null until capi.hip has registered
 

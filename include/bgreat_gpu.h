@@ -376,6 +376,26 @@ typedef struct { uint32_t depth, a, c, g, t, n; } bgr_pileup_base;
 int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on);
 int bgr_aligner_pileup(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped);
 int bgr_aligner_reset_pileup(bgr_aligner* a);
+/* SNV sites on the unitigs, called from the pileup table on the device.  For thresholds min_depth >= 1, min_alt >= 1 and min_af_ppm in 0 .. 1 000 000
+ * a base (unitig, pos) is a SITE when its depth >= min_depth and at least one allele passes; allele X of A C G T, other than the unitig's own letter,
+ * PASSES when its count c_X >= min_alt and c_X * 1 000 000 >= min_af_ppm * depth (64-bit integers: no floating point anywhere).  N is never an allele.
+ * A site's record holds the numbers of bgr_pileup_base at that base, unitig the 1-based ordinal, pos 0-based; sites come in (unitig, pos) order.
+ * bgr_aligner_pileup_sites calls the sites of this aligner's table where it lies: it synchronises (the aligner's stream and its internal ones), applies
+ * the guard of bgr_aligner_pileup (BGR_E_CAPACITY when a unitig's reads reach 2^32), runs five launches on the aligner's stream -- per-tile sums of the
+ * difference array, their scan, a classify pass that counts each tile's sites, the scan of the counts, and the same pass again writing every record at
+ * its final place (tiles of BGR_VARIANTS_TILE words of the difference array; no sort, no atomics on the output, no workgroup waits for another) -- and
+ * copies only the records: *n = their number, always; BGR_E_CAPACITY, with *n set and nothing copied, when cap is smaller.  The table itself never
+ * leaves the device.  BGR_E_ARG: the pileup was never enabled on the aligner, or thresholds out of range.  bgr_aligner_pileup_sites_times: the
+ * milliseconds of the last call's five launches (zeroes when none ran).
+ * bgr_aligner_pileup_add adds src's pileup table into dst's (both enabled, same graph, neither an internal stream; mod 2^32, the skipped counter too;
+ * the abundance tables are not touched -- a caller that relies on dst's guard adds those itself): one kernel when both are on one device, else in
+ * pieces through a staging buffer on dst's device of at most 64 MiB (peer copy, then the kernel). */
+#define BGR_VARIANTS_TILE 2048u
+typedef struct { uint32_t unitig, pos, depth, a, c, g, t, n; } bgr_variant_site;
+typedef struct { uint32_t min_depth, min_alt, min_af_ppm; } bgr_variant_params;
+int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, bgr_variant_site* out, uint64_t cap, uint64_t* n);
+int bgr_aligner_pileup_sites_times(bgr_aligner* a, double ms[5]);
+int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src);
 /* Diagnostic (the host tests pin the kernel's canonicalisation through it): the canonical form of the link (a, b) as the kernel computes it (the same inline code, compiled for the host): out = {from, to, 0}, and, if key is
  * not NULL, the 64-bit integer the tables hold for it -- (|from| << 33) | (from < 0) << 32 | (|to| << 1) | (to < 0), whose order is the order of the keys. */
 int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key);
@@ -596,6 +616,29 @@ int bgr_graph_pileup_enabled(const bgr_graph* g);   /* the switch as it stands: 
 int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped);
 int bgr_write_pileup(const char* path, const bgr_graph* g);
 int bgr_write_depth(const char* path, const bgr_graph* g);
+
+/* The SNV sites of a whole run (bgr_variant_site above).  bgr_graph_variants_enable(g, &params) is a sticky switch on the graph like
+ * bgr_graph_links_enable (NULL switches it off; BGR_E_ARG for thresholds out of range, non-ACGT unitig characters, no host blob): every later
+ * bgr_align_all counts unitig abundance and the pileup in every aligner.  When the run collects its aligners, the first table becomes the run's --
+ * its device buffer is moved, nothing is allocated -- and every further aligner's table is added into it on the device (bgr_aligner_pileup_add's two
+ * ways); at the run's end the summed abundance guards it (BGR_E_CAPACITY), the five launches run once and the graph keeps the sites and the
+ * thresholds they were called with.  No table crosses to the host unless bgr_graph_pileup_enable is on as well, in which case its totals are gathered
+ * exactly as without this switch, in addition.  Refusals and failed runs as the pileup's (exhaustive mode: BGR_E_ARG, the message names --vcf).
+ * bgr_graph_variants: the sites of the last such run (*n always; BGR_E_CAPACITY when cap is smaller; BGR_E_ARG when there are none);
+ * bgr_graph_variants_params: the thresholds of those sites.
+ * bgr_write_vcf (host code, deterministic bytes; needs the graph's host blob for the reference letters) writes `sites` -- in (unitig, pos) order, as
+ * delivered -- as VCF 4.2: "##fileformat=VCFv4.2", "##source=bgreat-mi355x", "##bgreat_thresholds=<min_depth=..,min_alt=..,min_af_ppm=..>", the INFO
+ * lines of DP, AD and NN, one "##contig=<ID=id,length=len>" per unitig that carries a site, the "#CHROM POS ID REF ALT QUAL FILTER INFO" line, and per
+ * site: id, pos + 1, ".", the unitig's letter, the passing alleles (by count descending, ties A < C < G < T) comma-separated, ".", "PASS",
+ * "DP=depth;AD=ref,alt1,..;NN=n" with ref = depth - (a + c + g + t + n).  BGR_E_ARG for a site outside the graph, out of order or without a passing allele.
+ * bgr_parse_af_ppm: an allele fraction written as a decimal ("0", "1", "0.2", "0.000001": digits, at most six decimals, value <= 1) -> parts per
+ * million, exactly; BGR_E_ARG for anything else. */
+int bgr_graph_variants_enable(bgr_graph* g, const bgr_variant_params* params);
+int bgr_graph_variants_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_variants(const bgr_graph* g, bgr_variant_site* out, uint64_t cap, uint64_t* n);
+int bgr_graph_variants_params(const bgr_graph* g, bgr_variant_params* out);
+int bgr_write_vcf(const char* path, const bgr_graph* g, const bgr_variant_params* params, const bgr_variant_site* sites, uint64_t n);
+int bgr_parse_af_ppm(const char* text, uint32_t* ppm);
 
 /* The CPUs next to a device (the `local_cpulist` of its PCI function in sysfs, e.g. "0-63,128-191"): threads that feed a GPU and the
  * page-locked memory they allocate belong on its NUMA node.  BGR_E_IO when the platform does not say. */

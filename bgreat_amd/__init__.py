@@ -42,6 +42,8 @@ SYMBOLS = [
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
     "bgr_graph_variants_params", "bgr_write_vcf", "bgr_parse_af_ppm",
+    "bgr_aligner_pileup_strands_enable", "bgr_aligner_pileup_forward", "bgr_aligner_pileup_strand_sites", "bgr_graph_pileup_strands_enable", "bgr_graph_pileup_strands_enabled",
+    "bgr_graph_pileup_forward", "bgr_graph_variants_strands_enable", "bgr_graph_variant_strand_sites", "bgr_write_pileup_strands", "bgr_write_vcf_strands", "bgr_parse_min_alt_strand",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
@@ -279,6 +281,17 @@ def lib():
     L.bgr_graph_variants_params.argtypes = [vp, vp]
     L.bgr_write_vcf.argtypes = [C.c_char_p, vp, vp, vp, u64]
     L.bgr_parse_af_ppm.argtypes = [C.c_char_p, vp]
+    L.bgr_aligner_pileup_strands_enable.argtypes = [vp, u32]
+    L.bgr_aligner_pileup_forward.argtypes = [vp, vp, u64]
+    L.bgr_aligner_pileup_strand_sites.argtypes = [vp, vp, vp, u64, vp]
+    L.bgr_graph_pileup_strands_enable.argtypes = [vp, u32]
+    L.bgr_graph_pileup_strands_enabled.argtypes = [vp]
+    L.bgr_graph_pileup_forward.argtypes = [vp, vp, u64]
+    L.bgr_graph_variants_strands_enable.argtypes = [vp, vp]
+    L.bgr_graph_variant_strand_sites.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_pileup_strands.argtypes = [C.c_char_p, vp]
+    L.bgr_write_vcf_strands.argtypes = [C.c_char_p, vp, vp, vp, u64]
+    L.bgr_parse_min_alt_strand.argtypes = [C.c_char_p, vp]
     L.bgr_write_depth.argtypes = [C.c_char_p, vp]
     L.bgr_link_canonical.argtypes = [C.c_int32, C.c_int32, vp, vp]
     _lib = L
@@ -559,6 +572,39 @@ class Graph:
         sites = np.ascontiguousarray(sites, dtype=VARIANT_DTYPE)
         _check(lib().bgr_write_vcf(path.encode(), self.h, C.byref(prm), sites.ctypes.data if len(sites) else None, len(sites)))
 
+    def pileup_strands_enable(self, on=True):
+        """bgr_graph_pileup_strands_enable: sticky -- every later align_all also counts the forward pileup and gathers it next to the totals
+        (switches pileup_enable on as well; on=False leaves that on)."""
+        _check(lib().bgr_graph_pileup_strands_enable(self.h, int(bool(on))))
+
+    def pileup_strands_enabled(self):
+        """bgr_graph_pileup_strands_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_pileup_strands_enabled(self.h))
+
+    def pileup_forward(self):
+        """bgr_graph_pileup_forward: the forward totals of the last align_all with the strands switch on -> array of PILEUP_DTYPE, one row per base."""
+        return _fetch_forward(lib().bgr_graph_pileup_forward, self)
+
+    def write_pileup_strands(self, path):
+        """bgr_write_pileup_strands: write_pileup's lines with the six forward numbers appended."""
+        _check(lib().bgr_write_pileup_strands(path.encode(), self.h))
+
+    def variants_strands_enable(self, min_depth=2, min_alt=2, min_af_ppm=200000, min_alt_strand=0, on=True):
+        """bgr_graph_variants_strands_enable: variants_enable with the strand filter -- an allele must also be read at least min_alt_strand times on
+        each strand; the run keeps records of VARIANT_STRAND_DTYPE.  on=False switches the variants switch off."""
+        prm = VariantStrandParams(int(min_depth), int(min_alt), int(min_af_ppm), int(min_alt_strand))
+        _check(lib().bgr_graph_variants_strands_enable(self.h, C.byref(prm) if on else None))
+
+    def variant_strand_sites(self):
+        """bgr_graph_variant_strand_sites: the sites of the last align_all with variants_strands_enable on -> array of VARIANT_STRAND_DTYPE."""
+        return _fetch_sites(lambda out, cap, n: lib().bgr_graph_variant_strand_sites(self.h, out, cap, n), VARIANT_STRAND_DTYPE)
+
+    def write_vcf_strands(self, path, sites, params):
+        """bgr_write_vcf_strands: `sites` (VARIANT_STRAND_DTYPE) called with params = (min_depth, min_alt, min_af_ppm, min_alt_strand) as VCF 4.2 with ADF / ADR."""
+        prm = VariantStrandParams(*(int(v) for v in params))
+        sites = np.ascontiguousarray(sites, dtype=VARIANT_STRAND_DTYPE)
+        _check(lib().bgr_write_vcf_strands(path.encode(), self.h, C.byref(prm), sites.ctypes.data if len(sites) else None, len(sites)))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -776,6 +822,20 @@ class Aligner:
         prm = VariantParams(int(min_depth), int(min_alt), int(min_af_ppm))
         return _fetch_sites(lambda out, cap, n: lib().bgr_aligner_pileup_sites(self.h, C.byref(prm), out, cap, n))
 
+    def pileup_strands_enable(self, on=True):
+        """bgr_aligner_pileup_strands_enable: the pileup kernel of every launch from now on also adds the forward observations to a second table
+        (enables the pileup as well; on=False keeps the table and leaves the pileup on)."""
+        _check(lib().bgr_aligner_pileup_strands_enable(self.h, int(bool(on))))
+
+    def pileup_forward(self):
+        """bgr_aligner_pileup_forward -> array of PILEUP_DTYPE: the forward pileup since enable / reset, one row per base, flat in unitig order."""
+        return _fetch_forward(lib().bgr_aligner_pileup_forward, self)
+
+    def pileup_strand_sites(self, min_depth=2, min_alt=2, min_af_ppm=200000, min_alt_strand=0):
+        """bgr_aligner_pileup_strand_sites -> array of VARIANT_STRAND_DTYPE: pileup_sites under the strand filter, with the forward numbers."""
+        prm = VariantStrandParams(int(min_depth), int(min_alt), int(min_af_ppm), int(min_alt_strand))
+        return _fetch_sites(lambda out, cap, n: lib().bgr_aligner_pileup_strand_sites(self.h, C.byref(prm), out, cap, n), VARIANT_STRAND_DTYPE)
+
     def pileup_sites_times(self):
         """bgr_aligner_pileup_sites_times -> the milliseconds of the last pileup_sites' five launches (tile sums, scan, classify, scan, emit)."""
         ms = (C.c_double * 5)()
@@ -897,16 +957,40 @@ class VariantParams(C.Structure):  # bgr_variant_params
     _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_af_ppm", C.c_uint32)]
 
 
-def _fetch_sites(fn):
+# an array of bgr_variant_strand_site: the numbers of bgr_variant_site, those of the forward table, two reserved words
+VARIANT_STRAND_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "pos", "depth", "a", "c", "g", "t", "n", "fdepth", "fa", "fc", "fg", "ft", "fn", "reserved0", "reserved1")])
+
+
+class VariantStrandParams(C.Structure):  # bgr_variant_strand_params
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_af_ppm", C.c_uint32), ("min_alt_strand", C.c_uint32)]
+
+
+def _fetch_forward(fn, obj):
+    g = obj if isinstance(obj, Graph) else obj.graph
+    n = g.info()["total_bases"] // 2
+    out = np.zeros(n, dtype=PILEUP_DTYPE)
+    _check(fn(obj.h, out.ctypes.data, n))
+    return out
+
+
+def _fetch_sites(fn, dtype=None):
     """the two-call form of bgr_aligner_pileup_sites / bgr_graph_variants: the number first (BGR_E_CAPACITY), then the records"""
+    dtype = VARIANT_DTYPE if dtype is None else dtype
     n = C.c_uint64(0)
     rc = fn(None, 0, C.byref(n))
     if rc != -4 or n.value == 0:
         _check(rc)
-        return np.zeros(0, dtype=VARIANT_DTYPE)
-    out = np.zeros(n.value, dtype=VARIANT_DTYPE)
+        return np.zeros(0, dtype=dtype)
+    out = np.zeros(n.value, dtype=dtype)
     _check(fn(out.ctypes.data, n.value, C.byref(n)))
     return out[: n.value]
+
+
+def parse_min_alt_strand(text):
+    """bgr_parse_min_alt_strand: the CLI's --min-alt-strand parser; BgrError for anything but at most nine digits."""
+    v = C.c_uint32(0)
+    _check(lib().bgr_parse_min_alt_strand(text.encode(), C.byref(v)))
+    return int(v.value)
 
 
 def parse_af_ppm(text):

@@ -83,6 +83,12 @@ struct bgr_graph {
     bgr_variant_params variants_prm = {2, 2, 200000}, variants_called = {0, 0, 0};
     struct VariantsRun* variants_run = nullptr;
     std::vector<bgr_variant_site> variants_sites;
+    // strands (bgr_graph_pileup_strands_enable, bgr_graph_variants_strands_enable): the run's aligners also count the forward table; with the pileup
+    // switch its totals are gathered next to pileup_words, with the variants switch it travels with the run's table and the records are 64 bytes
+    bool pileup_strands_on = false, pileup_fwd_valid = false, variants_strands_on = false, variants_strands_valid = false;
+    uint32_t variants_min_alt_strand = 0, variants_called_strand = 0;
+    std::vector<uint32_t> pileup_fwd_words;
+    std::vector<bgr_variant_strand_site> variants_strand_sites;
 };
 
 namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
@@ -124,13 +130,13 @@ struct VariantsRun {   // the pileup table of a run with bgr_graph_variants_enab
     int device = 0, num_cus = 0;
     hipStream_t stream = nullptr;
     BgrDeviceGraph dg;
-    DevBuf table, offs, stage;
+    DevBuf table, offs, stage, table_fwd;   // (table_fwd: only in a run that counts strands)
 };
 static void variants_run_free(bgr_graph* g) {
     if (!g->variants_run) return;
     if (hipSetDevice(g->variants_run->device) == hipSuccess) {
         if (g->variants_run->stream) (void)hipStreamDestroy(g->variants_run->stream);
-        g->variants_run->table.release(); g->variants_run->offs.release(); g->variants_run->stage.release();
+        g->variants_run->table.release(); g->variants_run->offs.release(); g->variants_run->stage.release(); g->variants_run->table_fwd.release();
     }
     delete g->variants_run;
     g->variants_run = nullptr;
@@ -206,6 +212,9 @@ struct bgr_aligner {
     DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
     uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
     const uint64_t* pileup_base_offs = nullptr;
+    bool strands_on = false;        // bgr_aligner_pileup_strands_enable: the pileup kernel also adds the forward observations to a second table
+    DevBuf pileup_fwd;              // that table: the layout of `pileup`, its tail stays 0
+    uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
@@ -595,7 +604,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -897,7 +906,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         if (inline_pack) { pr.ascii = static_cast<const uint8_t*>(d_reads); pr.src_off = static_cast<const uint32_t*>(d_src_off); pr.ascii_bytes = reads_bytes; }
         else { pr.fw3 = io.fw3; pr.nmw = io.nmw; pr.hasn = io.hasn; }
         e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
-                               P.arena_cap, io.read_offs, io.n_reads, pr, a->pileup_base_offs, a->pileup_tab, (uint32_t)a->num_cus, a->stream);
+                               P.arena_cap, io.read_offs, io.n_reads, pr, a->pileup_base_offs, a->pileup_tab, a->strands_on ? a->pileup_fwd_tab : nullptr, (uint32_t)a->num_cus, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_pileup_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_pileup_kernel"));
     }
@@ -1093,7 +1102,10 @@ static int pileup_refusal(const bgr_graph* g, const char* who) {
     return BGR_OK;
 }
 static void pileup_share(bgr_aligner* a) {   // the twins add to the aligner's table
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) { tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on; }
+    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
+        tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;
+        tw->pileup_fwd_tab = a->pileup_fwd_tab; tw->strands_on = a->strands_on;
+    }
 }
 
 int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on) {
@@ -1122,6 +1134,38 @@ int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on) {
         a->pileup_base_offs = static_cast<const uint64_t*>(a->pileup_offs.p);
     }
     a->pileup_on = on != 0;
+    pileup_share(a);
+    return BGR_OK;
+}
+
+int bgr_aligner_pileup_strands_enable(bgr_aligner* a, uint32_t on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: an internal stream of another aligner");
+    bool fresh = false;
+    if (on && !a->pileup_fwd_tab) {   // the second table first: a refusal leaves the aligner as it was
+        const int rc0 = pileup_refusal(a->graph, "bgr_aligner_pileup_strands_enable");
+        if (rc0 != BGR_OK) return rc0;
+        const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2, bytes = bgr::pileup_table_bytes(T, n);
+        HIP_TRY(hipSetDevice(a->device));
+        const hipError_t e = a->pileup_fwd.ensure(bytes);
+        if (e != hipSuccess) {
+            a->pileup_fwd.release();
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_pileup_strands_enable: " + std::to_string(bytes) + " bytes for the forward pileup table (20 more per base of the graph): " + hipGetErrorString(e));
+        }
+        HIP_TRY(hipMemsetAsync(a->pileup_fwd.p, 0, bytes, a->stream));
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        a->pileup_fwd_tab = static_cast<uint32_t*>(a->pileup_fwd.p);
+        fresh = true;
+    }
+    if (on) {
+        const int rc = bgr_aligner_pileup_enable(a, 1);   // (as the pileup enables abundance)
+        if (rc != BGR_OK) {
+            if (fresh) { a->pileup_fwd.release(); a->pileup_fwd_tab = nullptr; }   // (nothing stays allocated behind a refusal)
+            return rc;
+        }
+    }
+    a->strands_on = on != 0;
     pileup_share(a);
     return BGR_OK;
 }
@@ -1155,7 +1199,8 @@ static int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char
     return BGR_OK;
 }
 // the aligner's table on the host (every stream that adds to it waited for), behind the guard
-static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t>& words, uint64_t* skipped) {
+static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t>& words, uint64_t* skipped, bool fwd = false) {
+    if (fwd && !a->pileup_fwd_tab) return fail(BGR_E_ARG, std::string(who) + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
     if (!a->pileup_tab) return fail(BGR_E_ARG, std::string(who) + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
     const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2;
     std::vector<bgr_unitig_abundance> ab(n);
@@ -1165,9 +1210,10 @@ static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t
     HIP_TRY(hipSetDevice(a->device));
     for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     words.resize(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n));
-    if (!words.empty()) HIP_TRY(hipMemcpy(words.data(), a->pileup_tab, words.size() * 4, hipMemcpyDeviceToHost));
+    const uint32_t* tab = fwd ? a->pileup_fwd_tab : a->pileup_tab;
+    if (!words.empty()) HIP_TRY(hipMemcpy(words.data(), tab, words.size() * 4, hipMemcpyDeviceToHost));
     unsigned long long sk = 0;
-    HIP_TRY(hipMemcpy(&sk, reinterpret_cast<const char*>(a->pileup_tab) + bgr::pileup_tail_byte(T, n), 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&sk, reinterpret_cast<const char*>(tab) + bgr::pileup_tail_byte(T, n), 8, hipMemcpyDeviceToHost));
     *skipped = sk;
     return BGR_OK;
 }
@@ -1186,6 +1232,18 @@ int bgr_aligner_pileup(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases, u
     return BGR_OK;
 }
 
+int bgr_aligner_pileup_forward(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases) {
+    if (!a || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: null argument");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: an internal stream of another aligner");
+    if (n_bases != a->graph->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: n_bases is not the sum of the graph's unitig lengths");
+    std::vector<uint32_t> words;
+    uint64_t sk = 0;
+    const int rc = pileup_snapshot(a, "bgr_aligner_pileup_forward", words, &sk, true);
+    if (rc != BGR_OK) return rc;
+    pileup_rows(a->graph, words.data(), out);
+    return BGR_OK;
+}
+
 int bgr_aligner_reset_pileup(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: null aligner");
     if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: an internal stream of another aligner");
@@ -1193,6 +1251,7 @@ int bgr_aligner_reset_pileup(bgr_aligner* a) {
     HIP_TRY(hipSetDevice(a->device));
     for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
+    if (a->pileup_fwd.p) HIP_TRY(hipMemsetAsync(a->pileup_fwd.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     return BGR_OK;   // (the abundance table stays: the guard's column then counts more launches than the pileup holds, which errs on the safe side)
 }
@@ -1202,20 +1261,26 @@ static int variants_collect(bgr_graph* g, bgr_aligner* a);
 static int variants_end(bgr_graph* g, bool ok);
 static bool run_pileup_wanted(const bgr_graph* g) { return g && (g->pileup_on || g->variants_on); }
 static bool run_pileup_variants(const bgr_graph* g) { return g && g->variants_on; }
+static bool run_pileup_strands(const bgr_graph* g) { return g && ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)); }
 static void run_pileup_begin(bgr_graph* g) {
     std::lock_guard<std::mutex> l(g->abundance_m);
     if (g->pileup_on) {
         g->pileup_words.clear();
         g->pileup_skipped = 0;
         g->pileup_valid = false;
+        g->pileup_fwd_words.clear();
+        g->pileup_fwd_valid = false;
     }
     if (g->variants_on) {
         variants_run_free(g);
         g->variants_sites.clear();
         g->variants_valid = false;
+        g->variants_strand_sites.clear();
+        g->variants_strands_valid = false;
     }
 }
 static int run_pileup_enable(bgr_aligner* a) { return bgr_aligner_pileup_enable(a, 1); }
+static int run_pileup_enable_strands(bgr_aligner* a) { return bgr_aligner_pileup_strands_enable(a, 1); }
 static int run_pileup_collect(bgr_graph* g, bgr_aligner* a) {
     if (g->pileup_on) {
         std::vector<uint32_t> words;
@@ -1226,6 +1291,15 @@ static int run_pileup_collect(bgr_graph* g, bgr_aligner* a) {
         if (g->pileup_words.empty()) g->pileup_words.swap(words);
         else for (size_t i = 0; i < words.size(); ++i) g->pileup_words[i] += words[i];   // (mod 2^32: the delta sums commute)
         g->pileup_skipped += sk;
+    }
+    if (g->pileup_on && g->pileup_strands_on) {   // the forward table likewise (its tail is 0)
+        std::vector<uint32_t> words;
+        uint64_t sk = 0;
+        const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk, true);
+        if (rc != BGR_OK) return rc;
+        std::lock_guard<std::mutex> l(g->abundance_m);
+        if (g->pileup_fwd_words.empty()) g->pileup_fwd_words.swap(words);
+        else for (size_t i = 0; i < words.size(); ++i) g->pileup_fwd_words[i] += words[i];
     }
     return g->variants_on ? variants_collect(g, a) : BGR_OK;   // (behind the snapshot: the first aligner's table leaves it here)
 }
@@ -1240,6 +1314,9 @@ static int run_pileup_end(bgr_graph* g, bool ok) {   // behind the abundance's e
         }
         if (!ok || rc != BGR_OK) { g->pileup_words.clear(); g->pileup_words.shrink_to_fit(); }
         g->pileup_valid = ok && rc == BGR_OK;
+        if (g->pileup_strands_on && g->pileup_valid && g->pileup_fwd_words.empty()) g->pileup_fwd_words.assign(g->pileup_words.size(), 0u);
+        if (!g->pileup_strands_on || !g->pileup_valid) { g->pileup_fwd_words.clear(); g->pileup_fwd_words.shrink_to_fit(); }
+        g->pileup_fwd_valid = g->pileup_strands_on && g->pileup_valid;
     }
     if (g->variants_on) {
         const int vrc = variants_end(g, ok && rc == BGR_OK);
@@ -1247,7 +1324,7 @@ static int run_pileup_end(bgr_graph* g, bool ok) {   // behind the abundance's e
     }
     return rc;
 }
-static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end, run_pileup_variants}, true);
+static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end, run_pileup_variants, run_pileup_strands, run_pileup_enable_strands}, true);
 
 int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on) {
     if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_enable: null graph");
@@ -1261,6 +1338,18 @@ int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on) {
 }
 
 int bgr_graph_pileup_enabled(const bgr_graph* g) { return g && g->pileup_on ? 1 : 0; }
+
+int bgr_graph_pileup_strands_enable(bgr_graph* g, uint32_t on) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_strands_enable: null graph");
+    if (on) {
+        const int rc = bgr_graph_pileup_enable(g, 1);   // (as the aligner's switch enables the aligner's pileup)
+        if (rc != BGR_OK) return rc;
+    }
+    g->pileup_strands_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_pileup_strands_enabled(const bgr_graph* g) { return g && g->pileup_strands_on ? 1 : 0; }
 
 static int graph_pileup_check(const bgr_graph* g, const char* who) {
     if (!g->pileup_valid) return fail(BGR_E_ARG, std::string(who) + ": no totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_enable on");
@@ -1277,24 +1366,44 @@ int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases,
     return BGR_OK;
 }
 
-// the two writers: host code, deterministic bytes, straight from the graph's totals
-static int pileup_write(const char* path, const bgr_graph* g, bool sites, const char* who) {
-    if (!path || !g) return fail(BGR_E_ARG, std::string(who) + ": null argument");
-    const int rc = graph_pileup_check(g, who);
+static int graph_pileup_fwd_check(const bgr_graph* g, const char* who) {
+    if (!g->pileup_valid || !g->pileup_fwd_valid)
+        return fail(BGR_E_ARG, std::string(who) + ": no forward totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_strands_enable on");
+    return BGR_OK;
+}
+
+int bgr_graph_pileup_forward(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases) {
+    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: null argument");
+    const int rc = graph_pileup_fwd_check(g, "bgr_graph_pileup_forward");
     if (rc != BGR_OK) return rc;
+    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: n_bases is not the sum of the graph's unitig lengths");
+    pileup_rows(g, g->pileup_fwd_words.data(), out);
+    return BGR_OK;
+}
+
+// the writers: host code, deterministic bytes, straight from the graph's totals
+static int pileup_write(const char* path, const bgr_graph* g, bool sites, const char* who, bool strands = false) {
+    if (!path || !g) return fail(BGR_E_ARG, std::string(who) + ": null argument");
+    const int rc = strands ? graph_pileup_fwd_check(g, who) : graph_pileup_check(g, who);
+    if (rc != BGR_OK) return rc;
+    std::vector<bgr_pileup_base> frows(strands ? g->header.max_unitig_len + 1 : 0);
     const uint64_t n = g->header.n_unitigs;
     std::vector<bgr_pileup_base> rows(g->header.max_unitig_len + 1);   // (converted unitig by unitig: no second table on the host)
     const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
     const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
     FILE* f = fopen(path, "wb");
     if (!f) return fail(BGR_E_IO, std::string(who) + ": cannot open " + path);
-    std::string buf = sites ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\n" : "";
+    std::string buf = strands ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tdepth+\tA+\tC+\tG+\tT+\tN+\n" : sites ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\n" : "";
     bool ok = true;
     auto flush = [&](bool all) { if (ok && !buf.empty() && (all || buf.size() > (1u << 20))) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); } };
     for (uint64_t id = 1; id <= n && ok; ++id) {
         const uint64_t len = meta[id].len;
         if (len > rows.size()) rows.resize(len);
         pileup_unitig_rows(g, g->pileup_words.data(), id, rows.data());
+        if (strands) {
+            if (len > frows.size()) frows.resize(len);
+            pileup_unitig_rows(g, g->pileup_fwd_words.data(), id, frows.data());
+        }
         const bgr_pileup_base* r = rows.data();
         if (sites) {
             for (uint64_t pos = 0; pos < len; ++pos) {
@@ -1304,6 +1413,7 @@ static int pileup_write(const char* path, const bgr_graph* g, bool sites, const 
                 buf += std::to_string(id); buf += '\t'; buf += std::to_string(pos); buf += '\t';
                 buf += "ACGT"[(seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u];
                 for (const uint32_t v : {b.depth, b.a, b.c, b.g, b.t, b.n}) { buf += '\t'; buf += std::to_string(v); }
+                if (strands) { const bgr_pileup_base& fb = frows[pos]; for (const uint32_t v : {fb.depth, fb.a, fb.c, fb.g, fb.t, fb.n}) { buf += '\t'; buf += std::to_string(v); } }
                 buf += '\n';
             }
         } else {
@@ -1323,6 +1433,7 @@ static int pileup_write(const char* path, const bgr_graph* g, bool sites, const 
 }
 int bgr_write_pileup(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup"); }
 int bgr_write_depth(const char* path, const bgr_graph* g) { return pileup_write(path, g, false, "bgr_write_depth"); }
+int bgr_write_pileup_strands(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup_strands", true); }
 
 
 // ---- SNV sites (bgr_variant_site in include/bgreat_gpu.h has the definition; variants_kernels.h the passes) -------------------------------------
@@ -1360,6 +1471,47 @@ static int variants_call(const BgrDeviceGraph& dg, const bgr_graph* g, const uin
         if (ms) HIP_TRY(hipEventRecord(ev[5], stream));
         if (vec) { vec->resize(total); out = vec->data(); }
         HIP_TRY(hipMemcpyAsync(out, outbuf.p, total * sizeof(bgr_variant_site), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (ms)
+        for (int i = 0; i < (total ? 5 : 4); ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, ev[i], ev[i + 1])); ms[i] = f; }
+    return BGR_OK;
+}
+
+// the same with the forward table next to the total one: 64-byte records under the strand filter
+static int variants_strands_call(const BgrDeviceGraph& dg, const bgr_graph* g, const uint32_t* table, const uint32_t* table_fwd, const uint64_t* base_offs, const bgr_variant_strand_params& prm,
+                                 DevBuf& scratch, DevBuf& outbuf, hipStream_t stream, const char* who, std::vector<bgr_variant_strand_site>* vec, bgr_variant_strand_site* out, uint64_t cap,
+                                 uint64_t* n, double* ms) {
+    static_assert(sizeof(bgr_variant_strand_site) == 64, "sixteen u32 per site");
+    const uint64_t nu = g->header.n_unitigs, T = g->header.total_bases / 2, tiles = bgr::variants_tiles(T, nu);
+    *n = 0;
+    if (ms) for (int i = 0; i < 5; ++i) ms[i] = 0;
+    if (vec) vec->clear();
+    if (tiles == 0 || nu == 0) return BGR_OK;
+    hipError_t e = scratch.ensure(bgr::variants_strands_scratch_bytes(tiles));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the passes' tile arrays: " + hipGetErrorString(e)); }
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 6; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+    if (ms) {
+        for (int i = 0; i < 6; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+        HIP_TRY(hipEventRecord(ev[0], stream));
+    }
+    e = bgr::launch_variants_strands_count(dg, nu, T, table, table_fwd, base_offs, prm, scratch.p, stream, ms ? ev + 1 : nullptr);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_*_kernel, strands): " + hipGetErrorString(e));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, bgr::variants_total_word(scratch.p, tiles), 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n = total;
+    if (total > T) return fail(BGR_E_INTERNAL, std::string(who) + ": more sites than bases");
+    if (!vec && total > cap) return fail(BGR_E_CAPACITY, std::string(who) + ": " + std::to_string(total) + " sites, room for " + std::to_string(cap));
+    if (total) {
+        e = outbuf.ensure(total * sizeof(bgr_variant_strand_site));
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": " + std::to_string(total) + " site records on the device: " + hipGetErrorString(e)); }
+        e = bgr::launch_variants_strands_emit(dg, nu, T, table, table_fwd, base_offs, prm, scratch.p, static_cast<bgr_variant_strand_site*>(outbuf.p), stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_classify_kernel, strands, emit): " + hipGetErrorString(e));
+        if (ms) HIP_TRY(hipEventRecord(ev[5], stream));
+        if (vec) { vec->resize(total); out = vec->data(); }
+        HIP_TRY(hipMemcpyAsync(out, outbuf.p, total * sizeof(bgr_variant_strand_site), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
     }
     if (ms)
@@ -1410,6 +1562,24 @@ int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, b
                          a->knob_no_events ? nullptr : a->var_ms);
 }
 
+int bgr_aligner_pileup_strand_sites(bgr_aligner* a, const bgr_variant_strand_params* params, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!a || !params || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: null argument");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: an internal stream of another aligner");
+    if (!bgr::variants_params_ok(bgr_variant_params{params->min_depth, params->min_alt, params->min_af_ppm}))
+        return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
+    if (!a->pileup_tab || !a->pileup_fwd_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
+    const uint64_t nu = a->graph->header.n_unitigs;
+    std::vector<bgr_unitig_abundance> ab(nu);
+    int rc = bgr_aligner_abundance(a, ab.data(), nu);   // (synchronises the aligner's stream and its twins')
+    if (rc == BGR_OK) rc = pileup_guard(ab.data(), nu, "bgr_aligner_pileup_strand_sites");
+    if (rc != BGR_OK) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    return variants_strands_call(a->dg, a->graph, a->pileup_tab, a->pileup_fwd_tab, a->pileup_base_offs, *params, a->var_scratch, a->var_out, a->stream, "bgr_aligner_pileup_strand_sites", nullptr,
+                                 out, cap, n, a->knob_no_events ? nullptr : a->var_ms);
+}
+
 int bgr_aligner_pileup_sites_times(bgr_aligner* a, double ms[5]) {
     if (!a || !ms) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites_times: null argument");
     for (int i = 0; i < 5; ++i) ms[i] = a->var_ms[i];
@@ -1421,17 +1591,23 @@ int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src) {
     if (dst->is_twin || src->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: an internal stream of another aligner");
     if (dst == src || dst->graph != src->graph) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: two different aligners of one graph are needed");
     if (!dst->pileup_tab || !src->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: the pileup was never enabled on one of the aligners (bgr_aligner_pileup_enable)");
+    if (!dst->pileup_fwd_tab != !src->pileup_fwd_tab)
+        return fail(BGR_E_ARG, "bgr_aligner_pileup_add: one of the aligners has a forward table (bgr_aligner_pileup_strands_enable) and the other has none");
     HIP_TRY(hipSetDevice(src->device));
     for (bgr_aligner* x = src; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     HIP_TRY(hipSetDevice(dst->device));
     for (bgr_aligner* x = dst; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     const uint64_t bytes = bgr::pileup_table_bytes(dst->graph->header.total_bases / 2, dst->graph->header.n_unitigs);
-    return variants_table_add(dst->pileup_tab, dst->device, src->pileup_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
+    const int rc = variants_table_add(dst->pileup_tab, dst->device, src->pileup_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
+    if (rc != BGR_OK || !dst->pileup_fwd_tab) return rc;
+    return variants_table_add(dst->pileup_fwd_tab, dst->device, src->pileup_fwd_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
 }
 
 // a run's aligner, its streams idle from here on: the first one's table becomes the run's (the buffers move: nothing is allocated), the others' are added
 static int variants_collect(bgr_graph* g, bgr_aligner* a) {
     if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_align_all: the pileup was never enabled on an aligner of the run");
+    const bool strands = g->variants_strands_on;   // the forward table travels with the total one
+    if (strands && !a->pileup_fwd_tab) return fail(BGR_E_ARG, "bgr_align_all: strands were never counted on an aligner of the run");
     HIP_TRY(hipSetDevice(a->device));
     for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     std::lock_guard<std::mutex> l(g->abundance_m);   // (the lanes of a split run end side by side: one at a time here)
@@ -1441,6 +1617,7 @@ static int variants_collect(bgr_graph* g, bgr_aligner* a) {
         if (hipStreamCreate(&r->stream) != hipSuccess) { delete r; (void)hipGetLastError(); return fail(BGR_E_HIP, "bgr_align_all: a stream for the run's pileup table"); }
         std::swap(r->table, a->pileup);
         std::swap(r->offs, a->pileup_offs);
+        if (strands) { std::swap(r->table_fwd, a->pileup_fwd); a->pileup_fwd_tab = nullptr; a->strands_on = false; }
         a->pileup_tab = nullptr; a->pileup_base_offs = nullptr; a->pileup_on = false;
         pileup_share(a);
         g->variants_run = r;
@@ -1448,8 +1625,11 @@ static int variants_collect(bgr_graph* g, bgr_aligner* a) {
     }
     VariantsRun* r = g->variants_run;
     HIP_TRY(hipSetDevice(r->device));
-    return variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->pileup_tab, a->device, bgr::pileup_table_bytes(g->header.total_bases / 2, g->header.n_unitigs),
-                              r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
+    const uint64_t bytes = bgr::pileup_table_bytes(g->header.total_bases / 2, g->header.n_unitigs);
+    const int rc = variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->pileup_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
+    if (rc != BGR_OK || !strands) return rc;
+    if (!r->table_fwd.p) return fail(BGR_E_INTERNAL, "bgr_align_all: the run's pileup table has no forward table");
+    return variants_table_add(static_cast<uint32_t*>(r->table_fwd.p), r->device, a->pileup_fwd_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
 }
 // the run's end: behind the guard of the summed abundance the passes run once on the run's table; the table is freed whatever happens
 static int variants_end(bgr_graph* g, bool ok) {
@@ -1461,16 +1641,29 @@ static int variants_end(bgr_graph* g, bool ok) {
             VariantsRun* r = g->variants_run;
             DevBuf scratch, outbuf;
             uint64_t n = 0;
-            rc = hipSetDevice(r->device) == hipSuccess ? variants_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint64_t*>(r->offs.p), g->variants_prm, scratch, outbuf,
-                                                                       r->stream, "bgr_align_all", &g->variants_sites, nullptr, 0, &n, nullptr)
-                                                       : fail(BGR_E_HIP, "bgr_align_all: hipSetDevice for the run's pileup table");
+            if (hipSetDevice(r->device) != hipSuccess) rc = fail(BGR_E_HIP, "bgr_align_all: hipSetDevice for the run's pileup table");
+            else if (!g->variants_strands_on)
+                rc = variants_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint64_t*>(r->offs.p), g->variants_prm, scratch, outbuf, r->stream, "bgr_align_all",
+                                   &g->variants_sites, nullptr, 0, &n, nullptr);
+            else if (!r->table_fwd.p) rc = fail(BGR_E_INTERNAL, "bgr_align_all: the run's pileup table has no forward table");
+            else {
+                const bgr_variant_strand_params sp = {g->variants_prm.min_depth, g->variants_prm.min_alt, g->variants_prm.min_af_ppm, g->variants_min_alt_strand};
+                rc = variants_strands_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint32_t*>(r->table_fwd.p), static_cast<const uint64_t*>(r->offs.p), sp, scratch,
+                                           outbuf, r->stream, "bgr_align_all", &g->variants_strand_sites, nullptr, 0, &n, nullptr);
+                if (rc == BGR_OK) {   // (bgr_graph_variants then delivers the same sites without the forward numbers)
+                    g->variants_sites.resize(g->variants_strand_sites.size());
+                    for (size_t i = 0; i < g->variants_sites.size(); ++i) memcpy(&g->variants_sites[i], &g->variants_strand_sites[i], sizeof(bgr_variant_site));
+                }
+            }
             scratch.release(); outbuf.release();
         }
     }
     variants_run_free(g);
-    if (!ok || rc != BGR_OK) { g->variants_sites.clear(); g->variants_sites.shrink_to_fit(); }
+    if (!ok || rc != BGR_OK) { g->variants_sites.clear(); g->variants_sites.shrink_to_fit(); g->variants_strand_sites.clear(); g->variants_strand_sites.shrink_to_fit(); }
     g->variants_called = g->variants_prm;
+    g->variants_called_strand = g->variants_min_alt_strand;
     g->variants_valid = ok && rc == BGR_OK;
+    g->variants_strands_valid = g->variants_valid && g->variants_strands_on;
     return rc;
 }
 
@@ -1484,6 +1677,28 @@ int bgr_graph_variants_enable(bgr_graph* g, const bgr_variant_params* params) {
         g->variants_prm = *params;
     }
     g->variants_on = params != nullptr;
+    g->variants_strands_on = false;   // (the plain switch: 32-byte records, no forward table)
+    return BGR_OK;
+}
+
+int bgr_graph_variants_strands_enable(bgr_graph* g, const bgr_variant_strand_params* params) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_variants_strands_enable: null graph");
+    if (!params) return bgr_graph_variants_enable(g, nullptr);
+    const bgr_variant_params prm = {params->min_depth, params->min_alt, params->min_af_ppm};
+    const int rc = bgr_graph_variants_enable(g, &prm);
+    if (rc != BGR_OK) return rc;
+    g->variants_strands_on = true;
+    g->variants_min_alt_strand = params->min_alt_strand;
+    return BGR_OK;
+}
+
+int bgr_graph_variant_strand_sites(const bgr_graph* g, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_variant_strand_sites: null argument");
+    if (!g->variants_strands_valid) return fail(BGR_E_ARG, "bgr_graph_variant_strand_sites: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_strands_enable on");
+    *n = g->variants_strand_sites.size();
+    if (g->variants_strand_sites.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_variant_strand_sites: " + std::to_string(g->variants_strand_sites.size()) + " sites, room for " + std::to_string(cap));
+    if (!g->variants_strand_sites.empty()) memcpy(out, g->variants_strand_sites.data(), g->variants_strand_sites.size() * sizeof(bgr_variant_strand_site));
     return BGR_OK;
 }
 
@@ -1519,6 +1734,28 @@ int bgr_write_vcf(const char* path, const bgr_graph* g, const bgr_variant_params
     bool ok = bgr::vcf_write(f, meta, seq, g->header.n_unitigs, *params, sites, n, &err);
     if (fclose(f) != 0) ok = false;
     if (!ok) return fail(BGR_E_IO, std::string("bgr_write_vcf: write to ") + path + " failed");
+    return BGR_OK;
+}
+
+int bgr_write_vcf_strands(const char* path, const bgr_graph* g, const bgr_variant_strand_params* params, const bgr_variant_strand_site* sites, uint64_t n) {
+    if (!path || !g || !params || (n && !sites)) return fail(BGR_E_ARG, "bgr_write_vcf_strands: null argument");
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_vcf_strands: the graph has no host blob (the reference letters are read from it)");
+    if (g->header.has_exc) return fail(BGR_E_ARG, "bgr_write_vcf_strands: a graph of ACGT-only unitigs is needed (--vcf): the 2-bit store does not spell other characters");
+    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
+    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
+    std::string err;
+    if (!bgr::vcf_strands_write(nullptr, meta, seq, g->header.n_unitigs, *params, sites, n, &err)) return fail(BGR_E_ARG, "bgr_write_vcf_strands: " + err);   // (the checks alone)
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string("bgr_write_vcf_strands: cannot open ") + path);
+    bool ok = bgr::vcf_strands_write(f, meta, seq, g->header.n_unitigs, *params, sites, n, &err);
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_vcf_strands: write to ") + path + " failed");
+    return BGR_OK;
+}
+
+int bgr_parse_min_alt_strand(const char* text, uint32_t* out) {
+    if (!text || !out) return fail(BGR_E_ARG, "bgr_parse_min_alt_strand: null argument");
+    if (!bgr::parse_min_alt_strand(text, out)) return fail(BGR_E_ARG, std::string("bgr_parse_min_alt_strand: '") + text + "' is no non-negative integer of at most nine digits");
     return BGR_OK;
 }
 
@@ -2235,6 +2472,7 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
         tw->knob_abundance_form = a->knob_abundance_form;
         tw->knob_links_form = a->knob_links_form;
         tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;   // (likewise)
+        tw->pileup_fwd_tab = a->pileup_fwd_tab; tw->strands_on = a->strands_on;
         tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on;   // (one table for the aligner and its twins: the atomics are device-scope)
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         al[t] = tw;

@@ -28,6 +28,10 @@
 //                                                               at least the fraction F of the covering reads (0.2: a decimal with at most six places); called on the
 //                                                               device from the pileup counted while mapping -- the table never crosses to the host; greedy modes, ACGT-only
 //                                                               unitigs: include/bgreat_gpu.h)
+//                                                   --strands [--min-alt-strand N] (with --pileup and / or --vcf: count the pileup per strand as well -- a read counts forward on a unitig when, as given
+//                                                               in the input, it runs along the strand the unitig file spells; --pileup FILE gains the columns depth+ A+ C+ G+ T+ N+,
+//                                                               --vcf FILE the INFO fields ADF / ADR, and an ALT must be read at least N times (0) on each strand;
+//                                                               --min-alt-strand implies --strands and needs --vcf)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -52,7 +56,8 @@ int main(int argc, char** argv) {
     std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
-    bool vprm_given = false;
+    bool vprm_given = false, strands = false, strand_given = false;
+    uint32_t min_alt_strand = 0;   // --min-alt-strand
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
@@ -61,7 +66,7 @@ int main(int argc, char** argv) {
                                 {"set", required_argument, nullptr, 1007}, {"gaf", no_argument, nullptr, 1008}, {"abundance", required_argument, nullptr, 1009}, {"gfa", required_argument, nullptr, 1010},
                                 {"pileup", required_argument, nullptr, 1011}, {"depth", required_argument, nullptr, 1012},
                                 {"vcf", required_argument, nullptr, 1013}, {"min-depth", required_argument, nullptr, 1014}, {"min-alt", required_argument, nullptr, 1015},
-                                {"min-af", required_argument, nullptr, 1016},
+                                {"min-af", required_argument, nullptr, 1016}, {"strands", no_argument, nullptr, 1017}, {"min-alt-strand", required_argument, nullptr, 1018},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -113,6 +118,15 @@ int main(int argc, char** argv) {
                 if (bgr_parse_af_ppm(optarg, &vprm.min_af_ppm) != BGR_OK) die("--min-af");
                 vprm_given = true;
                 break;
+            case 1017: strands = true; break;
+            case 1018: {   // a non-negative integer, digits only
+                if (bgr_parse_min_alt_strand(optarg, &min_alt_strand) != BGR_OK) {
+                    fprintf(stderr, "bgreat: --min-alt-strand takes a non-negative integer of at most nine digits, not '%s'\n", optarg);
+                    return 2;
+                }
+                strands = strand_given = true;
+                break;
+            }
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -125,6 +139,8 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (vprm_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-depth, --min-alt and --min-af are thresholds of --vcf FILE\n"); return 2; }
+    if (strand_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-alt-strand is a threshold of --vcf FILE\n"); return 2; }
+    if (strands && vcfFile.empty() && pileupFile.empty()) { fprintf(stderr, "bgreat: --strands adds the per-strand counts to --pileup FILE and / or --vcf FILE\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -160,7 +176,10 @@ int main(int argc, char** argv) {
     if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
-    if (!vcfFile.empty() && bgr_graph_variants_enable(graph, &vprm) != BGR_OK) die("--vcf");   // (likewise; it implies the counting of the pileup, whose tables then stay on the devices)
+    const bgr_variant_strand_params sprm = {vprm.min_depth, vprm.min_alt, vprm.min_af_ppm, min_alt_strand};
+    if (strands && !pileupFile.empty() && bgr_graph_pileup_strands_enable(graph, 1) != BGR_OK) die("--strands");   // (the forward totals reach the host next to the totals)
+    if (!vcfFile.empty() && strands) { if (bgr_graph_variants_strands_enable(graph, &sprm) != BGR_OK) die("--vcf"); }
+    else if (!vcfFile.empty() && bgr_graph_variants_enable(graph, &vprm) != BGR_OK) die("--vcf");   // (likewise; it implies the counting of the pileup, whose tables then stay on the devices)
     auto start = std::chrono::system_clock::now();
     uint64_t tot[5] = {0, 0, 0, 0, 0};
     double map_secs = 0;
@@ -188,9 +207,15 @@ int main(int argc, char** argv) {
         if (n_links && bgr_graph_links(graph, links.data(), n_links, &n_links) != BGR_OK) die("gfa");
         if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), n_links) != BGR_OK) die("gfa");
     }
-    if (!pileupFile.empty() && bgr_write_pileup(pileupFile.c_str(), graph) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
+    if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");
-    if (!vcfFile.empty()) {   // (the run has called the sites: they, not the table, are what the graph keeps)
+    if (!vcfFile.empty() && strands) {   // (the 64-byte records of a run that counted strands)
+        uint64_t n_sites = 0;
+        if (bgr_graph_variant_strand_sites(graph, nullptr, 0, &n_sites) != BGR_OK && n_sites == 0) die("--vcf");   // (BGR_E_CAPACITY with the number of sites)
+        std::vector<bgr_variant_strand_site> sites(n_sites);
+        if (n_sites && bgr_graph_variant_strand_sites(graph, sites.data(), n_sites, &n_sites) != BGR_OK) die("--vcf");
+        if (bgr_write_vcf_strands(vcfFile.c_str(), graph, &sprm, sites.data(), n_sites) != BGR_OK) die("--vcf");
+    } else if (!vcfFile.empty()) {   // (the run has called the sites: they, not the table, are what the graph keeps)
         uint64_t n_sites = 0;
         if (bgr_graph_variants(graph, nullptr, 0, &n_sites) != BGR_OK && n_sites == 0) die("--vcf");   // (BGR_E_CAPACITY with the number of sites)
         std::vector<bgr_variant_site> sites(n_sites);

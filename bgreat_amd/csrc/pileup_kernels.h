@@ -37,8 +37,10 @@ struct PileupReads {
 
 // base_offs: u64[n_unitigs + 2], base_offs[id] = sum of the lengths of the unitigs 1 .. id - 1 (base_offs[n_unitigs + 1] = T); table as above,
 // added into.  arena_ints: ints the arena buffer holds (a row that would end beyond it is skipped).  Launches nothing for zero reads.
+// table_fwd: null, or a second table of the same layout and size that receives the forward observations only (an occurrence whose read, as given
+// in the input, is collinear with the strand the unitig file spells); its tail stays 0.  Null launches the kernel as it is without the switch.
 hipError_t launch_pileup(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint2* results, const int32_t* arena, uint64_t arena_ints,
-                         const uint64_t* read_offs, uint32_t n_reads, const PileupReads& reads, const uint64_t* base_offs, uint32_t* table, uint32_t num_cus,
+                         const uint64_t* read_offs, uint32_t n_reads, const PileupReads& reads, const uint64_t* base_offs, uint32_t* table, uint32_t* table_fwd, uint32_t num_cus,
                          hipStream_t stream);
 
 }  // namespace bgr

@@ -15,6 +15,9 @@
 // complement's.  A path that spells no walk (gaf_stat's condition) adds nothing and counts in the tail word: a path of more than sixteen
 // unitigs is therefore walked once before anything is added.
 // Integer adds commute (mod 2^32): the table does not depend on the geometry or the order of the launches.
+// Strands (bgr_aligner_pileup_strands_enable): sB, the half of the store the read runs along, is 0 exactly when the read as given in the input is
+// collinear with the strand the unitig file spells (no ST_RC and glued on forward, or ST_RC and glued on reversed).  The STRANDS instances repeat
+// the adds of such an occurrence into a second table of the same layout, at the same indices: the forward pileup.
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
@@ -31,10 +34,13 @@ constexpr int kSrcAscii = 0, kSrcText = 1, kSrcPlanes = 2;
 
 using bgr::u64;
 
-template <bool WIDE, int SRC>
+// STRANDS: an occurrence the read runs along forward -- the read as given in the input is collinear with the strand the unitig file spells, sB == 0 --
+// repeats its two delta atomics and each of its alt atomics into a second table of the same layout (alt_f, delta_f): the forward pileup of
+// bgr_aligner_pileup_forward.  A compile-time constant: the instances without it are the kernel as it was.
+template <bool WIDE, int SRC, bool STRANDS>
 __global__ void __launch_bounds__(256) bgr_pileup_kernel(BgrDeviceGraph g, uint32_t n_unitigs, u64 total_bases, const uint2* results, const int32_t* arena, u64 arena_ints,
                                                          const u64* read_offs, uint32_t n_reads, bgr::PileupReads rd, const u64* base_offs, uint32_t* alt, uint32_t* delta,
-                                                         unsigned long long* skipped) {
+                                                         unsigned long long* skipped, uint32_t* alt_f, uint32_t* delta_f) {
     using namespace bgr;
     const u64 alt_words = 4 * total_bases, delta_words = total_bases + n_unitigs;
     const uint32_t sub = threadIdx.x & 15, per_block = blockDim.x >> 4, stride = gridDim.x * per_block;
@@ -73,6 +79,10 @@ __global__ void __launch_bounds__(256) bgr_pileup_kernel(BgrDeviceGraph g, uint3
                 if (db < delta_words) {   // (da < db: both inside the unitig's len + 1 words)
                     atomicAdd(delta + da, 1u);
                     atomicAdd(delta + db, 0xFFFFFFFFu);
+                    if (STRANDS && w.st == (rc ? 1u : 0u)) {   // (sB == 0, below)
+                        atomicAdd(delta_f + da, 1u);
+                        atomicAdd(delta_f + db, 0xFFFFFFFFu);
+                    }
                 }
             }
             // what the compare needs of lane v's unitig: its extent in read positions, cst, and where a base of the store counts
@@ -141,7 +151,10 @@ __global__ void __launch_bounds__(256) bgr_pileup_kernel(BgrDeviceGraph g, uint3
                                 }
                                 const int64_t B = (int64_t)(t0 + i) + cv;
                                 const u64 idx = 4 * (u64)(vS ? kv - B : kv + B) + (code == 4u ? ref : code);
-                                if (idx < alt_words) atomicAdd(alt + idx, 1u);
+                                if (idx < alt_words) {
+                                    atomicAdd(alt + idx, 1u);
+                                    if (STRANDS && !vS) atomicAdd(alt_f + idx, 1u);
+                                }
                             }
                         }
                     }
@@ -154,22 +167,22 @@ __global__ void __launch_bounds__(256) bgr_pileup_kernel(BgrDeviceGraph g, uint3
 
 namespace bgr {
 
-template <bool WIDE>
+template <bool WIDE, bool STRANDS>
 static void launch_src(int src, uint32_t blocks, hipStream_t stream, const BgrDeviceGraph& g, uint32_t nu, uint64_t total_bases, const uint2* results, const int32_t* arena,
                        uint64_t arena_ints, const uint64_t* read_offs, uint32_t n_reads, const PileupReads& rd, const uint64_t* base_offs, uint32_t* alt, uint32_t* delta,
-                       unsigned long long* skipped) {
+                       unsigned long long* skipped, uint32_t* alt_f, uint32_t* delta_f) {
     const u64* ro = reinterpret_cast<const u64*>(read_offs);
     const u64* bo = reinterpret_cast<const u64*>(base_offs);
     if (src == kSrcAscii)
-        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcAscii>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped);
+        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcAscii, STRANDS>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped, alt_f, delta_f);
     else if (src == kSrcText)
-        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcText>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped);
+        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcText, STRANDS>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped, alt_f, delta_f);
     else
-        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcPlanes>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped);
+        hipLaunchKernelGGL((bgr_pileup_kernel<WIDE, kSrcPlanes, STRANDS>), dim3(blocks), dim3(256), 0, stream, g, nu, (u64)total_bases, results, arena, (u64)arena_ints, ro, n_reads, rd, bo, alt, delta, skipped, alt_f, delta_f);
 }
 
 hipError_t launch_pileup(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint2* results, const int32_t* arena, uint64_t arena_ints,
-                         const uint64_t* read_offs, uint32_t n_reads, const PileupReads& reads, const uint64_t* base_offs, uint32_t* table, uint32_t num_cus,
+                         const uint64_t* read_offs, uint32_t n_reads, const PileupReads& reads, const uint64_t* base_offs, uint32_t* table, uint32_t* table_fwd, uint32_t num_cus,
                          hipStream_t stream) {
     if (n_reads == 0) return hipSuccess;
     if (n_unitigs >= 0x40000000ull || !table || !base_offs || !read_offs) return hipErrorInvalidValue;
@@ -182,8 +195,12 @@ hipError_t launch_pileup(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t t
     uint32_t* alt = table;
     uint32_t* delta = table + pileup_alt_words(total_bases);
     unsigned long long* skipped = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(table) + pileup_tail_byte(total_bases, n_unitigs));
-    if (g.k > 33) launch_src<true>(src, (uint32_t)blocks, stream, g, (uint32_t)n_unitigs, total_bases, results, arena, arena_ints, read_offs, n_reads, reads, base_offs, alt, delta, skipped);
-    else launch_src<false>(src, (uint32_t)blocks, stream, g, (uint32_t)n_unitigs, total_bases, results, arena, arena_ints, read_offs, n_reads, reads, base_offs, alt, delta, skipped);
+    uint32_t* alt_f = table_fwd;   // (null: the kernel without the second table)
+    uint32_t* delta_f = table_fwd ? table_fwd + pileup_alt_words(total_bases) : nullptr;
+#define BGR_PILEUP_LAUNCH(W, S) launch_src<W, S>(src, (uint32_t)blocks, stream, g, (uint32_t)n_unitigs, total_bases, results, arena, arena_ints, read_offs, n_reads, reads, base_offs, alt, delta, skipped, alt_f, delta_f)
+    if (g.k > 33) { if (table_fwd) BGR_PILEUP_LAUNCH(true, true); else BGR_PILEUP_LAUNCH(true, false); }
+    else { if (table_fwd) BGR_PILEUP_LAUNCH(false, true); else BGR_PILEUP_LAUNCH(false, false); }
+#undef BGR_PILEUP_LAUNCH
     return hipGetLastError();
 }
 

@@ -48,7 +48,7 @@ RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abu
 RunLinks g_run_links = {nullptr, nullptr, nullptr, nullptr, nullptr};    // run_links.h: likewise
 // the graph's switch (bgr_graph_links_enable): the run counts links, and unitig abundance with them, whatever bgr_run_options.abundance says
 static bool run_links(const bgr_graph* g) { return g_run_links.wanted && g_run_links.wanted(g); }
-RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
+RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
 // the graph's switches (bgr_graph_pileup_enable, bgr_graph_variants_enable): the run counts per-base depth and mismatches, and unitig abundance with them
 static bool run_pileup(const bgr_graph* g) { return g_run_pileup.wanted && g_run_pileup.wanted(g); }
 }
@@ -627,7 +627,8 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
             if (opt->abundance || bgr::run_links(graph) || bgr::run_pileup(graph)) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
             if (rc == BGR_OK && bgr::run_links(graph)) rc = bgr::g_run_links.enable(a);   // ... and by the links kernel
-            if (rc == BGR_OK && bgr::run_pileup(graph)) rc = bgr::g_run_pileup.enable(a);   // ... and by the pileup kernel
+            if (rc == BGR_OK && bgr::run_pileup(graph))   // ... and by the pileup kernel (with a strands switch on: the one that fills the forward table too)
+                rc = bgr::g_run_pileup.strands && bgr::g_run_pileup.enable_strands && bgr::g_run_pileup.strands(graph) ? bgr::g_run_pileup.enable_strands(a) : bgr::g_run_pileup.enable(a);
             aligners.push_back(a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);

@@ -17,6 +17,8 @@ struct RunPileup {
     int (*collect)(bgr_graph* g, bgr_aligner* a); // the aligner's table (its stream waited for) joins the run's totals in the graph
     int (*end)(bgr_graph* g, bool ok);            // totals only of a run that ended well; BGR_E_CAPACITY when a depth may have wrapped (behind the abundance's end)
     bool (*variants)(const bgr_graph* g);         // the graph's variants switch (bgr_graph_variants_enable) is among what `wanted` answers for: the run calls SNV sites (--vcf)
+    bool (*strands)(const bgr_graph* g);          // a strands switch (bgr_graph_pileup_strands_enable, bgr_graph_variants_strands_enable) is on as well (--strands)
+    int (*enable_strands)(bgr_aligner* a);        // `enable`, and every launch also counts the forward observations in a second table
 };
 extern RunPileup g_run_pileup;  // pipeline.cpp; all null until capi.hip has registered
 

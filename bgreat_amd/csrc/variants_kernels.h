@@ -45,6 +45,17 @@ hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, ui
 // pass 5, behind launch_variants_count on the same stream with the same arguments: `out` has room for the number of sites
 hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
                                 const bgr_variant_params& prm, const void* scratch, bgr_variant_site* out, hipStream_t stream);
+// The same with a forward table next to the total one (bgr_variant_strand_site): pass 1 sums both difference arrays (a grid of tiles x 2), pass 2
+// scans both arrays of sums (two workgroups), passes 3 and 5 rescan both tables' words, read the forward alt words of a base that has a candidate
+// allele, apply variants_strand_passing (variants_host.h) and write 64-byte records.  The forward words of a unitig sum to 0 as the total's do:
+// the forward scan runs flat too.  Still five launches, no sort, no atomics on the output, no workgroup waits for another.
+// scratch: variants_strands_scratch_bytes; the number of sites lies at variants_total_word as above.
+inline uint64_t variants_strands_scratch_bytes(uint64_t tiles) { return variants_scratch_bytes(tiles) + (tiles + 1) * 8 + ((tiles + 1) / 2) * 8; }
+hipError_t launch_variants_strands_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                         const uint64_t* base_offs, const bgr_variant_strand_params& prm, void* scratch, hipStream_t stream, hipEvent_t* after);
+hipError_t launch_variants_strands_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                        const uint64_t* base_offs, const bgr_variant_strand_params& prm, const void* scratch, bgr_variant_strand_site* out,
+                                        hipStream_t stream);
 // dst[i] += src[i] (mod 2^32) over n_words 32-bit words; with tail_u64 the last two words of both are one u64 counter (the table's tail) and are
 // added as such.  Both on the device of `stream`; dst and src 16-byte aligned.
 hipError_t launch_pileup_add(uint32_t* dst, const uint32_t* src, uint64_t n_words, bool tail_u64, uint32_t num_cus, hipStream_t stream);

@@ -51,7 +51,7 @@ __device__ __forceinline__ void load8(const uint32_t* delta, u64 w, u64 words, u
 }  // namespace
 
 // pass 1: sums[t] = the tile's delta words added up
-__global__ void __launch_bounds__(256) bgr_variants_tile_sums_kernel(const uint32_t* delta, u64 words, uint32_t* sums) {
+__device__ __forceinline__ void tile_sums_body(const uint32_t* delta, u64 words, uint32_t* sums) {
     __shared__ uint32_t sw[kThreads / 64];
     const u64 w0 = (u64)blockIdx.x * kTile;
     uint32_t s = 0;
@@ -65,10 +65,15 @@ __global__ void __launch_bounds__(256) bgr_variants_tile_sums_kernel(const uint3
     (void)block_scan_excl(s, sw, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
+__global__ void __launch_bounds__(256) bgr_variants_tile_sums_kernel(const uint32_t* delta, u64 words, uint32_t* sums) { tile_sums_body(delta, words, sums); }
+// with strands: the total table's words (blockIdx.y == 0) and the forward table's (1) in one launch
+__global__ void __launch_bounds__(256) bgr_variants_tile_sums2_kernel(const uint32_t* delta, const uint32_t* delta_f, u64 words, uint32_t* sums, uint32_t* sums_f) {
+    if (blockIdx.y == 0) tile_sums_body(delta, words, sums); else tile_sums_body(delta_f, words, sums_f);
+}
 
 // passes 2 and 4: out[t] = in[0] + .. + in[t - 1] for t = 0 .. n (64-bit; its low word is the sum mod 2^32).  One workgroup; a thread takes
 // sixteen consecutive values of a turn (the arrays are a few bytes per tile: nothing here is bound by bandwidth).
-__global__ void __launch_bounds__(256) bgr_variants_scan_kernel(const uint32_t* in, u64 n, u64* out) {
+__device__ __forceinline__ void scan_body(const uint32_t* in, u64 n, u64* out) {
     __shared__ u64 sw64[kThreads / 64];
     constexpr uint32_t kEach = 16;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -95,12 +100,20 @@ __global__ void __launch_bounds__(256) bgr_variants_scan_kernel(const uint32_t* 
     }
     if (threadIdx.x == 0) out[n] = run;
 }
+__global__ void __launch_bounds__(256) bgr_variants_scan_kernel(const uint32_t* in, u64 n, u64* out) { scan_body(in, n, out); }
+// with strands, pass 2: two workgroups, one per table's tile sums (neither waits for the other)
+__global__ void __launch_bounds__(256) bgr_variants_scan2_kernel(const uint32_t* in, const uint32_t* in_f, u64 n, u64* out, u64* out_f) {
+    if (blockIdx.x == 0) scan_body(in, n, out); else scan_body(in_f, n, out_f);
+}
 
-// passes 3 and 5
-template <bool EMIT>
+// passes 3 and 5.  STRANDS: the forward table (alt_f, delta_f, carry_f) is scanned along; a base with a candidate allele also reads its four forward
+// alt words, an allele must pass variants_strand_passing as well, and a record is a 64-byte bgr_variant_strand_site (out_s).  A compile-time
+// constant: the instances without it are the kernel as it was.
+template <bool EMIT, bool STRANDS>
 __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGraph g, u64 n_unitigs, u64 total_bases, const uint32_t* alt, const uint32_t* delta,
                                                                    const u64* base_offs, bgr_variant_params prm, const u64* carry, uint32_t* counts, const u64* offs,
-                                                                   bgr_variant_site* out) {
+                                                                   bgr_variant_site* out, const uint32_t* alt_f, const uint32_t* delta_f, const u64* carry_f,
+                                                                   uint32_t min_alt_strand, bgr_variant_strand_site* out_s) {
     __shared__ uint32_t sw[kThreads / 64];
     __shared__ u64 s_start[kStarts], s_F[kStarts];
     __shared__ u64 s_id0;
@@ -132,6 +145,13 @@ __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGra
     for (uint32_t i = 1; i < kPer; ++i) d[i] += d[i - 1];
     uint32_t tile_sum;
     const uint32_t before = (uint32_t)carry[blockIdx.x] + block_scan_excl(d[kPer - 1], sw, &tile_sum);   // the running sum in front of this thread's words
+    uint32_t df[kPer], before_f = 0;   // the same of the forward table
+    if (STRANDS) {
+        load8(delta_f, wf, words, df);
+#pragma unroll
+        for (uint32_t i = 1; i < kPer; ++i) df[i] += df[i - 1];
+        before_f = (uint32_t)carry_f[blockIdx.x] + block_scan_excl(df[kPer - 1], sw, &tile_sum);
+    }
 
     // this thread's first word: the last j with start_at(j) <= wf, among the starts in LDS (they ascend; those of ids beyond n + 1 are ~0)
     u64 j = 0;
@@ -143,7 +163,7 @@ __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGra
     u64 cur = start_at(j), next = start_at(j + 1), F = F_at(j);
     // what the emit pass keeps of a site until its rank is known, in registers (the loops are unrolled: every index is a constant)
     uint32_t site_mask = 0, refs = 0, s_id[kPer], s_pos[kPer];
-    uint4 s_alt[kPer];
+    uint4 s_alt[kPer], s_falt[kPer];
     u64 seq_word = 0, seq_at = ~0ull;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {
@@ -157,7 +177,14 @@ __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGra
                 if ((p >> 5) != seq_at) { seq_at = p >> 5; seq_word = g.seq[seq_at]; }
                 const uint32_t ref = (uint32_t)(seq_word >> (62 - 2 * (p & 31))) & 3u;
                 const uint32_t c[4] = {a4.x, a4.y, a4.z, a4.w};
-                if (bgr::variants_passing(depth, c, ref, prm.min_depth, prm.min_alt, prm.min_af_ppm)) {
+                uint32_t m = bgr::variants_passing(depth, c, ref, prm.min_depth, prm.min_alt, prm.min_af_ppm);
+                if (STRANDS && m) {
+                    const uint4 f4 = *reinterpret_cast<const uint4*>(alt_f + 4 * b);
+                    const uint32_t cf[4] = {f4.x, f4.y, f4.z, f4.w};
+                    m = bgr::variants_strand_passing(m, c, cf, min_alt_strand);
+                    if (EMIT) s_falt[i] = f4;
+                }
+                if (m) {
                     site_mask |= 1u << i;
                     if (EMIT) { refs |= ref << (2 * i); s_id[i] = (uint32_t)id; s_pos[i] = (uint32_t)pos; s_alt[i] = a4; }
                 }
@@ -168,7 +195,7 @@ __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGra
     const uint32_t rank = block_scan_excl((uint32_t)__popc(site_mask), sw, &tile_sites);
     if (EMIT) {
         if (tile_sites != counts[blockIdx.x]) return;   // (cannot be: both passes read the same table; never write beyond what was counted)
-        uint4* o = reinterpret_cast<uint4*>(out + offs[blockIdx.x] + rank);
+        uint4* o = STRANDS ? reinterpret_cast<uint4*>(out_s + offs[blockIdx.x] + rank) : reinterpret_cast<uint4*>(out + offs[blockIdx.x] + rank);
         uint32_t slot = 0;
 #pragma unroll
         for (uint32_t i = 0; i < kPer; ++i)
@@ -176,8 +203,17 @@ __global__ void __launch_bounds__(256) bgr_variants_classify_kernel(BgrDeviceGra
                 const uint32_t ref = (refs >> (2 * i)) & 3u;
                 const uint4 a4 = s_alt[i];
                 const uint32_t nn = ref == 0 ? a4.x : ref == 1 ? a4.y : ref == 2 ? a4.z : a4.w;
-                o[2 * slot] = make_uint4(s_id[i], s_pos[i], before + d[i], ref == 0 ? 0u : a4.x);
-                o[2 * slot + 1] = make_uint4(ref == 1 ? 0u : a4.y, ref == 2 ? 0u : a4.z, ref == 3 ? 0u : a4.w, nn);
+                if (STRANDS) {
+                    const uint4 f4 = s_falt[i];
+                    const uint32_t fn = ref == 0 ? f4.x : ref == 1 ? f4.y : ref == 2 ? f4.z : f4.w;
+                    o[4 * slot] = make_uint4(s_id[i], s_pos[i], before + d[i], ref == 0 ? 0u : a4.x);
+                    o[4 * slot + 1] = make_uint4(ref == 1 ? 0u : a4.y, ref == 2 ? 0u : a4.z, ref == 3 ? 0u : a4.w, nn);
+                    o[4 * slot + 2] = make_uint4(before_f + df[i], ref == 0 ? 0u : f4.x, ref == 1 ? 0u : f4.y, ref == 2 ? 0u : f4.z);
+                    o[4 * slot + 3] = make_uint4(ref == 3 ? 0u : f4.w, fn, 0u, 0u);
+                } else {
+                    o[2 * slot] = make_uint4(s_id[i], s_pos[i], before + d[i], ref == 0 ? 0u : a4.x);
+                    o[2 * slot + 1] = make_uint4(ref == 1 ? 0u : a4.y, ref == 2 ? 0u : a4.z, ref == 3 ? 0u : a4.w, nn);
+                }
                 ++slot;
             }
     } else if (threadIdx.x == 0) {
@@ -213,6 +249,13 @@ struct Scratch {
         sums = reinterpret_cast<uint32_t*>(offs + tiles + 1); counts = sums + tiles;
     }
 };
+struct StrandScratch {   // behind Scratch's arrays: the forward table's carries and tile sums
+    u64* carry_f; uint32_t* sums_f;
+    StrandScratch(void* p, uint64_t tiles) {
+        carry_f = reinterpret_cast<u64*>(static_cast<char*>(p) + variants_scratch_bytes(tiles));
+        sums_f = reinterpret_cast<uint32_t*>(carry_f + tiles + 1);
+    }
+};
 }  // namespace
 
 hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
@@ -230,8 +273,9 @@ hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, ui
     if ((e = mark(0)) != hipSuccess) return e;
     hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (u64)tiles, s.carry);
     if ((e = mark(1)) != hipSuccess) return e;
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<false>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
-                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr);
+    hipLaunchKernelGGL((bgr_variants_classify_kernel<false, false>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
+                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const u64*)nullptr, 0u, (bgr_variant_strand_site*)nullptr);
     if ((e = mark(2)) != hipSuccess) return e;
     hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.counts, (u64)tiles, s.offs);
     if ((e = mark(3)) != hipSuccess) return e;
@@ -244,8 +288,51 @@ hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uin
     if (n_unitigs == 0 || tiles == 0) return hipSuccess;
     if (!table || !base_offs || !scratch || !out || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
     const Scratch s(const_cast<void*>(scratch), tiles);
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<true>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
-                       table + pileup_alt_words(total_bases), reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, out);
+    hipLaunchKernelGGL((bgr_variants_classify_kernel<true, false>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
+                       table + pileup_alt_words(total_bases), reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, out,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const u64*)nullptr, 0u, (bgr_variant_strand_site*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_variants_strands_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                         const uint64_t* base_offs, const bgr_variant_strand_params& sp, void* scratch, hipStream_t stream, hipEvent_t* after) {
+    const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
+    if (n_unitigs == 0 || tiles == 0) return hipSuccess;
+    const bgr_variant_params prm = {sp.min_depth, sp.min_alt, sp.min_af_ppm};
+    if (!table || !table_fwd || !base_offs || !scratch || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
+    const Scratch s(scratch, tiles);
+    const StrandScratch f(scratch, tiles);
+    const uint32_t* alt = table;
+    const uint32_t* delta = table + pileup_alt_words(total_bases);
+    const uint32_t* alt_f = table_fwd;
+    const uint32_t* delta_f = table_fwd + pileup_alt_words(total_bases);
+    const u64 words = pileup_delta_words(total_bases, n_unitigs);
+    auto mark = [&](int i) -> hipError_t { return after ? hipEventRecord(after[i], stream) : hipSuccess; };
+    hipError_t e;
+    hipLaunchKernelGGL(bgr_variants_tile_sums2_kernel, dim3((uint32_t)tiles, 2), dim3(kThreads), 0, stream, delta, delta_f, words, s.sums, f.sums_f);
+    if ((e = mark(0)) != hipSuccess) return e;
+    hipLaunchKernelGGL(bgr_variants_scan2_kernel, dim3(2), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (const uint32_t*)f.sums_f, (u64)tiles, s.carry, f.carry_f);
+    if ((e = mark(1)) != hipSuccess) return e;
+    hipLaunchKernelGGL((bgr_variants_classify_kernel<false, true>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
+                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr, alt_f, delta_f,
+                       (const u64*)f.carry_f, sp.min_alt_strand, (bgr_variant_strand_site*)nullptr);
+    if ((e = mark(2)) != hipSuccess) return e;
+    hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.counts, (u64)tiles, s.offs);
+    if ((e = mark(3)) != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_variants_strands_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                        const uint64_t* base_offs, const bgr_variant_strand_params& sp, const void* scratch, bgr_variant_strand_site* out, hipStream_t stream) {
+    const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
+    if (n_unitigs == 0 || tiles == 0) return hipSuccess;
+    const bgr_variant_params prm = {sp.min_depth, sp.min_alt, sp.min_af_ppm};
+    if (!table || !table_fwd || !base_offs || !scratch || !out || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
+    const Scratch s(const_cast<void*>(scratch), tiles);
+    const StrandScratch f(const_cast<void*>(scratch), tiles);
+    hipLaunchKernelGGL((bgr_variants_classify_kernel<true, true>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
+                       table + pileup_alt_words(total_bases), reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs,
+                       (bgr_variant_site*)nullptr, table_fwd, table_fwd + pileup_alt_words(total_bases), (const u64*)f.carry_f, sp.min_alt_strand, out);
     return hipGetLastError();
 }
 

@@ -396,6 +396,30 @@ typedef struct { uint32_t min_depth, min_alt, min_af_ppm; } bgr_variant_params;
 int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, bgr_variant_site* out, uint64_t cap, uint64_t* n);
 int bgr_aligner_pileup_sites_times(bgr_aligner* a, double ms[5]);
 int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src);
+/* Strands.  Occurrence j of a mapped read is a FORWARD OBSERVATION when the read as given in the input is collinear with the strand the unitig file
+ * spells: the row's status has no BGR_ST_RC and the occurrence is glued on forward, or it has BGR_ST_RC and the occurrence is glued on reversed.  The
+ * FORWARD PILEUP is bgr_pileup_base over the forward observations only -- same positions, same complementing, same N rule; the reverse part is the
+ * total minus it, element by element, so 0 <= forward <= total everywhere, and for every unitig the forward depths sum to the bases its forward
+ * occurrences cover.  Rows that spell no walk add to neither table: skipped is the total table's alone.
+ * bgr_aligner_pileup_strands_enable(a, 1) enables the pileup as well (as the pileup enables abundance) and allocates a second table of the pileup's
+ * layout, 20 more bytes per base: 328 MiB per aligner in total on bench.py's default graph, 14.6 GiB on the chr1-scale graph; BGR_E_NOMEM with nothing
+ * allocated when the device does not have it.  While it is on, the pileup kernel of every launch is the instance that repeats the two delta atomics
+ * and each alt atomic of a forward observation into that table ("bgr_pileup_kernel" in the times as before); the internal streams share it.
+ * Switching off keeps the table (and leaves the pileup on); bgr_aligner_reset_pileup clears both tables; bgr_aligner_pileup_add adds the forward
+ * tables too when both aligners have one (BGR_E_ARG when exactly one has); the 2^32 guard is the total table's, unchanged, and bgr_aligner_pileup /
+ * bgr_aligner_pileup_sites deliver what they deliver without the switch.  bgr_aligner_pileup_forward: the forward table as bgr_aligner_pileup
+ * delivers the total (BGR_E_ARG when strands were never enabled).
+ * bgr_aligner_pileup_strand_sites: bgr_aligner_pileup_sites with the STRAND FILTER on top -- for min_alt_strand >= 0 allele X passes when it passes
+ * the test above and forward.X >= min_alt_strand and total.X - forward.X >= min_alt_strand (0: exactly the sites of bgr_aligner_pileup_sites).
+ * Still five launches: the tile sums and the scan take both difference arrays, the two classify passes rescan both and read the forward alt words of
+ * a base that has a candidate allele.  A record is 64 bytes: the numbers of bgr_variant_site, then fdepth, fa .. fn of the forward table, then two
+ * zero words.  Capacity protocol, guard and refusals as bgr_aligner_pileup_sites (BGR_E_ARG when strands were never enabled);
+ * bgr_aligner_pileup_sites_times reads its launches too. */
+typedef struct { uint32_t min_depth, min_alt, min_af_ppm, min_alt_strand; } bgr_variant_strand_params;
+typedef struct { uint32_t unitig, pos, depth, a, c, g, t, n, fdepth, fa, fc, fg, ft, fn, reserved[2]; } bgr_variant_strand_site;   /* 64 bytes */
+int bgr_aligner_pileup_strands_enable(bgr_aligner* a, uint32_t on);
+int bgr_aligner_pileup_forward(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases);
+int bgr_aligner_pileup_strand_sites(bgr_aligner* a, const bgr_variant_strand_params* params, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n);
 /* Diagnostic (the host tests pin the kernel's canonicalisation through it): the canonical form of the link (a, b) as the kernel computes it (the same inline code, compiled for the host): out = {from, to, 0}, and, if key is
  * not NULL, the 64-bit integer the tables hold for it -- (|from| << 33) | (from < 0) << 32 | (|to| << 1) | (to < 0), whose order is the order of the keys. */
 int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key);
@@ -639,6 +663,29 @@ int bgr_graph_variants(const bgr_graph* g, bgr_variant_site* out, uint64_t cap, 
 int bgr_graph_variants_params(const bgr_graph* g, bgr_variant_params* out);
 int bgr_write_vcf(const char* path, const bgr_graph* g, const bgr_variant_params* params, const bgr_variant_site* sites, uint64_t n);
 int bgr_parse_af_ppm(const char* text, uint32_t* ppm);
+
+/* Strands in a whole run (the definitions stand at bgr_aligner_pileup_strands_enable).  bgr_graph_pileup_strands_enable(g, 1) is sticky and switches
+ * bgr_graph_pileup_enable on as well (0 leaves that on): every aligner of a later bgr_align_all also counts the forward table, and the forward totals
+ * are gathered on the host next to the totals -- HOST MEMORY DOUBLES: 40 bytes per base kept in the graph, 60 at the peak while a run ends.
+ * bgr_graph_pileup_forward delivers them (BGR_E_ARG when the last successful run had the switch off); bgr_write_pileup_strands writes
+ * bgr_write_pileup's lines -- the same selection: any of the six TOTAL numbers non-zero -- with the six forward numbers appended, under the header
+ * "#unitig pos ref depth A C G T N depth+ A+ C+ G+ T+ N+" (tab-separated).
+ * bgr_graph_variants_strands_enable(g, &params) is bgr_graph_variants_enable with the strand filter (NULL switches both off; a later
+ * bgr_graph_variants_enable switches the filter and the forward table off again): the forward table travels with the run's table -- moved from the
+ * first aligner, added on the device from the others, staged across devices -- and the run's end keeps 64-byte records: bgr_graph_variant_strand_sites
+ * (as bgr_graph_variants; BGR_E_ARG when the last run had no strands).  bgr_graph_variants then delivers the same sites without the forward numbers.
+ * bgr_write_vcf_strands is bgr_write_vcf for such records: the thresholds line ends in ",min_alt_strand=..>", the INFO lines of ADF and ADR follow
+ * AD's, ALT lists the alleles that pass the strand filter too, and INFO is "DP=..;AD=..;ADF=..;ADR=..;NN=.." with ADF = forward ref, then the forward
+ * count of each ALT, forward ref = fdepth - (fa + fc + fg + ft + fn), and ADR = AD - ADF element by element.  BGR_E_ARG also for a record whose
+ * forward numbers do not fit its totals. */
+int bgr_graph_pileup_strands_enable(bgr_graph* g, uint32_t on);
+int bgr_graph_pileup_strands_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_pileup_forward(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases);
+int bgr_graph_variants_strands_enable(bgr_graph* g, const bgr_variant_strand_params* params);
+int bgr_graph_variant_strand_sites(const bgr_graph* g, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n);
+int bgr_write_pileup_strands(const char* path, const bgr_graph* g);
+int bgr_write_vcf_strands(const char* path, const bgr_graph* g, const bgr_variant_strand_params* params, const bgr_variant_strand_site* sites, uint64_t n);
+int bgr_parse_min_alt_strand(const char* text, uint32_t* out);   /* the CLI's --min-alt-strand: digits only, at most nine; BGR_E_ARG for anything else */
 
 /* The CPUs next to a device (the `local_cpulist` of its PCI function in sysfs, e.g. "0-63,128-191"): threads that feed a GPU and the
  * page-locked memory they allocate belong on its NUMA node.  BGR_E_IO when the platform does not say. */

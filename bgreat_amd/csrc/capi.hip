@@ -1,4 +1,6 @@
-// capi.hip -- implementation of the C-ABI declared in include/bgreat_gpu.h.  Thin: argument checks, HIP memory
+// capi.hip -- implementation of the C-ABI declared in include/bgreat_gpu.h: index, distribution, mapping, text route, batches, the
+// asynchronous form, host buffers and readsets (the counting features have their own units: capi_abundance.hip, capi_links.hip,
+// capi_pileup.hip, capi_variants.hip; capi_internal.h has what they share).  Thin: argument checks, HIP memory
 // and stream management, launch geometry; the algorithm lives in graph_build.cpp (index) and
 // the *_kernels.hip files (mapping; launch interface align_kernels.h).  There is no CPU mapping path in this library.
 #include <hip/hip_runtime.h>
@@ -28,217 +30,16 @@
 #include "links_kernels.h"
 #include "pileup_kernels.h"
 #include "read_pack.h"
-#include "run_abundance.h"
-#include "run_links.h"
-#include "run_pileup.h"
 #include "text_kernels.h"
-#include "variants_kernels.h"
 #include "options.h"
-
-namespace {
-
-thread_local std::string tl_err;
-int fail(int code, const std::string& msg) { tl_err = msg; return code; }
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(BGR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-const int kTimerRing = 64;   // launches between two drains of the timers
-const int kTimerSlots = 8;   // kernels of one launch timed separately (pre-pass, passes)
-
-}  // namespace
+#include "capi_internal.h"
 
 namespace bgr {
-int set_error(int code, const std::string& msg) { return fail(code, msg); }  // for pipeline.cpp
+static thread_local std::string tl_err;
+int set_error(int code, const std::string& msg) { tl_err = msg; return code; }  // (`fail` in every unit of the C-ABI, and pipeline.cpp)
 }
-
-struct bgr_graph {
-    bgr::HostGraph host;  // empty when adopted from a device blob
-    std::vector<char> ascii;            // the unitig characters as given (only graphs built from sequences have them):
-    std::vector<uint64_t> ascii_offs;   // correction mode spells reads from these, like the reference's vector<string>
-    BgrBlobHeader header;
-    struct Dev { void* ptr; bool owned; };
-    std::map<int, Dev> dev;
-    uint32_t fanout_method = 0;  // how bgr_devices_init moved the blob between devices last time
-    // per-unitig totals of the last bgr_align_all with bgr_run_options.abundance (row i = unitig id i + 1); the run's aligners add theirs as they finish
-    std::vector<bgr_unitig_abundance> abundance;
-    bool abundance_valid = false;
-    std::mutex abundance_m;   // (the lanes of a split run end side by side)
-    // links (bgr_graph_links_enable): the sticky switch, the bound of distinct links (computed from the host blob the first time it is asked for),
-    // and the totals of the last bgr_align_all with the switch on: {key, count} as the aligners delivered them until the run ends, then merged and sorted
-    bool links_on = false, links_valid = false, links_bound_known = false;
-    uint64_t links_bound = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> links;
-    // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
-    // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
-    bool pileup_on = false, pileup_valid = false;
-    std::vector<uint64_t> base_offs;          // [n_unitigs + 2]: base_offs[id] = sum of len of the unitigs 1 .. id - 1
-    std::vector<uint32_t> pileup_words;       // alt[4 T] then delta[T + n] (pileup_kernels.h)
-    uint64_t pileup_skipped = 0;
-    // SNV sites (bgr_graph_variants_enable): the sticky switch and its thresholds; while a run collects its aligners, the run's pileup table on a device
-    // (the first aligner's, adopted; the others' added into it); then the sites of the last successful run and the thresholds they were called with
-    bool variants_on = false, variants_valid = false;
-    bgr_variant_params variants_prm = {2, 2, 200000}, variants_called = {0, 0, 0};
-    struct VariantsRun* variants_run = nullptr;
-    std::vector<bgr_variant_site> variants_sites;
-    // strands (bgr_graph_pileup_strands_enable, bgr_graph_variants_strands_enable): the run's aligners also count the forward table; with the pileup
-    // switch its totals are gathered next to pileup_words, with the variants switch it travels with the run's table and the records are 64 bytes
-    bool pileup_strands_on = false, pileup_fwd_valid = false, variants_strands_on = false, variants_strands_valid = false;
-    uint32_t variants_min_alt_strand = 0, variants_called_strand = 0;
-    std::vector<uint32_t> pileup_fwd_words;
-    std::vector<bgr_variant_strand_site> variants_strand_sites;
-};
-
-namespace {  // for pipeline.cpp (run_abundance.h): the totals of a run with bgr_run_options.abundance
-void graph_abundance_begin(bgr_graph* g) {  // a new run: the totals of the one before are gone, whatever becomes of this one
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    g->abundance.assign(g->header.n_unitigs, bgr_unitig_abundance{0, 0, 0});
-    g->abundance_valid = false;
-}
-void graph_abundance_add(bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n) {  // one aligner's table
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    for (uint64_t i = 0; i < n && i < g->abundance.size(); ++i) { g->abundance[i].reads += rows[i].reads; g->abundance[i].bases += rows[i].bases; g->abundance[i].kmers += rows[i].kmers; }
-}
-void graph_abundance_end(bgr_graph* g, bool ok) {  // totals only of a run that ended well
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (!ok) g->abundance.clear();
-    g->abundance_valid = ok;
-}
-}  // namespace
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        // diagnostic (bgr_set_option("poison_device_buffers", 1); tools/fuzz_*.py, the GPU suite): fresh device memory usually reads as zeroes, recycled memory of
-        // a long-lived process does not -- fill every new buffer with a pattern so that a kernel that reads what nothing has written shows in ANY run
-        const bool poison = bgr::opt("poison_device_buffers") != 0;
-        if (e == hipSuccess && poison) { e = hipMemset(p, 0xA5, want); if (e == hipSuccess) e = hipDeviceSynchronize(); }  // (the fill runs on the null stream: the aligner's streams do not wait for it)
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-struct VariantsRun {   // the pileup table of a run with bgr_graph_variants_enable while its aligners are collected (bgr_graph has the rest)
-    int device = 0, num_cus = 0;
-    hipStream_t stream = nullptr;
-    BgrDeviceGraph dg;
-    DevBuf table, offs, stage, table_fwd;   // (table_fwd: only in a run that counts strands)
-};
-static void variants_run_free(bgr_graph* g) {
-    if (!g->variants_run) return;
-    if (hipSetDevice(g->variants_run->device) == hipSuccess) {
-        if (g->variants_run->stream) (void)hipStreamDestroy(g->variants_run->stream);
-        g->variants_run->table.release(); g->variants_run->offs.release(); g->variants_run->stage.release(); g->variants_run->table_fwd.release();
-    }
-    delete g->variants_run;
-    g->variants_run = nullptr;
-}
-
-struct bgr_text_stage {  // one piece of text on its way to / resident in a device: buffer, copy stream, "it has arrived" event
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr, ev0 = nullptr;  // ev0: BGREAT_TIMING only, start of the copy
-    DevBuf buf;
-    uint64_t bytes = 0;
-    bool timing = false, pending = false;
-    double copy_ms = 0, copy_bytes = 0;
-    void settle() {  // BGREAT_TIMING: duration of the last copy (it has completed)
-        if (!timing || !pending) return;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev) == hipSuccess) { copy_ms += ms; copy_bytes += (double)bytes; }
-        pending = false;
-    }
-};
-
-struct bgr_aligner {
-    bgr_graph* graph = nullptr;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    BgrDeviceGraph dg;
-    // the text route (bgr_align_fasta_text): the piece, its records, the formatted streams
-    DevBuf tx_in, tx_sums, tx_state, tx_rec, tx_idx, tx_accrec, tx_accsrc, tx_offs, tx_psz, tx_nsz, tx_poff, tx_noff, tx_pout, tx_nout, tx_info, tx_gaf, path_stats;
-    uint64_t tx_n_acc = 0, tx_pbytes = 0, tx_nbytes = 0;
-    bool blocking_sync = bgr::opt("blocking_sync") != 0;
-    hipEvent_t ev_wait = nullptr;
-    const uint8_t* tx_text = nullptr;  // where the last call's piece lies in HBM (tx_in, or the caller's stage)
-    uint32_t tx_flip = 0;              // which of the two info blocks the current piece uses
-    uint32_t tx_epoch = 0, tx_ticket[2] = {0, 0};   // the one-launch kernels' chains: epoch of the last launch; tickets earlier launches took (parse, format)
-    bool tx_written = false;           // the streams lie in tx_pout / tx_nout (the format launch wrote them: every stretch ended below the capacities)
-    uint32_t tx_want = 0;              // its want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
-    double tx_phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
-
-    DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: kSmall* (align_kernels.h)
-    struct DeepRun {  // the last pass of the exhaustive launch in flight, as enqueued: settle_launch runs it again for reads whose table filled up
-        bool open = false;
-        bgr::Pass pass;
-        bgr::BatchIO io;
-        bgr::KernelParams kp;
-        BgrDeviceGraph dg;
-        uint32_t per_wave_lds = 0, path_cap = 0, memo_cap = 0, runs = 0;
-    } deep;
-    bgr::PlanDevice plan_dev;     // CUs, LDS, resident waves per kernel: asked once
-    bool plan_dev_known = false;
-    uint64_t last_n = 0;
-    uint32_t last_mode = 0;       // mode of the last mapping launch (bgr_aligner_path_stats)
-    DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
-    uint64_t wave_times_n = 0;
-    uint64_t ticket_serial = 0;       // bgr_align_batch_begin: tickets handed out; the batch of the last one is in flight until its wait
-    bool ticket_open = false;
-    std::vector<uint64_t> ticket_offs;  // that batch's offsets made relative (kept alive for the asynchronous copy)
-    uint32_t last_launch[4] = {0, 0, 0, 0};
-    uint32_t cfg_waves = 0, cfg_blocks_per_cu = 0, cfg_lds_mphf = 0;
-    bool exh_filter = bgr::opt("exh_filter") != 0;  // exhaustive mode through the minimizer filter too (option exh_filter = 0: without)
-    // bgr_aligner_set_knob (test / diagnostic hooks, read here instead of from the environment on every launch)
-    uint32_t knob_frame_cap = 0, knob_search = 0, knob_debug_stop = 0, knob_greedy_fast = 0, knob_exh_fast = 0, knob_anc_fast = 0, knob_memo_cap = 0, knob_prepass = 0, knob_no_events = 0;
-    uint64_t knob_split_limit = 0;
-    uint32_t knob_overlap = 0;      // BGR_KNOB_BATCH_OVERLAP
-    uint32_t knob_abundance_form = 0;  // BGR_KNOB_ABUNDANCE_FORM
-    bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel
-    DevBuf abundance;               // u64[n_unitigs + 1][3], allocated and zeroed on the first enable
-    uint32_t knob_links_form = 0;   // BGR_KNOB_LINKS_FORM
-    bool links_on = false;          // bgr_aligner_links_enable: every greedy / anchors launch is followed by the links kernel
-    DevBuf links;                   // {u64 key, u64 count}[links_cap] + the tail words (links_kernels.h), allocated and zeroed on the first enable
-    unsigned long long* links_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
-    uint64_t links_cap = 0, links_bound = 0;
-    bool pileup_on = false;         // bgr_aligner_pileup_enable: every greedy / anchors launch is followed by the pileup kernel
-    DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
-    uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
-    const uint64_t* pileup_base_offs = nullptr;
-    bool strands_on = false;        // bgr_aligner_pileup_strands_enable: the pileup kernel also adds the forward observations to a second table
-    DevBuf pileup_fwd;              // that table: the layout of `pileup`, its tail stays 0
-    uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
-    DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
-    double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
-    bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
-    bool is_twin = false;
-    int num_cus = 0;
-    size_t lds_per_cu = 0;
-    hipEvent_t ev[kTimerRing][kTimerSlots + 1];  // ev[i][0] = start of launch i, ev[i][j] = behind its j-th kernel
-    int ev_marks[kTimerRing];                    // kernels timed in launch i
-    int ev_used = 0;
-    uint64_t t_launches = 0;
-    double t_ms = 0, t_slot_ms[kTimerSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const char* t_slot_name[kTimerSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-};
 
 namespace {
-
-// Wait for the aligner's stream.  By default hipStreamSynchronize (the runtime spins: lowest latency, one busy CPU per waiting thread);
-// with BGREAT_BLOCKING_SYNC=1 an event made with hipEventBlockingSync is recorded and waited for instead: the thread sleeps until the
-// interrupt, so more stream workers per device than CPUs to spare can overlap their calls (bgr_align_all's text route).
-hipError_t wait_stream(bgr_aligner* a) {
-    if (!a->blocking_sync) return hipStreamSynchronize(a->stream);
-    hipError_t e = hipEventRecord(a->ev_wait, a->stream);
-    return e == hipSuccess ? hipEventSynchronize(a->ev_wait) : e;
-}
 
 int drain_timers(bgr_aligner* a) {
     if (a->ev_used == 0) return BGR_OK;
@@ -261,7 +62,7 @@ int drain_timers(bgr_aligner* a) {
 
 extern "C" {
 
-const char* bgr_last_error(void) { return tl_err.c_str(); }
+const char* bgr_last_error(void) { return bgr::tl_err.c_str(); }
 
 int bgr_set_option(const char* name, int64_t value) {
     bgr::Option* o = name ? bgr::find_option(name) : nullptr;
@@ -715,11 +516,6 @@ static DevBuf* list_buf(bgr_aligner* a, bgr::List l) {
 // buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
 // (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
 // d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
-// the geometry and form of the abundance kernel behind a launch of this size (bgr_aligner_abundance_plan reports what this returns)
-static bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases) {
-    return bgr::plan_abundance(a->graph->header.n_unitigs, a->dg.k, n_reads, total_bases, (uint32_t)a->num_cus, a->lds_per_cu, a->knob_abundance_form);
-}
-
 static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
                              uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
                              bool cursor_is_zero = false) {
@@ -976,1014 +772,6 @@ static int settle_launch_sync(bgr_aligner* a) {
     HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return settle_launch(a, cur);
-}
-
-// ---- unitig abundance (bgr_run_options.abundance has the definition) ------------------------------------------------------------------
-static int abundance_set(bgr_aligner* a, bool on) {
-    if (on && !a->abundance.p) {
-        HIP_TRY(hipSetDevice(a->device));
-        HIP_TRY(a->abundance.ensure((a->graph->header.n_unitigs + 1) * sizeof(bgr_unitig_abundance)));
-        HIP_TRY(hipMemsetAsync(a->abundance.p, 0, a->abundance.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
-        HIP_TRY(hipStreamSynchronize(a->stream));
-        HIP_TRY(bgr::prepare_abundance(a->lds_per_cu));   // (once per aligner, not per launch: form B's tables beyond 48 KB)
-    }
-    a->abundance_on = on;
-    return BGR_OK;
-}
-
-int bgr_aligner_abundance_enable(bgr_aligner* a, uint32_t on) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_abundance_enable: null aligner");
-    for (bgr_aligner* x = a; x; x = x->twin) { const int rc = abundance_set(x, on != 0); if (rc != BGR_OK) return rc; }
-    return BGR_OK;
-}
-
-int bgr_aligner_abundance(bgr_aligner* a, bgr_unitig_abundance* out, uint64_t n_rows) {
-    static_assert(sizeof(bgr_unitig_abundance) == 24, "three u64 per unitig, as the kernel adds them");
-    if (!a || (n_rows && !out)) return fail(BGR_E_ARG, "bgr_aligner_abundance: null argument");
-    if (n_rows != a->graph->header.n_unitigs) return fail(BGR_E_ARG, "bgr_aligner_abundance: n_rows is not the graph's number of unitigs");
-    if (!a->abundance.p) return fail(BGR_E_ARG, "bgr_aligner_abundance: abundance was never enabled on this aligner (bgr_aligner_abundance_enable)");
-    if (n_rows == 0) return BGR_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    HIP_TRY(hipMemcpy(out, static_cast<const bgr_unitig_abundance*>(a->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
-    std::vector<bgr_unitig_abundance> t;
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
-        if (!tw->abundance.p) continue;
-        t.resize(n_rows);
-        HIP_TRY(hipStreamSynchronize(tw->stream));
-        HIP_TRY(hipMemcpy(t.data(), static_cast<const bgr_unitig_abundance*>(tw->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n_rows; ++i) { out[i].reads += t[i].reads; out[i].bases += t[i].bases; out[i].kmers += t[i].kmers; }
-    }
-    return BGR_OK;
-}
-
-int bgr_aligner_abundance_plan(bgr_aligner* a, uint64_t n_reads, uint64_t total_bases, uint32_t out[4]) {
-    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_abundance_plan: null argument");
-    const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
-    out[0] = ap.form; out[1] = ap.blocks; out[2] = ap.threads; out[3] = ap.lds_bytes;
-    return BGR_OK;
-}
-
-int bgr_plan_abundance(uint64_t n_unitigs, uint32_t k, uint64_t n_reads, uint64_t total_bases, uint32_t num_cus, uint64_t lds_per_cu, uint32_t form_knob, uint32_t out[4]) {
-    if (!out || form_knob > 2) return fail(BGR_E_ARG, "bgr_plan_abundance: null argument or a form beyond 2");
-    const bgr::AbundancePlan ap = bgr::plan_abundance(n_unitigs, k, n_reads, total_bases, num_cus, lds_per_cu, form_knob);
-    out[0] = ap.form; out[1] = ap.blocks; out[2] = ap.threads; out[3] = ap.lds_bytes;
-    return BGR_OK;
-}
-
-int bgr_aligner_reset_abundance(bgr_aligner* a) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_abundance: null aligner");
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) {
-        if (!x->abundance.p) continue;
-        HIP_TRY(hipMemsetAsync(x->abundance.p, 0, x->abundance.cap, x->stream));
-        HIP_TRY(hipStreamSynchronize(x->stream));
-    }
-    return BGR_OK;
-}
-
-// what a whole run calls (run_abundance.h)
-static int run_abundance_enable(bgr_aligner* a) { return bgr_aligner_abundance_enable(a, 1); }
-static int run_abundance_collect(bgr_graph* g, bgr_aligner* a) {
-    std::vector<bgr_unitig_abundance> rows(g->header.n_unitigs);
-    const int rc = bgr_aligner_abundance(a, rows.data(), rows.size());
-    if (rc == BGR_OK) graph_abundance_add(g, rows.data(), rows.size());
-    return rc;
-}
-static const bool g_run_abundance_registered = (bgr::g_run_abundance = bgr::RunAbundance{graph_abundance_begin, run_abundance_enable, run_abundance_collect, graph_abundance_end}, true);
-
-int bgr_graph_abundance(const bgr_graph* g, bgr_unitig_abundance* out, uint64_t n_rows) {
-    if (!g || (n_rows && !out)) return fail(BGR_E_ARG, "bgr_graph_abundance: null argument");
-    if (!g->abundance_valid) return fail(BGR_E_ARG, "bgr_graph_abundance: no totals -- they are those of the last successful bgr_align_all with bgr_run_options.abundance = 1");
-    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_graph_abundance: n_rows is not the graph's number of unitigs");
-    if (n_rows) memcpy(out, g->abundance.data(), n_rows * sizeof(bgr_unitig_abundance));
-    return BGR_OK;
-}
-
-int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows) {
-    if (!path || !g || (n_rows && !rows)) return fail(BGR_E_ARG, "bgr_write_abundance: null argument");
-    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_write_abundance: n_rows is not the graph's number of unitigs");
-    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_abundance: the graph has no host blob (the unitig lengths are read from it)");
-    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_abundance: cannot open ") + path);
-    std::string buf = "#unitig\tlength\treads\tbases\tkmers\n";
-    bool ok = true;
-    for (uint64_t i = 0; i < n_rows && ok; ++i) {
-        buf += std::to_string(i + 1); buf += '\t';
-        buf += std::to_string(meta[i + 1].len); buf += '\t';
-        buf += std::to_string(rows[i].reads); buf += '\t';
-        buf += std::to_string(rows[i].bases); buf += '\t';
-        buf += std::to_string(rows[i].kmers); buf += '\n';
-        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
-    }
-    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_abundance: write to ") + path + " failed");
-    return BGR_OK;
-}
-
-
-// ---- pileup (bgr_pileup_base in include/bgreat_gpu.h has the definition) -------------------------------------------------------------------
-static int graph_base_offs(bgr_graph* g, const char* who) {   // prefix sums of the unitig lengths, once per graph
-    if (g->host.blob.empty()) return fail(BGR_E_ARG, std::string(who) + ": the graph has no host blob (the unitig lengths and characters are read from it)");
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (g->base_offs.empty()) {
-        const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-        std::vector<uint64_t> o(g->header.n_unitigs + 2, 0);
-        for (uint64_t i = 1; i <= g->header.n_unitigs; ++i) o[i + 1] = o[i] + meta[i].len;
-        g->base_offs.swap(o);
-    }
-    return BGR_OK;
-}
-static int pileup_refusal(const bgr_graph* g, const char* who) {
-    if (g->header.has_exc)
-        return fail(BGR_E_ARG, std::string(who) + ": the pileup (--pileup, --depth) needs a graph of ACGT-only unitigs: on one with other characters the 2-bit store does not spell them and a path read backwards does not spell the reverse complement");
-    return BGR_OK;
-}
-static void pileup_share(bgr_aligner* a) {   // the twins add to the aligner's table
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;
-        tw->pileup_fwd_tab = a->pileup_fwd_tab; tw->strands_on = a->strands_on;
-    }
-}
-
-int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_pileup_enable: null aligner");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_enable: an internal stream of another aligner");
-    if (on) {
-        int rc = pileup_refusal(a->graph, "bgr_aligner_pileup_enable");
-        if (rc == BGR_OK) rc = graph_base_offs(a->graph, "bgr_aligner_pileup_enable");
-        if (rc == BGR_OK) rc = bgr_aligner_abundance_enable(a, 1);   // (its reads column bounds every depth: bgr_aligner_pileup checks it)
-        if (rc != BGR_OK) return rc;
-    }
-    if (on && !a->pileup_tab) {
-        const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2, bytes = bgr::pileup_table_bytes(T, n);
-        HIP_TRY(hipSetDevice(a->device));
-        hipError_t e = a->pileup.ensure(bytes);
-        if (e == hipSuccess) e = a->pileup_offs.ensure((n + 2) * 8);
-        if (e != hipSuccess) {
-            a->pileup.release(); a->pileup_offs.release();
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_pileup_enable: " + std::to_string(bytes) + " bytes for the pileup table (20 per base of the graph): " + hipGetErrorString(e));
-        }
-        HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bytes, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
-        HIP_TRY(hipMemcpyAsync(a->pileup_offs.p, a->graph->base_offs.data(), (n + 2) * 8, hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipStreamSynchronize(a->stream));
-        a->pileup_tab = static_cast<uint32_t*>(a->pileup.p);
-        a->pileup_base_offs = static_cast<const uint64_t*>(a->pileup_offs.p);
-    }
-    a->pileup_on = on != 0;
-    pileup_share(a);
-    return BGR_OK;
-}
-
-int bgr_aligner_pileup_strands_enable(bgr_aligner* a, uint32_t on) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: null aligner");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: an internal stream of another aligner");
-    bool fresh = false;
-    if (on && !a->pileup_fwd_tab) {   // the second table first: a refusal leaves the aligner as it was
-        const int rc0 = pileup_refusal(a->graph, "bgr_aligner_pileup_strands_enable");
-        if (rc0 != BGR_OK) return rc0;
-        const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2, bytes = bgr::pileup_table_bytes(T, n);
-        HIP_TRY(hipSetDevice(a->device));
-        const hipError_t e = a->pileup_fwd.ensure(bytes);
-        if (e != hipSuccess) {
-            a->pileup_fwd.release();
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_pileup_strands_enable: " + std::to_string(bytes) + " bytes for the forward pileup table (20 more per base of the graph): " + hipGetErrorString(e));
-        }
-        HIP_TRY(hipMemsetAsync(a->pileup_fwd.p, 0, bytes, a->stream));
-        HIP_TRY(hipStreamSynchronize(a->stream));
-        a->pileup_fwd_tab = static_cast<uint32_t*>(a->pileup_fwd.p);
-        fresh = true;
-    }
-    if (on) {
-        const int rc = bgr_aligner_pileup_enable(a, 1);   // (as the pileup enables abundance)
-        if (rc != BGR_OK) {
-            if (fresh) { a->pileup_fwd.release(); a->pileup_fwd_tab = nullptr; }   // (nothing stays allocated behind a refusal)
-            return rc;
-        }
-    }
-    a->strands_on = on != 0;
-    pileup_share(a);
-    return BGR_OK;
-}
-
-// alt / delta words -> rows: the depth is the running sum of a unitig's delta words, N lies in the alt word of the unitig's own base
-static void pileup_unitig_rows(const bgr_graph* g, const uint32_t* words, uint64_t id, bgr_pileup_base* out) {   // the len rows of one unitig
-    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
-    const uint32_t* alt = words;
-    const uint32_t* delta = words + bgr::pileup_alt_words(g->header.total_bases / 2);
-    const uint64_t b0 = g->base_offs[id], d0 = b0 + id - 1, F = meta[id].F;
-    uint32_t depth = 0;
-    for (uint64_t pos = 0; pos < meta[id].len; ++pos) {
-        depth += delta[d0 + pos];   // (mod 2^32)
-        const uint64_t p = F + pos;
-        const uint32_t ref = (uint32_t)(seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u;
-        const uint32_t* w = alt + 4 * (b0 + pos);
-        uint32_t c[4] = {w[0], w[1], w[2], w[3]};
-        c[ref] = 0;   // (nothing that differs from the base has the base's code: that word counted the Ns)
-        out[pos] = bgr_pileup_base{depth, c[0], c[1], c[2], c[3], w[ref]};
-    }
-}
-static void pileup_rows(const bgr_graph* g, const uint32_t* words, bgr_pileup_base* out) {
-    for (uint64_t id = 1; id <= g->header.n_unitigs; ++id) pileup_unitig_rows(g, words, id, out + g->base_offs[id]);
-}
-// this aligner's reads column may not have reached 2^32 anywhere: it bounds every depth on the unitig, and a depth is kept mod 2^32
-static int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (rows[i].reads >> 32)
-            return fail(BGR_E_CAPACITY, std::string(who) + ": unitig " + std::to_string(i + 1) + " lies on " + std::to_string(rows[i].reads) + " reads' paths: a per-base depth (32 bits) may have wrapped; no pileup is delivered");
-    return BGR_OK;
-}
-// the aligner's table on the host (every stream that adds to it waited for), behind the guard
-static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t>& words, uint64_t* skipped, bool fwd = false) {
-    if (fwd && !a->pileup_fwd_tab) return fail(BGR_E_ARG, std::string(who) + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
-    if (!a->pileup_tab) return fail(BGR_E_ARG, std::string(who) + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
-    const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2;
-    std::vector<bgr_unitig_abundance> ab(n);
-    int rc = bgr_aligner_abundance(a, ab.data(), n);   // (synchronises the aligner's stream and its twins')
-    if (rc == BGR_OK) rc = pileup_guard(ab.data(), n, who);
-    if (rc != BGR_OK) return rc;
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    words.resize(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n));
-    const uint32_t* tab = fwd ? a->pileup_fwd_tab : a->pileup_tab;
-    if (!words.empty()) HIP_TRY(hipMemcpy(words.data(), tab, words.size() * 4, hipMemcpyDeviceToHost));
-    unsigned long long sk = 0;
-    HIP_TRY(hipMemcpy(&sk, reinterpret_cast<const char*>(tab) + bgr::pileup_tail_byte(T, n), 8, hipMemcpyDeviceToHost));
-    *skipped = sk;
-    return BGR_OK;
-}
-
-int bgr_aligner_pileup(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) {
-    static_assert(sizeof(bgr_pileup_base) == 24, "six u32 per base");
-    if (!a || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup: null argument");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup: an internal stream of another aligner");
-    if (n_bases != a->graph->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_aligner_pileup: n_bases is not the sum of the graph's unitig lengths");
-    std::vector<uint32_t> words;
-    uint64_t sk = 0;
-    const int rc = pileup_snapshot(a, "bgr_aligner_pileup", words, &sk);
-    if (rc != BGR_OK) return rc;
-    pileup_rows(a->graph, words.data(), out);
-    if (skipped) *skipped = sk;
-    return BGR_OK;
-}
-
-int bgr_aligner_pileup_forward(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_bases) {
-    if (!a || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: null argument");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: an internal stream of another aligner");
-    if (n_bases != a->graph->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_aligner_pileup_forward: n_bases is not the sum of the graph's unitig lengths");
-    std::vector<uint32_t> words;
-    uint64_t sk = 0;
-    const int rc = pileup_snapshot(a, "bgr_aligner_pileup_forward", words, &sk, true);
-    if (rc != BGR_OK) return rc;
-    pileup_rows(a->graph, words.data(), out);
-    return BGR_OK;
-}
-
-int bgr_aligner_reset_pileup(bgr_aligner* a) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: null aligner");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: an internal stream of another aligner");
-    if (!a->pileup.p) return BGR_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
-    if (a->pileup_fwd.p) HIP_TRY(hipMemsetAsync(a->pileup_fwd.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    return BGR_OK;   // (the abundance table stays: the guard's column then counts more launches than the pileup holds, which errs on the safe side)
-}
-
-// what a whole run calls (run_pileup.h): the graph's pileup switch gathers the tables on the host, its variants switch (further down) on a device
-static int variants_collect(bgr_graph* g, bgr_aligner* a);
-static int variants_end(bgr_graph* g, bool ok);
-static bool run_pileup_wanted(const bgr_graph* g) { return g && (g->pileup_on || g->variants_on); }
-static bool run_pileup_variants(const bgr_graph* g) { return g && g->variants_on; }
-static bool run_pileup_strands(const bgr_graph* g) { return g && ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)); }
-static void run_pileup_begin(bgr_graph* g) {
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (g->pileup_on) {
-        g->pileup_words.clear();
-        g->pileup_skipped = 0;
-        g->pileup_valid = false;
-        g->pileup_fwd_words.clear();
-        g->pileup_fwd_valid = false;
-    }
-    if (g->variants_on) {
-        variants_run_free(g);
-        g->variants_sites.clear();
-        g->variants_valid = false;
-        g->variants_strand_sites.clear();
-        g->variants_strands_valid = false;
-    }
-}
-static int run_pileup_enable(bgr_aligner* a) { return bgr_aligner_pileup_enable(a, 1); }
-static int run_pileup_enable_strands(bgr_aligner* a) { return bgr_aligner_pileup_strands_enable(a, 1); }
-static int run_pileup_collect(bgr_graph* g, bgr_aligner* a) {
-    if (g->pileup_on) {
-        std::vector<uint32_t> words;
-        uint64_t sk = 0;
-        const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk);
-        if (rc != BGR_OK) return rc;
-        std::lock_guard<std::mutex> l(g->abundance_m);
-        if (g->pileup_words.empty()) g->pileup_words.swap(words);
-        else for (size_t i = 0; i < words.size(); ++i) g->pileup_words[i] += words[i];   // (mod 2^32: the delta sums commute)
-        g->pileup_skipped += sk;
-    }
-    if (g->pileup_on && g->pileup_strands_on) {   // the forward table likewise (its tail is 0)
-        std::vector<uint32_t> words;
-        uint64_t sk = 0;
-        const int rc = pileup_snapshot(a, "bgr_align_all", words, &sk, true);
-        if (rc != BGR_OK) return rc;
-        std::lock_guard<std::mutex> l(g->abundance_m);
-        if (g->pileup_fwd_words.empty()) g->pileup_fwd_words.swap(words);
-        else for (size_t i = 0; i < words.size(); ++i) g->pileup_fwd_words[i] += words[i];
-    }
-    return g->variants_on ? variants_collect(g, a) : BGR_OK;   // (behind the snapshot: the first aligner's table leaves it here)
-}
-static int run_pileup_end(bgr_graph* g, bool ok) {   // behind the abundance's end: the summed reads column guards the summed table
-    int rc = BGR_OK;
-    if (g->pileup_on) {
-        std::lock_guard<std::mutex> l(g->abundance_m);
-        if (ok) {
-            const uint64_t T = g->header.total_bases / 2, n = g->header.n_unitigs;
-            if (g->pileup_words.empty()) g->pileup_words.assign(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n), 0u);   // (a run without aligners' tables: nothing mapped)
-            rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: a pileup without the abundance totals that guard it");
-        }
-        if (!ok || rc != BGR_OK) { g->pileup_words.clear(); g->pileup_words.shrink_to_fit(); }
-        g->pileup_valid = ok && rc == BGR_OK;
-        if (g->pileup_strands_on && g->pileup_valid && g->pileup_fwd_words.empty()) g->pileup_fwd_words.assign(g->pileup_words.size(), 0u);
-        if (!g->pileup_strands_on || !g->pileup_valid) { g->pileup_fwd_words.clear(); g->pileup_fwd_words.shrink_to_fit(); }
-        g->pileup_fwd_valid = g->pileup_strands_on && g->pileup_valid;
-    }
-    if (g->variants_on) {
-        const int vrc = variants_end(g, ok && rc == BGR_OK);
-        if (rc == BGR_OK) rc = vrc;
-    }
-    return rc;
-}
-static const bool g_run_pileup_registered = (bgr::g_run_pileup = bgr::RunPileup{run_pileup_wanted, run_pileup_begin, run_pileup_enable, run_pileup_collect, run_pileup_end, run_pileup_variants, run_pileup_strands, run_pileup_enable_strands}, true);
-
-int bgr_graph_pileup_enable(bgr_graph* g, uint32_t on) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_enable: null graph");
-    if (on) {
-        int rc = pileup_refusal(g, "bgr_graph_pileup_enable");
-        if (rc == BGR_OK) rc = graph_base_offs(g, "bgr_graph_pileup_enable");
-        if (rc != BGR_OK) return rc;
-    }
-    g->pileup_on = on != 0;
-    return BGR_OK;
-}
-
-int bgr_graph_pileup_enabled(const bgr_graph* g) { return g && g->pileup_on ? 1 : 0; }
-
-int bgr_graph_pileup_strands_enable(bgr_graph* g, uint32_t on) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_pileup_strands_enable: null graph");
-    if (on) {
-        const int rc = bgr_graph_pileup_enable(g, 1);   // (as the aligner's switch enables the aligner's pileup)
-        if (rc != BGR_OK) return rc;
-    }
-    g->pileup_strands_on = on != 0;
-    return BGR_OK;
-}
-
-int bgr_graph_pileup_strands_enabled(const bgr_graph* g) { return g && g->pileup_strands_on ? 1 : 0; }
-
-static int graph_pileup_check(const bgr_graph* g, const char* who) {
-    if (!g->pileup_valid) return fail(BGR_E_ARG, std::string(who) + ": no totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_enable on");
-    return BGR_OK;
-}
-
-int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) {
-    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup: null argument");
-    const int rc = graph_pileup_check(g, "bgr_graph_pileup");
-    if (rc != BGR_OK) return rc;
-    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup: n_bases is not the sum of the graph's unitig lengths");
-    pileup_rows(g, g->pileup_words.data(), out);
-    if (skipped) *skipped = g->pileup_skipped;
-    return BGR_OK;
-}
-
-static int graph_pileup_fwd_check(const bgr_graph* g, const char* who) {
-    if (!g->pileup_valid || !g->pileup_fwd_valid)
-        return fail(BGR_E_ARG, std::string(who) + ": no forward totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_strands_enable on");
-    return BGR_OK;
-}
-
-int bgr_graph_pileup_forward(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases) {
-    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: null argument");
-    const int rc = graph_pileup_fwd_check(g, "bgr_graph_pileup_forward");
-    if (rc != BGR_OK) return rc;
-    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: n_bases is not the sum of the graph's unitig lengths");
-    pileup_rows(g, g->pileup_fwd_words.data(), out);
-    return BGR_OK;
-}
-
-// the writers: host code, deterministic bytes, straight from the graph's totals
-static int pileup_write(const char* path, const bgr_graph* g, bool sites, const char* who, bool strands = false) {
-    if (!path || !g) return fail(BGR_E_ARG, std::string(who) + ": null argument");
-    const int rc = strands ? graph_pileup_fwd_check(g, who) : graph_pileup_check(g, who);
-    if (rc != BGR_OK) return rc;
-    std::vector<bgr_pileup_base> frows(strands ? g->header.max_unitig_len + 1 : 0);
-    const uint64_t n = g->header.n_unitigs;
-    std::vector<bgr_pileup_base> rows(g->header.max_unitig_len + 1);   // (converted unitig by unitig: no second table on the host)
-    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string(who) + ": cannot open " + path);
-    std::string buf = strands ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tdepth+\tA+\tC+\tG+\tT+\tN+\n" : sites ? "#unitig\tpos\tref\tdepth\tA\tC\tG\tT\tN\n" : "";
-    bool ok = true;
-    auto flush = [&](bool all) { if (ok && !buf.empty() && (all || buf.size() > (1u << 20))) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); } };
-    for (uint64_t id = 1; id <= n && ok; ++id) {
-        const uint64_t len = meta[id].len;
-        if (len > rows.size()) rows.resize(len);
-        pileup_unitig_rows(g, g->pileup_words.data(), id, rows.data());
-        if (strands) {
-            if (len > frows.size()) frows.resize(len);
-            pileup_unitig_rows(g, g->pileup_fwd_words.data(), id, frows.data());
-        }
-        const bgr_pileup_base* r = rows.data();
-        if (sites) {
-            for (uint64_t pos = 0; pos < len; ++pos) {
-                const bgr_pileup_base& b = r[pos];
-                if (!(b.depth | b.a | b.c | b.g | b.t | b.n)) continue;
-                const uint64_t p = meta[id].F + pos;
-                buf += std::to_string(id); buf += '\t'; buf += std::to_string(pos); buf += '\t';
-                buf += "ACGT"[(seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u];
-                for (const uint32_t v : {b.depth, b.a, b.c, b.g, b.t, b.n}) { buf += '\t'; buf += std::to_string(v); }
-                if (strands) { const bgr_pileup_base& fb = frows[pos]; for (const uint32_t v : {fb.depth, fb.a, fb.c, fb.g, fb.t, fb.n}) { buf += '\t'; buf += std::to_string(v); } }
-                buf += '\n';
-            }
-        } else {
-            for (uint64_t pos = 0; pos < len;) {   // maximal runs of equal non-zero depth
-                uint64_t e = pos + 1;
-                while (e < len && r[e].depth == r[pos].depth) ++e;
-                if (r[pos].depth) { buf += std::to_string(id); buf += '\t'; buf += std::to_string(pos); buf += '\t'; buf += std::to_string(e); buf += '\t'; buf += std::to_string(r[pos].depth); buf += '\n'; }
-                pos = e;
-            }
-        }
-        flush(false);
-    }
-    flush(true);
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string(who) + ": write to " + path + " failed");
-    return BGR_OK;
-}
-int bgr_write_pileup(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup"); }
-int bgr_write_depth(const char* path, const bgr_graph* g) { return pileup_write(path, g, false, "bgr_write_depth"); }
-int bgr_write_pileup_strands(const char* path, const bgr_graph* g) { return pileup_write(path, g, true, "bgr_write_pileup_strands", true); }
-
-
-// ---- SNV sites (bgr_variant_site in include/bgreat_gpu.h has the definition; variants_kernels.h the passes) -------------------------------------
-// the five launches over one table on `stream` of the current device, then the records' way to the host: into `vec` (as many as there are), or into
-// `out` when they are at most `cap`.  *n = their number in any case.  ms: null, or the five launches' milliseconds
-static int variants_call(const BgrDeviceGraph& dg, const bgr_graph* g, const uint32_t* table, const uint64_t* base_offs, const bgr_variant_params& prm, DevBuf& scratch,
-                         DevBuf& outbuf, hipStream_t stream, const char* who, std::vector<bgr_variant_site>* vec, bgr_variant_site* out, uint64_t cap, uint64_t* n, double* ms) {
-    static_assert(sizeof(bgr_variant_site) == 32, "eight u32 per site");
-    const uint64_t nu = g->header.n_unitigs, T = g->header.total_bases / 2, tiles = bgr::variants_tiles(T, nu);
-    *n = 0;
-    if (ms) for (int i = 0; i < 5; ++i) ms[i] = 0;
-    if (vec) vec->clear();
-    if (tiles == 0 || nu == 0) return BGR_OK;
-    hipError_t e = scratch.ensure(bgr::variants_scratch_bytes(tiles));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the passes' tile arrays: " + hipGetErrorString(e)); }
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 6; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    if (ms) {
-        for (int i = 0; i < 6; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-        HIP_TRY(hipEventRecord(ev[0], stream));
-    }
-    e = bgr::launch_variants_count(dg, nu, T, table, base_offs, prm, scratch.p, stream, ms ? ev + 1 : nullptr);
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_*_kernel): " + hipGetErrorString(e));
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, bgr::variants_total_word(scratch.p, tiles), 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n = total;
-    if (total > T) return fail(BGR_E_INTERNAL, std::string(who) + ": more sites than bases");
-    if (!vec && total > cap) return fail(BGR_E_CAPACITY, std::string(who) + ": " + std::to_string(total) + " sites, room for " + std::to_string(cap));
-    if (total) {
-        e = outbuf.ensure(total * sizeof(bgr_variant_site));
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": " + std::to_string(total) + " site records on the device: " + hipGetErrorString(e)); }
-        e = bgr::launch_variants_emit(dg, nu, T, table, base_offs, prm, scratch.p, static_cast<bgr_variant_site*>(outbuf.p), stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_classify_kernel, emit): " + hipGetErrorString(e));
-        if (ms) HIP_TRY(hipEventRecord(ev[5], stream));
-        if (vec) { vec->resize(total); out = vec->data(); }
-        HIP_TRY(hipMemcpyAsync(out, outbuf.p, total * sizeof(bgr_variant_site), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (ms)
-        for (int i = 0; i < (total ? 5 : 4); ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, ev[i], ev[i + 1])); ms[i] = f; }
-    return BGR_OK;
-}
-
-// the same with the forward table next to the total one: 64-byte records under the strand filter
-static int variants_strands_call(const BgrDeviceGraph& dg, const bgr_graph* g, const uint32_t* table, const uint32_t* table_fwd, const uint64_t* base_offs, const bgr_variant_strand_params& prm,
-                                 DevBuf& scratch, DevBuf& outbuf, hipStream_t stream, const char* who, std::vector<bgr_variant_strand_site>* vec, bgr_variant_strand_site* out, uint64_t cap,
-                                 uint64_t* n, double* ms) {
-    static_assert(sizeof(bgr_variant_strand_site) == 64, "sixteen u32 per site");
-    const uint64_t nu = g->header.n_unitigs, T = g->header.total_bases / 2, tiles = bgr::variants_tiles(T, nu);
-    *n = 0;
-    if (ms) for (int i = 0; i < 5; ++i) ms[i] = 0;
-    if (vec) vec->clear();
-    if (tiles == 0 || nu == 0) return BGR_OK;
-    hipError_t e = scratch.ensure(bgr::variants_strands_scratch_bytes(tiles));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the passes' tile arrays: " + hipGetErrorString(e)); }
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 6; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    if (ms) {
-        for (int i = 0; i < 6; ++i) HIP_TRY(hipEventCreate(&ev[i]));
-        HIP_TRY(hipEventRecord(ev[0], stream));
-    }
-    e = bgr::launch_variants_strands_count(dg, nu, T, table, table_fwd, base_offs, prm, scratch.p, stream, ms ? ev + 1 : nullptr);
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_*_kernel, strands): " + hipGetErrorString(e));
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, bgr::variants_total_word(scratch.p, tiles), 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n = total;
-    if (total > T) return fail(BGR_E_INTERNAL, std::string(who) + ": more sites than bases");
-    if (!vec && total > cap) return fail(BGR_E_CAPACITY, std::string(who) + ": " + std::to_string(total) + " sites, room for " + std::to_string(cap));
-    if (total) {
-        e = outbuf.ensure(total * sizeof(bgr_variant_strand_site));
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": " + std::to_string(total) + " site records on the device: " + hipGetErrorString(e)); }
-        e = bgr::launch_variants_strands_emit(dg, nu, T, table, table_fwd, base_offs, prm, scratch.p, static_cast<bgr_variant_strand_site*>(outbuf.p), stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_variants_classify_kernel, strands, emit): " + hipGetErrorString(e));
-        if (ms) HIP_TRY(hipEventRecord(ev[5], stream));
-        if (vec) { vec->resize(total); out = vec->data(); }
-        HIP_TRY(hipMemcpyAsync(out, outbuf.p, total * sizeof(bgr_variant_strand_site), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (ms)
-        for (int i = 0; i < (total ? 5 : 4); ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, ev[i], ev[i + 1])); ms[i] = f; }
-    return BGR_OK;
-}
-
-// dst += src, two whole pileup tables of `bytes` bytes; the current device is dst's, `stream` one of its streams, waited for before the return.
-// On one device one kernel; across devices -- or whenever the test hook names a piece size -- through `stage`, a piece of at most 64 MiB at a time
-static int variants_table_add(uint32_t* dst, int dst_device, const uint32_t* src, int src_device, uint64_t bytes, DevBuf& stage, uint32_t num_cus, hipStream_t stream, const char* who) {
-    const int64_t hook = bgr::opt("test.variants_stage_bytes");
-    hipError_t e;
-    if (dst_device == src_device && hook == 0) {
-        e = bgr::launch_pileup_add(dst, src, bytes / 4, true, num_cus, stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_pileup_add_kernel): " + hipGetErrorString(e));
-    } else {
-        uint64_t piece = hook > 0 ? ((uint64_t)hook + 15) / 16 * 16 : (64ull << 20);
-        if (piece > (64ull << 20)) piece = 64ull << 20;
-        if (piece > bytes) piece = (bytes + 15) / 16 * 16;
-        e = stage.ensure(piece);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string(who) + ": the staging piece of a table from another device: " + hipGetErrorString(e)); }
-        for (uint64_t off = 0; off < bytes; off += piece) {   // (the pieces follow each other on one stream: the copy of the next waits for the add of this one)
-            const uint64_t len = bytes - off < piece ? bytes - off : piece;
-            if (dst_device == src_device) HIP_TRY(hipMemcpyAsync(stage.p, reinterpret_cast<const char*>(src) + off, len, hipMemcpyDeviceToDevice, stream));
-            else HIP_TRY(hipMemcpyPeerAsync(stage.p, dst_device, reinterpret_cast<const char*>(src) + off, src_device, len, stream));
-            e = bgr::launch_pileup_add(dst + off / 4, static_cast<const uint32_t*>(stage.p), len / 4, off + len == bytes, num_cus, stream);
-            if (e != hipSuccess) return fail(BGR_E_HIP, std::string(who) + ": kernel launch (bgr_pileup_add_kernel): " + hipGetErrorString(e));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return BGR_OK;
-}
-
-int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, bgr_variant_site* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!a || !params || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: null argument");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: an internal stream of another aligner");
-    if (!bgr::variants_params_ok(*params)) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
-    if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites: the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
-    const uint64_t nu = a->graph->header.n_unitigs;
-    std::vector<bgr_unitig_abundance> ab(nu);
-    int rc = bgr_aligner_abundance(a, ab.data(), nu);   // (synchronises the aligner's stream and its twins')
-    if (rc == BGR_OK) rc = pileup_guard(ab.data(), nu, "bgr_aligner_pileup_sites");
-    if (rc != BGR_OK) return rc;
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    return variants_call(a->dg, a->graph, a->pileup_tab, a->pileup_base_offs, *params, a->var_scratch, a->var_out, a->stream, "bgr_aligner_pileup_sites", nullptr, out, cap, n,
-                         a->knob_no_events ? nullptr : a->var_ms);
-}
-
-int bgr_aligner_pileup_strand_sites(bgr_aligner* a, const bgr_variant_strand_params* params, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!a || !params || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: null argument");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: an internal stream of another aligner");
-    if (!bgr::variants_params_ok(bgr_variant_params{params->min_depth, params->min_alt, params->min_af_ppm}))
-        return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
-    if (!a->pileup_tab || !a->pileup_fwd_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_strand_sites: strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
-    const uint64_t nu = a->graph->header.n_unitigs;
-    std::vector<bgr_unitig_abundance> ab(nu);
-    int rc = bgr_aligner_abundance(a, ab.data(), nu);   // (synchronises the aligner's stream and its twins')
-    if (rc == BGR_OK) rc = pileup_guard(ab.data(), nu, "bgr_aligner_pileup_strand_sites");
-    if (rc != BGR_OK) return rc;
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    return variants_strands_call(a->dg, a->graph, a->pileup_tab, a->pileup_fwd_tab, a->pileup_base_offs, *params, a->var_scratch, a->var_out, a->stream, "bgr_aligner_pileup_strand_sites", nullptr,
-                                 out, cap, n, a->knob_no_events ? nullptr : a->var_ms);
-}
-
-int bgr_aligner_pileup_sites_times(bgr_aligner* a, double ms[5]) {
-    if (!a || !ms) return fail(BGR_E_ARG, "bgr_aligner_pileup_sites_times: null argument");
-    for (int i = 0; i < 5; ++i) ms[i] = a->var_ms[i];
-    return BGR_OK;
-}
-
-int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src) {
-    if (!dst || !src) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: null aligner");
-    if (dst->is_twin || src->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: an internal stream of another aligner");
-    if (dst == src || dst->graph != src->graph) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: two different aligners of one graph are needed");
-    if (!dst->pileup_tab || !src->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: the pileup was never enabled on one of the aligners (bgr_aligner_pileup_enable)");
-    if (!dst->pileup_fwd_tab != !src->pileup_fwd_tab)
-        return fail(BGR_E_ARG, "bgr_aligner_pileup_add: one of the aligners has a forward table (bgr_aligner_pileup_strands_enable) and the other has none");
-    HIP_TRY(hipSetDevice(src->device));
-    for (bgr_aligner* x = src; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipSetDevice(dst->device));
-    for (bgr_aligner* x = dst; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    const uint64_t bytes = bgr::pileup_table_bytes(dst->graph->header.total_bases / 2, dst->graph->header.n_unitigs);
-    const int rc = variants_table_add(dst->pileup_tab, dst->device, src->pileup_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
-    if (rc != BGR_OK || !dst->pileup_fwd_tab) return rc;
-    return variants_table_add(dst->pileup_fwd_tab, dst->device, src->pileup_fwd_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
-}
-
-// a run's aligner, its streams idle from here on: the first one's table becomes the run's (the buffers move: nothing is allocated), the others' are added
-static int variants_collect(bgr_graph* g, bgr_aligner* a) {
-    if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_align_all: the pileup was never enabled on an aligner of the run");
-    const bool strands = g->variants_strands_on;   // the forward table travels with the total one
-    if (strands && !a->pileup_fwd_tab) return fail(BGR_E_ARG, "bgr_align_all: strands were never counted on an aligner of the run");
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    std::lock_guard<std::mutex> l(g->abundance_m);   // (the lanes of a split run end side by side: one at a time here)
-    if (!g->variants_run) {
-        VariantsRun* r = new VariantsRun();
-        r->device = a->device; r->num_cus = a->num_cus; r->dg = a->dg;
-        if (hipStreamCreate(&r->stream) != hipSuccess) { delete r; (void)hipGetLastError(); return fail(BGR_E_HIP, "bgr_align_all: a stream for the run's pileup table"); }
-        std::swap(r->table, a->pileup);
-        std::swap(r->offs, a->pileup_offs);
-        if (strands) { std::swap(r->table_fwd, a->pileup_fwd); a->pileup_fwd_tab = nullptr; a->strands_on = false; }
-        a->pileup_tab = nullptr; a->pileup_base_offs = nullptr; a->pileup_on = false;
-        pileup_share(a);
-        g->variants_run = r;
-        return BGR_OK;
-    }
-    VariantsRun* r = g->variants_run;
-    HIP_TRY(hipSetDevice(r->device));
-    const uint64_t bytes = bgr::pileup_table_bytes(g->header.total_bases / 2, g->header.n_unitigs);
-    const int rc = variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->pileup_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
-    if (rc != BGR_OK || !strands) return rc;
-    if (!r->table_fwd.p) return fail(BGR_E_INTERNAL, "bgr_align_all: the run's pileup table has no forward table");
-    return variants_table_add(static_cast<uint32_t*>(r->table_fwd.p), r->device, a->pileup_fwd_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
-}
-// the run's end: behind the guard of the summed abundance the passes run once on the run's table; the table is freed whatever happens
-static int variants_end(bgr_graph* g, bool ok) {
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    int rc = BGR_OK;
-    if (ok) {
-        rc = g->abundance_valid ? pileup_guard(g->abundance.data(), g->abundance.size(), "bgr_align_all") : fail(BGR_E_INTERNAL, "bgr_align_all: sites without the abundance totals that guard them");
-        if (rc == BGR_OK && g->variants_run) {
-            VariantsRun* r = g->variants_run;
-            DevBuf scratch, outbuf;
-            uint64_t n = 0;
-            if (hipSetDevice(r->device) != hipSuccess) rc = fail(BGR_E_HIP, "bgr_align_all: hipSetDevice for the run's pileup table");
-            else if (!g->variants_strands_on)
-                rc = variants_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint64_t*>(r->offs.p), g->variants_prm, scratch, outbuf, r->stream, "bgr_align_all",
-                                   &g->variants_sites, nullptr, 0, &n, nullptr);
-            else if (!r->table_fwd.p) rc = fail(BGR_E_INTERNAL, "bgr_align_all: the run's pileup table has no forward table");
-            else {
-                const bgr_variant_strand_params sp = {g->variants_prm.min_depth, g->variants_prm.min_alt, g->variants_prm.min_af_ppm, g->variants_min_alt_strand};
-                rc = variants_strands_call(r->dg, g, static_cast<const uint32_t*>(r->table.p), static_cast<const uint32_t*>(r->table_fwd.p), static_cast<const uint64_t*>(r->offs.p), sp, scratch,
-                                           outbuf, r->stream, "bgr_align_all", &g->variants_strand_sites, nullptr, 0, &n, nullptr);
-                if (rc == BGR_OK) {   // (bgr_graph_variants then delivers the same sites without the forward numbers)
-                    g->variants_sites.resize(g->variants_strand_sites.size());
-                    for (size_t i = 0; i < g->variants_sites.size(); ++i) memcpy(&g->variants_sites[i], &g->variants_strand_sites[i], sizeof(bgr_variant_site));
-                }
-            }
-            scratch.release(); outbuf.release();
-        }
-    }
-    variants_run_free(g);
-    if (!ok || rc != BGR_OK) { g->variants_sites.clear(); g->variants_sites.shrink_to_fit(); g->variants_strand_sites.clear(); g->variants_strand_sites.shrink_to_fit(); }
-    g->variants_called = g->variants_prm;
-    g->variants_called_strand = g->variants_min_alt_strand;
-    g->variants_valid = ok && rc == BGR_OK;
-    g->variants_strands_valid = g->variants_valid && g->variants_strands_on;
-    return rc;
-}
-
-int bgr_graph_variants_enable(bgr_graph* g, const bgr_variant_params* params) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_variants_enable: null graph");
-    if (params) {
-        if (!bgr::variants_params_ok(*params)) return fail(BGR_E_ARG, "bgr_graph_variants_enable: thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
-        int rc = pileup_refusal(g, "bgr_graph_variants_enable");
-        if (rc == BGR_OK) rc = graph_base_offs(g, "bgr_graph_variants_enable");
-        if (rc != BGR_OK) return rc;
-        g->variants_prm = *params;
-    }
-    g->variants_on = params != nullptr;
-    g->variants_strands_on = false;   // (the plain switch: 32-byte records, no forward table)
-    return BGR_OK;
-}
-
-int bgr_graph_variants_strands_enable(bgr_graph* g, const bgr_variant_strand_params* params) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_variants_strands_enable: null graph");
-    if (!params) return bgr_graph_variants_enable(g, nullptr);
-    const bgr_variant_params prm = {params->min_depth, params->min_alt, params->min_af_ppm};
-    const int rc = bgr_graph_variants_enable(g, &prm);
-    if (rc != BGR_OK) return rc;
-    g->variants_strands_on = true;
-    g->variants_min_alt_strand = params->min_alt_strand;
-    return BGR_OK;
-}
-
-int bgr_graph_variant_strand_sites(const bgr_graph* g, bgr_variant_strand_site* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_variant_strand_sites: null argument");
-    if (!g->variants_strands_valid) return fail(BGR_E_ARG, "bgr_graph_variant_strand_sites: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_strands_enable on");
-    *n = g->variants_strand_sites.size();
-    if (g->variants_strand_sites.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_variant_strand_sites: " + std::to_string(g->variants_strand_sites.size()) + " sites, room for " + std::to_string(cap));
-    if (!g->variants_strand_sites.empty()) memcpy(out, g->variants_strand_sites.data(), g->variants_strand_sites.size() * sizeof(bgr_variant_strand_site));
-    return BGR_OK;
-}
-
-int bgr_graph_variants_enabled(const bgr_graph* g) { return g && g->variants_on ? 1 : 0; }
-
-int bgr_graph_variants(const bgr_graph* g, bgr_variant_site* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_variants: null argument");
-    if (!g->variants_valid) return fail(BGR_E_ARG, "bgr_graph_variants: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_enable on");
-    *n = g->variants_sites.size();
-    if (g->variants_sites.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_variants: " + std::to_string(g->variants_sites.size()) + " sites, room for " + std::to_string(cap));
-    if (!g->variants_sites.empty()) memcpy(out, g->variants_sites.data(), g->variants_sites.size() * sizeof(bgr_variant_site));
-    return BGR_OK;
-}
-
-int bgr_graph_variants_params(const bgr_graph* g, bgr_variant_params* out) {
-    if (!g || !out) return fail(BGR_E_ARG, "bgr_graph_variants_params: null argument");
-    if (!g->variants_valid) return fail(BGR_E_ARG, "bgr_graph_variants_params: no totals -- they are those of the last successful bgr_align_all with bgr_graph_variants_enable on");
-    *out = g->variants_called;
-    return BGR_OK;
-}
-
-int bgr_write_vcf(const char* path, const bgr_graph* g, const bgr_variant_params* params, const bgr_variant_site* sites, uint64_t n) {
-    if (!path || !g || !params || (n && !sites)) return fail(BGR_E_ARG, "bgr_write_vcf: null argument");
-    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_vcf: the graph has no host blob (the reference letters are read from it)");
-    if (g->header.has_exc) return fail(BGR_E_ARG, "bgr_write_vcf: a graph of ACGT-only unitigs is needed (--vcf): the 2-bit store does not spell other characters");
-    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
-    std::string err;
-    if (!bgr::vcf_write(nullptr, meta, seq, g->header.n_unitigs, *params, sites, n, &err)) return fail(BGR_E_ARG, "bgr_write_vcf: " + err);   // (the checks alone: no file for sites that are none)
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_vcf: cannot open ") + path);
-    bool ok = bgr::vcf_write(f, meta, seq, g->header.n_unitigs, *params, sites, n, &err);
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_vcf: write to ") + path + " failed");
-    return BGR_OK;
-}
-
-int bgr_write_vcf_strands(const char* path, const bgr_graph* g, const bgr_variant_strand_params* params, const bgr_variant_strand_site* sites, uint64_t n) {
-    if (!path || !g || !params || (n && !sites)) return fail(BGR_E_ARG, "bgr_write_vcf_strands: null argument");
-    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_vcf_strands: the graph has no host blob (the reference letters are read from it)");
-    if (g->header.has_exc) return fail(BGR_E_ARG, "bgr_write_vcf_strands: a graph of ACGT-only unitigs is needed (--vcf): the 2-bit store does not spell other characters");
-    const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    const uint64_t* seq = reinterpret_cast<const uint64_t*>(g->host.base() + g->header.off_seq);
-    std::string err;
-    if (!bgr::vcf_strands_write(nullptr, meta, seq, g->header.n_unitigs, *params, sites, n, &err)) return fail(BGR_E_ARG, "bgr_write_vcf_strands: " + err);   // (the checks alone)
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_vcf_strands: cannot open ") + path);
-    bool ok = bgr::vcf_strands_write(f, meta, seq, g->header.n_unitigs, *params, sites, n, &err);
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_vcf_strands: write to ") + path + " failed");
-    return BGR_OK;
-}
-
-int bgr_parse_min_alt_strand(const char* text, uint32_t* out) {
-    if (!text || !out) return fail(BGR_E_ARG, "bgr_parse_min_alt_strand: null argument");
-    if (!bgr::parse_min_alt_strand(text, out)) return fail(BGR_E_ARG, std::string("bgr_parse_min_alt_strand: '") + text + "' is no non-negative integer of at most nine digits");
-    return BGR_OK;
-}
-
-int bgr_parse_af_ppm(const char* text, uint32_t* ppm) {
-    if (!text || !ppm) return fail(BGR_E_ARG, "bgr_parse_af_ppm: null argument");
-    if (!bgr::parse_af_ppm(text, ppm)) return fail(BGR_E_ARG, std::string("bgr_parse_af_ppm: '") + text + "' is no fraction between 0 and 1 with at most six decimals");
-    return BGR_OK;
-}
-
-
-// ---- links (bgr_link in include/bgreat_gpu.h has the definition) ---------------------------------------------------------------------------
-static int graph_links_bound(bgr_graph* g, uint64_t* bound) {
-    if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_links_bound: the graph has no host blob (the bound is counted over its slots)");
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (!g->links_bound_known) { g->links_bound = bgr::links_bound_of_blob(g->host.header(), g->host.base()); g->links_bound_known = true; }
-    *bound = g->links_bound;
-    return BGR_OK;
-}
-int bgr_graph_links_bound(bgr_graph* g, uint64_t* bound) {
-    if (!g || !bound) return fail(BGR_E_ARG, "bgr_graph_links_bound: null argument");
-    return graph_links_bound(g, bound);
-}
-
-int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key) {
-    if (!out || a == 0 || b == 0 || a == INT32_MIN || b == INT32_MIN || std::abs((int64_t)a) >= 0x40000000 || std::abs((int64_t)b) >= 0x40000000)
-        return fail(BGR_E_ARG, "bgr_link_canonical: null argument or an id that is 0 or beyond 2^30");
-    const uint64_t c = bgr::links_canonical(a, b);   // (the function the kernel calls)
-    *out = bgr_link{bgr::links_key_from(c), bgr::links_key_to(c), 0};
-    if (key) *key = c;
-    return BGR_OK;
-}
-
-static void links_share(bgr_aligner* a) {   // the twins add to the aligner's table
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) { tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on; }
-}
-
-int bgr_aligner_links_enable(bgr_aligner* a, uint32_t on) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_links_enable: null aligner");
-    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_links_enable: an internal stream of another aligner");
-    if (on && !a->links_tab) {
-        uint64_t bound = 0;
-        const int rc = graph_links_bound(a->graph, &bound);
-        if (rc != BGR_OK) return rc;
-        uint64_t cap = bgr::links_capacity(bound);
-        if (const int64_t c = bgr::opt("test.links_capacity")) { cap = 2; while (cap < (uint64_t)c) cap <<= 1; }
-        HIP_TRY(hipSetDevice(a->device));
-        const hipError_t e = a->links.ensure(bgr::links_table_bytes(cap));
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, "bgr_aligner_links_enable: " + std::to_string(bgr::links_table_bytes(cap)) + " bytes for the table of links: " + hipGetErrorString(e));
-        HIP_TRY(hipMemsetAsync(a->links.p, 0, a->links.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
-        HIP_TRY(hipStreamSynchronize(a->stream));
-        a->links_tab = static_cast<unsigned long long*>(a->links.p);
-        a->links_cap = cap;
-        a->links_bound = bound;
-    }
-    a->links_on = on != 0;
-    links_share(a);
-    return BGR_OK;
-}
-
-// the words behind the aligner's table (links_kernels.h), every stream that adds to it waited for; BGR_E_CAPACITY when the overflow word is set
-static int links_tail(bgr_aligner* a, const char* who, uint64_t tail[bgr::kLinksTailWords]) {
-    if (!a->links_tab) return fail(BGR_E_ARG, std::string(who) + ": links were never enabled on this aligner (bgr_aligner_links_enable)");
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
-    HIP_TRY(hipMemcpy(tail, a->links_tab + 2 * a->links_cap, bgr::kLinksTailWords * 8, hipMemcpyDeviceToHost));
-    if (tail[0])
-        return fail(BGR_E_CAPACITY, std::string(who) + ": the table of links (" + std::to_string(a->links_cap) + " slots) was full: " + std::to_string(tail[0]) +
-                                        " traversals found no place; the counts are incomplete until bgr_aligner_reset_links");
-    return BGR_OK;
-}
-// ... and the table as it stands: the used slots as {key, count}, sorted by key.  Only if there are at most `room` of them (the kernel counts the
-// slots it claims): a caller that asks for the number first does not pay for the table's way to the host twice
-static int links_snapshot(bgr_aligner* a, const char* who, uint64_t room, std::vector<std::pair<uint64_t, uint64_t>>& kv, uint64_t tail[bgr::kLinksTailWords]) {
-    const int rc = links_tail(a, who, tail);
-    if (rc != BGR_OK) return rc;
-    kv.clear();
-    if (tail[2] > room || tail[2] == 0) return BGR_OK;
-    std::vector<uint64_t> t(2 * a->links_cap);
-    HIP_TRY(hipMemcpy(t.data(), a->links_tab, t.size() * 8, hipMemcpyDeviceToHost));
-    for (uint64_t s = 0; s < a->links_cap; ++s)
-        if (t[2 * s]) kv.emplace_back(t[2 * s], t[2 * s + 1]);
-    std::sort(kv.begin(), kv.end());
-    return BGR_OK;
-}
-static void links_deliver(const std::vector<std::pair<uint64_t, uint64_t>>& kv, bgr_link* out) {
-    for (size_t i = 0; i < kv.size(); ++i) out[i] = bgr_link{bgr::links_key_from(kv[i].first), bgr::links_key_to(kv[i].first), kv[i].second};
-}
-
-int bgr_aligner_links(bgr_aligner* a, bgr_link* out, uint64_t cap, uint64_t* n) {
-    static_assert(sizeof(bgr_link) == 16, "two ids and a 64-bit count");
-    if (n) *n = 0;
-    if (!a || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_aligner_links: null argument");
-    std::vector<std::pair<uint64_t, uint64_t>> kv;
-    uint64_t tail[bgr::kLinksTailWords];
-    const int rc = links_snapshot(a, "bgr_aligner_links", cap, kv, tail);
-    if (rc != BGR_OK) return rc;
-    *n = tail[2];
-    if (tail[2] > cap) return fail(BGR_E_CAPACITY, "bgr_aligner_links: " + std::to_string(tail[2]) + " links, room for " + std::to_string(cap));
-    if (kv.size() != tail[2]) return fail(BGR_E_INTERNAL, "bgr_aligner_links: the table's used slots and their counter disagree");
-    links_deliver(kv, out);
-    return BGR_OK;
-}
-
-int bgr_aligner_links_info(bgr_aligner* a, uint64_t out[4]) {
-    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_links_info: null argument");
-    uint64_t tail[bgr::kLinksTailWords] = {0, 0, 0};
-    const int rc = links_tail(a, "bgr_aligner_links_info", tail);
-    if (rc != BGR_OK && rc != BGR_E_CAPACITY) return rc;   // (an overflow is what this call reports)
-    out[0] = a->links_cap; out[1] = a->links_bound; out[2] = tail[0]; out[3] = tail[1];
-    return BGR_OK;
-}
-
-int bgr_aligner_links_plan(bgr_aligner* a, uint64_t n_reads, uint32_t out[4]) {
-    if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_links_plan: null argument");
-    uint64_t bound = a->links_bound;
-    if (!a->links_tab) { const int rc = graph_links_bound(a->graph, &bound); if (rc != BGR_OK) return rc; }
-    const bgr::LinksPlan lp = bgr::plan_links(bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
-    out[0] = lp.form; out[1] = lp.blocks; out[2] = lp.threads; out[3] = lp.lds_bytes;
-    return BGR_OK;
-}
-
-int bgr_plan_links(uint64_t links_bound, uint64_t n_reads, uint32_t num_cus, uint32_t form_knob, uint32_t out[4]) {
-    if (!out || form_knob > 2) return fail(BGR_E_ARG, "bgr_plan_links: null argument or a form beyond 2");
-    const bgr::LinksPlan lp = bgr::plan_links(links_bound, n_reads, num_cus, form_knob);
-    out[0] = lp.form; out[1] = lp.blocks; out[2] = lp.threads; out[3] = lp.lds_bytes;
-    return BGR_OK;
-}
-
-int bgr_aligner_reset_links(bgr_aligner* a) {
-    if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_links: null aligner");
-    if (!a->links.p) return BGR_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));   // (the twins add to the same table)
-    HIP_TRY(hipMemsetAsync(a->links.p, 0, a->links.cap, a->stream));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    return BGR_OK;
-}
-
-// what a whole run calls (run_links.h)
-static bool run_links_wanted(const bgr_graph* g) { return g && g->links_on; }
-static void run_links_begin(bgr_graph* g) {
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    g->links.clear();
-    g->links_valid = false;
-}
-static int run_links_enable(bgr_aligner* a) { return bgr_aligner_links_enable(a, 1); }
-static int run_links_collect(bgr_graph* g, bgr_aligner* a) {
-    std::vector<std::pair<uint64_t, uint64_t>> kv;
-    uint64_t tail[bgr::kLinksTailWords];
-    const int rc = links_snapshot(a, "bgr_align_all", ~0ull, kv, tail);
-    if (rc != BGR_OK) return rc;
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    g->links.insert(g->links.end(), kv.begin(), kv.end());
-    return BGR_OK;
-}
-static void run_links_end(bgr_graph* g, bool ok) {   // the aligners' tables, one behind the other: sorted, equal keys summed
-    std::lock_guard<std::mutex> l(g->abundance_m);
-    if (!ok) g->links.clear();
-    else {
-        std::sort(g->links.begin(), g->links.end());
-        size_t w = 0;
-        for (size_t i = 0; i < g->links.size(); ++i) {
-            if (w && g->links[w - 1].first == g->links[i].first) g->links[w - 1].second += g->links[i].second;
-            else g->links[w++] = g->links[i];
-        }
-        g->links.resize(w);
-    }
-    g->links_valid = ok;
-}
-static const bool g_run_links_registered = (bgr::g_run_links = bgr::RunLinks{run_links_wanted, run_links_begin, run_links_enable, run_links_collect, run_links_end}, true);
-
-int bgr_graph_links_enable(bgr_graph* g, uint32_t on) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_links_enable: null graph");
-    if (on && g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_links_enable: the graph has no host blob (the table of links is sized from it)");
-    g->links_on = on != 0;
-    return BGR_OK;
-}
-
-int bgr_graph_links_enabled(const bgr_graph* g) { return g && g->links_on ? 1 : 0; }
-
-int bgr_graph_links(const bgr_graph* g, bgr_link* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_links: null argument");
-    if (!g->links_valid) return fail(BGR_E_ARG, "bgr_graph_links: no totals -- they are those of the last successful bgr_align_all with bgr_graph_links_enable on");
-    *n = g->links.size();
-    if (g->links.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_links: " + std::to_string(g->links.size()) + " links, room for " + std::to_string(cap));
-    links_deliver(g->links, out);
-    return BGR_OK;
-}
-
-int bgr_write_gfa(const char* path, const bgr_graph* g, const bgr_unitig_abundance* rows, uint64_t n_rows, const bgr_link* links, uint64_t n_links) {
-    if (!path || !g || (n_rows && !rows) || (n_links && !links)) return fail(BGR_E_ARG, "bgr_write_gfa: null argument");
-    if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_write_gfa: n_rows is not the graph's number of unitigs");
-    if (g->ascii_offs.empty() && n_rows) return fail(BGR_E_ARG, "bgr_write_gfa: this graph was created from a blob and carries no unitig characters");
-    for (uint64_t i = 0; i < n_links; ++i) {
-        const bgr_link& l = links[i];
-        if (l.from == 0 || l.to == 0 || l.from == INT32_MIN || l.to == INT32_MIN || (uint64_t)std::abs((int64_t)l.from) > n_rows || (uint64_t)std::abs((int64_t)l.to) > n_rows)
-            return fail(BGR_E_ARG, "bgr_write_gfa: a link names a unitig the graph does not have");
-        if (i && bgr::links_pack(links[i - 1].from, links[i - 1].to) >= bgr::links_pack(l.from, l.to)) return fail(BGR_E_ARG, "bgr_write_gfa: the links are not sorted by key");
-    }
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_gfa: cannot open ") + path);
-    std::string buf = "H\tVN:Z:1.0\n";
-    bool ok = true;
-    auto drain = [&](bool all) { if (ok && (all ? !buf.empty() : buf.size() > (1u << 20))) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); } };
-    for (uint64_t i = 0; i < n_rows && ok; ++i) {
-        const uint64_t b = g->ascii_offs[i], e = g->ascii_offs[i + 1];
-        buf += "S\t"; buf += std::to_string(i + 1); buf += '\t';
-        buf.append(g->ascii.data() + b, e - b);
-        buf += "\tLN:i:"; buf += std::to_string(e - b);
-        buf += "\tRC:i:"; buf += std::to_string(rows[i].reads);
-        buf += "\tKC:i:"; buf += std::to_string(rows[i].kmers); buf += '\n';
-        drain(false);
-    }
-    const std::string overlap = std::to_string(g->header.k - 1) + "M";
-    for (uint64_t i = 0; i < n_links && ok; ++i) {
-        const bgr_link& l = links[i];
-        if (!l.count) continue;
-        buf += "L\t"; buf += std::to_string(std::abs((int64_t)l.from)); buf += l.from < 0 ? "\t-\t" : "\t+\t";
-        buf += std::to_string(std::abs((int64_t)l.to)); buf += l.to < 0 ? "\t-\t" : "\t+\t";
-        buf += overlap; buf += "\tRC:i:"; buf += std::to_string(l.count); buf += '\n';
-        drain(false);
-    }
-    drain(true);
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_gfa: write to ") + path + " failed");
-    return BGR_OK;
 }
 
 int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
@@ -2471,12 +1259,11 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
         tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
         tw->knob_abundance_form = a->knob_abundance_form;
         tw->knob_links_form = a->knob_links_form;
-        tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;   // (likewise)
-        tw->pileup_fwd_tab = a->pileup_fwd_tab; tw->strands_on = a->strands_on;
-        tw->links_tab = a->links_tab; tw->links_cap = a->links_cap; tw->links_bound = a->links_bound; tw->links_on = a->links_on;   // (one table for the aligner and its twins: the atomics are device-scope)
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         al[t] = tw;
     }
+    pileup_share(a);   // (one pileup table and one table of links for the aligner and its twins: the atomics are device-scope)
+    links_share(a);
     uint64_t cut[kOverlapMaxPieces + 1];
     for (unsigned k = 0; k <= n_pieces; ++k) cut[k] = n * k / n_pieces;
     std::mutex mu;

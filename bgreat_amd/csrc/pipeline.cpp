@@ -38,19 +38,11 @@
 #include "file_image.h"
 #include "read_pack.h"
 #include "options.h"
-#include "run_abundance.h"
-#include "run_links.h"
-#include "run_pileup.h"
+#include "run_counts.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip
-RunAbundance g_run_abundance = {nullptr, nullptr, nullptr, nullptr};  // run_abundance.h: registered by capi.hip
-RunLinks g_run_links = {nullptr, nullptr, nullptr, nullptr, nullptr};    // run_links.h: likewise
-// the graph's switch (bgr_graph_links_enable): the run counts links, and unitig abundance with them, whatever bgr_run_options.abundance says
-static bool run_links(const bgr_graph* g) { return g_run_links.wanted && g_run_links.wanted(g); }
-RunPileup g_run_pileup = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // run_pileup.h: likewise
-// the graph's switches (bgr_graph_pileup_enable, bgr_graph_variants_enable): the run counts per-base depth and mismatches, and unitig abundance with them
-static bool run_pileup(const bgr_graph* g) { return g_run_pileup.wanted && g_run_pileup.wanted(g); }
+RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
 }
 
 namespace {
@@ -518,8 +510,8 @@ struct InputSpan {
 };
 
 // One pipeline: the devices first_device .. first_device + n_gpus - 1 of `opt` map `inputs` in order into ONE pair of output files.
-// `cancel` (optional): shared with the other lanes of a split run -- a lane that fails stops them all.
-int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt, const std::vector<InputSpan>& inputs,
+// `cancel` (optional): shared with the other lanes of a split run -- a lane that fails stops them all.  `counts`: what the run counts (run_counts.h).
+int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt, uint32_t counts, const std::vector<InputSpan>& inputs,
                    const char* paths_file, const char* notaligned_file, uint64_t counters_out[5], double* mapping_seconds, std::atomic<bool>* cancel) {
     const unsigned n_gpus = std::max<uint32_t>(1, opt->n_gpus);
     // (option test.lanes_on_one_device, a test hook: every device of the run is the first one -- the N-device code path on a one-GPU box)
@@ -625,10 +617,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             }
             // (nobody reads bgr_aligner_kernel_times here: no events around the kernels -- they cost a 262 144-read piece's mapping launch a tenth of its time)
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
-            if (opt->abundance || bgr::run_links(graph) || bgr::run_pileup(graph)) rc = bgr::g_run_abundance.enable(a);  // every launch of the run is followed by the abundance kernel (bgr_align_all has checked the table)
-            if (rc == BGR_OK && bgr::run_links(graph)) rc = bgr::g_run_links.enable(a);   // ... and by the links kernel
-            if (rc == BGR_OK && bgr::run_pileup(graph))   // ... and by the pileup kernel (with a strands switch on: the one that fills the forward table too)
-                rc = bgr::g_run_pileup.strands && bgr::g_run_pileup.enable_strands && bgr::g_run_pileup.strands(graph) ? bgr::g_run_pileup.enable_strands(a) : bgr::g_run_pileup.enable(a);
+            if (counts) rc = bgr::g_run_counts.enable(a, counts);  // every launch of the run is followed by the kernels of what it counts (bgr_align_all has checked the table)
             aligners.push_back(a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);
@@ -1422,17 +1411,9 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     for (auto* a : aligners) {
         uint64_t c5[5];
         if (!failed && bgr_aligner_counters(a, c5) == BGR_OK) for (int j = 0; j < 5; ++j) tot[j] += c5[j];
-        if (!failed && bgr::run_links(graph)) {  // likewise its table of links
-            const int lrc = bgr::g_run_links.collect(graph, a);
-            if (lrc != BGR_OK) fail(lrc, bgr_last_error());
-        }
-        if (!failed && bgr::run_pileup(graph)) {  // likewise its pileup table
-            const int prc = bgr::g_run_pileup.collect(graph, a);
-            if (prc != BGR_OK) fail(prc, bgr_last_error());
-        }
-        if (!failed && (opt->abundance || bgr::run_links(graph) || bgr::run_pileup(graph))) {  // this aligner's table joins the run's totals in the graph (summed on the host: once per run, 24 bytes per unitig)
-            const int arc = bgr::g_run_abundance.collect(graph, a);
-            if (arc != BGR_OK) fail(arc, bgr_last_error());
+        if (!failed && counts) {  // likewise its tables of what the run counts: they join the run's totals in the graph
+            const int crc = bgr::g_run_counts.collect(graph, a, counts);
+            if (crc != BGR_OK) fail(crc, bgr_last_error());
         }
         bgr_aligner_destroy(a);
     }
@@ -1457,7 +1438,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
 // The reference's N workers share ONE reader and ONE writer under a mutex each (alignerGreedy.cpp:372-377,407-411).  Here every
 // device gets a lane of its own -- producer, gatherer, stream workers, ordered writer, output pair -- over a contiguous share of the
 // input, so nothing is shared between devices but the graph and the page cache; `cat` of the pairs in device order is the -t 1 stream.
-static int align_all_lanes(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt, const std::vector<std::string>& files,
+static int align_all_lanes(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt, uint32_t counts, const std::vector<std::string>& files,
                            const char* paths_file, const char* notaligned_file, uint64_t counters_out[5], double* mapping_seconds) {
     const unsigned n = std::max<uint32_t>(1, opt->n_gpus);
     const auto t0 = std::chrono::steady_clock::now();
@@ -1528,7 +1509,7 @@ static int align_all_lanes(bgr_graph* graph, const bgr_params* prm, const bgr_ru
             const std::string pf = std::string(paths_file) + "." + std::to_string(d), nf = std::string(notaligned_file) + "." + std::to_string(d);
             cnt[d].fill(0);
             double secs = 0;
-            rcs[d] = align_all_impl(graph, prm, &o, in, pf.c_str(), nf.c_str(), cnt[d].data(), &secs, &cancel);
+            rcs[d] = align_all_impl(graph, prm, &o, counts, in, pf.c_str(), nf.c_str(), cnt[d].data(), &secs, &cancel);
             lane_end[d] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             lane_secs[d] = secs;
             if (bgr::opt("timing")) fprintf(stderr, "bgreat: lane %u (device %u): %llu reads in %.3f s, done %.3f s after the start of the run\n", d, o.first_device, (unsigned long long)cnt[d][0], secs, lane_end[d]);
@@ -1584,40 +1565,37 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
     }
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
-    const bool links = bgr::run_links(graph), pileup = bgr::run_pileup(graph), abundance = opt->abundance || links || pileup;
-    if (pileup) {   // the graph's switch (bgr_graph_pileup_enable): per-base counts, defined on the rows of the greedy modes
+    // what the run counts (run_counts.h): the graph's sticky switches, which imply unitig abundance whatever bgr_run_options.abundance says, and that option
+    const uint32_t counts = (bgr::g_run_counts.wanted ? bgr::g_run_counts.wanted(graph) : 0) | (opt->abundance ? bgr::kCountAbundance : 0);
+    if (counts & bgr::kCountPileup) {   // the graph's switch (bgr_graph_pileup_enable): per-base counts, defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, bgr::g_run_pileup.variants && bgr::g_run_pileup.variants(graph)
+            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountVariants
                                                   ? "bgr_align_all: SNV sites (--vcf, bgr_graph_variants_enable) are called from the pileup, which is for the greedy modes; the rows of exhaustive mode (-b) have another layout"
                                                   : "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     }
-    if (links) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
+    if (counts & bgr::kCountLinks) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     }
     if (opt->abundance) {   // unitig abundance: defined on the rows of the greedy modes; refused before any device work
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_abundance.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     }
-    if (abundance) bgr::g_run_abundance.begin(graph);
-    if (links) bgr::g_run_links.begin(graph);
-    if (pileup) bgr::g_run_pileup.begin(graph);
+    if (counts) bgr::g_run_counts.begin(graph, counts);
     int run_rc;
     if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)
-        run_rc = align_all_lanes(graph, prm, opt, files, paths_file, notaligned_file, counters_out, mapping_seconds);
+        run_rc = align_all_lanes(graph, prm, opt, counts, files, paths_file, notaligned_file, counters_out, mapping_seconds);
     else {
         std::vector<InputSpan> inputs(files.size());
         for (size_t i = 0; i < files.size(); ++i) inputs[i].file = files[i];
-        run_rc = align_all_impl(graph, prm, opt, inputs, paths_file, notaligned_file, counters_out, mapping_seconds, nullptr);
+        run_rc = align_all_impl(graph, prm, opt, counts, inputs, paths_file, notaligned_file, counters_out, mapping_seconds, nullptr);
     }
-    if (abundance) bgr::g_run_abundance.end(graph, run_rc == BGR_OK);   // (the message of a failed run stays: this sets none)
-    if (links) bgr::g_run_links.end(graph, run_rc == BGR_OK);
-    if (pileup) {   // (behind the abundance totals: their reads column bounds every depth, and the end refuses totals that may have wrapped)
-        const int prc = bgr::g_run_pileup.end(graph, run_rc == BGR_OK);
-        if (run_rc == BGR_OK) run_rc = prc;
+    if (counts) {   // (the message of a failed run stays; behind a good one the pileup's end refuses totals that may have wrapped)
+        const int erc = bgr::g_run_counts.end(graph, counts, run_rc == BGR_OK);
+        if (run_rc == BGR_OK) run_rc = erc;
     }
     return run_rc;
 }

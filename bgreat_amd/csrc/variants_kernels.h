@@ -34,28 +34,24 @@ const uint32_t kVariantsTile = BGR_VARIANTS_TILE;
 const uint32_t kVariantsThreads = 256;   // each thread owns kVariantsTile / kVariantsThreads = 8 consecutive words
 
 inline uint64_t variants_tiles(uint64_t total_bases, uint64_t n_unitigs) { return (pileup_delta_words(total_bases, n_unitigs) + kVariantsTile - 1) / kVariantsTile; }
-// scratch of one call: u64 carry[tiles + 1], u64 offs[tiles + 1], u32 sums[tiles], u32 counts[tiles]
-inline uint64_t variants_scratch_bytes(uint64_t tiles) { return (tiles + 1) * 16 + tiles * 8; }
+// scratch of one call: u64 carry[tiles + 1], u64 offs[tiles + 1], u32 sums[tiles], u32 counts[tiles]; with strands behind them the forward table's
+// u64 carry_f[tiles + 1], u32 sums_f[tiles] (rounded up to 8 bytes)
+inline uint64_t variants_scratch_bytes(uint64_t tiles, bool strands) { return (tiles + 1) * 16 + tiles * 8 + (strands ? (tiles + 1) * 8 + ((tiles + 1) / 2) * 8 : 0); }
 inline const uint64_t* variants_total_word(const void* scratch, uint64_t tiles) { return static_cast<const uint64_t*>(scratch) + (tiles + 1) + tiles; }   // offs[tiles]
 
+// table_fwd: null, or a forward table next to the total one (bgr_variant_strand_site).  With it pass 1 sums both difference arrays (a grid of
+// tiles x 2), pass 2 scans both arrays of sums (two workgroups), passes 3 and 5 rescan both tables' words, read the forward alt words of a base
+// that has a candidate allele, apply variants_strand_passing (variants_host.h) and write 64-byte records.  The forward words of a unitig sum to 0
+// as the total's do: the forward scan runs flat too.  Still five launches, no sort, no atomics on the output, no workgroup waits for another.
+// Without it prm.min_alt_strand is ignored.  scratch: variants_scratch_bytes(tiles, table_fwd != null).
 // passes 1 - 4: the number of sites lies in *variants_total_word(scratch, tiles) when the stream has run them.  Launches nothing for an empty graph.
 // after: null, or four events, recorded one behind each launch.
-hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
-                                 const bgr_variant_params& prm, void* scratch, hipStream_t stream, hipEvent_t* after);
-// pass 5, behind launch_variants_count on the same stream with the same arguments: `out` has room for the number of sites
-hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
-                                const bgr_variant_params& prm, const void* scratch, bgr_variant_site* out, hipStream_t stream);
-// The same with a forward table next to the total one (bgr_variant_strand_site): pass 1 sums both difference arrays (a grid of tiles x 2), pass 2
-// scans both arrays of sums (two workgroups), passes 3 and 5 rescan both tables' words, read the forward alt words of a base that has a candidate
-// allele, apply variants_strand_passing (variants_host.h) and write 64-byte records.  The forward words of a unitig sum to 0 as the total's do:
-// the forward scan runs flat too.  Still five launches, no sort, no atomics on the output, no workgroup waits for another.
-// scratch: variants_strands_scratch_bytes; the number of sites lies at variants_total_word as above.
-inline uint64_t variants_strands_scratch_bytes(uint64_t tiles) { return variants_scratch_bytes(tiles) + (tiles + 1) * 8 + ((tiles + 1) / 2) * 8; }
-hipError_t launch_variants_strands_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
-                                         const uint64_t* base_offs, const bgr_variant_strand_params& prm, void* scratch, hipStream_t stream, hipEvent_t* after);
-hipError_t launch_variants_strands_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
-                                        const uint64_t* base_offs, const bgr_variant_strand_params& prm, const void* scratch, bgr_variant_strand_site* out,
-                                        hipStream_t stream);
+hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                 const uint64_t* base_offs, const bgr_variant_strand_params& prm, void* scratch, hipStream_t stream, hipEvent_t* after);
+// pass 5, behind launch_variants_count on the same stream with the same arguments: `out` has room for the number of sites (bgr_variant_site
+// records, with table_fwd bgr_variant_strand_site records)
+hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                const uint64_t* base_offs, const bgr_variant_strand_params& prm, const void* scratch, void* out, hipStream_t stream);
 // dst[i] += src[i] (mod 2^32) over n_words 32-bit words; with tail_u64 the last two words of both are one u64 counter (the table's tail) and are
 // added as such.  Both on the device of `stream`; dst and src 16-byte aligned.
 hipError_t launch_pileup_add(uint32_t* dst, const uint32_t* src, uint64_t n_words, bool tail_u64, uint32_t num_cus, hipStream_t stream);

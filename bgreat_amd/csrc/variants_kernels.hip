@@ -242,97 +242,63 @@ __global__ void __launch_bounds__(256) bgr_pileup_add_kernel(uint32_t* dst, cons
 namespace bgr {
 
 namespace {
-struct Scratch {
-    u64* carry; u64* offs; uint32_t* sums; uint32_t* counts;
+struct Scratch {   // (carry_f, sums_f: the forward table's carries and tile sums, there only with strands)
+    u64* carry; u64* offs; uint32_t* sums; uint32_t* counts; u64* carry_f; uint32_t* sums_f;
     Scratch(void* p, uint64_t tiles) {
         carry = static_cast<u64*>(p); offs = carry + tiles + 1;
         sums = reinterpret_cast<uint32_t*>(offs + tiles + 1); counts = sums + tiles;
-    }
-};
-struct StrandScratch {   // behind Scratch's arrays: the forward table's carries and tile sums
-    u64* carry_f; uint32_t* sums_f;
-    StrandScratch(void* p, uint64_t tiles) {
-        carry_f = reinterpret_cast<u64*>(static_cast<char*>(p) + variants_scratch_bytes(tiles));
+        carry_f = reinterpret_cast<u64*>(static_cast<char*>(p) + variants_scratch_bytes(tiles, false));
         sums_f = reinterpret_cast<uint32_t*>(carry_f + tiles + 1);
     }
 };
+// what both launchers refuse
+bool variants_args_ok(uint64_t n_unitigs, uint64_t tiles, const uint32_t* table, const uint64_t* base_offs, const bgr_variant_strand_params& sp, const void* scratch) {
+    return table && base_offs && scratch && n_unitigs < 0x40000000ull && tiles <= 0x7FFFFFFFull && variants_params_ok(bgr_variant_params{sp.min_depth, sp.min_alt, sp.min_af_ppm});
+}
+// the classify kernel's instances, [strands][emit]
+const decltype(&bgr_variants_classify_kernel<false, false>) kClassify[2][2] = {{bgr_variants_classify_kernel<false, false>, bgr_variants_classify_kernel<true, false>},
+                                                                               {bgr_variants_classify_kernel<false, true>, bgr_variants_classify_kernel<true, true>}};
 }  // namespace
 
-hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
-                                 const bgr_variant_params& prm, void* scratch, hipStream_t stream, hipEvent_t* after) {
+hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                 const uint64_t* base_offs, const bgr_variant_strand_params& sp, void* scratch, hipStream_t stream, hipEvent_t* after) {
     const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
     if (n_unitigs == 0 || tiles == 0) return hipSuccess;
-    if (!table || !base_offs || !scratch || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
+    if (!variants_args_ok(n_unitigs, tiles, table, base_offs, sp, scratch)) return hipErrorInvalidValue;
+    const bgr_variant_params prm = {sp.min_depth, sp.min_alt, sp.min_af_ppm};
     const Scratch s(scratch, tiles);
     const uint32_t* alt = table;
     const uint32_t* delta = table + pileup_alt_words(total_bases);
+    const uint32_t* delta_f = table_fwd ? table_fwd + pileup_alt_words(total_bases) : nullptr;
     const u64 words = pileup_delta_words(total_bases, n_unitigs);
     auto mark = [&](int i) -> hipError_t { return after ? hipEventRecord(after[i], stream) : hipSuccess; };
     hipError_t e;
-    hipLaunchKernelGGL(bgr_variants_tile_sums_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, delta, words, s.sums);
+    if (table_fwd) hipLaunchKernelGGL(bgr_variants_tile_sums2_kernel, dim3((uint32_t)tiles, 2), dim3(kThreads), 0, stream, delta, delta_f, words, s.sums, s.sums_f);
+    else hipLaunchKernelGGL(bgr_variants_tile_sums_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, delta, words, s.sums);
     if ((e = mark(0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (u64)tiles, s.carry);
+    if (table_fwd) hipLaunchKernelGGL(bgr_variants_scan2_kernel, dim3(2), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (const uint32_t*)s.sums_f, (u64)tiles, s.carry, s.carry_f);
+    else hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (u64)tiles, s.carry);
     if ((e = mark(1)) != hipSuccess) return e;
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<false, false>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
-                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const u64*)nullptr, 0u, (bgr_variant_strand_site*)nullptr);
+    hipLaunchKernelGGL(kClassify[table_fwd != nullptr][0], dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
+                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr, table_fwd, delta_f,
+                       table_fwd ? (const u64*)s.carry_f : nullptr, table_fwd ? sp.min_alt_strand : 0u, (bgr_variant_strand_site*)nullptr);
     if ((e = mark(2)) != hipSuccess) return e;
     hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.counts, (u64)tiles, s.offs);
     if ((e = mark(3)) != hipSuccess) return e;
     return hipGetLastError();
 }
 
-hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint64_t* base_offs,
-                                const bgr_variant_params& prm, const void* scratch, bgr_variant_site* out, hipStream_t stream) {
+hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
+                                const uint64_t* base_offs, const bgr_variant_strand_params& sp, const void* scratch, void* out, hipStream_t stream) {
     const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
     if (n_unitigs == 0 || tiles == 0) return hipSuccess;
-    if (!table || !base_offs || !scratch || !out || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
-    const Scratch s(const_cast<void*>(scratch), tiles);
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<true, false>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
-                       table + pileup_alt_words(total_bases), reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, out,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const u64*)nullptr, 0u, (bgr_variant_strand_site*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_variants_strands_count(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
-                                         const uint64_t* base_offs, const bgr_variant_strand_params& sp, void* scratch, hipStream_t stream, hipEvent_t* after) {
-    const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
-    if (n_unitigs == 0 || tiles == 0) return hipSuccess;
+    if (!variants_args_ok(n_unitigs, tiles, table, base_offs, sp, scratch) || !out) return hipErrorInvalidValue;
     const bgr_variant_params prm = {sp.min_depth, sp.min_alt, sp.min_af_ppm};
-    if (!table || !table_fwd || !base_offs || !scratch || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
-    const Scratch s(scratch, tiles);
-    const StrandScratch f(scratch, tiles);
-    const uint32_t* alt = table;
-    const uint32_t* delta = table + pileup_alt_words(total_bases);
-    const uint32_t* alt_f = table_fwd;
-    const uint32_t* delta_f = table_fwd + pileup_alt_words(total_bases);
-    const u64 words = pileup_delta_words(total_bases, n_unitigs);
-    auto mark = [&](int i) -> hipError_t { return after ? hipEventRecord(after[i], stream) : hipSuccess; };
-    hipError_t e;
-    hipLaunchKernelGGL(bgr_variants_tile_sums2_kernel, dim3((uint32_t)tiles, 2), dim3(kThreads), 0, stream, delta, delta_f, words, s.sums, f.sums_f);
-    if ((e = mark(0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(bgr_variants_scan2_kernel, dim3(2), dim3(kThreads), 0, stream, (const uint32_t*)s.sums, (const uint32_t*)f.sums_f, (u64)tiles, s.carry, f.carry_f);
-    if ((e = mark(1)) != hipSuccess) return e;
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<false, true>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, alt, delta,
-                       reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs, (bgr_variant_site*)nullptr, alt_f, delta_f,
-                       (const u64*)f.carry_f, sp.min_alt_strand, (bgr_variant_strand_site*)nullptr);
-    if ((e = mark(2)) != hipSuccess) return e;
-    hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, (const uint32_t*)s.counts, (u64)tiles, s.offs);
-    if ((e = mark(3)) != hipSuccess) return e;
-    return hipGetLastError();
-}
-
-hipError_t launch_variants_strands_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
-                                        const uint64_t* base_offs, const bgr_variant_strand_params& sp, const void* scratch, bgr_variant_strand_site* out, hipStream_t stream) {
-    const uint64_t tiles = variants_tiles(total_bases, n_unitigs);
-    if (n_unitigs == 0 || tiles == 0) return hipSuccess;
-    const bgr_variant_params prm = {sp.min_depth, sp.min_alt, sp.min_af_ppm};
-    if (!table || !table_fwd || !base_offs || !scratch || !out || n_unitigs >= 0x40000000ull || tiles > 0x7FFFFFFFull || !variants_params_ok(prm)) return hipErrorInvalidValue;
     const Scratch s(const_cast<void*>(scratch), tiles);
-    const StrandScratch f(const_cast<void*>(scratch), tiles);
-    hipLaunchKernelGGL((bgr_variants_classify_kernel<true, true>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
+    hipLaunchKernelGGL(kClassify[table_fwd != nullptr][1], dim3((uint32_t)tiles), dim3(kThreads), 0, stream, g, (u64)n_unitigs, (u64)total_bases, table,
                        table + pileup_alt_words(total_bases), reinterpret_cast<const u64*>(base_offs), prm, (const u64*)s.carry, s.counts, (const u64*)s.offs,
-                       (bgr_variant_site*)nullptr, table_fwd, table_fwd + pileup_alt_words(total_bases), (const u64*)f.carry_f, sp.min_alt_strand, out);
+                       table_fwd ? nullptr : static_cast<bgr_variant_site*>(out), table_fwd, table_fwd ? table_fwd + pileup_alt_words(total_bases) : nullptr,
+                       table_fwd ? (const u64*)s.carry_f : nullptr, table_fwd ? sp.min_alt_strand : 0u, table_fwd ? static_cast<bgr_variant_strand_site*>(out) : nullptr);
     return hipGetLastError();
 }
 

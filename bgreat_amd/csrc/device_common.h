@@ -246,28 +246,26 @@ __device__ __forceinline__ uint32_t find_key_wide(const BgrDeviceGraph& g, TP ta
     return res;
 }
 
-// scan_find_key's cut: the lanes of the lane's half (position order, lane & 31) up to and including its half's first hit -- need2: its
-// second -- so the number of lanes worth confirming; all 32 when there is no such hit.
-__device__ __forceinline__ uint32_t scan_hits_upto(u64 hits, bool need2, uint32_t lane) {
-    uint32_t h = (lane & 32u) ? (uint32_t)(hits >> 32) : (uint32_t)hits;
-    if (need2) h &= h - 1;
+// scan_find_key's cut: the lanes of the lane's half (position order, lane & 31) up to and including its half's first hit, so the number
+// of lanes worth confirming; all 32 when there is no hit.
+__device__ __forceinline__ uint32_t scan_hits_upto(u64 hits, uint32_t lane) {
+    const uint32_t h = (lane & 32u) ? (uint32_t)(hits >> 32) : (uint32_t)hits;
     return (uint32_t)__builtin_popcount(h ^ (h - 1));
 }
 // find_key for the anchor scan of bgr_align_greedy_multi_kernel with its key table staged in LDS.  The wave scans two reads at once: lanes
 // 0-31 hold 32 consecutive positions of one read and lanes 32-63 of another, lane & 31 = position order within a half, and each half's
-// step only asks for its first key in lane order and -- need2, the lane's half's -- the second one.  The answer is find_key's in every lane
-// up to and including its half's needed hit (in all lanes of the half when it has fewer hits); a lane behind it may say BGR_NONE although
-// it holds a key (it never names a slot that is not its key's).  The cut is each half's own: a hit of one read must not cut the candidates
-// of the other.
+// step only asks for its first key in lane order.  The answer is find_key's in every lane up to and including its half's first hit (in
+// all lanes of the half when it has none); a lane behind it may say BGR_NONE although it holds a key (it never names a slot that is not
+// its key's).  The cut is each half's own: a hit of one read must not cut the candidates of the other.
 // The common step (no lane with two fingerprint candidates) costs one key load per candidate lane and no loop:
 //  - fingerprints: one broadcast, and per bucket word the short zero-byte test (x - 0x01..) & ~x & 0x80..: exact up to the lowest zero byte,
 //    above it a byte 0x01 can be flagged as well -- a candidate the key compare rejects, never a lost one;
 //  - each lane confirms its FIRST candidate (bucket 1's lowest, else bucket 2's) with one load and one compare;
 //  - only lanes whose first candidate failed and that have more (fingerprint collisions in both buckets or twice in one: a few steps in a
-//    hundred), and that lie before the step's first (need2: second) confirmed hit, go through find_key's general loop for the rest.
+//    hundred), and that lie before their half's first confirmed hit, go through find_key's general loop for the rest.
 // (inactive lanes read their two bucket words as well -- the buckets of any key lie inside the table -- and confirm nothing)
 template <typename TP>
-__device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP tab, u64 key, bool active, bool need2, uint32_t lane) {
+__device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP tab, u64 key, bool active, uint32_t lane) {
     const u64 m = bgr_mix64(key);
     const uint32_t b1 = __umulhi((uint32_t)m, g.n_buckets), b2 = __umulhi((uint32_t)(m >> 32), g.n_buckets);
     const uint32_t w1 = tab[b1], w2 = tab[b2];
@@ -284,8 +282,8 @@ __device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP ta
     }
     uint32_t upto;
     if (__ballot(ncand >= 2)) {  // rare: the rest of the candidates, as find_key does
-        // lanes up to the step's first (need2: second) hit so far: what lies behind it cannot change the answer
-        upto = scan_hits_upto(__ballot(res != BGR_NONE), need2, lane);  // the half's lanes below this number (no such hit: all 32)
+        // lanes up to their half's first hit so far: what lies behind it cannot change the answer
+        upto = scan_hits_upto(__ballot(res != BGR_NONE), lane);  // the half's lanes below this number (no such hit: all 32)
         if (ncand >= 2 && (lane & 31u) < upto) {
             if (first1) c1 &= c1 - 1;
             else c2 &= c2 - 1;
@@ -305,7 +303,7 @@ __device__ __forceinline__ uint32_t scan_find_key(const BgrDeviceGraph& g, TP ta
         }
     }
     if (g.flags & BGR_GF_HAS_FALLBACK) {
-        upto = scan_hits_upto(__ballot(res != BGR_NONE), need2, lane);
+        upto = scan_hits_upto(__ballot(res != BGR_NONE), lane);
         const bool look = active && res == BGR_NONE && (lane & 31u) < upto;
         if (wave_any(look) && look) {  // bisection in the sorted fallback list, as in find_key
             const uint32_t nfb = (uint32_t)g.hdr->n_fallback;

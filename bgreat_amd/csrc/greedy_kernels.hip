@@ -335,20 +335,18 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         }
         wave_sync();
 
-        // ---- anchors (getNOverlap, aligner.cpp:345-378): the next overlap (k-1)-mer of each item from where its scan stands and,
-        // when it lies in the same step's positions, the one after it; record | canonical << 28
-        uint32_t a_pos = 0, a_rec = BGR_NONE, b_pos = 0;  // (b_pos: the hit after a_pos when the scan's step saw one, else 0)
+        // ---- anchors (getNOverlap, aligner.cpp:345-378): the next overlap (k-1)-mer of each item from where its scan stands;
+        // record | canonical << 28
+        uint32_t a_pos = 0, a_rec = BGR_NONE;
         if constexpr (STAGE) {
             // Two scanners per wave: lanes 0-31 scan one item, lanes 32-63 another, 32 positions per step each.  A half is done with its
-            // item once it has seen the hit the item needs (and the next one, for b_pos, when that lies in the same 32 positions) or has
-            // passed npos; it then takes the next item in group order, so a step rarely spends lanes beyond the hit an item needs
-            // (E. coli scale: 22.7 -> 19.1 steps per sixteen reads, tools/scan_halves.py).  A step still looks up 64 (k-1)-mers.
+            // item once it has seen the item's first hit or has passed npos; it then takes the next item in group order, so a step rarely
+            // spends lanes beyond the hit an item needs (E. coli scale: 22.7 -> 19.1 steps per sixteen reads, tools/scan_halves.py).  A step
+            // still looks up 64 (k-1)-mers.
             // Per half, all uniform: the item's group hq, the step's first position hb and the item's npos hn (0: the half is idle).
             // `pend`: bit GL q = group q's item is still to be scanned (an item with nothing left to scan never gets there: no anchor).
             const uint32_t g_from = st & G4_ST_POS_MASK;  // where the group's item resumes: the first position it may report
-            uint32_t Ls = L;  // (an opaque copy: npos is worked out again behind the walks, and kept across them it would cost them a register)
-            asm volatile("" : "+v"(Ls));
-            uint32_t g_npos = Ls >= K1 ? Ls - K1 + 1 : 0;
+            uint32_t g_npos = L >= K1 ? L - K1 + 1 : 0;
             if (!prm.effort && g_npos > 1) g_npos = 1;
             u64 pend = __ballot(act != 0 && sub == 0 && g_from < g_npos);
 #ifdef BGR_PHASE_TIMING
@@ -363,9 +361,9 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             //   li = (its position - the resume position) << 6 | the window's shift, ln = (npos - the resume position) << 6 (0: idle):
             //        li < ln, unsigned, says that the position is one of the item's AND not below where the item resumes (the lanes below
             //        wrap around; they are off in the item's first step only, so an anchor that has failed is never seen again);
-            //   wa, wb = the LDS byte addresses of the dword its window starts in and of the next one; l2 = need2.
+            //   wa, wb = the LDS byte addresses of the dword its window starts in and of the next one.
             // What a half needs of an item is worked out for all sixteen groups at once, here, and fetched by readlane when the half takes
-            // the item: g_ln -> ln, g_wa = where the item's dword (resume position / 16) lies, were the dwords in base order, | need2.
+            // the item: g_ln -> ln, g_wa = where the item's dword (resume position / 16) lies, were the dwords in base order.
             const bool hi = lane >= 32;
             const uint32_t g_ln = (g_npos - g_from) << 6;
             // (the lane's two constants are worked out here, once per sixteen items, behind an empty asm that keeps the compiler from
@@ -375,11 +373,10 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             const uint32_t lc = ((sl & 31u) << 6) | (32u - 2u * (sl & 15u));
             const uint32_t c4 = 4u * ((sl >> 4) & 1u);  // lanes 16-31 of a half start one dword further on
             // (the address of the group's words, F, worked out again from the lane number: as lds_addr(F) it would be hoisted as well)
-            const uint32_t g_wa = (lds_addr(lds + 64 + ktab_words) + (sl / GL) * (W * 8u) + ((g_from >> 4) << 2))
-                                | (eff - ((st >> G4_ST_TRIED_SHIFT) & 0x7FFu) >= 2 ? 1u : 0u);  // (bit 0: anchors this strand may still try >= 2)
-            uint32_t li = 0, ln = 0, wa = 0, wb = 0, l2 = 0;
+            const uint32_t g_wa = lds_addr(lds + 64 + ktab_words) + (sl / GL) * (W * 8u) + ((g_from >> 4) << 2);
+            uint32_t li = 0, ln = 0, wa = 0, wb = 0;
             auto take = [&](bool h, uint32_t& hq, uint32_t& hb, uint32_t& hn) {
-                uint32_t s_li = 0, s_ln = 0, s_l2 = 0, s_wa = 0;
+                uint32_t s_li = 0, s_ln = 0, s_wa = 0;
                 hn = 0;
                 if (pend) {
                     const int at = __ffsll((long long)pend) - 1;
@@ -387,8 +384,6 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                     const uint32_t from = rl32(st, at) & G4_ST_POS_MASK;
                     s_ln = rl32(g_ln, at);
                     s_wa = rl32(g_wa, at);
-                    s_l2 = s_wa & 1u;
-                    s_wa &= ~1u;
                     s_li = (from & 15u) << 6;
                     hq = (uint32_t)at / GL;
                     hb = from & ~15u;
@@ -397,7 +392,6 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                 if (hi == h) {
                     li = lc - s_li;
                     ln = s_ln;
-                    l2 = s_l2;
                     // dword d of an item's words, in base order, is dword d ^ 1 in memory: the words start at a multiple of 8 bytes
                     const uint32_t t = s_wa + c4;
                     wa = t ^ 4u;
@@ -415,22 +409,19 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                 u64 num = 0;
                 if (valid) num = lds_win32_fixed(wa, wb, li) >> (64 - 2 * K1);
                 const u64 rcn = rcb_fast(num, K1);  // no N in the read: the rolling reverse k-mer is rcb of the forward one
-                uint32_t idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, l2 != 0, (uint32_t)lane);
+                uint32_t idx = scan_find_key(g, ktab, num < rcn ? num : rcn, valid, (uint32_t)lane);
                 const u64 mask = __ballot(idx != BGR_NONE);
                 li += 32u << 6;
                 wa += 8;
                 wb += 8;
                 if (mask) {
                     if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;
-                    // each half's first hit (and second) goes to its item's group: a readlane of the hit lane, a select on grp
+                    // each half's first hit goes to its item's group: a readlane of the hit lane, a select on grp
                     auto settle = [&](uint32_t mh, int off, uint32_t hq, uint32_t hb, uint32_t& hn) {
                         if (mh) {
-                            const uint32_t h2 = rl32(l2, off);  // the half's need2, from its first lane
-                            const uint32_t f = (uint32_t)__builtin_ctz(mh), mh2 = mh & (mh - 1);
+                            const uint32_t f = (uint32_t)__builtin_ctz(mh);
                             const uint32_t h = rl32(idx, off + (int)f);
-                            // a second anchor is tried when the first fails: where a follow-up item resumes
-                            const uint32_t p2 = (mh2 && h2) ? hb + (uint32_t)__builtin_ctz(mh2) : 0u;
-                            if (grp == hq) { a_pos = hb + f; a_rec = h; b_pos = p2; }
+                            if (grp == hq) { a_pos = hb + f; a_rec = h; }
                             hn = 0;
                         }
                     };
@@ -453,7 +444,6 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
 #endif
                 const uint32_t Lq = rl32(L, (int)(GL * q)), stq = rl32(st, (int)(GL * q));
                 const u64* A = RD + q * W;
-                const uint32_t left_q = eff - ((stq >> G4_ST_TRIED_SHIFT) & 0x7FFu);  // anchors this strand may still try (>= 1)
                 uint32_t npos = Lq >= K1 ? Lq - K1 + 1 : 0;
                 if (!prm.effort && npos > 1) npos = 1;
                 for (uint32_t base = stq & G4_ST_POS_MASK; base < npos; base += scan_step) {
@@ -471,11 +461,8 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                     if (mask) {
                         if (idx != BGR_NONE && num <= rcn) idx |= G4_CANON;
                         const int s1 = __ffsll((long long)mask) - 1;
-                        const u64 mask2 = mask & (mask - 1);
                         const uint32_t h1 = rl32(idx, s1);
-                        uint32_t p2 = 0;
-                        if (mask2 && left_q >= 2) p2 = base + (uint32_t)(__ffsll((long long)mask2) - 1);  // a second anchor is tried when the first fails: where a follow-up item resumes
-                        if (grp == q) { a_pos = base + (uint32_t)s1; a_rec = h1; b_pos = p2; }
+                        if (grp == q) { a_pos = base + (uint32_t)s1; a_rec = h1; }
                         break;
                     }
                 }
@@ -483,7 +470,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         }
 
         // ---- extension (alignReadGreedy's loop body, alignerGreedy.cpp:41-52), the wave's items abreast; a group whose anchor fails
-        // starts over from the next one, if the scan has seen it, while the others go on ----
+        // leaves a follow-up item that scans on behind it, while the others go on ----
         // phase: 1 left walk, 2 first right step, 3 later right steps; 0 the walk is over (aligned, or there was no anchor),
         // 4 the path outgrew the registers, 5 every anchor seen failed.  `tried` counts on in the item's state word.
         // The two walks of an anchor run at the same time on the two lane pairs of the group (g2_step): lanes 0-1 walk left, lanes 2-3
@@ -552,12 +539,9 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         if (lph == 4 || lph == 5) phase = lph;
         else if (rph == 4) phase = tot <= m ? 4u : 5u;
         else phase = (rph == 5 || tot > m) ? 5u : 0u;
-        if (phase == 5) {
-            st += 1u << G4_ST_TRIED_SHIFT;
-            // (the next anchor of getNOverlap's list, when the scan saw it, is taken up by a follow-up item that resumes AT it -- rounds 3-4
-            // restarted the walk in this loop, which kept all sixteen groups' loop going for one walk: profiles/r05_scan_schemes.txt)
-            if (b_pos) { a_pos = b_pos - 1; b_pos = 0; }
-        }
+        // (the next anchor of getNOverlap's list is taken up by a follow-up item that resumes behind this one -- rounds 3-4 restarted the
+        // walk in this loop, which kept all sixteen groups' loop going for one walk: profiles/r05_scan_schemes.txt)
+        if (phase == 5) st += 1u << G4_ST_TRIED_SHIFT;
 
         // ---- what became of each item (alignerGreedy.cpp:35-57) ---------------------------------------------------------------
         // 0 = aligned, 1 = no anchor on this strand and none tried before (++noOverlapRead), 2 = not aligned (both strands done),

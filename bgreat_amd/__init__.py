@@ -396,6 +396,19 @@ class DeviceBuffer:
             pass
 
 
+def device_upload(device, ptr, array):
+    """bgr_device_upload: the bytes of a numpy array -> device memory at ptr (the caller answers for the room there)."""
+    a = np.ascontiguousarray(array)
+    _check(lib().bgr_device_upload(device, ptr, a.ctypes.data, a.nbytes))
+
+
+def device_download(device, ptr, count, dtype=np.uint8):
+    """bgr_device_download: `count` items of `dtype` from device memory at ptr -> numpy array."""
+    out = np.empty(count, dtype=dtype)
+    _check(lib().bgr_device_download(device, out.ctypes.data, ptr, out.nbytes))
+    return out
+
+
 def _as_u8(a):
     if isinstance(a, (bytes, bytearray)):
         a = np.frombuffer(a, dtype=np.uint8)
@@ -750,6 +763,13 @@ class Aligner:
         status = np.empty(max(n, 1), dtype=np.uint8)
         _check(lib().bgr_aligner_fetch(self.h, n, paths.ctypes.data, cap, poffs.ctypes.data, status.ctypes.data))
         return paths[: int(poffs[n])].copy(), poffs, status[:n]
+
+    def device_results(self):
+        """bgr_aligner_device_results -> (results, arena, cursor): the device pointers of the last launch's uint2 per read {arena index of its row,
+        ints of the row | status << 24}, of the int32 arena the rows lie in and of the cursor block (valid until the next launch grows them)."""
+        r, a, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().bgr_aligner_device_results(self.h, C.byref(r), C.byref(a), C.byref(c)))
+        return r.value, a.value, c.value
 
     def path_stats(self, d_reads_ptr, d_offsets_ptr, n):
         """bgr_aligner_path_stats over the last align_device launch (the same device reads again) -> structured array of n rows with the fields

@@ -512,6 +512,53 @@ static DevBuf* list_buf(bgr_aligner* a, bgr::List l) {
     }
 }
 
+// HIP events on the aligner's stream behind the kernels of a launch (bgr_aligner_kernel_times); timed = false: none
+struct LaunchMarks {
+    bgr_aligner* a;
+    bool timed;
+    int marks = 0;
+    hipError_t operator()(const char* name) {
+        if (!timed || marks >= kTimerSlots) return hipSuccess;
+        a->t_slot_name[marks] = name;
+        return hipEventRecord(a->ev[a->ev_used][++marks], a->stream);
+    }
+};
+
+// The counting kernels over the rows that (a->results, a->arena) hold, each only if its feature is enabled, queued on the aligner's stream: behind
+// the passes of a mapping launch, and -- option test.count_with_path_stats -- behind the kernel of bgr_aligner_path_stats over whatever rows the
+// buffers hold then.  mark(name): the launch's timer slot behind each kernel.
+static int queue_counting(bgr_aligner* a, uint64_t arena_cap, const uint64_t* read_offs, uint64_t n_reads, uint64_t total_bases, const bgr::PileupReads& pr, LaunchMarks& mark) {
+    hipError_t e = hipSuccess;
+    // Unitig abundance (bgr_aligner_abundance_enable): one kernel behind the last pass adds this launch's rows to the aligner's table.  Every route
+    // comes through here once per batch (a fetch into larger buffers after BGR_E_CAPACITY launches nothing), so nothing is counted twice.
+    // (The kernel is queued before anybody knows how the launch ends: one that fails later -- an arena overflow, found when its cursors are read -- has
+    // added the rows it did write.  include/bgreat_gpu.h says so: after a failed launch the table is undefined until bgr_aligner_reset_abundance.)
+    if (a->abundance_on) {
+        const uint64_t nu = a->graph->header.n_unitigs;
+        const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
+        e = bgr::launch_abundance(a->dg, nu, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, read_offs, (uint32_t)n_reads,
+                                  static_cast<unsigned long long*>(a->abundance.p), ap, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_abundance_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_abundance_kernel"));
+    }
+    // Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
+    if (a->links_on) {
+        const bgr::LinksPlan lp = bgr::plan_links(a->links_bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
+        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->links_tab,
+                              a->links_cap, lp, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_links_kernel"));
+    }
+    // Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches, the read characters from `pr`.
+    if (a->pileup_on) {
+        e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
+                               arena_cap, read_offs, (uint32_t)n_reads, pr, a->pileup_base_offs, a->pileup_tab, a->strands_on ? a->pileup_fwd_tab : nullptr, (uint32_t)a->num_cus, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_pileup_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_pileup_kernel"));
+    }
+    return BGR_OK;
+}
+
 // The mapping launch of one batch: the passes come from plan_launch (launch_plan.h, a pure function of numbers), this function sizes the
 // buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
 // (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
@@ -557,6 +604,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     const bgr::Pass& first = P.pass[0];
     if (P.deep_scratch_bytes) HIP_TRY(a->deepbuf.ensure(P.deep_scratch_bytes));
     HIP_TRY(a->arena.ensure(P.arena_cap * 4));
+    a->last_arena_cap = P.arena_cap; a->last_total_bases = total_bases;
     for (uint32_t i = 0; i < P.n_passes; ++i) {  // the lists the passes leave each other, and the rings of follow-up items of the sixteen-reads-per-wave kernel
         const bgr::Pass& ps = P.pass[i];
         if (ps.appends != bgr::List::kNone) HIP_TRY(list_buf(a, ps.appends)->ensure(n_reads * 4));
@@ -613,16 +661,11 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     // the cursor block: arena cursor, overflow flag, list counts (the text form: the parse launch cleared it)
     if (!cursor_is_zero) HIP_TRY(hipMemsetAsync(a->small.p, 0, bgr::kCurWords * 4, a->stream));
     // HIP events on the aligner's stream: one in front of the launch, one behind every kernel of it (bgr_aligner_kernel_times)
-    int marks = 0;
     // (timing a kernel is not free: the events make the runtime dispatch with completion stamps and keep the kernels of a launch apart -- three events around two
     // kernels cost a 262 144-read launch 16 of its 167 us, 1 730 -> 1 560 Mreads/s, and stamps taken by the dispatch packets themselves (hipExtLaunchKernelGGL)
     // cost the same, profiles/r05_mode_by_batch_size.txt; BGR_KNOB_KERNEL_EVENTS 0: none -- bgr_align_all without its timing option)
     const bool timed = !a->knob_no_events;
-    auto mark = [&](const char* name) -> hipError_t {
-        if (!timed || marks >= kTimerSlots) return hipSuccess;
-        a->t_slot_name[marks] = name;
-        return hipEventRecord(a->ev[a->ev_used][++marks], a->stream);
-    };
+    LaunchMarks mark{a, timed};
     if (timed) HIP_TRY(hipEventRecord(a->ev[a->ev_used][0], a->stream));
     hipError_t e = hipSuccess;
     if (!planes_ready && !inline_pack) {
@@ -675,39 +718,17 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
             a->deep.runs = 1;
         }
     }
-    // Unitig abundance (bgr_aligner_abundance_enable): one kernel behind the last pass adds this launch's rows to the aligner's table.  Every route
-    // comes through here once per batch (a fetch into larger buffers after BGR_E_CAPACITY launches nothing), so nothing is counted twice.
-    // (The kernel is queued before anybody knows how the launch ends: one that fails later -- an arena overflow, found when its cursors are read -- has
-    // added the rows it did write.  include/bgreat_gpu.h says so: after a failed launch the table is undefined until bgr_aligner_reset_abundance.)
-    if (a->abundance_on) {
-        const uint64_t nu = a->graph->header.n_unitigs;
-        const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
-        e = bgr::launch_abundance(a->dg, nu, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), P.arena_cap, io.read_offs, io.n_reads,
-                                  static_cast<unsigned long long*>(a->abundance.p), ap, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_abundance_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_abundance_kernel"));
-    }
-    // Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
-    if (a->links_on) {
-        const bgr::LinksPlan lp = bgr::plan_links(a->links_bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
-        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), P.arena_cap, io.n_reads, a->links_tab,
-                              a->links_cap, lp, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_links_kernel"));
-    }
-    // Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches.  It reads the read characters where this launch
-    // has them: the ASCII bytes when the mapping kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
-    if (a->pileup_on) {
+    // The counting kernels behind the last pass.  The pileup reads the read characters where this launch has them: the ASCII bytes when the mapping
+    // kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
+    {
         bgr::PileupReads pr;
         if (inline_pack) { pr.ascii = static_cast<const uint8_t*>(d_reads); pr.src_off = static_cast<const uint32_t*>(d_src_off); pr.ascii_bytes = reads_bytes; }
         else { pr.fw3 = io.fw3; pr.nmw = io.nmw; pr.hasn = io.hasn; }
-        e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
-                               P.arena_cap, io.read_offs, io.n_reads, pr, a->pileup_base_offs, a->pileup_tab, a->strands_on ? a->pileup_fwd_tab : nullptr, (uint32_t)a->num_cus, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_pileup_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_pileup_kernel"));
+        const int crc = queue_counting(a, P.arena_cap, io.read_offs, n_reads, total_bases, pr, mark);
+        if (crc != BGR_OK) return crc;
     }
     if (timed) {
-        a->ev_marks[a->ev_used] = marks;
+        a->ev_marks[a->ev_used] = mark.marks;
         ++a->ev_used;
     }
     return BGR_OK;
@@ -1192,6 +1213,13 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
     hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->results.p),
                                           static_cast<const int32_t*>(a->arena.p), (uint32_t)n, static_cast<uint32_t*>(a->path_stats.p), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path stats launch: ") + hipGetErrorString(e));
+    if (bgr::opt("test.count_with_path_stats")) {   // test hook: the counting kernels once over the rows the buffers hold now, the reads' characters from the caller's buffer
+        bgr::PileupReads pr;
+        pr.ascii = static_cast<const uint8_t*>(d_reads); pr.ascii_bytes = a->last_total_bases;
+        LaunchMarks none{a, false};
+        const int crc = queue_counting(a, a->last_arena_cap, static_cast<const uint64_t*>(d_read_offsets), n, a->last_total_bases, pr, none);
+        if (crc != BGR_OK) return crc;
+    }
     HIP_TRY(hipMemcpyAsync(out, a->path_stats.p, n * sizeof(bgr_path_stat), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return BGR_OK;

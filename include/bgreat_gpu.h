@@ -583,6 +583,8 @@ typedef struct {
                                   positions [off, off + cl).  For every occurrence j, with o_j = max(0, min(off + cl, e_j) - max(off, s_j)):
                                   reads[|id_j|] += 1 (every occurrence, whatever o_j: what counting the ids of the paths file gives),
                                   bases[|id_j|] += o_j (the k-1 characters two neighbours share count for both), kmers[|id_j|] += max(0, o_j - K1).
+                                  An occurrence whose id is 0 or beyond n_unitigs (the mapper writes none) adds nothing and has len_j = 0 in the walk;
+                                  the next e then lies in front of it, and plen is the largest e_j of such a row.
                                   Neither a unitig's orientation nor the read's strand enters; unmapped reads add nothing; integer adds commute, so
                                   the totals do not depend on batches, routes, streams or devices.  Any graph greedy mode maps (k up to 64, exception
                                   planes), together with fastq, correction, gaf, no_overlap_file, several devices, split_output, both routes; the

@@ -11,11 +11,17 @@ def unitig_lens(unitigs):
     return [len(u) for u in unitigs]
 
 
+def valid_id(lens, x):
+    """a signed path int names a unitig of the graph (the mapper writes no other; a row somebody else wrote may)"""
+    return 0 < abs(x) < len(lens)
+
+
 def extents(lens, k, path):
-    """-> [(s_j, e_j)] of the walk path[1:] spells: s_1 = 0, e_j = s_j + len_j, s_(j+1) = e_j - (k - 1)"""
+    """-> [(s_j, e_j)] of the walk path[1:] spells: s_1 = 0, e_j = s_j + len_j, s_(j+1) = e_j - (k - 1); an id that is 0 or beyond the graph's
+    has length 0 in the walk"""
     out, s = [], 0
     for x in path[1:]:
-        e = s + lens[abs(x)]
+        e = s + (lens[abs(x)] if valid_id(lens, x) else 0)
         out.append((s, e))
         s = e - (k - 1)
     return out
@@ -24,17 +30,17 @@ def extents(lens, k, path):
 def covered(lens, k, L, path):
     """-> (off, cl): the read covers the walk positions [off, off + cl)"""
     ext = extents(lens, k, path)
-    plen = ext[-1][1] if ext else 0
+    plen = max(e for _, e in ext) if ext else 0   # (e_n -- unless an id outside the graph made the walk step back: then the largest e_j)
     off = path[0]
     return off, max(0, min(L, plen - off))
 
 
 def occurrences(lens, k, L, path):
-    """-> [(unitig id, o_j)] per occurrence of a mapped read's path"""
+    """-> [(unitig id, o_j)] per occurrence of a mapped read's path; an occurrence whose id is 0 or beyond the graph's adds nothing"""
     if len(path) < 2:
         return []
     off, cl = covered(lens, k, L, path)
-    return [(abs(x), max(0, min(off + cl, e) - max(off, s))) for x, (s, e) in zip(path[1:], extents(lens, k, path))]
+    return [(abs(x), max(0, min(off + cl, e) - max(off, s))) for x, (s, e) in zip(path[1:], extents(lens, k, path)) if valid_id(lens, x)]
 
 
 def add_read(table, lens, k, L, path):

@@ -178,3 +178,23 @@ def test_plan_chooses_the_form_from_the_numbers():
     assert P(6388, 31, 0, 0)["blocks"] == 0
     out = (C.c_uint32 * 4)()
     assert B.lib().bgr_plan_abundance(6, 31, 1, 1, 0, 0, 3, out) == -1
+
+
+def test_ids_outside_the_graph_add_nothing_and_have_length_0():
+    """rows the mapper never writes (somebody else's: tests/test_gpu_crafted_rows.py): an occurrence whose id is 0 or beyond the graph's adds nothing
+    and has length 0 in the walk -- the next unitig still steps back by k - 1 -- by hand, k = 4"""
+    lens, k = [0, 10, 12, 9], 4
+    for bad in (0, 4, -4, 2000, -(2 ** 31)):
+        # extents (0, 10), (7, 7), (4, 16): the read covers [2, 10) = 8 bases of unitig 1 and [4, 10) = 6 of unitig 2
+        path = [2, 1, bad, 2]
+        assert A.extents(lens, k, path) == [(0, 10), (7, 7), (4, 16)] and A.covered(lens, k, 8, path) == (2, 8)
+        assert A.occurrences(lens, k, 8, path) == [(1, 8), (2, 6)]
+        assert A.abundance_of(lens, k, [8], [(2, path)]) == [[0, 0, 0], [1, 8, 5], [1, 6, 3], [0, 0, 0]]
+        # in front: extents (0, 0), (-3, 7); the read covers [0, 5), all of it on unitig 1
+        assert A.extents(lens, k, [0, bad, 1]) == [(0, 0), (-3, 7)] and A.occurrences(lens, k, 5, [0, bad, 1]) == [(1, 5)]
+        # behind: extents (0, 10), (7, 7) -- the walk's size is the largest e, 10, so a read of 9 covers [0, 9) of unitig 1
+        assert A.extents(lens, k, [0, 1, bad]) == [(0, 10), (7, 7)] and A.covered(lens, k, 9, [0, 1, bad]) == (0, 9) and A.occurrences(lens, k, 9, [0, 1, bad]) == [(1, 9)]
+        assert A.covered(lens, k, 20, [2, 1, bad]) == (2, 8) and A.covered(lens, k, 20, [11, 1, bad]) == (11, 0)
+        # nothing else in the row: no walk at all
+        assert A.abundance_of(lens, k, [8, 8], [(2, [0, bad]), (2, [3, bad, bad])]) == [[0, 0, 0]] * 4
+    assert A.valid_id(lens, 3) and A.valid_id(lens, -3) and not A.valid_id(lens, 0) and not A.valid_id(lens, 4)

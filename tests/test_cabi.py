@@ -635,7 +635,8 @@ def test_structs_of_another_header_version_are_refused(tmp_path):
 
 def test_options_are_named_bounded_and_put_back():
     names = dict(B.option_names())
-    assert {"timing", "build_filter", "poison_device_buffers", "test.bases_cap", "test.lanes_on_one_device"} <= set(names)
+    assert {"timing", "build_filter", "poison_device_buffers", "test.bases_cap", "test.lanes_on_one_device", "test.count_with_path_stats"} <= set(names)
+    assert B.get_option("test.count_with_path_stats") == 0
     assert B.get_option("build_filter") == -1
     with B.options(build_filter=2, timing=1):
         assert B.get_option("build_filter") == 2 and B.get_option("timing") == 1

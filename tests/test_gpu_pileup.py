@@ -2,9 +2,10 @@
 text and device-resident calls -- against pileup_ref.py (the definition in plain Python, pinned by test_pileup_host.py) over rows of the oracle
 (goldens), of wide_greedy_ref (k > 32) or of the batch API itself (pinned to both elsewhere).
 
-Not covered on the GPU: a unitig glued on in the strand its sign does not name (none of the goldens' rows has one, and no ACGT-only input is known
-to produce one -- the kernel takes the strand from the walk's state, and test_pileup_host.py tests the definition for it), and a read that
-overhangs its walk's end (the kernel clamps as the definition says)."""
+Not covered here, because no ACGT-only input is known to make the mapper write such a row -- test_gpu_crafted_rows.py writes them into the result
+buffers itself and covers them on the GPU: a unitig glued on in the strand its sign does not name, a read that overhangs its walk's end, a path
+that spells no walk (skipped > 0), ids outside the graph.  Still not covered on the GPU: a row that does not lie wholly inside the arena (the
+kernel skips it), and such crafted rows with the read characters taken from the 2-bit planes or from a text (there they come as ASCII reads)."""
 import os
 import random
 import shutil

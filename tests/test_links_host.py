@@ -34,6 +34,8 @@ def test_hand_checked_rows():
     # sorted by key = (|a|, a < 0, |b|, b < 0)
     assert K.sorted_links(c) == [(4, 4, 2), (4, -4, 2), (-4, 4, 1), (9, 9, 1), (363, 364, 2), (364, -366, 2), (-366, 367, 2)]
     assert K.sorted_links({(2, 3): 1, (2, -3): 1, (-2, 3): 1, (-2, -1): 1, (2, 10): 0, (1, 7): 5}) == [(1, 7, 5), (2, 3, 1), (2, -3, 1), (-2, -1, 1), (-2, 3, 1)]
+    # ... on either side of a pair, the first place and INT32_MIN (whose magnitude no int32 holds) included
+    assert K.links_of([(2, [0, 0, 5, 6, 1010, 6, 7, -(2 ** 31), 7, 8]), (2, [0, -(2 ** 31), 1, 2]), (2, [0, 1, -1010])], 1009) == {(5, 6): 1, (6, 7): 1, (7, 8): 1, (1, 2): 1}
     assert K.add_counts({(1, 2): 1}, {(1, 2): 2, (3, 4): 1}) == {(1, 2): 3, (3, 4): 1}
     assert K.gaf_pairs([(False, 1005), (True, 1006), (True, 1008)]) == [(-1005, 1006), (1006, 1008)]
     text = K.gfa_text(["", "ACGTA", "CGTAN"], 4, [[0, 0, 0], [2, 9, 3], [0, 0, 0]], {(1, -2): 2 ** 64 - 1, (1, 2): 0})

@@ -38,6 +38,7 @@ SYMBOLS = [
     "bgr_aligner_abundance_enable", "bgr_aligner_abundance", "bgr_aligner_reset_abundance", "bgr_aligner_abundance_plan", "bgr_plan_abundance", "bgr_graph_abundance", "bgr_write_abundance",
     "bgr_aligner_links_enable", "bgr_aligner_links", "bgr_aligner_reset_links", "bgr_aligner_links_info", "bgr_aligner_links_plan", "bgr_plan_links", "bgr_graph_links_bound",
     "bgr_graph_links_enable", "bgr_graph_links", "bgr_write_gfa", "bgr_link_canonical", "bgr_graph_links_enabled",
+    "bgr_links_bubbles", "bgr_aligner_bubbles", "bgr_aligner_bubbles_times", "bgr_graph_bubbles_enable", "bgr_graph_bubbles_enabled", "bgr_graph_bubbles", "bgr_write_bubbles",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -100,6 +101,14 @@ class Link(C.Structure):  # bgr_link
 
 
 LINK_DTYPE = np.dtype([("from", np.int32), ("to", np.int32), ("count", np.uint64)])   # an array of bgr_link
+
+
+class Bubble(C.Structure):  # bgr_bubble
+    _fields_ = [("source", C.c_int32), ("sink", C.c_int32), ("branch", C.c_int32 * 2), ("count", C.c_uint64 * 4)]
+
+
+BUBBLE_DTYPE = np.dtype([("source", np.int32), ("sink", np.int32), ("branch", np.int32, (2,)), ("count", np.uint64, (4,))])   # an array of bgr_bubble
+BUBBLES_TILE = 1024   # BGR_BUBBLES_TILE: oriented ids per tile of the count and emit passes
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -265,6 +274,13 @@ def lib():
     L.bgr_graph_links.argtypes = [vp, vp, u64, vp]
     L.bgr_write_gfa.argtypes = [C.c_char_p, vp, vp, u64, vp, u64]
     L.bgr_graph_links_enabled.argtypes = [vp]
+    L.bgr_links_bubbles.argtypes = [C.c_int, vp, u64, u64, u64, vp, u64, vp]
+    L.bgr_aligner_bubbles.argtypes = [vp, u64, vp, u64, vp]
+    L.bgr_aligner_bubbles_times.argtypes = [vp, vp]
+    L.bgr_graph_bubbles_enable.argtypes = [vp, u32, u64]
+    L.bgr_graph_bubbles_enabled.argtypes = [vp]
+    L.bgr_graph_bubbles.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_bubbles.argtypes = [C.c_char_p, vp, vp, u64]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -529,6 +545,18 @@ class Graph:
     def links_enabled(self):
         """bgr_graph_links_enabled: the switch as it stands."""
         return bool(lib().bgr_graph_links_enabled(self.h))
+
+    def bubbles_enable(self, on=True, min_link=1):
+        """bgr_graph_bubbles_enable: sticky -- every later align_all on this graph counts unitig abundance and links and calls the bubbles of the run's links."""
+        _check(lib().bgr_graph_bubbles_enable(self.h, int(bool(on)), int(min_link)))
+
+    def bubbles_enabled(self):
+        """bgr_graph_bubbles_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_bubbles_enabled(self.h))
+
+    def bubbles(self):
+        """bgr_graph_bubbles: the bubbles of the last align_all with the switch on -> array of BUBBLE_DTYPE, ordered by (|source|, source < 0)."""
+        return _fetch_bubbles(lambda out, cap, n: lib().bgr_graph_bubbles(self.h, out, cap, n))
 
     def links(self):
         """bgr_graph_links: the links of the last align_all with the switch on -> array of LINK_DTYPE (from, to, count), canonical, sorted by key.
@@ -808,6 +836,17 @@ class Aligner:
         """bgr_aligner_links -> array of LINK_DTYPE (from, to, count) since enable / reset: canonical links, sorted by key."""
         return _fetch_links(lib().bgr_aligner_links, self.h)
 
+    def bubbles(self, min_link=1):
+        """bgr_aligner_bubbles: the bubbles of the aligner's table of links as it stands, called on the device -> array of BUBBLE_DTYPE, ordered by
+        (|source|, source < 0)."""
+        return _fetch_bubbles(lambda out, cap, n: lib().bgr_aligner_bubbles(self.h, int(min_link), out, cap, n))
+
+    def bubbles_times(self):
+        """bgr_aligner_bubbles_times -> the last bubbles() call's four launches in milliseconds (adjacency, count, scan, emit)."""
+        out = (C.c_double * 4)()
+        _check(lib().bgr_aligner_bubbles_times(self.h, out))
+        return [float(x) for x in out]
+
     def links_info(self):
         """bgr_aligner_links_info -> dict(capacity, bound, overflow, lds_fell_through)."""
         out = (C.c_uint64 * 4)()
@@ -1042,6 +1081,39 @@ def _fetch_links(fn, handle):
     assert LINK_DTYPE.itemsize == C.sizeof(Link) == 16
     _check(fn(handle, out.ctypes.data, n.value, C.byref(n)))
     return out[: n.value]
+
+
+def _fetch_bubbles(call):
+    """the two-call form of the bubble calls: the number first (BGR_E_CAPACITY with it), then the records"""
+    assert BUBBLE_DTYPE.itemsize == C.sizeof(Bubble) == 48
+    n = C.c_uint64(0)
+    rc = call(None, 0, C.byref(n))
+    if rc != -4 or n.value == 0:   # (no bubbles, or an error that is not "there are n of them")
+        _check(rc)
+        return np.zeros(0, dtype=BUBBLE_DTYPE)
+    out = np.zeros(n.value, dtype=BUBBLE_DTYPE)
+    _check(call(out.ctypes.data, n.value, C.byref(n)))
+    return out[: n.value]
+
+
+def _as_links(links):
+    if not (isinstance(links, np.ndarray) and links.dtype == LINK_DTYPE):
+        links = np.array([(int(a), int(b), int(c)) for a, b, c in links], dtype=LINK_DTYPE)
+    return np.ascontiguousarray(links)
+
+
+def links_bubbles(links, n_unitigs, min_link=1, device=0):
+    """bgr_links_bubbles: the bubbles of a list of links (an array of LINK_DTYPE, or (from, to, count) triples; canonical, strictly ascending by key,
+    as Aligner.links() delivers them) on a graph of n_unitigs unitigs, called on `device` -> array of BUBBLE_DTYPE."""
+    links = _as_links(links)
+    return _fetch_bubbles(lambda out, cap, n: lib().bgr_links_bubbles(int(device), links.ctypes.data, links.shape[0], int(n_unitigs), int(min_link), out, cap, n))
+
+
+def write_bubbles(path, graph, bubbles):
+    """bgr_write_bubbles: `bubbles` (an array of BUBBLE_DTYPE) as text -- "#source sink branch1 branch2 len1 len2 in1 out1 in2 out2 kind diff", one
+    tab-separated line per bubble."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    _check(lib().bgr_write_bubbles(path.encode(), graph.h, bubbles.ctypes.data, bubbles.shape[0]))
 
 
 def link_canonical(a, b):

@@ -138,7 +138,8 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
 static uint32_t run_counts_wanted(const bgr_graph* g) {
     if (!g) return 0;
     uint32_t what = 0;
-    if (g->links_on) what |= bgr::kCountLinks;
+    if (g->links_on || g->bubbles_on) what |= bgr::kCountLinks;
+    if (g->bubbles_on) what |= bgr::kCountBubbles;
     if (g->pileup_on || g->variants_on) what |= bgr::kCountPileup;
     if (g->variants_on) what |= bgr::kCountVariants;
     if ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)) what |= bgr::kCountStrands;
@@ -147,6 +148,7 @@ static uint32_t run_counts_wanted(const bgr_graph* g) {
 static void run_counts_begin(bgr_graph* g, uint32_t what) {
     if (what & bgr::kCountAbundance) graph_abundance_begin(g);
     if (what & bgr::kCountLinks) run_links_begin(g);
+    if (what & bgr::kCountBubbles) run_bubbles_begin(g);
     if (what & bgr::kCountPileup) run_pileup_begin(g);
 }
 static int run_counts_enable(bgr_aligner* a, uint32_t what) {   // every launch of the aligner is followed by the kernels of what the run counts
@@ -157,13 +159,17 @@ static int run_counts_enable(bgr_aligner* a, uint32_t what) {   // every launch 
 }
 static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
     int rc = what & bgr::kCountLinks ? run_links_collect(g, a) : BGR_OK;
+    if (rc == BGR_OK && (what & bgr::kCountBubbles)) run_bubbles_collect(g, a);
     if (rc == BGR_OK && (what & bgr::kCountPileup)) rc = run_pileup_collect(g, a);
     if (rc == BGR_OK && (what & bgr::kCountAbundance)) rc = run_abundance_collect(g, a);
     return rc;
 }
-static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) {   // (the message of a failed run stays: only a refusal of the pileup's end sets one)
+static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) {   // (the message of a failed run stays: only a refusal of the bubbles' or the pileup's end sets one)
     if (what & bgr::kCountAbundance) graph_abundance_end(g, ok);
     if (what & bgr::kCountLinks) run_links_end(g, ok);
-    return what & bgr::kCountPileup ? run_pileup_end(g, ok) : BGR_OK;
+    const int brc = what & bgr::kCountBubbles ? run_bubbles_end(g, ok) : BGR_OK;   // (behind the links' end: it reads the merged links)
+    if (brc != BGR_OK) { graph_abundance_end(g, false); run_links_end(g, false); }   // (the run has failed after all: it leaves no totals)
+    const int prc = what & bgr::kCountPileup ? run_pileup_end(g, ok && brc == BGR_OK) : BGR_OK;
+    return brc != BGR_OK ? brc : prc;
 }
 static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end}, true);

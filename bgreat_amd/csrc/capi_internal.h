@@ -1,5 +1,5 @@
 // capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; capi_abundance.hip,
-// capi_links.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
+// capi_links.hip, capi_bubbles.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
 // waits, and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or leaves the library.
 #ifndef BGREAT_AMD_CAPI_INTERNAL_H
 #define BGREAT_AMD_CAPI_INTERNAL_H
@@ -52,6 +52,12 @@ struct bgr_graph {
     bool links_on = false, links_valid = false, links_bound_known = false;
     uint64_t links_bound = 0;
     std::vector<std::pair<uint64_t, uint64_t>> links;
+    // bubbles (bgr_graph_bubbles_enable): the sticky switch with its threshold; the device of the first aligner a run collected (-1: none yet), where
+    // the run's merged links are called when it ends; the records of the last successful run and the threshold they were called with
+    bool bubbles_on = false, bubbles_valid = false;
+    uint64_t bubbles_min_link = 1, bubbles_called = 0;
+    int bubbles_device = -1;
+    std::vector<bgr_bubble> bubbles;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -173,6 +179,7 @@ struct bgr_aligner {
     uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
+    double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
     bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
     bool is_twin = false;
     int num_cus = 0;
@@ -206,9 +213,14 @@ int abundance_set(bgr_aligner* a, bool on);   // this one aligner's (or twin's) 
 bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases);   // geometry and form of the abundance kernel behind a launch of this size
 // capi_links.hip
 void links_share(bgr_aligner* a);   // the twins add to the aligner's table of links: its fields copied to each of them
+int links_tail(bgr_aligner* a, const char* who, uint64_t* tail);   // the three words behind the aligner's table, every stream that adds to it waited for; BGR_E_ARG when links were never enabled, BGR_E_CAPACITY when the table has overflowed
 void run_links_begin(bgr_graph* g);                   // a whole run (run_counts.h): the totals of the run before are gone,
 int run_links_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's table joins the run's,
 void run_links_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
+// capi_bubbles.hip
+void run_bubbles_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
+void run_bubbles_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's links will be called,
+int run_bubbles_end(bgr_graph* g, bool ok);             // ... behind the links' end: the merged links uploaded once, the four passes, the records kept
 // capi_pileup.hip
 void pileup_share(bgr_aligner* a);   // the twins add to the aligner's pileup tables: its fields copied to each of them
 int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who);   // BGR_E_CAPACITY when a reads column reached 2^32: a depth may have wrapped

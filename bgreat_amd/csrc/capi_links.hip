@@ -59,7 +59,7 @@ int bgr_aligner_links_enable(bgr_aligner* a, uint32_t on) {
 }
 
 // the words behind the aligner's table (links_kernels.h), every stream that adds to it waited for; BGR_E_CAPACITY when the overflow word is set
-static int links_tail(bgr_aligner* a, const char* who, uint64_t tail[bgr::kLinksTailWords]) {
+int links_tail(bgr_aligner* a, const char* who, uint64_t* tail) {   // (tail: bgr::kLinksTailWords words; capi_bubbles.hip calls it too)
     if (!a->links_tab) return fail(BGR_E_ARG, std::string(who) + ": links were never enabled on this aligner (bgr_aligner_links_enable)");
     if (const int rc = sync_all(a); rc != BGR_OK) return rc;
     HIP_TRY(hipMemcpy(tail, a->links_tab + 2 * a->links_cap, bgr::kLinksTailWords * 8, hipMemcpyDeviceToHost));

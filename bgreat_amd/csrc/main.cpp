@@ -32,6 +32,11 @@
 //                                                               in the input, it runs along the strand the unitig file spells; --pileup FILE gains the columns depth+ A+ C+ G+ T+ N+,
 //                                                               --vcf FILE the INFO fields ADF / ADR, and an ALT must be read at least N times (0) on each strand;
 //                                                               --min-alt-strand implies --strands and needs --vcf)
+//                                                   --bubbles FILE [--min-link N] (the variants the graph already holds: a unitig that leaves through two links to two branch unitigs which
+//                                                               both rejoin one unitig, called on the device from the run's link counts -- a link counts when at least
+//                                                               N (1) mapped reads cross it; one tab-separated line per bubble with the four signed ids, the branches'
+//                                                               lengths, the four link counts and how the branches differ (snv with pos:X>Y, mnv, indel); counts links
+//                                                               and unitig abundance as --gfa does; greedy modes, ACGT-only unitigs: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -53,11 +58,13 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
     bool vprm_given = false, strands = false, strand_given = false;
     uint32_t min_alt_strand = 0;   // --min-alt-strand
+    uint64_t min_link = 1;         // --min-link
+    bool min_link_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
@@ -67,6 +74,7 @@ int main(int argc, char** argv) {
                                 {"pileup", required_argument, nullptr, 1011}, {"depth", required_argument, nullptr, 1012},
                                 {"vcf", required_argument, nullptr, 1013}, {"min-depth", required_argument, nullptr, 1014}, {"min-alt", required_argument, nullptr, 1015},
                                 {"min-af", required_argument, nullptr, 1016}, {"strands", no_argument, nullptr, 1017}, {"min-alt-strand", required_argument, nullptr, 1018},
+                                {"bubbles", required_argument, nullptr, 1019}, {"min-link", required_argument, nullptr, 1020},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -127,6 +135,17 @@ int main(int argc, char** argv) {
                 strands = strand_given = true;
                 break;
             }
+            case 1019: bubblesFile = optarg; break;
+            case 1020: {   // a positive integer, digits only
+                const std::string v = optarg;
+                if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stol(v) < 1) {
+                    fprintf(stderr, "bgreat: --min-link takes a positive integer of at most nine digits, not '%s'\n", optarg);
+                    return 2;
+                }
+                min_link = (uint64_t)std::stol(v);
+                min_link_given = true;
+                break;
+            }
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -141,6 +160,7 @@ int main(int argc, char** argv) {
     if (vprm_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-depth, --min-alt and --min-af are thresholds of --vcf FILE\n"); return 2; }
     if (strand_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-alt-strand is a threshold of --vcf FILE\n"); return 2; }
     if (strands && vcfFile.empty() && pileupFile.empty()) { fprintf(stderr, "bgreat: --strands adds the per-strand counts to --pileup FILE and / or --vcf FILE\n"); return 2; }
+    if (min_link_given && bubblesFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -174,6 +194,7 @@ int main(int argc, char** argv) {
     opt.gaf = gaf ? 1u : 0u;
     opt.abundance = abundanceFile.empty() ? 0u : 1u;
     if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
+    if (!bubblesFile.empty() && bgr_graph_bubbles_enable(graph, 1, min_link) != BGR_OK) die("--bubbles");   // (likewise; it implies the counting of links)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
     const bgr_variant_strand_params sprm = {vprm.min_depth, vprm.min_alt, vprm.min_af_ppm, min_alt_strand};
@@ -206,6 +227,13 @@ int main(int argc, char** argv) {
         std::vector<bgr_link> links(n_links);
         if (n_links && bgr_graph_links(graph, links.data(), n_links, &n_links) != BGR_OK) die("gfa");
         if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), n_links) != BGR_OK) die("gfa");
+    }
+    if (!bubblesFile.empty()) {  // (the run has called them from its merged links)
+        uint64_t n_bubbles = 0;
+        if (bgr_graph_bubbles(graph, nullptr, 0, &n_bubbles) != BGR_OK && n_bubbles == 0) die("--bubbles");   // (BGR_E_CAPACITY with the number of bubbles)
+        std::vector<bgr_bubble> bubbles(n_bubbles);
+        if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--bubbles");
+        if (bgr_write_bubbles(bubblesFile.c_str(), graph, bubbles.data(), n_bubbles) != BGR_OK) die("--bubbles");
     }
     if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");

@@ -52,6 +52,9 @@ hipError_t launch_variants_count(const BgrDeviceGraph& g, uint64_t n_unitigs, ui
 // records, with table_fwd bgr_variant_strand_site records)
 hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uint64_t total_bases, const uint32_t* table, const uint32_t* table_fwd,
                                 const uint64_t* base_offs, const bgr_variant_strand_params& prm, const void* scratch, void* out, hipStream_t stream);
+// the passes' scan by itself (passes 2 and 4 as they stand: one workgroup): out[t] = in[0] + .. + in[t - 1] for t = 0 .. n, 64-bit.  Other compactions
+// (bubbles_kernels.hip) scan their tile counts with it.
+hipError_t launch_variants_scan(const uint32_t* in, uint64_t n, uint64_t* out, hipStream_t stream);
 // dst[i] += src[i] (mod 2^32) over n_words 32-bit words; with tail_u64 the last two words of both are one u64 counter (the table's tail) and are
 // added as such.  Both on the device of `stream`; dst and src 16-byte aligned.
 hipError_t launch_pileup_add(uint32_t* dst, const uint32_t* src, uint64_t n_words, bool tail_u64, uint32_t num_cus, hipStream_t stream);

@@ -302,6 +302,12 @@ hipError_t launch_variants_emit(const BgrDeviceGraph& g, uint64_t n_unitigs, uin
     return hipGetLastError();
 }
 
+hipError_t launch_variants_scan(const uint32_t* in, uint64_t n, uint64_t* out, hipStream_t stream) {
+    if (!in || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bgr_variants_scan_kernel, dim3(1), dim3(kThreads), 0, stream, in, (u64)n, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_pileup_add(uint32_t* dst, const uint32_t* src, uint64_t n_words, bool tail_u64, uint32_t num_cus, hipStream_t stream) {
     if (n_words == 0) return hipSuccess;
     if (!dst || !src || (tail_u64 && (n_words < 2 || (n_words & 1)))) return hipErrorInvalidValue;

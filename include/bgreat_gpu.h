@@ -623,6 +623,52 @@ int bgr_graph_links_enabled(const bgr_graph* g);   /* the switch as it stands: 1
 int bgr_graph_links(const bgr_graph* g, bgr_link* out, uint64_t cap, uint64_t* n);
 int bgr_write_gfa(const char* path, const bgr_graph* g, const bgr_unitig_abundance* abundance_rows, uint64_t n_rows, const bgr_link* links, uint64_t n_links);
 
+/* Bubbles: the variants the graph already holds.  A variant that was abundant enough to enter a compacted de Bruijn graph is no mismatch anywhere
+ * (bgr_variant_site is silent about it): a unitig s leaves through two links to two branch unitigs that both rejoin one unitig t, and the reads of
+ * either allele map onto their own branch.  The bubbles are a function of a set of counted links alone:
+ *   input      canonical links with counts (bgr_link) and a threshold min_link >= 1
+ *   supported  a link with count >= min_link
+ *   edges      a supported canonical link (a, b) is the oriented edge a -> b and its strand mate -b -> -a (one edge when b == -a).  out(x) = the
+ *              supported successors of the signed id x; in(x) has as many members as out(-x)
+ *   bubble     an oriented s opens the bubble (s, t, b, c) when |out(s)| == 2 with out(s) = {b, c}; |in(b)| == |in(c)| == 1; |out(b)| == |out(c)| == 1
+ *              and both lead to the same t; |in(t)| == 2; and |s|, |b|, |c|, |t| are four different unitigs
+ *   mates      (s, t, b, c) and (-t, -s, -b, -c) are one bubble read from the two strands: it is reported once, under whichever of (s, t) and
+ *              (-t, -s) has the smaller key (bgr_link_canonical's order; never equal, because |s| != |t|)
+ *   record     source = s, sink = t, branch[0] the branch with the smaller (|id|, id < 0), count = the traversals of source -> branch[0],
+ *              branch[0] -> sink, source -> branch[1], branch[1] -> sink
+ *   order      by (|source|, source < 0): an oriented id opens at most one bubble, so the order is total
+ * Exact integers, independent of batching, routes, streams and devices.  For an isolated SNV both branches are 2k - 1 long and differ at index k - 1;
+ * three alleles at one site give |out(s)| == 3 and no bubble.
+ * The device side (bgreat_amd/csrc/bubbles_kernels.h) runs four launches in stream order over {key, count} pairs in HBM -- adjacency with one 32-bit
+ * atomic per oriented edge (the first two successors of an id are kept, later ones only counted), a count per tile of BGR_BUBBLES_TILE oriented ids,
+ * a scan, and the emit at each record's final place: no sort, no atomics on the output, no workgroup waits for another -- in 56 bytes of scratch per
+ * unitig (222 MB on the chr1-scale graph), allocated for the call and freed behind it: BGR_E_NOMEM, with nothing left allocated, when the device
+ * does not have it.  All three calls set *n to the number of bubbles, always, and return BGR_E_CAPACITY with nothing copied when cap is smaller.
+ * bgr_links_bubbles: a list (sorted by key, canonical, ids within 1 .. n_unitigs, as bgr_aligner_links delivers it -- anything else, min_link == 0
+ * and n_unitigs >= 2^30 are BGR_E_ARG before any device work) is uploaded to `device` and called there.
+ * bgr_aligner_bubbles: the aligner's live table of links is called where it lies, its streams waited for; only the records cross to the host.
+ * BGR_E_ARG when links were never enabled, BGR_E_CAPACITY (with a message) when the table has overflowed, as bgr_aligner_links.
+ * bgr_aligner_bubbles_times: the last such call's four launches in milliseconds (zeroes when events are switched off).
+ * bgr_graph_bubbles_enable(g, on, min_link) is a sticky switch like bgr_graph_links_enable and implies it for the run (BGR_E_ARG for min_link == 0,
+ * a graph without a host blob or with non-ACGT unitig characters): at the end of a successful bgr_align_all the run's merged links -- gathered on
+ * the host exactly as without the switch -- are uploaded once (16 bytes per link) to the device of the first aligner that was collected and called
+ * there; bgr_graph_bubbles delivers the records (BGR_E_ARG when there are none: a failed run, BGR_E_COMPACTION too, leaves no totals).  Merging the
+ * aligners' tables on the device instead is out of scope here.
+ * bgr_write_bubbles (host code, deterministic bytes; BGR_E_ARG on a graph created from a blob, which carries no unitig characters, and for a record
+ * that names a unitig the graph does not have) writes the line "#source sink branch1 branch2 len1 len2 in1 out1 in2 out2 kind diff" and one line per
+ * record, all tab-separated: the four signed ids as in the paths file, the branches' lengths, count[0 .. 3], and how the two branches compare as
+ * oriented (a branch with a negative id is reverse-complemented): kind "snv" (equal length, exactly one position differs) with diff "pos:X>Y", pos
+ * 0-based on oriented branch1, X its letter and Y branch2's; "mnv" (equal length otherwise) and "indel" (lengths differ), both with diff ".". */
+#define BGR_BUBBLES_TILE 1024u
+typedef struct { int32_t source, sink, branch[2]; uint64_t count[4]; } bgr_bubble;
+int bgr_links_bubbles(int device, const bgr_link* links, uint64_t n_links, uint64_t n_unitigs, uint64_t min_link, bgr_bubble* out, uint64_t cap, uint64_t* n);
+int bgr_aligner_bubbles(bgr_aligner* a, uint64_t min_link, bgr_bubble* out, uint64_t cap, uint64_t* n);
+int bgr_aligner_bubbles_times(bgr_aligner* a, double ms[4]);
+int bgr_graph_bubbles_enable(bgr_graph* g, uint32_t on, uint64_t min_link);
+int bgr_graph_bubbles_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_bubbles(const bgr_graph* g, bgr_bubble* out, uint64_t cap, uint64_t* n);
+int bgr_write_bubbles(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n);
+
 /* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
  * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig
  * abundance and the pileup in every aligner of the run; the tables of all aligners and devices are summed (mod 2^32: the differences commute) when

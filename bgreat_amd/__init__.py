@@ -26,7 +26,7 @@ SYMBOLS = [
     "bgr_last_error", "bgr_device_count", "bgr_graph_build", "bgr_graph_build_from_fasta", "bgr_graph_blob",
     "bgr_graph_from_blob", "bgr_graph_info", "bgr_graph_destroy", "bgr_graph_upload", "bgr_graph_device_blob",
     "bgr_graph_adopt_device_blob", "bgr_aligner_create", "bgr_aligner_destroy", "bgr_align_batch", "bgr_align_device", "bgr_aligner_path_stats",
-    "bgr_aligner_sync", "bgr_aligner_device_results", "bgr_aligner_fetch", "bgr_aligner_counters",
+    "bgr_aligner_sync", "bgr_aligner_device_results", "bgr_aligner_arena_ints", "bgr_aligner_fetch", "bgr_aligner_counters",
     "bgr_aligner_reset_counters", "bgr_aligner_kernel_time", "bgr_aligner_reset_kernel_time", "bgr_aligner_launch_info",
     "bgr_aligner_configure", "bgr_readset_load", "bgr_readset_count", "bgr_readset_view", "bgr_readset_destroy",
     "bgr_write_records", "bgr_graph_unitigs", "bgr_readset_load_parallel", "bgr_align_all", "bgr_host_alloc", "bgr_host_free",
@@ -39,6 +39,9 @@ SYMBOLS = [
     "bgr_aligner_links_enable", "bgr_aligner_links", "bgr_aligner_reset_links", "bgr_aligner_links_info", "bgr_aligner_links_plan", "bgr_plan_links", "bgr_graph_links_bound",
     "bgr_graph_links_enable", "bgr_graph_links", "bgr_write_gfa", "bgr_link_canonical", "bgr_graph_links_enabled",
     "bgr_links_bubbles", "bgr_aligner_bubbles", "bgr_aligner_bubbles_times", "bgr_graph_bubbles_enable", "bgr_graph_bubbles_enabled", "bgr_graph_bubbles", "bgr_write_bubbles",
+    "bgr_aligner_triples_enable", "bgr_aligner_triples", "bgr_aligner_reset_triples", "bgr_aligner_triples_info", "bgr_triple_canonical", "bgr_graph_triples_bound",
+    "bgr_graph_triples_enable", "bgr_graph_triples_enabled", "bgr_graph_triples", "bgr_write_triples",
+    "bgr_bubbles_phase", "bgr_graph_phase_enable", "bgr_graph_phase_enabled", "bgr_graph_phase", "bgr_write_phase",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -109,6 +112,21 @@ class Bubble(C.Structure):  # bgr_bubble
 
 BUBBLE_DTYPE = np.dtype([("source", np.int32), ("sink", np.int32), ("branch", np.int32, (2,)), ("count", np.uint64, (4,))])   # an array of bgr_bubble
 BUBBLES_TILE = 1024   # BGR_BUBBLES_TILE: oriented ids per tile of the count and emit passes
+
+
+class Triple(C.Structure):  # bgr_triple
+    _fields_ = [("from_", C.c_int32), ("via", C.c_int32), ("to", C.c_int32), ("reserved", C.c_int32), ("count", C.c_uint64)]
+
+
+TRIPLE_DTYPE = np.dtype([("from", np.int32), ("via", np.int32), ("to", np.int32), ("reserved", np.int32), ("count", np.uint64)])   # an array of bgr_triple
+
+
+class Phase(C.Structure):  # bgr_phase
+    _fields_ = [("via", C.c_int32), ("source", C.c_int32), ("in_", C.c_int32 * 2), ("out", C.c_int32 * 2), ("sink", C.c_int32), ("reserved", C.c_int32), ("count", C.c_uint64 * 4)]
+
+
+PHASE_DTYPE = np.dtype([("via", np.int32), ("source", np.int32), ("in", np.int32, (2,)), ("out", np.int32, (2,)), ("sink", np.int32), ("reserved", np.int32),
+                        ("count", np.uint64, (4,))])   # an array of bgr_phase
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -222,6 +240,7 @@ def lib():
     L.bgr_text_stage_upload.argtypes = [vp, vp, u64]
     L.bgr_aligner_sync.argtypes = [vp]
     L.bgr_aligner_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.bgr_aligner_arena_ints.argtypes = [vp, vp]
     L.bgr_aligner_fetch.argtypes = [vp, u64, vp, u64, vp, vp]
     L.bgr_aligner_path_stats.argtypes = [vp, vp, vp, u64, vp]
     L.bgr_aligner_counters.argtypes = [vp, vp]
@@ -281,6 +300,21 @@ def lib():
     L.bgr_graph_bubbles_enabled.argtypes = [vp]
     L.bgr_graph_bubbles.argtypes = [vp, vp, u64, vp]
     L.bgr_write_bubbles.argtypes = [C.c_char_p, vp, vp, u64]
+    L.bgr_aligner_triples_enable.argtypes = [vp, u32]
+    L.bgr_aligner_triples.argtypes = [vp, vp, u64, vp]
+    L.bgr_aligner_reset_triples.argtypes = [vp]
+    L.bgr_aligner_triples_info.argtypes = [vp, vp]
+    L.bgr_triple_canonical.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp]
+    L.bgr_graph_triples_bound.argtypes = [vp, vp]
+    L.bgr_graph_triples_enable.argtypes = [vp, u32]
+    L.bgr_graph_triples_enabled.argtypes = [vp]
+    L.bgr_graph_triples.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_triples.argtypes = [C.c_char_p, vp, vp, u64]
+    L.bgr_bubbles_phase.argtypes = [vp, u64, vp, u64, vp, u64, vp]
+    L.bgr_graph_phase_enable.argtypes = [vp, u32, u64]
+    L.bgr_graph_phase_enabled.argtypes = [vp]
+    L.bgr_graph_phase.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_phase.argtypes = [C.c_char_p, vp, vp, u64]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -646,6 +680,36 @@ class Graph:
         sites = np.ascontiguousarray(sites, dtype=VARIANT_STRAND_DTYPE)
         _check(lib().bgr_write_vcf_strands(path.encode(), self.h, C.byref(prm), sites.ctypes.data if len(sites) else None, len(sites)))
 
+    def triples_enable(self, on=True):
+        """bgr_graph_triples_enable: sticky -- every later align_all on this graph counts unitig abundance and triples."""
+        _check(lib().bgr_graph_triples_enable(self.h, int(bool(on))))
+
+    def triples_enabled(self):
+        """bgr_graph_triples_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_triples_enabled(self.h))
+
+    def triples(self):
+        """bgr_graph_triples: the triples of the last align_all with the switch on -> array of TRIPLE_DTYPE, canonical, sorted by key."""
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_triples(self.h, out, cap, n), TRIPLE_DTYPE)
+
+    def triples_bound(self):
+        """bgr_graph_triples_bound: how many distinct triples any rows on this graph can hold (the table of triples has at least twice as many slots)."""
+        b = C.c_uint64(0)
+        _check(lib().bgr_graph_triples_bound(self.h, C.byref(b)))
+        return int(b.value)
+
+    def phase_enable(self, on=True, min_link=1):
+        """bgr_graph_phase_enable: sticky -- every later align_all on this graph counts links and triples, calls the bubbles and joins the neighbours."""
+        _check(lib().bgr_graph_phase_enable(self.h, int(bool(on)), int(min_link)))
+
+    def phase_enabled(self):
+        """bgr_graph_phase_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_phase_enabled(self.h))
+
+    def phase(self):
+        """bgr_graph_phase: the phase records of the last align_all with the switch on -> array of PHASE_DTYPE, ordered by via."""
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_phase(self.h, out, cap, n), PHASE_DTYPE)
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -799,6 +863,12 @@ class Aligner:
         _check(lib().bgr_aligner_device_results(self.h, C.byref(r), C.byref(a), C.byref(c)))
         return r.value, a.value, c.value
 
+    def arena_ints(self):
+        """bgr_aligner_arena_ints: ints of the arena as the last launch planned it (the bound the counting kernels check a row against)."""
+        n = C.c_uint64(0)
+        _check(lib().bgr_aligner_arena_ints(self.h, C.byref(n)))
+        return int(n.value)
+
     def path_stats(self, d_reads_ptr, d_offsets_ptr, n):
         """bgr_aligner_path_stats over the last align_device launch (the same device reads again) -> structured array of n rows with the fields
         path_len, path_start, aligned, mismatches (PATH_STAT_NO_WALK set there for a path that spells no walk; zeros for an unmapped read)."""
@@ -861,6 +931,23 @@ class Aligner:
 
     def reset_links(self):
         _check(lib().bgr_aligner_reset_links(self.h))
+
+    def triples_enable(self, on=True):
+        """bgr_aligner_triples_enable: every greedy / anchors launch from now on adds every three consecutive ids of its rows to the aligner's table of triples."""
+        _check(lib().bgr_aligner_triples_enable(self.h, int(bool(on))))
+
+    def triples(self):
+        """bgr_aligner_triples -> array of TRIPLE_DTYPE (from, via, to, reserved, count) since enable / reset: canonical triples, sorted by key."""
+        return _fetch_records(lambda out, cap, n: lib().bgr_aligner_triples(self.h, out, cap, n), TRIPLE_DTYPE)
+
+    def triples_info(self):
+        """bgr_aligner_triples_info -> dict(capacity, bound, overflow, used)."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().bgr_aligner_triples_info(self.h, out))
+        return dict(capacity=int(out[0]), bound=int(out[1]), overflow=int(out[2]), used=int(out[3]))
+
+    def reset_triples(self):
+        _check(lib().bgr_aligner_reset_triples(self.h))
 
     def pileup_enable(self, on=True):
         """bgr_aligner_pileup_enable: every greedy / anchors launch from now on adds per-base depth and mismatches to the aligner's table
@@ -1094,6 +1181,55 @@ def _fetch_bubbles(call):
     out = np.zeros(n.value, dtype=BUBBLE_DTYPE)
     _check(call(out.ctypes.data, n.value, C.byref(n)))
     return out[: n.value]
+
+
+def _fetch_records(call, dtype):
+    """the two-call form of the triples and phase calls: the number first (BGR_E_CAPACITY with it), then the records"""
+    assert TRIPLE_DTYPE.itemsize == C.sizeof(Triple) == 24 and PHASE_DTYPE.itemsize == C.sizeof(Phase) == 64
+    n = C.c_uint64(0)
+    rc = call(None, 0, C.byref(n))
+    if rc != -4 or n.value == 0:   # (no records, or an error that is not "there are n of them": an overflowed table says so)
+        _check(rc)
+        return np.zeros(0, dtype=dtype)
+    out = np.zeros(n.value, dtype=dtype)
+    _check(call(out.ctypes.data, n.value, C.byref(n)))
+    return out[: n.value]
+
+
+def _as_triples(triples):
+    if not (isinstance(triples, np.ndarray) and triples.dtype == TRIPLE_DTYPE):
+        triples = np.array([(int(a), int(b), int(c), 0, int(n)) for a, b, c, n in triples], dtype=TRIPLE_DTYPE)
+    return np.ascontiguousarray(triples)
+
+
+def triple_canonical(a, b, c):
+    """bgr_triple_canonical: the canonical form of the triple (a, b, c), by the code the kernel runs -> (from, via, to)."""
+    out = Triple()
+    _check(lib().bgr_triple_canonical(int(a), int(b), int(c), C.byref(out)))
+    return int(out.from_), int(out.via), int(out.to)
+
+
+def write_triples(path, graph, triples):
+    """bgr_write_triples: `triples` (an array of TRIPLE_DTYPE, or (from, via, to, count) tuples; sorted by key as Graph.triples() delivers them) as
+    text -- "#from via to count", one tab-separated line per triple."""
+    triples = _as_triples(triples)
+    _check(lib().bgr_write_triples(path.encode(), graph.h, triples.ctypes.data if len(triples) else None, triples.shape[0]))
+
+
+def bubbles_phase(bubbles, triples):
+    """bgr_bubbles_phase: the neighbour pairs of `bubbles` (an array of BUBBLE_DTYPE, as Graph.bubbles() delivers them) with the counts of the
+    triples (TRIPLE_DTYPE or (from, via, to, count) tuples; canonical, sorted) that thread them -> array of PHASE_DTYPE, ordered by via."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    triples = _as_triples(triples)
+    return _fetch_records(lambda out, cap, n: lib().bgr_bubbles_phase(bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0],
+                                                                      triples.ctypes.data if len(triples) else None, triples.shape[0], out, cap, n), PHASE_DTYPE)
+
+
+def write_phase(path, graph, records):
+    """bgr_write_phase: `records` (an array of PHASE_DTYPE) as text -- "#via source in1 in2 out1 out2 sink n11 n12 n21 n22 phase", one tab-separated
+    line per record."""
+    records = np.ascontiguousarray(records, dtype=PHASE_DTYPE)
+    _check(lib().bgr_write_phase(path.encode(), graph.h, records.ctypes.data if len(records) else None, records.shape[0]))
 
 
 def _as_links(links):

@@ -1,5 +1,5 @@
 // capi.hip -- implementation of the C-ABI declared in include/bgreat_gpu.h: index, distribution, mapping, text route, batches, the
-// asynchronous form, host buffers and readsets (the counting features have their own units: capi_abundance.hip, capi_links.hip,
+// asynchronous form, host buffers and readsets (the counting features have their own units: capi_abundance.hip, capi_links.hip, capi_triples.hip,
 // capi_pileup.hip, capi_variants.hip; capi_internal.h has what they share).  Thin: argument checks, HIP memory
 // and stream management, launch geometry; the algorithm lives in graph_build.cpp (index) and
 // the *_kernels.hip files (mapping; launch interface align_kernels.h).  There is no CPU mapping path in this library.
@@ -28,6 +28,7 @@
 #include "graph_build.h"
 #include "launch_plan.h"
 #include "links_kernels.h"
+#include "triples_kernels.h"
 #include "pileup_kernels.h"
 #include "read_pack.h"
 #include "text_kernels.h"
@@ -405,7 +406,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->triples.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -549,6 +550,13 @@ static int queue_counting(bgr_aligner* a, uint64_t arena_cap, const uint64_t* re
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_links_kernel"));
     }
+    // Triples (bgr_aligner_triples_enable): likewise one kernel that adds every three consecutive ids of this launch's rows to the aligner's hash table.
+    if (a->triples_on) {
+        e = bgr::launch_triples(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->triples_tab,
+                                a->triples_cap, (uint32_t)a->num_cus, a->stream);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_triples_kernel): ") + hipGetErrorString(e));
+        HIP_TRY(mark("bgr_triples_kernel"));
+    }
     // Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches, the read characters from `pr`.
     if (a->pileup_on) {
         e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
@@ -576,6 +584,8 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->links_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts links (bgr_aligner_links_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->triples_on && p->mode == BGR_MODE_EXHAUSTIVE)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts triples (bgr_aligner_triples_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     a->last_n = n_reads;
@@ -1155,6 +1165,12 @@ int bgr_aligner_sync(bgr_aligner* a) {
     return settle_launch_sync(a);  // (exhaustive mode: reads the last pass handed back are mapped before the results count as final)
 }
 
+int bgr_aligner_arena_ints(bgr_aligner* a, uint64_t* ints) {
+    if (!a || !ints) return fail(BGR_E_ARG, "bgr_aligner_arena_ints: null argument");
+    *ints = a->last_arena_cap;
+    return BGR_OK;
+}
+
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_device_results: null aligner");
     if (d_results) *d_results = a->results.p;
@@ -1292,6 +1308,7 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
     }
     pileup_share(a);   // (one pileup table and one table of links for the aligner and its twins: the atomics are device-scope)
     links_share(a);
+    triples_share(a);
     uint64_t cut[kOverlapMaxPieces + 1];
     for (unsigned k = 0; k <= n_pieces; ++k) cut[k] = n * k / n_pieces;
     std::mutex mu;

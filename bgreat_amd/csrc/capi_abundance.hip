@@ -138,8 +138,10 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
 static uint32_t run_counts_wanted(const bgr_graph* g) {
     if (!g) return 0;
     uint32_t what = 0;
-    if (g->links_on || g->bubbles_on) what |= bgr::kCountLinks;
-    if (g->bubbles_on) what |= bgr::kCountBubbles;
+    if (g->links_on || g->bubbles_on || g->phase_on) what |= bgr::kCountLinks;
+    if (g->bubbles_on || g->phase_on) what |= bgr::kCountBubbles;
+    if (g->triples_on || g->phase_on) what |= bgr::kCountTriples;
+    if (g->phase_on) what |= bgr::kCountPhase;
     if (g->pileup_on || g->variants_on) what |= bgr::kCountPileup;
     if (g->variants_on) what |= bgr::kCountVariants;
     if ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)) what |= bgr::kCountStrands;
@@ -149,17 +151,21 @@ static void run_counts_begin(bgr_graph* g, uint32_t what) {
     if (what & bgr::kCountAbundance) graph_abundance_begin(g);
     if (what & bgr::kCountLinks) run_links_begin(g);
     if (what & bgr::kCountBubbles) run_bubbles_begin(g);
+    if (what & bgr::kCountTriples) run_triples_begin(g);
+    if (what & bgr::kCountPhase) run_phase_begin(g);
     if (what & bgr::kCountPileup) run_pileup_begin(g);
 }
 static int run_counts_enable(bgr_aligner* a, uint32_t what) {   // every launch of the aligner is followed by the kernels of what the run counts
     int rc = what & bgr::kCountAbundance ? bgr_aligner_abundance_enable(a, 1) : BGR_OK;
     if (rc == BGR_OK && (what & bgr::kCountLinks)) rc = bgr_aligner_links_enable(a, 1);
+    if (rc == BGR_OK && (what & bgr::kCountTriples)) rc = bgr_aligner_triples_enable(a, 1);
     if (rc == BGR_OK && (what & bgr::kCountPileup)) rc = what & bgr::kCountStrands ? bgr_aligner_pileup_strands_enable(a, 1) : bgr_aligner_pileup_enable(a, 1);
     return rc;
 }
 static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
     int rc = what & bgr::kCountLinks ? run_links_collect(g, a) : BGR_OK;
     if (rc == BGR_OK && (what & bgr::kCountBubbles)) run_bubbles_collect(g, a);
+    if (rc == BGR_OK && (what & bgr::kCountTriples)) rc = run_triples_collect(g, a);
     if (rc == BGR_OK && (what & bgr::kCountPileup)) rc = run_pileup_collect(g, a);
     if (rc == BGR_OK && (what & bgr::kCountAbundance)) rc = run_abundance_collect(g, a);
     return rc;
@@ -167,8 +173,14 @@ static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
 static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) {   // (the message of a failed run stays: only a refusal of the bubbles' or the pileup's end sets one)
     if (what & bgr::kCountAbundance) graph_abundance_end(g, ok);
     if (what & bgr::kCountLinks) run_links_end(g, ok);
-    const int brc = what & bgr::kCountBubbles ? run_bubbles_end(g, ok) : BGR_OK;   // (behind the links' end: it reads the merged links)
-    if (brc != BGR_OK) { graph_abundance_end(g, false); run_links_end(g, false); }   // (the run has failed after all: it leaves no totals)
+    if (what & bgr::kCountTriples) run_triples_end(g, ok);
+    int brc = what & bgr::kCountBubbles ? run_bubbles_end(g, ok) : BGR_OK;   // (behind the links' end: it reads the merged links)
+    if (brc == BGR_OK && (what & bgr::kCountPhase)) brc = run_phase_end(g, ok);   // (behind the bubbles' and the triples' end: it joins the two)
+    if (brc != BGR_OK) {   // (the run has failed after all: it leaves no totals)
+        graph_abundance_end(g, false); run_links_end(g, false);
+        if (what & bgr::kCountTriples) run_triples_end(g, false);
+        if (what & bgr::kCountPhase) (void)run_phase_end(g, false);
+    }
     const int prc = what & bgr::kCountPileup ? run_pileup_end(g, ok && brc == BGR_OK) : BGR_OK;
     return brc != BGR_OK ? brc : prc;
 }

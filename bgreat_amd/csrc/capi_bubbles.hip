@@ -119,14 +119,15 @@ int run_bubbles_end(bgr_graph* g, bool ok) {   // behind run_links_end: g->links
     std::lock_guard<std::mutex> l(g->abundance_m);
     g->bubbles.clear();
     g->bubbles_valid = false;
-    g->bubbles_called = g->bubbles_min_link;
+    const uint64_t min_link = g->bubbles_on || !g->phase_on ? g->bubbles_min_link : g->phase_min_link;   // (a run that only phases calls its bubbles with the phase's threshold)
+    g->bubbles_called = min_link;
     if (!ok) return BGR_OK;
     int rc = BGR_OK;
     uint64_t n = 0;
     if (!g->links_valid) rc = fail(BGR_E_INTERNAL, "bgr_align_all: bubbles without the links they are called from");
     else if (!g->links.empty()) {
         if (g->bubbles_device < 0) rc = fail(BGR_E_INTERNAL, "bgr_align_all: links, but no aligner of the run was collected");
-        else rc = bubbles_of_pairs(g->bubbles_device, g->links.data(), g->links.size(), g->header.n_unitigs, g->bubbles_min_link, "bgr_align_all", &g->bubbles, nullptr, 0, &n);
+        else rc = bubbles_of_pairs(g->bubbles_device, g->links.data(), g->links.size(), g->header.n_unitigs, min_link, "bgr_align_all", &g->bubbles, nullptr, 0, &n);
     }
     if (rc != BGR_OK) { g->bubbles.clear(); g->bubbles.shrink_to_fit(); }
     g->bubbles_valid = rc == BGR_OK;

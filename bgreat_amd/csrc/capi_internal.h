@@ -1,5 +1,5 @@
 // capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; capi_abundance.hip,
-// capi_links.hip, capi_bubbles.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
+// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
 // waits, and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or leaves the library.
 #ifndef BGREAT_AMD_CAPI_INTERNAL_H
 #define BGREAT_AMD_CAPI_INTERNAL_H
@@ -58,6 +58,17 @@ struct bgr_graph {
     uint64_t bubbles_min_link = 1, bubbles_called = 0;
     int bubbles_device = -1;
     std::vector<bgr_bubble> bubbles;
+    // triples (bgr_graph_triples_enable): as the links -- the sticky switch, the bound of distinct triples (from the host blob, the first time it is asked
+    // for), the totals of the last bgr_align_all with the switch on: {k0, k1, count} as the aligners delivered them until the run ends, then merged and sorted
+    struct TripleRow { uint64_t k0, k1, count; };
+    bool triples_on = false, triples_valid = false, triples_bound_known = false;
+    uint64_t triples_bound = 0;
+    std::vector<TripleRow> triples;
+    // phase (bgr_graph_phase_enable): the sticky switch with the threshold its bubbles are called with when the bubbles' own switch is off; the records
+    // of the last successful run
+    bool phase_on = false, phase_valid = false;
+    uint64_t phase_min_link = 1;
+    std::vector<bgr_phase> phase;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -170,6 +181,10 @@ struct bgr_aligner {
     DevBuf links;                   // {u64 key, u64 count}[links_cap] + the tail words (links_kernels.h), allocated and zeroed on the first enable
     unsigned long long* links_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
     uint64_t links_cap = 0, links_bound = 0;
+    bool triples_on = false;        // bgr_aligner_triples_enable: every greedy / anchors launch is followed by the triples kernel
+    DevBuf triples;                 // {u64 k0, u64 k1, u64 count}[triples_cap] + the tail words (triples_kernels.h), allocated and zeroed on the first enable
+    unsigned long long* triples_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
+    uint64_t triples_cap = 0, triples_bound = 0;
     bool pileup_on = false;         // bgr_aligner_pileup_enable: every greedy / anchors launch is followed by the pileup kernel
     DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
     uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
@@ -217,6 +232,13 @@ int links_tail(bgr_aligner* a, const char* who, uint64_t* tail);   // the three 
 void run_links_begin(bgr_graph* g);                   // a whole run (run_counts.h): the totals of the run before are gone,
 int run_links_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's table joins the run's,
 void run_links_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
+// capi_triples.hip
+void triples_share(bgr_aligner* a);   // the twins add to the aligner's table of triples: its fields copied to each of them
+void run_triples_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
+int run_triples_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's table joins the run's,
+void run_triples_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
+void run_phase_begin(bgr_graph* g);
+int run_phase_end(bgr_graph* g, bool ok);               // ... behind the bubbles' and the triples' end: the run's bubbles joined with its triples on the host
 // capi_bubbles.hip
 void run_bubbles_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
 void run_bubbles_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's links will be called,

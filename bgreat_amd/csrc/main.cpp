@@ -37,6 +37,12 @@
 //                                                               N (1) mapped reads cross it; one tab-separated line per bubble with the four signed ids, the branches'
 //                                                               lengths, the four link counts and how the branches differ (snv with pos:X>Y, mnv, indel); counts links
 //                                                               and unitig abundance as --gfa does; greedy modes, ACGT-only unitigs: include/bgreat_gpu.h)
+//                                                   --triples FILE (every three consecutive unitigs that a mapped read's path threads -- which way into a unitig goes with which way out of
+//                                                               it -- with its count, counted on the device while mapping; one tab-separated line "from via to count" per
+//                                                               canonical triple, signed ids as in the paths file; counts unitig abundance as --gfa does; greedy modes)
+//                                                   --phase FILE [--min-link N] (read-backed phasing: every two bubbles of --bubbles that share a unitig, with the counts of the four
+//                                                               in x out combinations of their branches that the reads thread, and cis / trans / . ; counts links and
+//                                                               triples and calls the bubbles as --bubbles and --triples do; greedy modes, ACGT-only unitigs)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -58,7 +64,7 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
     bool vprm_given = false, strands = false, strand_given = false;
@@ -75,6 +81,7 @@ int main(int argc, char** argv) {
                                 {"vcf", required_argument, nullptr, 1013}, {"min-depth", required_argument, nullptr, 1014}, {"min-alt", required_argument, nullptr, 1015},
                                 {"min-af", required_argument, nullptr, 1016}, {"strands", no_argument, nullptr, 1017}, {"min-alt-strand", required_argument, nullptr, 1018},
                                 {"bubbles", required_argument, nullptr, 1019}, {"min-link", required_argument, nullptr, 1020},
+                                {"triples", required_argument, nullptr, 1021}, {"phase", required_argument, nullptr, 1022},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -146,6 +153,8 @@ int main(int argc, char** argv) {
                 min_link_given = true;
                 break;
             }
+            case 1021: triplesFile = optarg; break;
+            case 1022: phaseFile = optarg; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -160,7 +169,7 @@ int main(int argc, char** argv) {
     if (vprm_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-depth, --min-alt and --min-af are thresholds of --vcf FILE\n"); return 2; }
     if (strand_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-alt-strand is a threshold of --vcf FILE\n"); return 2; }
     if (strands && vcfFile.empty() && pileupFile.empty()) { fprintf(stderr, "bgreat: --strands adds the per-strand counts to --pileup FILE and / or --vcf FILE\n"); return 2; }
-    if (min_link_given && bubblesFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE\n"); return 2; }
+    if (min_link_given && bubblesFile.empty() && phaseFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE and --phase FILE\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -195,6 +204,8 @@ int main(int argc, char** argv) {
     opt.abundance = abundanceFile.empty() ? 0u : 1u;
     if (!gfaFile.empty() && bgr_graph_links_enable(graph, 1) != BGR_OK) die("gfa");   // the run counts unitig abundance and links (the switch is the graph's: bgr_run_options is full)
     if (!bubblesFile.empty() && bgr_graph_bubbles_enable(graph, 1, min_link) != BGR_OK) die("--bubbles");   // (likewise; it implies the counting of links)
+    if (!triplesFile.empty() && bgr_graph_triples_enable(graph, 1) != BGR_OK) die("--triples");   // (likewise: unitig abundance and triples)
+    if (!phaseFile.empty() && bgr_graph_phase_enable(graph, 1, min_link) != BGR_OK) die("--phase");   // (likewise; it implies links, triples and the bubbles)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
     const bgr_variant_strand_params sprm = {vprm.min_depth, vprm.min_alt, vprm.min_af_ppm, min_alt_strand};
@@ -234,6 +245,20 @@ int main(int argc, char** argv) {
         std::vector<bgr_bubble> bubbles(n_bubbles);
         if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--bubbles");
         if (bgr_write_bubbles(bubblesFile.c_str(), graph, bubbles.data(), n_bubbles) != BGR_OK) die("--bubbles");
+    }
+    if (!triplesFile.empty()) {  // (the run's aligners' tables, merged and sorted)
+        uint64_t n_triples = 0;
+        if (bgr_graph_triples(graph, nullptr, 0, &n_triples) != BGR_OK && n_triples == 0) die("--triples");   // (BGR_E_CAPACITY with the number of triples)
+        std::vector<bgr_triple> triples(n_triples);
+        if (n_triples && bgr_graph_triples(graph, triples.data(), n_triples, &n_triples) != BGR_OK) die("--triples");
+        if (bgr_write_triples(triplesFile.c_str(), graph, triples.data(), n_triples) != BGR_OK) die("--triples");
+    }
+    if (!phaseFile.empty()) {  // (the run has joined its bubbles with its triples)
+        uint64_t n_phase = 0;
+        if (bgr_graph_phase(graph, nullptr, 0, &n_phase) != BGR_OK && n_phase == 0) die("--phase");   // (BGR_E_CAPACITY with the number of records)
+        std::vector<bgr_phase> recs(n_phase);
+        if (n_phase && bgr_graph_phase(graph, recs.data(), n_phase, &n_phase) != BGR_OK) die("--phase");
+        if (bgr_write_phase(phaseFile.c_str(), graph, recs.data(), n_phase) != BGR_OK) die("--phase");
     }
     if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");

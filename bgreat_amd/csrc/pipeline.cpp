@@ -1576,9 +1576,16 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     if (counts & bgr::kCountLinks) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountBubbles
+            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountPhase
+                                                  ? "bgr_align_all: phasing (--phase, bgr_graph_phase_enable) joins bubbles and triples, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
+                                                  : counts & bgr::kCountBubbles
                                                   ? "bgr_align_all: bubbles (--bubbles, bgr_graph_bubbles_enable) are called from the link counts, which are for the greedy modes; the rows of exhaustive mode (-b) have another layout"
                                                   : "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
+        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
+    }
+    if (counts & bgr::kCountTriples) {   // the graph's switch (bgr_graph_triples_enable): triples and unitig abundance, defined on the rows of the greedy modes
+        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: triple counting (--triples, bgr_graph_triples_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
         if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     }
     if (opt->abundance) {   // unitig abundance: defined on the rows of the greedy modes; refused before any device work

@@ -277,6 +277,9 @@ int bgr_aligner_sync(bgr_aligner* a);
  * the launch's several-reads-per-wave first pass owns by read or wave number (so not all the ints in use), [1] = 1 if the arena overflowed.
  * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)]. */
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor);
+/* Ints of that arena as the last launch planned it (0 before any launch): a row lies in the arena when results[i][0] + its ints is at most this,
+ * and the counting kernels skip a row that does not. */
+int bgr_aligner_arena_ints(bgr_aligner* a, uint64_t* ints);
 /* What bgr_run_options.gaf writes per read, for a caller that keeps its own reads: over the results of the last bgr_align_device launch of this
  * aligner (greedy or anchors mode; the caller hands the same device reads again, the aligner keeps nothing alive), out[i] for read i: the size of the
  * walk its path spells, where the read starts on the path as GAF counts it (from the other end for a read mapped on its reverse complement), the
@@ -668,6 +671,71 @@ int bgr_graph_bubbles_enable(bgr_graph* g, uint32_t on, uint64_t min_link);
 int bgr_graph_bubbles_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
 int bgr_graph_bubbles(const bgr_graph* g, bgr_bubble* out, uint64_t cap, uint64_t* n);
 int bgr_write_bubbles(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n);
+
+/* Triples: which way INTO a unitig goes with which way OUT of it -- what only a whole read knows, and what neither the links nor the bubbles keep.
+ * A mapped read's row in the greedy modes is [off, id_1 .. id_n] with signed 1-based ids; every three consecutive ids (a, b, c) =
+ * (id_j, id_j+1, id_j+2), j = 1 .. n-2, are one traversal of a triple: a row of n ids gives n - 2.  (a, b, c) and (-c, -b, -a) are one triple read
+ * from the two strands: the canonical form is the one with the smaller tuple (|a|, a < 0, |b|, b < 0, |c|, c < 0), compared lexicographically (the two
+ * always differ: b != -b), and count[canonical triple] += 1 per traversal.  Neither the status nor off enters; a triple in which any id is 0 or beyond
+ * n_unitigs is skipped (INT32_MIN counts as beyond); a row that is not wholly inside the arena is skipped, as the links kernel skips it.  The counts
+ * are exact 64-bit integers and do not depend on batching, routes, streams or devices.
+ * Counted on the device as the links are: off unless enabled; while enabled every greedy / anchors launch of the aligner, through every entry point,
+ * is followed on its stream by one kernel ("bgr_triples_kernel" in bgr_aligner_kernel_times while a slot is free; sixteen lanes per read, behind the
+ * links kernel) that adds the launch's triples to an open-addressed hash table {u64 k0, u64 k1, u64 count} in device memory, k0 = the link key of
+ * (a, b), k1 = |c| << 1 | (c < 0).  The 93-bit key does not fit one compare-and-swap: a slot is claimed word by word, each word by one CAS from 0,
+ * lock-free and without any thread waiting for another (bgreat_amd/csrc/triples_kernels.hip has the insert and why no key lands in two slots).
+ * The table is sized when counting is first enabled, from the graph (one with a host blob, fewer than 2^30 unitigs): a walk glues unitigs only
+ * where they overlap in exactly k-1 characters, so bgr_graph_triples_bound = the sum over the unitigs u of (oriented unitigs that end with u's first
+ * (k-1)-mer) x (oriented unitigs that begin with its last) bounds the distinct canonical triples any rows on the graph can hold
+ * (bgreat_amd/csrc/triples_kernels.h has the argument); the capacity is the power of two that is at least twice that, at least 1024, 24 bytes per
+ * slot: BGR_E_NOMEM, with nothing left allocated, when the device does not have it.  Should an insert find no place all the same, it is counted in
+ * an overflow word, and bgr_aligner_triples / the run return BGR_E_CAPACITY with a message until bgr_aligner_reset_triples.  The internal streams
+ * of overlapped batches add to the same table.  An exhaustive launch on an enabled aligner is refused (BGR_E_ARG); disabling keeps the table; a
+ * launch that fails afterwards may have added part of its rows.  There is one form of the kernel, every traversal an insert in device memory: on a
+ * graph of a handful of triples all adds of a launch meet in a few addresses and serialise (no table in LDS in front, as the links have).
+ * bgr_aligner_triples synchronises and delivers the canonical triples with a count, sorted by the tuple above; *n = their number, always,
+ * BGR_E_CAPACITY when cap is smaller (the call with cap 0 moves two words, not the table) or the table has overflowed; BGR_E_ARG when triples were
+ * never enabled.  bgr_aligner_triples_info: out = {slots of the table, the graph's bound, traversals that found no place, used slots}.
+ * bgr_triple_canonical: the canonical form of (a, b, c) by the code the kernel runs (BGR_E_ARG for an id that is 0 or not below 2^30 in size).
+ * bgr_graph_triples_enable(g, 1) is sticky like bgr_graph_links_enable: every later bgr_align_all on the graph counts unitig abundance and triples
+ * in every aligner of the run; each aligner's used slots are gathered on the host, merged and sorted when the run ends, and bgr_graph_triples
+ * delivers them (BGR_E_ARG when there are none: a failed run, BGR_E_COMPACTION too, leaves no totals).  Exhaustive mode is refused before any device
+ * work.  bgr_write_triples (host code, deterministic bytes; the triples sorted as delivered, ids within the graph) writes "#from via to count" and
+ * one tab-separated line per triple with a count above 0. */
+typedef struct { int32_t from, via, to, reserved; uint64_t count; } bgr_triple;   /* reserved is 0 */
+int bgr_aligner_triples_enable(bgr_aligner* a, uint32_t on);
+int bgr_aligner_triples(bgr_aligner* a, bgr_triple* out, uint64_t cap, uint64_t* n);
+int bgr_aligner_reset_triples(bgr_aligner* a);
+int bgr_aligner_triples_info(bgr_aligner* a, uint64_t out[4]);
+int bgr_triple_canonical(int32_t a, int32_t b, int32_t c, bgr_triple* out);
+int bgr_graph_triples_bound(bgr_graph* g, uint64_t* bound);
+int bgr_graph_triples_enable(bgr_graph* g, uint32_t on);
+int bgr_graph_triples_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_triples(const bgr_graph* g, bgr_triple* out, uint64_t cap, uint64_t* n);
+int bgr_write_triples(const char* path, const bgr_graph* g, const bgr_triple* triples, uint64_t n);
+
+/* Read-backed phasing of neighbouring bubbles.  Two heterozygous sites close together are two bubbles that share a unitig; the reads that cross
+ * both say which alleles go together.  Take bubbles as bgr_graph_bubbles delivers them, each read in both orientations, (s, t, b, c) and
+ * (-t, -s, -b, -c).  Oriented bubbles X and Y are neighbours through m when X's sink is m and Y's source is m; the mate pair through -m is the same
+ * pair and is reported once, in the reading with m > 0.  An oriented id is the source of at most one bubble and the sink of at most one, so the
+ * pairs form chains.  A record: via = m, source = X's source, in[0 .. 1] = X's branches as oriented in this reading in (|id|, id < 0) order,
+ * out[0 .. 1] = Y's branches likewise, sink = Y's sink, count[2 i + j] = the count of the canonical triple of (in[i], m, out[j]) -- n11, n12, n21,
+ * n22.  Every neighbour pair is a record, those no read crosses too; the records are ordered by via.  Everything is integers.
+ * bgr_bubbles_phase: host code (a binary search over the sorted triples per count; a few thousand records at a run's end are no hot path).  The
+ * triples must be canonical and strictly ascending, as bgr_aligner_triples / bgr_graph_triples deliver them, every id non-zero and below 2^30 in
+ * size: BGR_E_ARG otherwise.  *n = the number of records, always; BGR_E_CAPACITY with nothing copied when cap is smaller.
+ * bgr_graph_phase_enable(g, on, min_link) is sticky and implies the triples, bubbles and links switches for the run (BGR_E_ARG for min_link == 0, a
+ * graph without a host blob or with non-ACGT unitig characters -- the bubbles' refusal).  The run's bubbles are called with min_link -- with the
+ * bubbles' own threshold when bgr_graph_bubbles_enable is on as well: a run has one set of bubbles -- and joined with its merged triples behind the
+ * bubbles' end; bgr_graph_phase delivers the records, bgr_graph_bubbles and bgr_graph_triples what they were joined from.
+ * bgr_write_phase (host code, deterministic bytes) writes "#via source in1 in2 out1 out2 sink n11 n12 n21 n22 phase" and one tab-separated line
+ * per record; phase is "cis" when n11 + n22 > n12 + n21, "trans" when it is smaller, "." when they are equal, zero included. */
+typedef struct { int32_t via, source, in[2], out[2], sink, reserved; uint64_t count[4]; } bgr_phase;   /* reserved is 0 */
+int bgr_bubbles_phase(const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_triple* triples, uint64_t n_triples, bgr_phase* out, uint64_t cap, uint64_t* n);
+int bgr_graph_phase_enable(bgr_graph* g, uint32_t on, uint64_t min_link);
+int bgr_graph_phase_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_phase(const bgr_graph* g, bgr_phase* out, uint64_t cap, uint64_t* n);
+int bgr_write_phase(const char* path, const bgr_graph* g, const bgr_phase* records, uint64_t n);
 
 /* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
  * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig

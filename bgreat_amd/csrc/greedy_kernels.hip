@@ -6,6 +6,7 @@
 //   bgr_align_greedy_wide_kernel  the same over two-word overlap keys (graphs with k > 32, or built under test.wide_keys); only the
 //                             position scan and the anchor's key differ, the walk is the same
 #include "device_common.h"
+#include "scan_take_word.h"
 
 namespace bgr {
 namespace {
@@ -362,38 +363,41 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             //        li < ln, unsigned, says that the position is one of the item's AND not below where the item resumes (the lanes below
             //        wrap around; they are off in the item's first step only, so an anchor that has failed is never seen again);
             //   wa, wb = the LDS byte addresses of the dword its window starts in and of the next one.
-            // What a half needs of an item is worked out for all sixteen groups at once, here, and fetched by readlane when the half takes
-            // the item: g_ln -> ln, g_wa = where the item's dword (resume position / 16) lies, were the dwords in base order.
+            // What a half needs of an item is worked out for all sixteen groups at once, here, as ONE word per group (scan_take_word.h: resume
+            // position, positions left, the item's dword counted from the wave's first read word, 16 - resume position % 16), and fetched by
+            // one readlane when the half takes the item; the half's uniforms and the lanes' li, ln, wa, wb all come out of that word.
+            static_assert(RPW == kTakeGroups, "scan_take_word.h counts sixteen groups per wave");
             const bool hi = lane >= 32;
-            const uint32_t g_ln = (g_npos - g_from) << 6;
             // (the lane's two constants are worked out here, once per sixteen items, behind an empty asm that keeps the compiler from
             // hoisting them out of the kernel's loop: they would cost the extension below two registers it does not have)
             uint32_t sl = threadIdx.x;
             asm volatile("" : "+v"(sl));
-            const uint32_t lc = ((sl & 31u) << 6) | (32u - 2u * (sl & 15u));
-            const uint32_t c4 = 4u * ((sl >> 4) & 1u);  // lanes 16-31 of a half start one dword further on
-            // (the address of the group's words, F, worked out again from the lane number: as lds_addr(F) it would be hoisted as well)
-            const uint32_t g_wa = lds_addr(lds + 64 + ktab_words) + (sl / GL) * (W * 8u) + ((g_from >> 4) << 2);
+            // li = lcm + ((16 - resume position % 16) << 6): the lane's position in its half, less 16, and the window's shift
+            const uint32_t lcm = (((sl & 31u) << 6) | (32u - 2u * (sl & 15u))) - (16u << 6);
+            // the wave's first read word (RD, worked out again from the lane number: as lds_addr(RD) it would be hoisted as well); lanes 16-31
+            // of a half start one dword further on
+            const uint32_t c4w = lds_addr(lds + 64 + ktab_words) + (sl >> 6) * (RPW * W * 8u) + 4u * ((sl >> 4) & 1u);
+            const uint32_t g_tw = take_word_pack(g_from, g_npos - g_from, ((sl & 63u) / GL) * (W * 2u) + (g_from >> 4));
             uint32_t li = 0, ln = 0, wa = 0, wb = 0;
             auto take = [&](bool h, uint32_t& hq, uint32_t& hb, uint32_t& hn) {
-                uint32_t s_li = 0, s_ln = 0, s_wa = 0;
+                uint32_t s_res = 16, s_left = 0, s_dw = 0;  // (no item left: the half idles, parked on the wave's first read word)
                 hn = 0;
                 if (pend) {
                     const int at = __ffsll((long long)pend) - 1;
                     pend &= pend - 1;
-                    const uint32_t from = rl32(st, at) & G4_ST_POS_MASK;
-                    s_ln = rl32(g_ln, at);
-                    s_wa = rl32(g_wa, at);
-                    s_li = (from & 15u) << 6;
+                    const uint32_t w = rl32(g_tw, at);
+                    s_res = take_word_res(w);
+                    s_left = take_word_left(w);
+                    s_dw = take_word_dword(w);
                     hq = (uint32_t)at / GL;
-                    hb = from & ~15u;
-                    hn = from + (s_ln >> 6);
+                    hb = take_word_resume(w) & ~15u;
+                    hn = take_word_resume(w) + s_left;
                 }
                 if (hi == h) {
-                    li = lc - s_li;
-                    ln = s_ln;
+                    li = lcm + (s_res << 6);
+                    ln = s_left << 6;
                     // dword d of an item's words, in base order, is dword d ^ 1 in memory: the words start at a multiple of 8 bytes
-                    const uint32_t t = s_wa + c4;
+                    const uint32_t t = c4w + (s_dw << 2);
                     wa = t ^ 4u;
                     wb = (t + 4u) ^ 4u;
                 }

@@ -13,6 +13,7 @@
 
 #include "../../include/bgreat_gpu.h"
 #include "align_kernels.h"
+#include "scan_take_word.h"
 
 namespace bgr {
 
@@ -218,7 +219,10 @@ inline LaunchPlan plan_launch(const PlanGraph& g, const PlanDevice& d, const Pla
     // Greedy mode, first pass: sixteen reads per wave (bgr_align_greedy_multi_kernel, the reference's retry ladder inside the launch)
     // when a read fits one lane per word and the graph has no exception planes; what it does not take (N reads, very long paths)
     // is listed and mapped by the general kernel right behind.
-    const uint32_t wfast = std::min<uint32_t>(words, 16);  // the many-reads-per-wave kernels take reads of < 16 words; longer ones of a mixed batch are listed
+    // the many-reads-per-wave kernels take reads of < 16 words; longer ones of a mixed batch are listed.  (The greedy one's anchor scan packs read
+    // positions and dword indices into fields whose widths stand on this cap and on sixteen reads per wave: scan_take_word.h)
+    static_assert(kG4ReadsPerWave == kTakeGroups, "scan_take_word.h: groups per wave");
+    const uint32_t wfast = std::min<uint32_t>(words, kTakeMaxWords);
     // (a graph with two-word keys has no sixteen-reads-per-wave kernel: bgr_align_greedy_wide_kernel maps every read)
     const bool fast_pass = b.mode == BGR_MODE_GREEDY && !t.no_greedy_fast && !g.has_exc && !g.wide_keys &&
                            geometry(kG4ReadsPerWave * 8 * wfast, (n_reads + kG4ReadsPerWave - 1) / kG4ReadsPerWave, true, true, cfg_fast, d.cap(KernelId::kGreedyMulti),

@@ -54,6 +54,7 @@ KNOB_ABUNDANCE_FORM = 12
 ABUNDANCE_AUTO, ABUNDANCE_GLOBAL, ABUNDANCE_LDS = 0, 1, 2
 KNOB_LINKS_FORM = 13
 LINKS_AUTO, LINKS_GLOBAL, LINKS_LDS = 0, 1, 2
+KNOB_DEVICE_OVERLAP = 14
 SEARCH_AUTO, SEARCH_DEPTH_FIRST, SEARCH_BY_LEVEL = 0, 1, 2
 
 

@@ -27,6 +27,7 @@
 #include "anchor_index.h"
 #include "graph_build.h"
 #include "launch_plan.h"
+#include "launch_taker.h"
 #include "links_kernels.h"
 #include "triples_kernels.h"
 #include "pileup_kernels.h"
@@ -58,6 +59,9 @@ int drain_timers(bgr_aligner* a) {
     a->ev_used = 0;
     return BGR_OK;
 }
+
+// No single launch whose results could be read again (a batch mapped in pieces, a text piece, a batch in flight): bgr_aligner_fetch finds n = 0, on the aligner itself
+void forget_launch(bgr_aligner* a) { a->last_n = 0; a->holder = nullptr; }
 
 }  // namespace
 
@@ -432,6 +436,7 @@ int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value) {
         case BGR_KNOB_BATCH_SPLIT_LIMIT: a->knob_split_limit = value; return BGR_OK;
         case BGR_KNOB_DEBUG_STOP: a->knob_debug_stop = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_BATCH_OVERLAP: a->knob_overlap = (uint32_t)value; return BGR_OK;
+        case BGR_KNOB_DEVICE_OVERLAP: a->knob_device_overlap = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_GREEDY_FAST: if (value > 1) break; a->knob_greedy_fast = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_EXH_FAST: if (value > 1) break; a->knob_exh_fast = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_ANCHORS_FAST: if (value > 1) break; a->knob_anc_fast = (uint32_t)value; return BGR_OK;
@@ -588,6 +593,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts triples (bgr_aligner_triples_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
+    a->holder = nullptr;   // (a launch on the aligner's own stream and buffers; bgr_align_device names the twin behind this call when that took it)
     a->last_n = n_reads;
     a->last_mode = p->mode;
     a->deep.open = false;
@@ -805,9 +811,62 @@ static int settle_launch_sync(bgr_aligner* a) {
     return settle_launch(a, cur);
 }
 
+// The aligner's first n_twins twins (a chain a -> twin -> twin's twin ...), created on first use, each with the aligner's configuration, knobs and
+// counting features as they stand now: its own abundance table (bgr_aligner_abundance sums them), the aligner's tables of links, triples and pileup.
+static int twins_setup(bgr_aligner* a, unsigned n_twins) {
+    bgr_aligner* prev = a;
+    for (unsigned t = 0; t < n_twins; ++t) {
+        if (!prev->twin) {
+            int rc = bgr_aligner_create(a->graph, a->device, &prev->twin);
+            if (rc != BGR_OK) return rc;
+            prev->twin->is_twin = true;
+        }
+        bgr_aligner* tw = prev->twin;
+        tw->cfg_waves = a->cfg_waves; tw->cfg_blocks_per_cu = a->cfg_blocks_per_cu; tw->cfg_lds_mphf = a->cfg_lds_mphf;
+        tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
+        tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
+        tw->knob_abundance_form = a->knob_abundance_form;
+        tw->knob_links_form = a->knob_links_form;
+        if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
+        prev = tw;
+    }
+    pileup_share(a);   // (one pileup table, one table of links and one of triples for the aligner and its twins: the atomics are device-scope)
+    links_share(a);
+    triples_share(a);
+    return BGR_OK;
+}
+
+// true / false: nothing queued or running on the aligner's stream
+static int stream_idle(bgr_aligner* a, bool* idle) {
+    const hipError_t e = hipStreamQuery(a->stream);
+    if (e != hipSuccess && e != hipErrorNotReady) return fail(BGR_E_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+    *idle = e == hipSuccess;
+    return BGR_OK;
+}
+
+// The public form: a greedy / anchors launch that finds the aligner's stream busy -- the caller has not waited for the launch before -- may go to the
+// twin (launch_taker.h), whose workgroups then start on the CU slots that the finished workgroups of the launch before free, instead of behind its last
+// straggler.  Everything inside the library that copies on a->stream around its launch (batch pieces, begin / wait, the packed and the text form) calls
+// align_device_impl and stays on its own stream.  An exhaustive launch stays too: what it has to settle lives in the aligner that launched it.
 int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
                      uint64_t total_bases, uint32_t max_read_len) {
-    return align_device_impl(a, p, d_reads, d_read_offsets, n_reads, total_bases, max_read_len, false);
+    if (!a || !p) return fail(BGR_E_ARG, "bgr_align_device: null argument");
+    bgr_aligner* taker = a;
+    if (!a->is_twin && !a->knob_device_overlap && p->mode != BGR_MODE_EXHAUSTIVE && n_reads) {
+        HIP_TRY(hipSetDevice(a->device));
+        bool primary_idle = true, twin_idle = true;
+        int rc = stream_idle(a, &primary_idle);
+        if (rc == BGR_OK && !primary_idle && a->twin) rc = stream_idle(a->twin, &twin_idle);
+        if (rc != BGR_OK) return rc;
+        if (bgr::launch_taker(primary_idle, twin_idle, a->holder != nullptr) == bgr::Taker::kTwin) {
+            rc = twins_setup(a, 1);
+            if (rc != BGR_OK) return rc;
+            taker = a->twin;
+        }
+    }
+    const int rc = align_device_impl(taker, p, d_reads, d_read_offsets, n_reads, total_bases, max_read_len, false);
+    if (rc == BGR_OK) a->holder = taker == a ? nullptr : taker;
+    return rc;
 }
 
 uint64_t bgr_packed_plane_words(uint64_t n_reads, uint64_t total_bases) { return bgr::packed_plane_words(n_reads, total_bases); }
@@ -843,7 +902,7 @@ int bgr_align_batch_packed(bgr_aligner* a, const bgr_params* p, const bgr_packed
     if (!a || !p || !pk || !path_offsets || (n && (!pk->read_offsets || !pk->fw3 || !pk->hasn || !status))) return fail(BGR_E_ARG, "bgr_align_batch_packed: null argument");
     if (pk->nm_count && (!pk->nm_index || !pk->nm_value)) return fail(BGR_E_ARG, "bgr_align_batch_packed: null N-mask list");
     path_offsets[0] = 0;
-    a->last_n = 0;
+    forget_launch(a);
     if (n == 0) return BGR_OK;
     if (pk->read_offsets[0] != 0) return fail(BGR_E_ARG, "bgr_align_batch_packed: read_offsets must start at 0 (they address the planes)");
     const uint64_t total = pk->read_offsets[n];
@@ -1006,7 +1065,7 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     a->tx_want = b->want_output;
     b->irregular = 0;
     b->n_records = b->n_accepted = b->paths_bytes = b->notaligned_bytes = 0;
-    a->last_n = 0;
+    forget_launch(a);
     a->tx_n_acc = a->tx_pbytes = a->tx_nbytes = 0;
     if (b->text_bytes == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(a->device));
@@ -1077,7 +1136,7 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     // 3. the mapping launch, its reads where they lie in the text (planes by the pre-pass, or -- greedy mode -- staged by the mapping kernels themselves)
     int rc = align_device_impl(a, p, text, a->tx_offs.p, n_acc, bases, max_len, false, a->tx_accsrc.p, nbytes, true);
     if (rc != BGR_OK) return rc;
-    a->last_n = 0;  // (bgr_aligner_fetch has no host read_offsets to pair its rows with: the text form hands out text)
+    forget_launch(a);  // (bgr_aligner_fetch has no host read_offsets to pair its rows with: the text form hands out text)
     a->tx_n_acc = n_acc;
     // Everything behind the mapping launch reads its results.  In exhaustive mode those are final only once the launch is settled (reads the last pass
     // handed back for a larger table are mapped again: settle_launch) -- which hardly ever happens: so the kernels below are enqueued at once, the
@@ -1161,18 +1220,24 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
 int bgr_aligner_sync(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_sync: null aligner");
     HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    return settle_launch_sync(a);  // (exhaustive mode: reads the last pass handed back are mapped before the results count as final)
+    // its own stream and its twins': un-waited bgr_align_device launches may run on the first twin's, and every launch has completed when this returns
+    for (bgr_aligner* x = a; x; x = x->twin) {
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        const int rc = settle_launch_sync(x);  // (exhaustive mode: reads the last pass handed back are mapped before the results count as final)
+        if (rc != BGR_OK) return rc;
+    }
+    return BGR_OK;
 }
 
 int bgr_aligner_arena_ints(bgr_aligner* a, uint64_t* ints) {
     if (!a || !ints) return fail(BGR_E_ARG, "bgr_aligner_arena_ints: null argument");
-    *ints = a->last_arena_cap;
+    *ints = holder_of(a)->last_arena_cap;
     return BGR_OK;
 }
 
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_device_results: null aligner");
+    a = holder_of(a);   // (the buffers of the last launch)
     if (d_results) *d_results = a->results.p;
     if (d_arena) *d_arena = a->arena.p;
     if (d_cursor) *d_cursor = a->small.p;
@@ -1218,6 +1283,7 @@ static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths
 
 int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n, bgr_path_stat* out) {
     if (!a || (n && (!d_reads || !d_read_offsets || !out))) return fail(BGR_E_ARG, "bgr_aligner_path_stats: null argument");
+    a = holder_of(a);   // (the rows of the last launch, on the stream that ran it)
     if (a->graph->header.has_exc)
         return fail(BGR_E_ARG, "bgr_aligner_path_stats: needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
     if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_path_stats: n_reads differs from the last bgr_align_device call");
@@ -1243,6 +1309,7 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
 
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status) {
     if (!a || !path_offsets || !status || (paths_cap && !paths_out)) return fail(BGR_E_ARG, "bgr_aligner_fetch: null argument");
+    a = holder_of(a);   // (the rows of the last launch, on the stream that ran it; a fetch into a larger buffer after BGR_E_CAPACITY finds them there again)
     if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_fetch: n_reads differs from the last bgr_align_device call");
     path_offsets[0] = 0;
     if (n == 0) return BGR_OK;
@@ -1275,7 +1342,7 @@ static int batch_piece_launch(bgr_aligner* a, const bgr_params* p, const char* r
         HIP_TRY(hipMemcpyAsync(a->in_offs.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
         HIP_TRY(hipStreamSynchronize(a->stream));
     }
-    return bgr_align_device(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len);
+    return align_device_impl(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len, false);   // (not the public form: the copies above are on a->stream)
 }
 
 // A large batch in pieces on several streams (this aligner's and its twins', one host thread each): the copies of one piece run under the
@@ -1290,25 +1357,8 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
     n_streams = (unsigned)std::min<int64_t>((int64_t)kOverlapMaxStreams, std::max<int64_t>(2, bgr::opt("overlap_streams")));  // (option overlap_streams: A/B measurements)
     const unsigned n_pieces = 2 * n_streams;
     bgr_aligner* al[kOverlapMaxStreams] = {a, nullptr, nullptr, nullptr};
-    for (unsigned t = 1; t < n_streams; ++t) {  // the twins: a chain a -> twin -> twin's twin ..., created on first use
-        bgr_aligner* prev = al[t - 1];
-        if (!prev->twin) {
-            int rc = bgr_aligner_create(a->graph, a->device, &prev->twin);
-            if (rc != BGR_OK) return rc;
-            prev->twin->is_twin = true;
-        }
-        bgr_aligner* tw = prev->twin;
-        tw->cfg_waves = a->cfg_waves; tw->cfg_blocks_per_cu = a->cfg_blocks_per_cu; tw->cfg_lds_mphf = a->cfg_lds_mphf;
-        tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
-        tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
-        tw->knob_abundance_form = a->knob_abundance_form;
-        tw->knob_links_form = a->knob_links_form;
-        if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
-        al[t] = tw;
-    }
-    pileup_share(a);   // (one pileup table and one table of links for the aligner and its twins: the atomics are device-scope)
-    links_share(a);
-    triples_share(a);
+    { const int rc = twins_setup(a, n_streams - 1); if (rc != BGR_OK) return rc; }
+    for (unsigned t = 1; t < n_streams; ++t) al[t] = al[t - 1]->twin;
     uint64_t cut[kOverlapMaxPieces + 1];
     for (unsigned k = 0; k <= n_pieces; ++k) cut[k] = n * k / n_pieces;
     std::mutex mu;
@@ -1361,7 +1411,7 @@ static int align_batch_overlapped(bgr_aligner* a, const bgr_params* p, const cha
     uint64_t all = 0;
     for (unsigned k = 0; k < n_pieces; ++k) all += totals[k];
     path_offsets[n] = all;
-    a->last_n = 0;  // several launches: bgr_aligner_fetch has nothing to re-read
+    forget_launch(a);  // several launches: bgr_aligner_fetch has nothing to re-read
     return BGR_OK;
 }
 
@@ -1369,7 +1419,7 @@ int bgr_align_batch(bgr_aligner* a, const bgr_params* p, const char* reads, cons
                     int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status) {
     if (!a || !p || !path_offsets || (n && (!reads || !read_offsets || !status))) return fail(BGR_E_ARG, "bgr_align_batch: null argument");
     path_offsets[0] = 0;
-    a->last_n = 0;
+    forget_launch(a);
     if (n == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(a->device));
     const uint64_t base = read_offsets[0], total = read_offsets[n] - base;
@@ -1388,7 +1438,7 @@ int bgr_align_batch(bgr_aligner* a, const bgr_params* p, const char* reads, cons
             w += got;
             i0 = i1;
         }
-        a->last_n = 0;  // several launches: bgr_aligner_fetch has nothing to re-read
+        forget_launch(a);  // several launches: bgr_aligner_fetch has nothing to re-read
         return BGR_OK;
     }
     // a large batch: in pieces on two streams, copies under kernels (BGR_KNOB_BATCH_OVERLAP = 1 turns it off)
@@ -1405,7 +1455,7 @@ int bgr_align_batch_begin(bgr_aligner* a, const bgr_params* p, const char* reads
     ticket->aligner = a;
     ticket->n_reads = n;
     ticket->serial = ++a->ticket_serial;
-    a->last_n = 0;
+    forget_launch(a);
     if (n == 0) { a->ticket_open = true; return BGR_OK; }
     HIP_TRY(hipSetDevice(a->device));
     const uint64_t base = read_offsets[0], total = read_offsets[n] - base;
@@ -1424,7 +1474,7 @@ int bgr_align_batch_begin(bgr_aligner* a, const bgr_params* p, const char* reads
     HIP_TRY(a->in_offs.ensure((n + 1) * 8));
     HIP_TRY(hipMemcpyAsync(a->in_reads.p, reads + base, total, hipMemcpyHostToDevice, a->stream));
     HIP_TRY(hipMemcpyAsync(a->in_offs.p, a->ticket_offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-    const int rc = bgr_align_device(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len);
+    const int rc = align_device_impl(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len, false);   // (not the public form: the copies above are on a->stream)
     if (rc != BGR_OK) return rc;
     a->ticket_open = true;
     return BGR_OK;
@@ -1535,7 +1585,7 @@ int bgr_aligner_reset_kernel_time(bgr_aligner* a) {
 
 int bgr_aligner_launch_info(bgr_aligner* a, uint32_t out[4]) {
     if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_launch_info: null argument");
-    memcpy(out, a->last_launch, sizeof(a->last_launch));
+    memcpy(out, holder_of(a)->last_launch, sizeof(a->last_launch));
     return BGR_OK;
 }
 
@@ -1543,6 +1593,7 @@ int bgr_aligner_launch_info(bgr_aligner* a, uint32_t out[4]) {
 // diagnostic builds only (not part of include/bgreat_gpu.h): the last launch's per-wave time stamps, four u64 per wave (100 MHz ticks)
 int bgr_debug_wave_times(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
     if (!a || !n_waves) return BGR_E_ARG;
+    a = holder_of(a);
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     *n_waves = a->wave_times_n;
@@ -1553,6 +1604,7 @@ int bgr_debug_wave_times(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint
 // the greedy multi kernel's anchor-scan counts per wave of the last launch: {scan steps, items scanned, groups of items, 0}
 int bgr_debug_scan_counts(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
     if (!a || !n_waves) return BGR_E_ARG;
+    a = holder_of(a);
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     *n_waves = a->wave_times_n;
@@ -1564,6 +1616,7 @@ int bgr_debug_scan_counts(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uin
 
 int bgr_aligner_last_pass_runs(const bgr_aligner* a, uint32_t* runs, uint32_t* memo_cap) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_last_pass_runs: null aligner");
+    a = holder_of(a);
     if (runs) *runs = a->deep.runs;
     if (memo_cap) *memo_cap = a->deep.memo_cap;
     return BGR_OK;
@@ -1571,6 +1624,7 @@ int bgr_aligner_last_pass_runs(const bgr_aligner* a, uint32_t* runs, uint32_t* m
 
 int bgr_aligner_pass_counts(bgr_aligner* a, uint32_t out[4]) {
     if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_pass_counts: null argument");
+    a = holder_of(a);   // (the cursor block of the last launch)
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     uint32_t cur[bgr::kCurWords];

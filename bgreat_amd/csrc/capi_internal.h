@@ -195,8 +195,10 @@ struct bgr_aligner {
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
-    bgr_aligner* twin = nullptr;    // second stream + buffers for the overlapped form of bgr_align_batch (created on first use)
+    bgr_aligner* twin = nullptr;    // second stream + buffers: the overlapped form of bgr_align_batch, un-waited consecutive bgr_align_device launches (created on first use)
     bool is_twin = false;
+    uint32_t knob_device_overlap = 0;   // BGR_KNOB_DEVICE_OVERLAP
+    bgr_aligner* holder = nullptr;  // who took this aligner's last mapping launch: null = itself, else its twin (launch_taker.h); "the last launch" is read there
     int num_cus = 0;
     size_t lds_per_cu = 0;
     hipEvent_t ev[kTimerRing][kTimerSlots + 1];  // ev[i][0] = start of launch i, ev[i][j] = behind its j-th kernel
@@ -221,6 +223,10 @@ inline int sync_all(bgr_aligner* a) {
     for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
     return BGR_OK;
 }
+
+// The aligner whose buffers hold the last mapping launch: the aligner itself, or its twin when that took it (bgr_align_device, launch_taker.h).
+inline bgr_aligner* holder_of(bgr_aligner* a) { return a->holder ? a->holder : a; }
+inline const bgr_aligner* holder_of(const bgr_aligner* a) { return a->holder ? a->holder : a; }
 
 // ---- the functions that cross units --------------------------------------------------------------------------------------------
 // capi_abundance.hip

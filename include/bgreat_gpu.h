@@ -265,17 +265,32 @@ int bgr_aligner_fetch_text(bgr_aligner* a, bgr_text_batch* b);
 /* Device-resident form: inputs already in this device's HBM (d_reads bytes, d_read_offsets uint64[n+1]);
  * results stay in aligner-owned device buffers (bgr_aligner_device_results).  Asynchronous on the
  * aligner's stream; max_read_len = longest read in the batch (< 2^24), total_bases = read_offsets[n].
- * Read characters must be from ACGTN (what getReads lets through).                                      */
+ * Read characters must be from ACGTN (what getReads lets through).
+ * Consecutive launches with no wait between them (bgr_aligner_sync, a fetch, counters ...) may run CONCURRENTLY and complete in either order: in
+ * greedy and anchors mode a launch that finds the aligner's stream busy goes to a second stream with a second set of launch buffers (created on
+ * first use), and further un-waited launches take turns between the two, each in order behind the launch that used its buffers before (at most
+ * two in flight side by side; bgreat_amd/csrc/launch_taker.h has the rule).  A launch that finds the aligner idle always uses the aligner's own
+ * stream and buffers, so a caller that waits between its launches sees no difference.  The input buffers of every launch in flight must stay
+ * untouched until it is waited for.  An aligner used this way holds two sets of launch buffers: 4 bytes per arena int (bgr_plan_launch:
+ * arena_ints, about 2 x (bases + 8 x reads) plus 16 ints per read), per read 8 bytes of results and 4 of the list for the second pass, plus the
+ * follow-up rings -- at 5 M x 150 bp 1 661 966 080 arena ints = 6.65 GB, 6.71 GB in all, an eighth more as allocated.  Most of an arena is never
+ * touched (a path has far fewer ints than its read has bases).  BGR_KNOB_DEVICE_OVERLAP 1 turns it off.
+ * Exhaustive launches always stay on the aligner's own stream.  The counting features (abundance, links, triples, pileup) count every launch
+ * once, whichever stream ran it. */
 int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
                      uint64_t total_bases, uint32_t max_read_len);
-/* Waits for the aligner's stream.  In exhaustive mode it also SETTLES the launch: reads whose search outgrew the last pass's table of remembered calls
+/* Waits for the aligner's stream, and for its second one when un-waited bgr_align_device launches went there: every launch has completed when it
+ * returns.  In exhaustive mode it also SETTLES the launch: reads whose search outgrew the last pass's table of remembered calls
  * are mapped again with a larger one (BGR_KNOB_EXH_MEMO_CAP) before the results count as final -- every fetch / counters call does the same; a caller
  * that reads the device results below by itself calls this first. */
 int bgr_aligner_sync(bgr_aligner* a);
 /* Device pointers of the last bgr_align_device results: results uint32[n][2] = {path offset in the arena,
  * path length | status << 24}, arena int32[], cursor u32[2]: [0] = path ints handed out from the part of the arena behind the rows
  * the launch's several-reads-per-wave first pass owns by read or wave number (so not all the ints in use), [1] = 1 if the arena overflowed.
- * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)]. */
+ * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)].
+ * The pointers are those of the LAST launch: behind un-waited consecutive launches (see bgr_align_device) they may differ from those of the launch
+ * before, whose results lie in the other set of buffers until the next launch but one.  Like this call, bgr_aligner_fetch, bgr_aligner_path_stats,
+ * bgr_aligner_arena_ints, bgr_aligner_pass_counts, bgr_aligner_launch_info and bgr_aligner_last_pass_runs describe the last launch. */
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor);
 /* Ints of that arena as the last launch planned it (0 before any launch): a row lies in the arena when results[i][0] + its ints is at most this,
  * and the counting kernels skip a row that does not. */
@@ -479,6 +494,8 @@ int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blo
 #define BGR_KNOB_LINKS_FORM 13u /* the links kernel (bgr_aligner_links_enable): 0 = choose per graph, 1 = form A (every traversal is an insert into the table in device memory), 2 = form B (a table of 2048 links per
                                   workgroup in LDS, flushed once; what finds no place in it goes the way of form A); same counts either way */
 #define BGR_KNOB_GREEDY_FAST 5u /* greedy mode: 0 = sixteen-reads-per-wave pass + general kernel for the rest (default), 1 = general kernel only */
+#define BGR_KNOB_DEVICE_OVERLAP 14u /* consecutive bgr_align_device launches (greedy / anchors mode) that nobody waited for: 0 = they take turns on two streams with two sets of
+                                       launch buffers, so that one starts on the CU slots the one before frees (default), 1 = every launch on the aligner's own stream and buffers */
 int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value);
 /* The launch geometry by itself (bgreat_amd/csrc/launch_plan.h: a pure function of these numbers; no device, no graph object needed -- CPU tests sweep
  * it over synthetic graph headers).  Zero fields of the device part mean "an MI355X" (256 CUs, 160 KB of LDS per CU, the shipped kernels' occupancies).

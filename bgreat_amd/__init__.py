@@ -42,6 +42,7 @@ SYMBOLS = [
     "bgr_aligner_triples_enable", "bgr_aligner_triples", "bgr_aligner_reset_triples", "bgr_aligner_triples_info", "bgr_triple_canonical", "bgr_graph_triples_bound",
     "bgr_graph_triples_enable", "bgr_graph_triples_enabled", "bgr_graph_triples", "bgr_write_triples",
     "bgr_bubbles_phase", "bgr_graph_phase_enable", "bgr_graph_phase_enabled", "bgr_graph_phase", "bgr_write_phase",
+    "bgr_phase_blocks", "bgr_phase_blocks_times", "bgr_graph_blocks_enable", "bgr_graph_blocks_enabled", "bgr_graph_blocks", "bgr_write_blocks",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -128,6 +129,15 @@ class Phase(C.Structure):  # bgr_phase
 
 PHASE_DTYPE = np.dtype([("via", np.int32), ("source", np.int32), ("in", np.int32, (2,)), ("out", np.int32, (2,)), ("sink", np.int32), ("reserved", np.int32),
                         ("count", np.uint64, (4,))])   # an array of bgr_phase
+
+
+class BlockEntry(C.Structure):  # bgr_block_entry
+    _fields_ = [("block", C.c_uint32), ("index", C.c_uint32), ("size", C.c_uint32), ("bubble", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BLOCK_DTYPE = np.dtype([("block", np.uint32), ("index", np.uint32), ("size", np.uint32), ("bubble", np.uint32), ("flags", np.uint32), ("reserved", np.uint32)])   # an array of bgr_block_entry
+BLOCK_REVERSED, BLOCK_HAP, BLOCK_CIRCULAR, BLOCK_CONFLICT = 1, 2, 4, 8
+BLOCKS_TILE = 1024   # BGR_BLOCKS_TILE: nodes per tile of the count and place passes
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -316,6 +326,12 @@ def lib():
     L.bgr_graph_phase_enabled.argtypes = [vp]
     L.bgr_graph_phase.argtypes = [vp, vp, u64, vp]
     L.bgr_write_phase.argtypes = [C.c_char_p, vp, vp, u64]
+    L.bgr_phase_blocks.argtypes = [C.c_int, vp, u64, vp, u64, u64, u64, vp, u64, vp]
+    L.bgr_phase_blocks_times.argtypes = [vp]
+    L.bgr_graph_blocks_enable.argtypes = [vp, u32, u64, u64]
+    L.bgr_graph_blocks_enabled.argtypes = [vp]
+    L.bgr_graph_blocks.argtypes = [vp, vp, u64, vp]
+    L.bgr_write_blocks.argtypes = [C.c_char_p, vp, vp, u64, vp, u64]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -710,6 +726,19 @@ class Graph:
     def phase(self):
         """bgr_graph_phase: the phase records of the last align_all with the switch on -> array of PHASE_DTYPE, ordered by via."""
         return _fetch_records(lambda out, cap, n: lib().bgr_graph_phase(self.h, out, cap, n), PHASE_DTYPE)
+
+    def blocks_enable(self, on=True, min_link=1, min_phase=1):
+        """bgr_graph_blocks_enable: sticky -- every later align_all on this graph does what phase_enable makes it do and chains the decided pairs into
+        haplotype blocks on the device."""
+        _check(lib().bgr_graph_blocks_enable(self.h, int(bool(on)), int(min_link), int(min_phase)))
+
+    def blocks_enabled(self):
+        """bgr_graph_blocks_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_blocks_enabled(self.h))
+
+    def blocks(self):
+        """bgr_graph_blocks: the block entries of the last align_all with the switch on -> array of BLOCK_DTYPE, block after block in chain order."""
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_blocks(self.h, out, cap, n), BLOCK_DTYPE)
 
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
@@ -1231,6 +1260,31 @@ def write_phase(path, graph, records):
     line per record."""
     records = np.ascontiguousarray(records, dtype=PHASE_DTYPE)
     _check(lib().bgr_write_phase(path.encode(), graph.h, records.ctypes.data if len(records) else None, records.shape[0]))
+
+
+def phase_blocks(bubbles, phase, n_unitigs, min_phase=1, device=0):
+    """bgr_phase_blocks: `bubbles` (an array of BUBBLE_DTYPE, as Graph.bubbles() delivers them) and the phase records made from them (PHASE_DTYPE, as
+    bubbles_phase delivers them) chained into haplotype blocks on `device` -> array of BLOCK_DTYPE, one entry per bubble."""
+    assert BLOCK_DTYPE.itemsize == C.sizeof(BlockEntry) == 24
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    phase = np.ascontiguousarray(phase, dtype=PHASE_DTYPE)
+    return _fetch_records(lambda out, cap, n: lib().bgr_phase_blocks(int(device), bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], phase.ctypes.data if len(phase) else None,
+                                                                     phase.shape[0], int(n_unitigs), int(min_phase), out, cap, n), BLOCK_DTYPE)
+
+
+def phase_blocks_times():
+    """bgr_phase_blocks_times: milliseconds of this thread's last phase_blocks -> dict(link, rank, place, total)."""
+    ms = (C.c_double * 4)()
+    _check(lib().bgr_phase_blocks_times(ms))
+    return dict(zip(("link", "rank", "place", "total"), (float(x) for x in ms)))
+
+
+def write_blocks(path, graph, bubbles, entries):
+    """bgr_write_blocks: `entries` (an array of BLOCK_DTYPE) over `bubbles` (BUBBLE_DTYPE) as text -- "#block index size bubble source sink hapA hapB
+    strand ring", one tab-separated line per entry."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
+    _check(lib().bgr_write_blocks(path.encode(), graph.h, bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0]))
 
 
 def _as_links(links):

@@ -1,0 +1,182 @@
+// capi_blocks.hip -- the C-ABI's haplotype blocks (bgr_block_entry in include/bgreat_gpu.h has the definition; blocks_kernels.h the passes): the
+// call on two uploaded lists, the run's entries in the graph object, the writer.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "capi_internal.h"
+#include "blocks_kernels.h"
+
+static thread_local double tl_blocks_ms[4] = {0, 0, 0, 0};   // bgr_phase_blocks_times: the calling thread's last call
+
+// The two lists checked on the host, uploaded to `device` on a stream of its own, chained there; the entries' way to the host: into `vec`, or into
+// `out` when cap has room.  *n = n_bubbles once the lists have passed the host's checks.  The buffers live for the call: whatever happens, nothing
+// stays allocated
+static int blocks_call(int device, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_phase* phase, uint64_t n_phase, uint64_t n_unitigs, uint64_t min_phase, const char* who,
+                       std::vector<bgr_block_entry>* vec, bgr_block_entry* out, uint64_t cap, uint64_t* n) {
+    static_assert(sizeof(bgr_block_entry) == 24, "six 32-bit words");
+    const std::string w = who;
+    *n = 0;
+    for (int i = 0; i < 4; ++i) tl_blocks_ms[i] = 0;
+    if (vec) vec->clear();
+    if (min_phase == 0) return fail(BGR_E_ARG, w + ": min_phase is at least 1");
+    if (n_unitigs >= 0x40000000ull) return fail(BGR_E_ARG, w + ": fewer than 2^30 unitigs");
+    if (device < 0) return fail(BGR_E_ARG, w + ": a negative device");
+    uint64_t bad = 0;
+    if (const int what = bgr::blocks_check(bubbles, n_bubbles, phase, n_phase, n_unitigs, &bad)) {
+        static const char* const msg[] = {"", "bubble %s names an id that is 0, beyond 2^30 or beyond n_unitigs", "bubble %s does not name four unitigs with its branches in (|id|, id < 0) order",
+                                          "bubble %s is not read canonically ((source, sink) against (-sink, -source))", "the bubbles are not strictly ascending by source (bubble %s)",
+                                          "phase record %s names an id that is 0, beyond 2^30 or beyond n_unitigs, or a via that is not positive",
+                                          "the phase records are not strictly ascending by via (record %s)", "%s bubbles: a node index and a flag share a 32-bit word"};
+        std::string m = msg[what];
+        m.replace(m.find("%s"), 2, std::to_string(bad));
+        return fail(BGR_E_ARG, w + ": " + m);
+    }
+    *n = n_bubbles;
+    if (n_bubbles == 0) return BGR_OK;   // (no bubble, no block: no device work)
+    if (!vec && n_bubbles > cap) return fail(BGR_E_CAPACITY, w + ": " + std::to_string(n_bubbles) + " entries, room for " + std::to_string(cap));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(device));
+    struct Res {
+        hipStream_t s = nullptr;
+        DevBuf in_b, in_p, scratch, outbuf;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Res() { in_b.release(); in_p.release(); scratch.release(); outbuf.release(); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (s) (void)hipStreamDestroy(s); }
+    } r;
+    HIP_TRY(hipStreamCreate(&r.s));
+    const uint64_t bytes[4] = {n_bubbles * sizeof(bgr_bubble), n_phase * sizeof(bgr_phase), bgr::blocks_scratch_bytes(n_bubbles, n_unitigs), n_bubbles * sizeof(bgr_block_entry)};
+    DevBuf* const bufs[4] = {&r.in_b, &r.in_p, &r.scratch, &r.outbuf};
+    for (int i = 0; i < 4; ++i) {
+        if (bytes[i] == 0) continue;
+        const hipError_t e = bufs[i]->ensure(bytes[i]);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, w + ": " + std::to_string(bytes[i]) + " bytes on the device for " + std::to_string(n_bubbles) + " bubbles, " +
+                                                                                std::to_string(n_phase) + " phase records and " + std::to_string(n_unitigs) + " unitigs: " + hipGetErrorString(e));
+        }
+    }
+    for (hipEvent_t& e : r.ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(r.in_b.p, bubbles, bytes[0], hipMemcpyHostToDevice, r.s));
+    if (n_phase) HIP_TRY(hipMemcpyAsync(r.in_p.p, phase, bytes[1], hipMemcpyHostToDevice, r.s));
+    const bgr::BlocksScratch sc(r.scratch.p, n_bubbles, n_unitigs);
+    const bgr_bubble* db = static_cast<const bgr_bubble*>(r.in_b.p);
+    HIP_TRY(hipEventRecord(r.ev[0], r.s));
+    hipError_t e = bgr::launch_blocks_link(db, n_bubbles, static_cast<const bgr_phase*>(r.in_p.p), n_phase, n_unitigs, min_phase, r.scratch.p, r.s);
+    if (e != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_index_kernel, bgr_blocks_link_kernel): " + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(r.ev[1], r.s));
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, sc.err, 4, hipMemcpyDeviceToHost, r.s));   // the error word, before anything is chained
+    HIP_TRY(hipStreamSynchronize(r.s));
+    if (err) {
+        const char* m = err & bgr::kBlocksErrId        ? "a record names a unitig outside 1 .. n_unitigs"
+                        : err & bgr::kBlocksErrSource  ? "two bubbles, read both ways, leave one oriented unitig: the list of bubbles is malformed"
+                        : err & bgr::kBlocksErrMissing ? "a decided phase record's source or via opens no bubble of the list"
+                        : err & bgr::kBlocksErrDiffers ? "a decided phase record's in, out or sink are not those of the bubbles it joins"
+                                                       : "two decided phase records leave or enter one bubble";
+        return fail(BGR_E_ARG, w + ": " + m + " (error word " + std::to_string(err) + ")");
+    }
+    if ((e = bgr::launch_blocks_rank(n_bubbles, n_unitigs, r.scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_rank_*_kernel): " + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(r.ev[2], r.s));
+    if ((e = bgr::launch_blocks_count(n_bubbles, n_unitigs, r.scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_heads_kernel): " + hipGetErrorString(e));
+    if ((e = bgr::launch_blocks_place(n_bubbles, n_unitigs, r.scratch.p, static_cast<bgr_block_entry*>(r.outbuf.p), r.s)) != hipSuccess)
+        return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_write_kernel): " + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(r.ev[3], r.s));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, sc.offs_s + bgr::blocks_tiles(n_bubbles), 8, hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(hipMemcpyAsync(&err, sc.err, 4, hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(hipStreamSynchronize(r.s));
+    if (total != n_bubbles || err) return fail(BGR_E_INTERNAL, w + ": " + std::to_string(total) + " entries placed for " + std::to_string(n_bubbles) + " bubbles (error word " + std::to_string(err) + ")");
+    if (vec) { vec->resize(n_bubbles); out = vec->data(); }
+    HIP_TRY(hipMemcpyAsync(out, r.outbuf.p, bytes[3], hipMemcpyDeviceToHost, r.s));   // (only now: a refused list copies nothing)
+    HIP_TRY(hipStreamSynchronize(r.s));
+    for (int i = 0; i < 3; ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, r.ev[i], r.ev[i + 1])); tl_blocks_ms[i] = f; }
+    tl_blocks_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return BGR_OK;
+}
+
+int bgr_phase_blocks(int device, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_phase* phase, uint64_t n_phase, uint64_t n_unitigs, uint64_t min_phase, bgr_block_entry* out,
+                     uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!n || (n_bubbles && !bubbles) || (n_phase && !phase) || (cap && !out)) return fail(BGR_E_ARG, "bgr_phase_blocks: null argument");
+    return blocks_call(device, bubbles, n_bubbles, phase, n_phase, n_unitigs, min_phase, "bgr_phase_blocks", nullptr, out, cap, n);
+}
+
+int bgr_phase_blocks_times(double ms[4]) {
+    if (!ms) return fail(BGR_E_ARG, "bgr_phase_blocks_times: null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = tl_blocks_ms[i];
+    return BGR_OK;
+}
+
+// ---- what a whole run calls (run_counts.h, through capi_abundance.hip) ---------------------------------------------------------------------
+void run_blocks_begin(bgr_graph* g) {
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->blocks.clear();
+    g->blocks_valid = false;
+}
+int run_blocks_end(bgr_graph* g, bool ok) {   // behind run_phase_end: the run's bubbles and phase records uploaded once to the device the bubbles were called on
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->blocks.clear();
+    g->blocks_valid = false;
+    if (!ok) return BGR_OK;
+    int rc = BGR_OK;
+    uint64_t n = 0;
+    if (!g->bubbles_valid || !g->phase_valid) rc = fail(BGR_E_INTERNAL, "bgr_align_all: blocks without the bubbles and the phase records they are chained from");
+    else if (!g->bubbles.empty()) {
+        if (g->bubbles_device < 0) rc = fail(BGR_E_INTERNAL, "bgr_align_all: bubbles, but no aligner of the run was collected");
+        else rc = blocks_call(g->bubbles_device, g->bubbles.data(), g->bubbles.size(), g->phase.data(), g->phase.size(), g->header.n_unitigs, g->blocks_min_phase, "bgr_align_all", &g->blocks,
+                              nullptr, 0, &n);
+    }
+    if (rc != BGR_OK) { g->blocks.clear(); g->blocks.shrink_to_fit(); }
+    g->blocks_valid = rc == BGR_OK;
+    return rc;
+}
+
+int bgr_graph_blocks_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64_t min_phase) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: null graph");
+    if (on) {
+        if (min_link == 0) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: min_link is at least 1");
+        if (min_phase == 0) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: min_phase is at least 1");
+        if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: the graph has no host blob (the tables of links and triples are sized from it)");
+        if (g->header.has_exc)
+            return fail(BGR_E_ARG, "bgr_graph_blocks_enable: blocks (--blocks) chain phased bubbles, which need a graph of ACGT-only unitigs: on one with other characters a branch read backwards does not spell the reverse complement");
+        g->blocks_min_link = min_link;
+        g->blocks_min_phase = min_phase;
+    }
+    g->blocks_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_blocks_enabled(const bgr_graph* g) { return g && g->blocks_on ? 1 : 0; }
+
+int bgr_graph_blocks(const bgr_graph* g, bgr_block_entry* out, uint64_t cap, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_blocks: null argument");
+    if (!g->blocks_valid) return fail(BGR_E_ARG, "bgr_graph_blocks: no entries -- they are those of the last successful bgr_align_all with bgr_graph_blocks_enable on");
+    *n = g->blocks.size();
+    if (g->blocks.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_blocks: " + std::to_string(g->blocks.size()) + " entries, room for " + std::to_string(cap));
+    if (!g->blocks.empty()) memcpy(out, g->blocks.data(), g->blocks.size() * sizeof(bgr_block_entry));
+    return BGR_OK;
+}
+
+int bgr_write_blocks(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n) {
+    if (!path || !g || (n_bubbles && !bubbles) || (n && !entries)) return fail(BGR_E_ARG, "bgr_write_blocks: null argument");
+    const uint64_t nu = g->header.n_unitigs;
+    uint64_t bad = 0;
+    for (uint64_t i = 0; i < n_bubbles; ++i)
+        for (int32_t x : {bubbles[i].source, bubbles[i].sink, bubbles[i].branch[0], bubbles[i].branch[1]})
+            if (!bgr::blocks_id_ok(x, nu)) return fail(BGR_E_ARG, "bgr_write_blocks: bubble " + std::to_string(i) + " names a unitig the graph does not have");
+    if (!bgr::blocks_entries_ok(entries, n, n_bubbles, &bad)) return fail(BGR_E_ARG, "bgr_write_blocks: entry " + std::to_string(bad) + " names no bubble of the list, or is none that bgr_phase_blocks makes");
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string("bgr_write_blocks: cannot open ") + path);
+    std::string buf = bgr::blocks_header();
+    bool ok = true;
+    for (uint64_t i = 0; i < n && ok; ++i) {
+        bgr::blocks_line(entries[i], bubbles[entries[i].bubble], &buf);
+        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
+    }
+    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_blocks: write to ") + path + " failed");
+    return BGR_OK;
+}

@@ -1,5 +1,5 @@
 // capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; capi_abundance.hip,
-// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
+// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
 // waits, and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or leaves the library.
 #ifndef BGREAT_AMD_CAPI_INTERNAL_H
 #define BGREAT_AMD_CAPI_INTERNAL_H
@@ -69,6 +69,11 @@ struct bgr_graph {
     bool phase_on = false, phase_valid = false;
     uint64_t phase_min_link = 1;
     std::vector<bgr_phase> phase;
+    // blocks (bgr_graph_blocks_enable): the sticky switch with the threshold of a decided link, and the threshold the run's bubbles are called with when
+    // neither the bubbles' nor the phase's own switch is on; the entries of the last successful run
+    bool blocks_on = false, blocks_valid = false;
+    uint64_t blocks_min_link = 1, blocks_min_phase = 1;
+    std::vector<bgr_block_entry> blocks;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -245,6 +250,9 @@ int run_triples_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's tabl
 void run_triples_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
 void run_phase_begin(bgr_graph* g);
 int run_phase_end(bgr_graph* g, bool ok);               // ... behind the bubbles' and the triples' end: the run's bubbles joined with its triples on the host
+// capi_blocks.hip
+void run_blocks_begin(bgr_graph* g);
+int run_blocks_end(bgr_graph* g, bool ok);              // ... behind the phase's end: the run's bubbles and phase records uploaded once, chained on the device, the entries kept
 // capi_bubbles.hip
 void run_bubbles_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
 void run_bubbles_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's links will be called,

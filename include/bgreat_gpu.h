@@ -754,6 +754,60 @@ int bgr_graph_phase_enabled(const bgr_graph* g);   /* the switch as it stands: 1
 int bgr_graph_phase(const bgr_graph* g, bgr_phase* out, uint64_t cap, uint64_t* n);
 int bgr_write_phase(const char* path, const bgr_graph* g, const bgr_phase* records, uint64_t n);
 
+/* Haplotype blocks: the phased pairs chained.  A phase file is a list of pairs; a block says which bubbles hang together, in what order, and which
+ * branch of each lies on the haplotype of the first bubble's first branch.  Input: `bubbles` as bgr_graph_bubbles / bgr_links_bubbles deliver them
+ * (sorted, canonical reading), `phase` as bgr_bubbles_phase makes them from exactly these bubbles, and a threshold min_phase >= 1.
+ * Nodes: node 2 i is bubble record i as given, (s, t, b0, b1) with the branches in (|id|, id < 0) order; node 2 i + 1 is its mate
+ * (-t, -s, -b0, -b1); bubble(x) = x >> 1, reversed(x) = x & 1, mate(x) = x ^ 1.
+ * Decided link: a phase record through m joins X (sink m) to Y (source m); it is decided when |(n11 + n22) - (n12 + n21)| >= min_phase (sums
+ * that do not wrap, as in bgr_write_phase), with parity 0 when cis and 1 when trans.  A decided record gives the link X -> Y and the mate link
+ * mate(Y) -> mate(X) with the same parity (its four counts are the transposed matrix: cis stays cis); an undecided record gives no link.  With
+ * min_phase == 1, decided is exactly "the phase file says cis or trans".
+ * Components: every node has at most one successor and one predecessor, so the components are paths and rings.  A component and its mate (every
+ * node mated, the order reversed) are two readings of one block; a component cannot be its own mate (that needs a node equal to its mate, or a
+ * link x -> mate(x), whose via would be its own negative), so every bubble record appears in exactly one reported block, exactly once.
+ * The reading that is reported: the first node of a path is its head, the first node of a ring its smallest node index, and the block is reported
+ * in the reading whose first node is smaller.  A ring is opened at the link that enters its first node, which becomes the head; every entry of it
+ * carries BGR_BLOCK_CIRCULAR, and BGR_BLOCK_CONFLICT as well when the parity of the removed link differs from the haplotype of the ring's last
+ * node: an odd number of trans links around the ring, phasing that contradicts itself.
+ * Haplotype: hap(head) = 0, hap(next(x)) = hap(x) ^ parity(x -> next(x)); branch[hap] of the bubble's record lies on haplotype A, the other on B.
+ * Order: blocks by their first node's index, numbered from 1; within a block the entries in chain order; a bubble with no decided link is a block
+ * of size 1, read as given.  An entry: block (1-based), index (0-based place in the block), size (the block's length), bubble (0-based index into
+ * the list of bubbles), flags.  Everything is integers and the result is deterministic.
+ * bgr_phase_blocks uploads the two lists to `device` and chains them there (bgreat_amd/csrc/blocks_kernels.h has the passes: an index of the
+ * nodes by source, one thread per phase record for the links, pointer jumping towards the heads with the parity carried along, rings opened and
+ * ranked again, then count / scan / place per tile of BGR_BLOCKS_TILE nodes; launches in stream order on one stream, no workgroup waits for
+ * another, no sort, no atomics on the output).  The lists are checked on the host first -- ids not 0, below 2^30 and within n_unitigs, the bubbles
+ * canonical and strictly ascending by source, the phase records strictly ascending by a positive via -- and the links on the device: a source two
+ * nodes share, a record whose bubbles are missing or differ from its in / out / sink, a second link into or out of a node.  All of these are
+ * BGR_E_ARG with a message and nothing copied.  *n is always set; for valid input it equals n_bubbles; BGR_E_CAPACITY with nothing copied when cap
+ * is smaller; n_bubbles == 0 is BGR_OK with *n = 0 and no device work; BGR_E_ARG for min_phase == 0.  The scratch (136 bytes per bubble and 8
+ * per unitig) lives for the call: BGR_E_NOMEM, with nothing left allocated, when the device does not have it.  bgr_phase_blocks_times: the
+ * milliseconds of the calling thread's last call -- index + link, ranking (all rounds), place (events on the call's stream), and the whole call with its
+ * allocations, copies and waits on the host's clock -- zeroes when the last call did no device work.
+ * bgr_graph_blocks_enable(g, on, min_link, min_phase) is sticky and implies the phase switch for the run, with its rule for whose min_link the
+ * run's one set of bubbles is called with (the bubbles' own when bgr_graph_bubbles_enable is on, else the phase's when bgr_graph_phase_enable is
+ * on, else this one) and its refusals, min_phase == 0 too.  When the run ends, its bubbles and phase records are uploaded once to the device of the
+ * first aligner it collected and chained there; bgr_graph_blocks delivers the entries (BGR_E_ARG when there are none: a failed run,
+ * BGR_E_COMPACTION too, leaves none).
+ * bgr_write_blocks (host code, deterministic bytes) writes "#block index size bubble source sink hapA hapB strand ring" and one tab-separated line
+ * per entry: bubble the 1-based line ordinal of the record in the bubbles file of the same run; source, sink, hapA, hapB the signed ids as the
+ * block's reading orients them (for a reversed entry -sink, -source, -branch[hap], -branch[1 - hap]); strand + or -; ring ".", "circular" or
+ * "conflict".  Left for later: spelling the haplotypes' sequences from the blocks. */
+typedef struct { uint32_t block, index, size, bubble; uint32_t flags; uint32_t reserved; } bgr_block_entry;   /* 24 bytes, reserved is 0 */
+#define BGR_BLOCK_REVERSED 1u   /* the bubble is read as its mate */
+#define BGR_BLOCK_HAP      2u   /* branch[1] of the record is on haplotype A */
+#define BGR_BLOCK_CIRCULAR 4u   /* set on every entry of an opened ring */
+#define BGR_BLOCK_CONFLICT 8u   /* likewise */
+#define BGR_BLOCKS_TILE 1024u
+int bgr_phase_blocks(int device, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_phase* phase, uint64_t n_phase, uint64_t n_unitigs,
+                     uint64_t min_phase, bgr_block_entry* out, uint64_t cap, uint64_t* n);
+int bgr_phase_blocks_times(double ms[4]);
+int bgr_graph_blocks_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64_t min_phase);
+int bgr_graph_blocks_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_blocks(const bgr_graph* g, bgr_block_entry* out, uint64_t cap, uint64_t* n);
+int bgr_write_blocks(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n);
+
 /* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
  * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig
  * abundance and the pileup in every aligner of the run; the tables of all aligners and devices are summed (mod 2^32: the differences commute) when

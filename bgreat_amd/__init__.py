@@ -43,6 +43,7 @@ SYMBOLS = [
     "bgr_graph_triples_enable", "bgr_graph_triples_enabled", "bgr_graph_triples", "bgr_write_triples",
     "bgr_bubbles_phase", "bgr_graph_phase_enable", "bgr_graph_phase_enabled", "bgr_graph_phase", "bgr_write_phase",
     "bgr_phase_blocks", "bgr_phase_blocks_times", "bgr_graph_blocks_enable", "bgr_graph_blocks_enabled", "bgr_graph_blocks", "bgr_write_blocks",
+    "bgr_blocks_haplotypes", "bgr_blocks_haplotypes_times", "bgr_graph_haplotypes_enable", "bgr_graph_haplotypes_enabled", "bgr_graph_haplotypes", "bgr_write_haplotypes",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -138,6 +139,13 @@ class BlockEntry(C.Structure):  # bgr_block_entry
 BLOCK_DTYPE = np.dtype([("block", np.uint32), ("index", np.uint32), ("size", np.uint32), ("bubble", np.uint32), ("flags", np.uint32), ("reserved", np.uint32)])   # an array of bgr_block_entry
 BLOCK_REVERSED, BLOCK_HAP, BLOCK_CIRCULAR, BLOCK_CONFLICT = 1, 2, 4, 8
 BLOCKS_TILE = 1024   # BGR_BLOCKS_TILE: nodes per tile of the count and place passes
+
+
+class Haplotype(C.Structure):  # bgr_haplotype
+    _fields_ = [("block", C.c_uint32), ("hap", C.c_uint32), ("size", C.c_uint32), ("flags", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64)]
+
+
+HAPLOTYPE_DTYPE = np.dtype([("block", np.uint32), ("hap", np.uint32), ("size", np.uint32), ("flags", np.uint32), ("offset", np.uint64), ("length", np.uint64)])   # an array of bgr_haplotype
 
 
 class PathStat(C.Structure):  # bgr_path_stat
@@ -332,6 +340,12 @@ def lib():
     L.bgr_graph_blocks_enabled.argtypes = [vp]
     L.bgr_graph_blocks.argtypes = [vp, vp, u64, vp]
     L.bgr_write_blocks.argtypes = [C.c_char_p, vp, vp, u64, vp, u64]
+    L.bgr_blocks_haplotypes.argtypes = [vp, C.c_int, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64, vp, vp]
+    L.bgr_blocks_haplotypes_times.argtypes = [vp]
+    L.bgr_graph_haplotypes_enable.argtypes = [vp, u32, u64, u64, u64]
+    L.bgr_graph_haplotypes_enabled.argtypes = [vp]
+    L.bgr_graph_haplotypes.argtypes = [vp, vp, u64, vp, vp, u64, vp]
+    L.bgr_write_haplotypes.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, u64, vp, u64]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -739,6 +753,20 @@ class Graph:
     def blocks(self):
         """bgr_graph_blocks: the block entries of the last align_all with the switch on -> array of BLOCK_DTYPE, block after block in chain order."""
         return _fetch_records(lambda out, cap, n: lib().bgr_graph_blocks(self.h, out, cap, n), BLOCK_DTYPE)
+
+    def haplotypes_enable(self, on=True, min_link=1, min_phase=1, min_block=1):
+        """bgr_graph_haplotypes_enable: sticky -- every later align_all on this graph does what blocks_enable makes it do and spells the two sequences
+        of every block of at least min_block bubbles on the device."""
+        _check(lib().bgr_graph_haplotypes_enable(self.h, int(bool(on)), int(min_link), int(min_phase), int(min_block)))
+
+    def haplotypes_enabled(self):
+        """bgr_graph_haplotypes_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_haplotypes_enabled(self.h))
+
+    def haplotypes(self):
+        """bgr_graph_haplotypes: the sequences of the last align_all with the switch on -> (array of HAPLOTYPE_DTYPE, block after block, A before B;
+        the characters as one uint8 array the records point into)."""
+        return _fetch_haplotypes(lambda out, cap, n, seq, seq_cap, seq_bytes: lib().bgr_graph_haplotypes(self.h, out, cap, n, seq, seq_cap, seq_bytes))
 
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
@@ -1285,6 +1313,50 @@ def write_blocks(path, graph, bubbles, entries):
     bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
     entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
     _check(lib().bgr_write_blocks(path.encode(), graph.h, bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0]))
+
+
+def _fetch_haplotypes(call):
+    """the two-call form with two buffers: both sizes first (BGR_E_CAPACITY with them), then the records and the characters"""
+    assert HAPLOTYPE_DTYPE.itemsize == C.sizeof(Haplotype) == 32
+    n, nb = C.c_uint64(0), C.c_uint64(0)
+    rc = call(None, 0, C.byref(n), None, 0, C.byref(nb))
+    if rc != -4 or n.value == 0:   # (no sequences, or an error that is not "there are n of them")
+        _check(rc)
+        return np.zeros(0, dtype=HAPLOTYPE_DTYPE), np.zeros(0, dtype=np.uint8)
+    out, seq = np.zeros(n.value, dtype=HAPLOTYPE_DTYPE), np.zeros(nb.value, dtype=np.uint8)
+    _check(call(out.ctypes.data, n.value, C.byref(n), seq.ctypes.data if nb.value else None, nb.value, C.byref(nb)))
+    return out[: n.value], seq[: nb.value]
+
+
+def blocks_haplotypes(graph, bubbles, entries, min_block=1, device=0):
+    """bgr_blocks_haplotypes: the two sequences of every block of at least min_block bubbles, spelled on `device` (where `graph` must be resident) from
+    `bubbles` (BUBBLE_DTYPE, as Graph.bubbles() delivers them) and `entries` (BLOCK_DTYPE, as phase_blocks / Graph.blocks() deliver them for these
+    bubbles) -> (array of HAPLOTYPE_DTYPE, the characters as one uint8 array, the number of bad junctions)."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
+    bad = C.c_uint64(0)
+    recs, seq = _fetch_haplotypes(lambda out, cap, n, sq, seq_cap, seq_bytes: lib().bgr_blocks_haplotypes(
+        graph.h, int(device), bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0], int(min_block), out, cap, n, sq,
+        seq_cap, seq_bytes, C.byref(bad)))
+    return recs, seq, int(bad.value)
+
+
+def blocks_haplotypes_times():
+    """bgr_blocks_haplotypes_times: milliseconds of this thread's last blocks_haplotypes -> dict(items, spell, records, total)."""
+    ms = (C.c_double * 4)()
+    _check(lib().bgr_blocks_haplotypes_times(ms))
+    return dict(zip(("items", "spell", "records", "total"), (float(x) for x in ms)))
+
+
+def write_haplotypes(path, graph, bubbles, entries, records, seq):
+    """bgr_write_haplotypes: per record the line ">block<b>_<A|B> bubbles=<size> length=<L> ring=<.|circular|conflict> walk=<w>" and the sequence on one
+    line; the walk (GAF notation) is built from `entries` (BLOCK_DTYPE) over `bubbles` (BUBBLE_DTYPE)."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
+    records = np.ascontiguousarray(records, dtype=HAPLOTYPE_DTYPE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    _check(lib().bgr_write_haplotypes(path.encode(), graph.h, bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0],
+                                      records.ctypes.data if len(records) else None, records.shape[0], seq.ctypes.data if len(seq) else None, seq.shape[0]))
 
 
 def _as_links(links):

@@ -138,12 +138,14 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
 static uint32_t run_counts_wanted(const bgr_graph* g) {
     if (!g) return 0;
     uint32_t what = 0;
-    const bool phase = g->phase_on || g->blocks_on;   // (the blocks' switch implies the phase's)
+    const bool blocks = g->blocks_on || g->haplotypes_on;   // (the haplotypes' switch implies the blocks')
+    const bool phase = g->phase_on || blocks;   // (the blocks' switch implies the phase's)
     if (g->links_on || g->bubbles_on || phase) what |= bgr::kCountLinks;
     if (g->bubbles_on || phase) what |= bgr::kCountBubbles;
     if (g->triples_on || phase) what |= bgr::kCountTriples;
     if (phase) what |= bgr::kCountPhase;
-    if (g->blocks_on) what |= bgr::kCountBlocks;
+    if (blocks) what |= bgr::kCountBlocks;
+    if (g->haplotypes_on) what |= bgr::kCountHaplotypes;
     if (g->pileup_on || g->variants_on) what |= bgr::kCountPileup;
     if (g->variants_on) what |= bgr::kCountVariants;
     if ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)) what |= bgr::kCountStrands;
@@ -156,6 +158,7 @@ static void run_counts_begin(bgr_graph* g, uint32_t what) {
     if (what & bgr::kCountTriples) run_triples_begin(g);
     if (what & bgr::kCountPhase) run_phase_begin(g);
     if (what & bgr::kCountBlocks) run_blocks_begin(g);
+    if (what & bgr::kCountHaplotypes) run_haplotypes_begin(g);
     if (what & bgr::kCountPileup) run_pileup_begin(g);
 }
 static int run_counts_enable(bgr_aligner* a, uint32_t what) {   // every launch of the aligner is followed by the kernels of what the run counts
@@ -180,11 +183,13 @@ static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) {   // (the mess
     int brc = what & bgr::kCountBubbles ? run_bubbles_end(g, ok) : BGR_OK;   // (behind the links' end: it reads the merged links)
     if (brc == BGR_OK && (what & bgr::kCountPhase)) brc = run_phase_end(g, ok);   // (behind the bubbles' and the triples' end: it joins the two)
     if (what & bgr::kCountBlocks) brc = brc == BGR_OK ? run_blocks_end(g, ok) : (run_blocks_end(g, false), brc);   // (behind the phase's end: it chains the records)
+    if (what & bgr::kCountHaplotypes) brc = brc == BGR_OK ? run_haplotypes_end(g, ok) : (run_haplotypes_end(g, false), brc);   // (behind the blocks' end: it spells the entries)
     if (brc != BGR_OK) {   // (the run has failed after all: it leaves no totals)
         graph_abundance_end(g, false); run_links_end(g, false);
         if (what & bgr::kCountTriples) run_triples_end(g, false);
         if (what & bgr::kCountPhase) (void)run_phase_end(g, false);
         if (what & bgr::kCountBlocks) (void)run_blocks_end(g, false);
+        if (what & bgr::kCountHaplotypes) (void)run_haplotypes_end(g, false);
     }
     const int prc = what & bgr::kCountPileup ? run_pileup_end(g, ok && brc == BGR_OK) : BGR_OK;
     return brc != BGR_OK ? brc : prc;

@@ -121,10 +121,11 @@ int run_blocks_end(bgr_graph* g, bool ok) {   // behind run_phase_end: the run's
     if (!ok) return BGR_OK;
     int rc = BGR_OK;
     uint64_t n = 0;
+    const uint64_t min_phase = g->blocks_on || !g->haplotypes_on ? g->blocks_min_phase : g->haplotypes_min_phase;   // (a run that only spells chains its blocks with the haplotypes' threshold)
     if (!g->bubbles_valid || !g->phase_valid) rc = fail(BGR_E_INTERNAL, "bgr_align_all: blocks without the bubbles and the phase records they are chained from");
     else if (!g->bubbles.empty()) {
         if (g->bubbles_device < 0) rc = fail(BGR_E_INTERNAL, "bgr_align_all: bubbles, but no aligner of the run was collected");
-        else rc = blocks_call(g->bubbles_device, g->bubbles.data(), g->bubbles.size(), g->phase.data(), g->phase.size(), g->header.n_unitigs, g->blocks_min_phase, "bgr_align_all", &g->blocks,
+        else rc = blocks_call(g->bubbles_device, g->bubbles.data(), g->bubbles.size(), g->phase.data(), g->phase.size(), g->header.n_unitigs, min_phase, "bgr_align_all", &g->blocks,
                               nullptr, 0, &n);
     }
     if (rc != BGR_OK) { g->blocks.clear(); g->blocks.shrink_to_fit(); }

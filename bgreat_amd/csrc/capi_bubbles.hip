@@ -119,8 +119,8 @@ int run_bubbles_end(bgr_graph* g, bool ok) {   // behind run_links_end: g->links
     std::lock_guard<std::mutex> l(g->abundance_m);
     g->bubbles.clear();
     g->bubbles_valid = false;
-    // (a run that only phases calls its bubbles with the phase's threshold, one that only chains blocks with the blocks')
-    const uint64_t min_link = g->bubbles_on ? g->bubbles_min_link : (g->phase_on ? g->phase_min_link : (g->blocks_on ? g->blocks_min_link : g->bubbles_min_link));
+    // (a run that only phases calls its bubbles with the phase's threshold, one that only chains blocks with the blocks', one that only spells with the haplotypes')
+    const uint64_t min_link = g->bubbles_on ? g->bubbles_min_link : (g->phase_on ? g->phase_min_link : (g->blocks_on ? g->blocks_min_link : (g->haplotypes_on ? g->haplotypes_min_link : g->bubbles_min_link)));
     g->bubbles_called = min_link;
     if (!ok) return BGR_OK;
     int rc = BGR_OK;

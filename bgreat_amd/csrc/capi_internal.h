@@ -1,5 +1,5 @@
 // capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; capi_abundance.hip,
-// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
+// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
 // waits, and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or leaves the library.
 #ifndef BGREAT_AMD_CAPI_INTERNAL_H
 #define BGREAT_AMD_CAPI_INTERNAL_H
@@ -74,6 +74,12 @@ struct bgr_graph {
     bool blocks_on = false, blocks_valid = false;
     uint64_t blocks_min_link = 1, blocks_min_phase = 1;
     std::vector<bgr_block_entry> blocks;
+    // haplotypes (bgr_graph_haplotypes_enable): the sticky switch with the smallest block that is spelled, and the thresholds the run's bubbles and blocks
+    // are called with when no switch before it in the chain (bubbles, phase, blocks) is on; the records and characters of the last successful run
+    bool haplotypes_on = false, haplotypes_valid = false;
+    uint64_t haplotypes_min_link = 1, haplotypes_min_phase = 1, haplotypes_min_block = 1;
+    std::vector<bgr_haplotype> haplotypes;
+    std::vector<char> haplotypes_seq;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -253,6 +259,9 @@ int run_phase_end(bgr_graph* g, bool ok);               // ... behind the bubble
 // capi_blocks.hip
 void run_blocks_begin(bgr_graph* g);
 int run_blocks_end(bgr_graph* g, bool ok);              // ... behind the phase's end: the run's bubbles and phase records uploaded once, chained on the device, the entries kept
+// capi_haplotypes.hip
+void run_haplotypes_begin(bgr_graph* g);
+int run_haplotypes_end(bgr_graph* g, bool ok);          // ... behind the blocks' end: the run's bubbles and entries uploaded once, spelled from the resident graph, records and bytes kept
 // capi_bubbles.hip
 void run_bubbles_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
 void run_bubbles_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's links will be called,

@@ -48,6 +48,10 @@
 //                                                               joins two bubbles when its cis and trans counts differ by at least N (1); one tab-separated line per
 //                                                               bubble with its block, place, the block's size, the bubble's line in --bubbles, the ids as the block
 //                                                               reads them and whether the block is a ring; counts and calls what --phase does: include/bgreat_gpu.h)
+//                                                   --haplotypes FILE [--min-block N] [--min-phase N] [--min-link N] (the two sequences every block of --blocks stands for, spelled on
+//                                                               the device from the graph's 2-bit store: per sequence a line ">block<b>_<A|B> bubbles= length= ring= walk=" and
+//                                                               the sequence on one line; blocks of fewer than N (1) bubbles are left out; counts, calls and chains what
+//                                                               --blocks does: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -69,7 +73,7 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile, haplotypesFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
     bool vprm_given = false, strands = false, strand_given = false;
@@ -78,6 +82,8 @@ int main(int argc, char** argv) {
     bool min_link_given = false;
     uint64_t min_phase = 1;        // --min-phase
     bool min_phase_given = false;
+    uint64_t min_block = 1;        // --min-block
+    bool min_block_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
@@ -90,6 +96,7 @@ int main(int argc, char** argv) {
                                 {"bubbles", required_argument, nullptr, 1019}, {"min-link", required_argument, nullptr, 1020},
                                 {"triples", required_argument, nullptr, 1021}, {"phase", required_argument, nullptr, 1022},
                                 {"blocks", required_argument, nullptr, 1023}, {"min-phase", required_argument, nullptr, 1024},
+                                {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -174,6 +181,17 @@ int main(int argc, char** argv) {
                 min_phase_given = true;
                 break;
             }
+            case 1025: haplotypesFile = optarg; break;
+            case 1026: {   // a positive integer, digits only
+                const std::string v = optarg;
+                if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stol(v) < 1) {
+                    fprintf(stderr, "bgreat: --min-block takes a positive integer of at most nine digits, not '%s'\n", optarg);
+                    return 2;
+                }
+                min_block = (uint64_t)std::stol(v);
+                min_block_given = true;
+                break;
+            }
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -188,8 +206,9 @@ int main(int argc, char** argv) {
     if (vprm_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-depth, --min-alt and --min-af are thresholds of --vcf FILE\n"); return 2; }
     if (strand_given && vcfFile.empty()) { fprintf(stderr, "bgreat: --min-alt-strand is a threshold of --vcf FILE\n"); return 2; }
     if (strands && vcfFile.empty() && pileupFile.empty()) { fprintf(stderr, "bgreat: --strands adds the per-strand counts to --pileup FILE and / or --vcf FILE\n"); return 2; }
-    if (min_link_given && bubblesFile.empty() && phaseFile.empty() && blocksFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE, --phase FILE and --blocks FILE\n"); return 2; }
-    if (min_phase_given && blocksFile.empty()) { fprintf(stderr, "bgreat: --min-phase is the threshold of --blocks FILE\n"); return 2; }
+    if (min_link_given && bubblesFile.empty() && phaseFile.empty() && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE, --phase FILE, --blocks FILE and --haplotypes FILE\n"); return 2; }
+    if (min_phase_given && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-phase is the threshold of --blocks FILE and --haplotypes FILE\n"); return 2; }
+    if (min_block_given && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-block is the threshold of --haplotypes FILE\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -227,6 +246,7 @@ int main(int argc, char** argv) {
     if (!triplesFile.empty() && bgr_graph_triples_enable(graph, 1) != BGR_OK) die("--triples");   // (likewise: unitig abundance and triples)
     if (!phaseFile.empty() && bgr_graph_phase_enable(graph, 1, min_link) != BGR_OK) die("--phase");   // (likewise; it implies links, triples and the bubbles)
     if (!blocksFile.empty() && bgr_graph_blocks_enable(graph, 1, min_link, min_phase) != BGR_OK) die("--blocks");   // (likewise; it implies what --phase does)
+    if (!haplotypesFile.empty() && bgr_graph_haplotypes_enable(graph, 1, min_link, min_phase, min_block) != BGR_OK) die("--haplotypes");   // (likewise; it implies what --blocks does)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
     const bgr_variant_strand_params sprm = {vprm.min_depth, vprm.min_alt, vprm.min_af_ppm, min_alt_strand};
@@ -290,6 +310,20 @@ int main(int argc, char** argv) {
         std::vector<bgr_block_entry> entries(n_entries);
         if (n_entries && bgr_graph_blocks(graph, entries.data(), n_entries, &n_entries) != BGR_OK) die("--blocks");
         if (bgr_write_blocks(blocksFile.c_str(), graph, bubbles.data(), n_bubbles, entries.data(), n_entries) != BGR_OK) die("--blocks");
+    }
+    if (!haplotypesFile.empty()) {  // (the run has spelled its blocks; the header lines name the walks over the run's bubbles)
+        uint64_t n_bubbles = 0, n_entries = 0, n_haps = 0, seq_bytes = 0;
+        if (bgr_graph_bubbles(graph, nullptr, 0, &n_bubbles) != BGR_OK && n_bubbles == 0) die("--haplotypes");   // (BGR_E_CAPACITY with the number of bubbles)
+        std::vector<bgr_bubble> bubbles(n_bubbles);
+        if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--haplotypes");
+        if (bgr_graph_blocks(graph, nullptr, 0, &n_entries) != BGR_OK && n_entries == 0) die("--haplotypes");
+        std::vector<bgr_block_entry> entries(n_entries);
+        if (n_entries && bgr_graph_blocks(graph, entries.data(), n_entries, &n_entries) != BGR_OK) die("--haplotypes");
+        if (bgr_graph_haplotypes(graph, nullptr, 0, &n_haps, nullptr, 0, &seq_bytes) != BGR_OK && n_haps == 0) die("--haplotypes");
+        std::vector<bgr_haplotype> haps(n_haps);
+        std::vector<char> seq(seq_bytes);
+        if (n_haps && bgr_graph_haplotypes(graph, haps.data(), n_haps, &n_haps, seq.data(), seq_bytes, &seq_bytes) != BGR_OK) die("--haplotypes");
+        if (bgr_write_haplotypes(haplotypesFile.c_str(), graph, bubbles.data(), n_bubbles, entries.data(), n_entries, haps.data(), n_haps, seq.data(), seq_bytes) != BGR_OK) die("--haplotypes");
     }
     if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");

@@ -1576,7 +1576,9 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     if (counts & bgr::kCountLinks) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
         if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountBlocks
+            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountHaplotypes
+                                                  ? "bgr_align_all: the haplotypes' sequences (--haplotypes, bgr_graph_haplotypes_enable) are spelled along phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
+                                                  : counts & bgr::kCountBlocks
                                                   ? "bgr_align_all: haplotype blocks (--blocks, bgr_graph_blocks_enable) chain phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
                                                   : counts & bgr::kCountPhase
                                                   ? "bgr_align_all: phasing (--phase, bgr_graph_phase_enable) joins bubbles and triples, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"

@@ -1,6 +1,6 @@
 // run_counts.h -- how a whole run (pipeline.cpp, host code that knows the device side only through the C-ABI) reaches what the counting
 // features keep: the graph's sticky switches, the aligners' tables on the device and the run's totals in the graph object (unitig abundance,
-// links and their bubbles, triples and the bubbles' phase and blocks, the pileup with its SNV sites and strands: capi_abundance.hip, capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_pileup.hip,
+// links and their bubbles, triples and the bubbles' phase, blocks and haplotypes, the pileup with its SNV sites and strands: capi_abundance.hip, capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip,
 // capi_variants.hip).  One unit of the
 // library (capi_abundance.hip) fills the table below when the library is loaded; pipeline.cpp calls through it, so it needs no symbol beyond
 // the ones it already used -- a build of pipeline.cpp against another implementation of the C-ABI (tests/sanitize_pipeline.cpp,
@@ -13,13 +13,13 @@
 
 namespace bgr {
 
-enum : uint32_t { kCountAbundance = 1, kCountLinks = 2, kCountPileup = 4, kCountVariants = 8, kCountStrands = 16, kCountBubbles = 32, kCountTriples = 64, kCountPhase = 128, kCountBlocks = 256 };   // `what` a run counts
+enum : uint32_t { kCountAbundance = 1, kCountLinks = 2, kCountPileup = 4, kCountVariants = 8, kCountStrands = 16, kCountBubbles = 32, kCountTriples = 64, kCountPhase = 128, kCountBlocks = 256, kCountHaplotypes = 512 };   // `what` a run counts
 struct RunCounts {
-    uint32_t (*wanted)(const bgr_graph* g);                        // the graph's sticky switches as a mask (links, triples and pileup imply abundance, bubbles imply links, phase implies bubbles and triples, blocks imply phase)
+    uint32_t (*wanted)(const bgr_graph* g);                        // the graph's sticky switches as a mask (links, triples and pileup imply abundance, bubbles imply links, phase implies bubbles and triples, blocks imply phase, haplotypes imply blocks)
     void (*begin)(bgr_graph* g, uint32_t what);                    // a new run: the totals of the one before are gone, whatever becomes of this one
     int (*enable)(bgr_aligner* a, uint32_t what);                  // every launch of this aligner counts
     int (*collect)(bgr_graph* g, bgr_aligner* a, uint32_t what);   // the aligner's tables (its streams waited for) join the run's totals: links, triples, pileup (+ variants), abundance, in that order
-    int (*end)(bgr_graph* g, uint32_t what, bool ok);              // totals only of a run that ended well: abundance, links, triples, the bubbles behind the links, the phase behind both, the blocks behind the phase, then the pileup behind the abundance totals (BGR_E_CAPACITY when a depth may have wrapped)
+    int (*end)(bgr_graph* g, uint32_t what, bool ok);              // totals only of a run that ended well: abundance, links, triples, the bubbles behind the links, the phase behind both, the blocks behind the phase, the haplotypes behind the blocks, then the pileup behind the abundance totals (BGR_E_CAPACITY when a depth may have wrapped)
 };
 extern RunCounts g_run_counts;   // pipeline.cpp; all null until the library's C-ABI units have registered
 

@@ -793,7 +793,7 @@ int bgr_write_phase(const char* path, const bgr_graph* g, const bgr_phase* recor
  * bgr_write_blocks (host code, deterministic bytes) writes "#block index size bubble source sink hapA hapB strand ring" and one tab-separated line
  * per entry: bubble the 1-based line ordinal of the record in the bubbles file of the same run; source, sink, hapA, hapB the signed ids as the
  * block's reading orients them (for a reversed entry -sink, -source, -branch[hap], -branch[1 - hap]); strand + or -; ring ".", "circular" or
- * "conflict".  Left for later: spelling the haplotypes' sequences from the blocks. */
+ * "conflict".  Spelling the haplotypes' sequences from the blocks: bgr_haplotype, below. */
 typedef struct { uint32_t block, index, size, bubble; uint32_t flags; uint32_t reserved; } bgr_block_entry;   /* 24 bytes, reserved is 0 */
 #define BGR_BLOCK_REVERSED 1u   /* the bubble is read as its mate */
 #define BGR_BLOCK_HAP      2u   /* branch[1] of the record is on haplotype A */
@@ -807,6 +807,57 @@ int bgr_graph_blocks_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64
 int bgr_graph_blocks_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
 int bgr_graph_blocks(const bgr_graph* g, bgr_block_entry* out, uint64_t cap, uint64_t* n);
 int bgr_write_blocks(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n);
+
+/* The haplotypes' sequences: the two sequences every block stands for, spelled on the device from the graph's 2-bit store (every unitig lies there
+ * in both strands, so an oriented unitig is a base offset and a length, and nothing is ever reversed).
+ * Input: `bubbles` as bgr_graph_bubbles delivers them; `entries` as bgr_phase_blocks / bgr_graph_blocks deliver them for exactly these bubbles,
+ * block after block, chain order inside a block; the graph's k; a threshold min_block >= 1.
+ * Oriented ids of an entry (the ones bgr_write_blocks prints): (src, snk, a, b) = (source, sink, branch[hap], branch[1 - hap]) of the bubble's
+ * record, with BGR_BLOCK_REVERSED (-sink, -source, -branch[hap], -branch[1 - hap]); hap = (flags >> 1) & 1.
+ * Walks: a block with the entries e_0 .. e_{n-1} has two walks of 2 n + 1 oriented unitigs, walk_A = src_0, a_0, snk_0, a_1, snk_1, .., a_{n-1},
+ * snk_{n-1}, and walk_B the same with b_i in the place of a_i.  snk_i == src_{i+1} must hold -- that is what a decided link is; entries for which
+ * it does not, entries that are not block after block in chain order, and what bgr_write_blocks refuses are BGR_E_ARG, checked on the host with
+ * nothing copied.
+ * Spelling: the oriented unitig w_0 goes in whole, every later w_j without its first k - 1 characters; a negative id is the reverse complement.
+ * Length = the sum of the 2 n + 1 lengths - 2 n (k - 1).
+ * Rings: an opened ring is spelled as the linear walk it was opened into: its first and last unitig are the same one.  The ring flags travel into
+ * the record and the header line; a `conflict` ring is spelled all the same.
+ * Junctions: junction j >= 1 of a walk is good when the last k - 1 characters of oriented w_{j-1} equal the first k - 1 of oriented w_j.  On lists
+ * that come from a run every junction is good (a path glues unitigs only where they overlap in exactly k - 1); on arbitrary lists the spelling is
+ * still defined as above, and the call delivers the number of bad junctions over all kept sequences (2 n per sequence are looked at) as one
+ * 64-bit count.
+ * Kept blocks and order: blocks with size >= min_block are kept; the sequences come in block order, A before B; a sequence's ordinal counts kept
+ * blocks only.  A record: block (the entries' number), hap (0 = A, 1 = B), size, flags (the ring bits only), and offset, length into one byte
+ * buffer of ACGT characters, the sequences back to back.  Everything is integers and the bytes are deterministic.
+ * bgr_blocks_haplotypes uploads the two lists to `device`, where the graph must be resident (bgr_graph_device_blob non-NULL: BGR_E_ARG otherwise),
+ * and spells there (bgreat_amd/csrc/haplotypes_kernels.h has the passes: one thread per (entry, hap) for the pieces, lengths and junctions, a
+ * 64-bit scan, the spelling assigned by output in aligned 16-byte stores, the records; launches in stream order on one stream, no workgroup waits
+ * for another, no atomics on the output).  BGR_E_ARG too for a graph with exception planes (non-ACGT unitig characters), min_block == 0, malformed
+ * lists and ids outside the graph.  *n, *seq_bytes and *bad_junctions are always set for valid input; when cap < *n or seq_cap < *seq_bytes the call
+ * returns BGR_E_CAPACITY with nothing copied, and only the first two passes have run: the sizing call is cheap.  n_entries == 0 is BGR_OK with
+ * zeroes and no device work.  The scratch (128 bytes per entry) and the output live on the device for the call: BGR_E_NOMEM, with nothing left
+ * allocated, when it lacks them.  bgr_blocks_haplotypes_times: the milliseconds of the calling thread's last call -- items + scan, spell, records
+ * (events on the call's stream; the one in front of the spell launch is recorded behind the sizing copies, the wait and the allocations of the
+ * output, so the spell stage is the kernel alone), and the whole call with its allocations, copies and waits on the host's clock -- zeroes when the
+ * last call did no device work (a sizing call reports its first stage and the whole).
+ * bgr_graph_haplotypes_enable(g, on, min_link, min_phase, min_block) is sticky and implies the blocks switch for the run, with its rules for the
+ * thresholds and its refusals, min_block == 0 too.  When the run ends, its bubbles and entries are spelled once on the device of the first aligner
+ * it collected; bgr_graph_haplotypes delivers the records and bytes of the last successful run (BGR_E_ARG when there are none: a failed run,
+ * BGR_E_COMPACTION too, leaves none; BGR_E_CAPACITY with both sizes and nothing copied when either capacity is smaller).  A run whose spelling
+ * finds a bad junction fails with BGR_E_INTERNAL.
+ * bgr_write_haplotypes (host code, deterministic bytes) writes per record the line
+ *   >block<b>_<A|B> bubbles=<size> length=<L> ring=<.|circular|conflict> walk=<w>
+ * and the sequence on one line; w is the walk in GAF notation (">12<7>9": > forward, < reverse complement, unitig ids from 1), built from the
+ * entries and the bubbles on the host.  Records that are not those of the entries' kept blocks, back to back in seq_bytes bytes, are BGR_E_ARG. */
+typedef struct { uint32_t block, hap, size, flags; uint64_t offset, length; } bgr_haplotype;   /* 32 bytes */
+int bgr_blocks_haplotypes(const bgr_graph* g, int device, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n_entries,
+                          uint64_t min_block, bgr_haplotype* out, uint64_t cap, uint64_t* n, char* seq, uint64_t seq_cap, uint64_t* seq_bytes, uint64_t* bad_junctions);
+int bgr_blocks_haplotypes_times(double ms[4]);
+int bgr_graph_haplotypes_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64_t min_phase, uint64_t min_block);
+int bgr_graph_haplotypes_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_haplotypes(const bgr_graph* g, bgr_haplotype* out, uint64_t cap, uint64_t* n, char* seq, uint64_t seq_cap, uint64_t* seq_bytes);
+int bgr_write_haplotypes(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n_entries,
+                         const bgr_haplotype* haps, uint64_t n, const char* seq, uint64_t seq_bytes);
 
 /* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
  * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig

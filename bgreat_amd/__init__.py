@@ -24,7 +24,7 @@ BUILD_NO_EVICTIONS = 2  # test hook: keys whose two buckets are full go to the f
 # every symbol include/bgreat_gpu.h declares (checked by tests/test_cabi.py)
 SYMBOLS = [
     "bgr_last_error", "bgr_device_count", "bgr_graph_build", "bgr_graph_build_from_fasta", "bgr_graph_blob",
-    "bgr_graph_from_blob", "bgr_graph_info", "bgr_graph_destroy", "bgr_graph_upload", "bgr_graph_device_blob",
+    "bgr_graph_from_blob", "bgr_graph_info", "bgr_graph_jump_index", "bgr_graph_destroy", "bgr_graph_upload", "bgr_graph_device_blob",
     "bgr_graph_adopt_device_blob", "bgr_aligner_create", "bgr_aligner_destroy", "bgr_align_batch", "bgr_align_device", "bgr_aligner_path_stats",
     "bgr_aligner_sync", "bgr_aligner_device_results", "bgr_aligner_arena_ints", "bgr_aligner_fetch", "bgr_aligner_counters",
     "bgr_aligner_reset_counters", "bgr_aligner_kernel_time", "bgr_aligner_reset_kernel_time", "bgr_aligner_launch_info",
@@ -57,6 +57,9 @@ ABUNDANCE_AUTO, ABUNDANCE_GLOBAL, ABUNDANCE_LDS = 0, 1, 2
 KNOB_LINKS_FORM = 13
 LINKS_AUTO, LINKS_GLOBAL, LINKS_LDS = 0, 1, 2
 KNOB_DEVICE_OVERLAP = 14
+KNOB_GREEDY_JUMP = 15
+JUMP_ABSENT = ("", "two-word overlap keys", "unitig bases outside ACGT", "key table not staged in LDS", "index beyond the cache cap",
+               "an interior (k-1)-mer of a unitig is an overlap key, or built with build_jump = 0")
 SEARCH_AUTO, SEARCH_DEPTH_FIRST, SEARCH_BY_LEVEL = 0, 1, 2
 
 
@@ -176,7 +179,8 @@ class GraphInfo(C.Structure):
                 ("n_left_keys", C.c_uint64), ("n_right_keys", C.c_uint64), ("n_fallback", C.c_uint64),
                 ("total_bases", C.c_uint64), ("blob_bytes", C.c_uint64), ("mphf_bytes", C.c_uint64),
                 ("max_unitig_len", C.c_uint64), ("has_exceptions", C.c_uint32), ("has_anchors", C.c_uint32),
-                ("gamma", C.c_double)]
+                ("gamma", C.c_double), ("jump_entries", C.c_uint64), ("jump_bytes", C.c_uint64), ("jump_stride", C.c_uint32), ("jump_absent", C.c_uint32),
+                ("jump_dropped_x1000", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 _lib = None
@@ -579,10 +583,30 @@ class Graph:
         v._owner = self   # the bytes belong to the graph: keep it alive as long as the view (or a view of it) is
         return v
 
+    def jump_index(self):
+        """The jump index of the greedy anchor scan as uint32[buckets, 4] (two entries {id | flags, offset << 8 | tag} per bucket), or None.
+        It is not part of blob()."""
+        n = C.c_uint64()
+        lib().bgr_graph_jump_index.restype = C.c_void_p
+        lib().bgr_graph_jump_index.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        p = lib().bgr_graph_jump_index(self.h, C.byref(n))
+        if not p:
+            return None
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n.value // 16, 4)).copy()
+
     def info(self):
         gi = GraphInfo()
         _check(lib().bgr_graph_info(self.h, C.byref(gi)))
-        return {f[0]: getattr(gi, f[0]) for f in GraphInfo._fields_ if f[0] != "reserved"}
+        return {f[0]: getattr(gi, f[0]) for f in GraphInfo._fields_ if f[0] != "reserved" and not f[0].startswith("jump_")}
+
+    def jump_info(self):
+        """The jump index of the greedy anchor scan (it lies behind the blob, so info() -- which describes the blob -- leaves it out): entries,
+        bytes, sampling stride, drop rate x 1000, and why the graph has none (jump_absent: BGR_JUMP_*, jump_absent_why: in words, "" when it has one)."""
+        gi = GraphInfo()
+        _check(lib().bgr_graph_info(self.h, C.byref(gi)))
+        d = {f[0]: getattr(gi, f[0]) for f in GraphInfo._fields_ if f[0].startswith("jump_")}
+        d["jump_absent_why"] = JUMP_ABSENT[gi.jump_absent]
+        return d
 
     def upload(self, device=0):
         _check(lib().bgr_graph_upload(self.h, device))

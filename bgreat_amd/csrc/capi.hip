@@ -113,6 +113,10 @@ int bgr_graph_build_ex(uint32_t k, uint64_t n_unitigs, const char* seqs, const u
         return fail(BGR_E_ARG, err);
     }
     g->header = *g->host.header();
+    if (g->host.jump_buckets) {  // (the graph object's header copy describes the device image: the blob's own header stays as it was)
+        g->header.off_jump = g->host.jump_off; g->header.jump_entries = g->host.jump_entries; g->header.jump_buckets = g->host.jump_buckets;
+        g->header.jump_stride = g->host.jump_stride; g->header.jump_dropped_x1000 = g->host.jump_dropped_x1000;
+    }
     const uint64_t nu = g->header.n_unitigs;  // loading stopped at the first short sequence
     g->ascii.assign(seqs + (nu ? offsets[0] : 0), seqs + (nu ? offsets[nu] : 0));
     g->ascii_offs.resize(nu + 1);
@@ -194,7 +198,16 @@ int bgr_graph_info(const bgr_graph* g, bgr_graph_info_t* o) {
     o->n_left_keys = h.n_left_keys; o->n_right_keys = h.n_right_keys; o->n_fallback = h.n_fallback;
     o->total_bases = h.total_bases; o->blob_bytes = h.blob_bytes; o->mphf_bytes = h.n_buckets * 4;
     o->max_unitig_len = h.max_unitig_len; o->has_exceptions = h.has_exc; o->has_anchors = h.anc_n ? 1 : 0; o->gamma = h.gamma;
+    o->jump_entries = h.jump_entries; o->jump_bytes = h.jump_buckets * 2 * sizeof(BgrJumpEntry); o->jump_stride = h.jump_stride;
+    o->jump_absent = bgr::jump_absent_reason(&h);
+    o->jump_dropped_x1000 = h.jump_dropped_x1000;
     return BGR_OK;
+}
+
+const void* bgr_graph_jump_index(const bgr_graph* g, uint64_t* bytes) {
+    const bool have = g && !g->host.blob.empty() && g->host.jump_buckets;
+    if (bytes) *bytes = have ? g->host.jump_buckets * 2 * sizeof(BgrJumpEntry) : 0;
+    return have ? g->host.base() + g->host.jump_off : nullptr;
 }
 
 void bgr_graph_destroy(bgr_graph* g) {
@@ -214,8 +227,12 @@ int bgr_graph_upload(bgr_graph* g, int device) {
     if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_upload: graph has no host blob (adopted graphs live on one device)");
     HIP_TRY(hipSetDevice(device));
     void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, g->header.blob_bytes));
-    hipError_t e = hipMemcpy(p, g->host.blob.data(), g->header.blob_bytes, hipMemcpyHostToDevice);
+    // (a graph with a jump index: the section behind the blob goes along, and the device copy's header gets its four fields)
+    const uint64_t image = g->host.image_bytes();
+    HIP_TRY(hipMalloc(&p, image));
+    hipError_t e = hipMemcpy(p, g->host.blob.data(), image, hipMemcpyHostToDevice);
+    if (e == hipSuccess && g->host.jump_buckets)
+        e = hipMemcpy(static_cast<char*>(p) + offsetof(BgrBlobHeader, off_jump), &g->header.off_jump, sizeof(BgrBlobHeader) - offsetof(BgrBlobHeader, off_jump), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (from pageable memory on the null stream; the aligners' streams are non-blocking: the blob is there before any of them starts)
     if (e != hipSuccess) { (void)hipFree(p); return fail(BGR_E_HIP, std::string("blob H2D: ") + hipGetErrorString(e)); }
     g->dev[device] = {p, true};
@@ -321,7 +338,7 @@ int bgr_devices_init(bgr_graph* g, int first_device, uint32_t n_devices, uint32_
     if (first_device < 0 || (uint64_t)first_device + n_devices > (uint64_t)nd) return fail(BGR_E_ARG, "bgr_devices_init: device range outside the visible devices");
     int rc = bgr_graph_upload(g, first_device);  // host -> first device (idempotent)
     if (rc != BGR_OK) return rc;
-    const uint64_t bytes = g->header.blob_bytes;
+    const uint64_t bytes = g->host.image_bytes();  // (the device image: the blob and, behind it, the jump index)
     bgr::FanoutOps ops;
     ops.alloc = [bytes](int dev, void** out) { return hipSetDevice(dev) == hipSuccess && hipMalloc(out, bytes) == hipSuccess; };
     ops.release = [](int dev, void* p) { if (p && hipSetDevice(dev) == hipSuccess) (void)hipFree(p); };
@@ -441,6 +458,7 @@ int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value) {
         case BGR_KNOB_EXH_FAST: if (value > 1) break; a->knob_exh_fast = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_ANCHORS_FAST: if (value > 1) break; a->knob_anc_fast = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_GREEDY_PREPASS: if (value > 1) break; a->knob_prepass = (uint32_t)value; return BGR_OK;
+        case BGR_KNOB_GREEDY_JUMP: if (value > 1) break; a->knob_no_jump = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_no_jump = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_KERNEL_EVENTS: if (value > 1) break; a->knob_no_events = value ? 0u : 1u; return BGR_OK;
         case BGR_KNOB_ABUNDANCE_FORM: if (value > 2) break; a->knob_abundance_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_abundance_form = (uint32_t)value; return BGR_OK;
         case BGR_KNOB_LINKS_FORM: if (value > 2) break; a->knob_links_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_links_form = (uint32_t)value; return BGR_OK;
@@ -723,7 +741,12 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
             a->wave_times_n = waves;
         }
 #endif
-        e = bgr::launch_align(ps.kernel, ps.variant, dgl, pio, kp, ps.cfg, a->stream);
+        // the staged sixteen-reads-per-wave greedy kernel jumps over verified unitig interiors when the graph has the index for it (graph_layout.h):
+        // a flag says so, and the kernel finds the section through the blob's header (BgrDeviceGraph must not grow: the kernel is short of
+        // SGPRs).  No other kernel is told.  BGR_KNOB_GREEDY_JUMP 1: not this one either.
+        BgrDeviceGraph dgp = dgl;
+        if (ps.kernel == bgr::KernelId::kGreedyMulti && ps.cfg.stage_mphf && a->graph->header.jump_buckets && !a->knob_no_jump) dgp.flags |= BGR_GF_JUMP;
+        e = bgr::launch_align(ps.kernel, ps.variant, dgp, pio, kp, ps.cfg, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (") + ps.name + "): " + hipGetErrorString(e));
         HIP_TRY(mark(ps.name));
         if (ps.kernel == bgr::KernelId::kExhaustiveLast) {  // what settle_launch needs to run the last pass again for the reads it handed back
@@ -824,7 +847,7 @@ static int twins_setup(bgr_aligner* a, unsigned n_twins) {
         bgr_aligner* tw = prev->twin;
         tw->cfg_waves = a->cfg_waves; tw->cfg_blocks_per_cu = a->cfg_blocks_per_cu; tw->cfg_lds_mphf = a->cfg_lds_mphf;
         tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
-        tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events;
+        tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events; tw->knob_no_jump = a->knob_no_jump;
         tw->knob_abundance_form = a->knob_abundance_form;
         tw->knob_links_form = a->knob_links_form;
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }

@@ -183,6 +183,7 @@ struct bgr_aligner {
     // bgr_aligner_set_knob (test / diagnostic hooks, read here instead of from the environment on every launch)
     uint32_t knob_frame_cap = 0, knob_search = 0, knob_debug_stop = 0, knob_greedy_fast = 0, knob_exh_fast = 0, knob_anc_fast = 0, knob_memo_cap = 0, knob_prepass = 0, knob_no_events = 0;
     uint64_t knob_split_limit = 0;
+    uint32_t knob_no_jump = 0;      // BGR_KNOB_GREEDY_JUMP
     uint32_t knob_overlap = 0;      // BGR_KNOB_BATCH_OVERLAP
     uint32_t knob_abundance_form = 0;  // BGR_KNOB_ABUNDANCE_FORM
     bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel

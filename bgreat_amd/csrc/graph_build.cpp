@@ -16,6 +16,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -238,6 +239,10 @@ bool validate_blob_header(const BgrBlobHeader* h, uint64_t bytes, std::string& e
         const uint64_t plane_words = (h->total_bases + 63) / 64 + 2;
         if (!inside(h->off_exc, plane_words, 8) || !inside(h->off_excn, plane_words, 8)) { err = "blob exception planes outside the blob"; return false; }
     }
+    if (h->jump_buckets) {  // the jump index: staged one-word graphs without exception bases; its bucket count is a 32-bit number in the kernel
+        if (h->wide_keys || h->has_exc || h->bloom_bits || h->jump_buckets > 0xFFFFFFFFull || h->jump_stride == 0 || h->jump_entries > 2 * h->jump_buckets) { err = "corrupt blob header (jump index)"; return false; }
+        if (!inside(h->off_jump, h->jump_buckets, 2 * sizeof(BgrJumpEntry))) { err = "blob section outside the blob"; return false; }
+    } else if (h->off_jump || h->jump_entries || h->jump_stride) { err = "corrupt blob header (jump index)"; return false; }
     if (h->anc_n) {
         if (!inside(h->off_anc_bits, h->anc_words, 8) || !inside(h->off_anc_ranks, h->anc_rank_words, 8) ||
             (h->anc_n_final && !inside(h->off_anc_final, h->anc_n_final, 16)) || !inside(h->off_anc_pos, h->anc_n, 8)) { err = "blob section outside the blob"; return false; }
@@ -316,6 +321,18 @@ bool read_unitig_fasta(const std::string& path, uint32_t k, std::vector<char>& s
 
 // LDS a CU has for key table copies next to 16 waves of sixteen 150-bp reads each (160 KB - 64, 512 B fixed per workgroup, 768 B per wave)
 static const double kStageTwice = (163776.0 / 2 - 512 - 16 * 768), kStageOnce = (163776.0 - 512 - 16 * 768);
+
+// why a graph has no jump index (BGR_JUMP_* of bgreat_gpu.h), from its header alone: a blob without the section is the same bytes whatever the
+// reason was, so the reason is worked out again here, in the builder's order (the cap from the sums the header keeps: the builder's own count)
+uint32_t jump_absent_reason(const BgrBlobHeader* h) {
+    if (h->jump_buckets) return 0;
+    if (h->wide_keys) return 1;
+    if (h->has_exc) return 2;
+    if (h->bloom_bits || (double)h->n_buckets * 4.0 > kStageTwice) return 3;
+    const uint64_t fwd = h->total_bases / 2, k1s = h->n_unitigs * (uint64_t)(h->k - 1);
+    if (((fwd > k1s ? fwd - k1s : 0) + h->n_unitigs + BGR_JUMP_STRIDE - 1) / BGR_JUMP_STRIDE * 2 * sizeof(BgrJumpEntry) > BGR_JUMP_CAP_BYTES) return 4;
+    return 5;
+}
 
 static void sort_keys(std::vector<uint64_t>& v, unsigned T) { parallel_sort(v, T); }
 static void sort_keys(std::vector<u128>& v, unsigned) { std::sort(v.begin(), v.end()); }
@@ -516,6 +533,15 @@ static bool build_graph_t(uint32_t k, uint64_t n_in, const char* seqs, const uin
     if (slots_bound >= BGR_HNONE - 8) { err = "too many unitigs for the slot handles (limit 2^27-8)"; return false; }
     off = align256(off + slots_bound * sizeof(BgrSlot));
     h.blob_bytes = off;
+    // the jump index (graph_layout.h) goes behind the slots, once property P has been checked against the finished key table; the blob is
+    // allocated for it here.  One bucket of two entries per sampled (k-1)-mer (as many as the sampling rate lets expect).  No index: two-word keys, exception bases, a key table that is
+    // not staged in LDS (the kernel that jumps is the staged one), an index beyond the cap, build_jump = 0.
+    uint64_t jump_nb = 0;
+    if (!kWide && opt("build_jump") && !has_exc && !large_table && !h.bloom_bits && !keys.empty()) {
+        jump_nb = (sum - n * K1 + n + BGR_JUMP_STRIDE - 1) / BGR_JUMP_STRIDE;  // one in BGR_JUMP_STRIDE of the (k-1)-mers of all forward strands
+        if (jump_nb * 2 * sizeof(BgrJumpEntry) > BGR_JUMP_CAP_BYTES) jump_nb = 0;
+    }
+    off += align256(jump_nb * 2 * sizeof(BgrJumpEntry));
 
     if (!out.blob.reset(off / 8)) { err = "out of memory for the graph blob"; return false; }  // zero pages, touched below in parallel
     uint8_t* base = reinterpret_cast<uint8_t*>(out.blob.data());
@@ -729,6 +755,56 @@ static bool build_graph_t(uint32_t k, uint64_t n_in, const char* seqs, const uin
         dense.release();
     }
     tm.lap("slots");
+
+    if constexpr (!kWide) if (jump_nb) {  // ---- jump index (graph_layout.h) ----
+        // property P: no interior (k-1)-mer of a unitig is an overlap key (arbitrary unitig sets can break it: then there is no index)
+        std::atomic<bool> p_fails{false};
+        parallel_ranges(T, n, [&](uint64_t b, uint64_t e, unsigned) {
+            for (uint64_t i = b + 1; i <= e; ++i) {
+                if (p_fails.load(std::memory_order_relaxed)) return;
+                const BgrUnitigMeta& m = mout[i];
+                for (uint32_t t = 1; t + K1 < m.len; ++t) {
+                    const uint64_t x = window(seq, m.F + t, K1), rc = bgr_rcb(x, K1);
+                    if (lookup_key<uint64_t>(hp, base, std::min(x, rc)) != BGR_NONE) { p_fails.store(true); return; }
+                }
+            }
+        });
+        tm.lap("jump_P");
+        if (!p_fails.load()) {
+            // filled by one thread in unitig order: the index does not depend on the thread count
+            BgrBlobHeader* hw = reinterpret_cast<BgrBlobHeader*>(base);
+            const uint64_t off_jump = hw->blob_bytes;
+            BgrJumpEntry* je = reinterpret_cast<BgrJumpEntry*>(base + off_jump);
+            const uint64_t drop_nth = (uint64_t)opt("test.jump_drop");
+            uint64_t seen = 0, wanted = 0, placed = 0;
+            for (uint64_t i = 1; i <= n; ++i) {
+                const BgrUnitigMeta& m = mout[i];
+                for (uint32_t t = 0; t + K1 <= m.len && t <= BGR_JUMP_MAX_T; ++t) {
+                    const uint64_t x = window(seq, m.F + t, K1), rc = bgr_rcb(x, K1);
+                    const uint64_t mx = bgr_mix64(std::min(x, rc));
+                    if (!bgr_jump_selects(mx) || x == rc) continue;  // (a palindrome says nothing about the strand)
+                    ++wanted;
+                    if (drop_nth && ++seen % drop_nth == 0) continue;
+                    BgrJumpEntry* e2 = je + 2 * (uint64_t)bgr_tab_bucket((uint32_t)mx, (uint32_t)jump_nb);
+                    if (e2[0].t_tag && e2[1].t_tag) continue;  // bucket full: dropped
+                    BgrJumpEntry& en = e2[0].t_tag ? e2[1] : e2[0];
+                    en.idc = (uint32_t)i | (x < rc ? BGR_JUMP_FWD_CANON : 0u);
+                    en.t_tag = t << 8 | bgr_tab_fp(mx);
+                    ++placed;
+                }
+            }
+            if (placed) {  // (behind the blob proper, outside blob_bytes: graph_build.h, HostGraph)
+                out.jump_off = off_jump;
+                out.jump_entries = placed;
+                out.jump_buckets = jump_nb;
+                out.jump_stride = BGR_JUMP_STRIDE;
+                out.jump_dropped_x1000 = (uint32_t)(1000 * (wanted - placed) / wanted);
+                static_assert(offsetof(BgrBlobHeader, off_jump) == 1096 && sizeof(BgrBlobHeader) == 1128, "the header's jump fields lie behind everything a blob of this version had");
+            }
+            if (opt("timing")) fprintf(stderr, "[build] jump index: %llu of %llu sampled (k-1)-mers placed, %llu buckets\n", (unsigned long long)placed, (unsigned long long)wanted, (unsigned long long)jump_nb);
+        } else if (opt("timing")) fprintf(stderr, "[build] jump index: none (an interior (k-1)-mer of a unitig is an overlap key)\n");
+        tm.lap("jump");
+    }
 
     if (h.anc_n) {  // aligner.cpp:465-476: anchorsPosition[lookup(canon)] = {i, j} in unitig order, i.e. the LAST one wins
         memcpy(base + h.off_anc_bits, anc.bits.data(), anc.bits.size() * 8);

@@ -31,6 +31,12 @@ private:
 
 struct HostGraph {
     ZeroPages blob;  // page-aligned storage; header at blob[0]
+    // The jump index (graph_layout.h), when the graph has one: it lies in the same storage, right behind the blob proper (at jump_off >=
+    // header()->blob_bytes), and is NOT part of bytes(): the blob a caller sees, saves or broadcasts is byte for byte what it always was.
+    // An upload copies it along and sets the four header fields of the device copy (device_image_bytes, patch below).
+    uint64_t jump_off = 0, jump_buckets = 0, jump_entries = 0;
+    uint32_t jump_stride = 0, jump_dropped_x1000 = 0;
+    uint64_t image_bytes() const { return jump_buckets ? jump_off + jump_buckets * 2 * sizeof(BgrJumpEntry) : bytes(); }  // what a device copy holds
     const BgrBlobHeader* header() const { return reinterpret_cast<const BgrBlobHeader*>(blob.data()); }
     uint64_t bytes() const { return header()->blob_bytes; }
     const uint8_t* base() const { return reinterpret_cast<const uint8_t*>(blob.data()); }
@@ -62,6 +68,9 @@ uint32_t host_lookup_wide(const BgrBlobHeader* h, const uint8_t* base, uint64_t 
 
 // Fill a BgrDeviceGraph whose pointers are `base` + section offsets (base may be a device address).
 void resolve_device_graph(const BgrBlobHeader* h, const void* base, BgrDeviceGraph& dg);
+
+// Why the graph has no jump index (graph_layout.h): a BGR_JUMP_* code of bgreat_gpu.h, 0 when it has one.
+uint32_t jump_absent_reason(const BgrBlobHeader* h);
 
 // A blob is trusted only after this: magic/version, every section inside `bytes` (overflow-checked), the MPHF level table
 // tiling the unit array, key counts consistent.  validate_blob_header needs the header only (a blob that lives in HBM).

@@ -167,13 +167,45 @@ typedef struct {
     uint64_t anc_active_levels;  // levels 0 .. anc_active_levels-1 hold set bits; the rest are all zero and cannot answer
     uint64_t off_anc_bits, off_anc_ranks, off_anc_final, off_anc_pos;
     BgrAncLevel anc_levels[BGR_ANC_LEVELS];
+    // jump index (all zero when the graph has none; behind everything else, where the header was zero before: see below)
+    uint64_t off_jump;       // jump_buckets buckets of two BgrJumpEntry each
+    uint64_t jump_entries;   // entries that found a place
+    uint64_t jump_buckets;
+    uint32_t jump_stride;    // one (k-1)-mer in jump_stride is sampled (bgr_jump_selects)
+    uint32_t jump_dropped_x1000;  // 1000 x the share of the sampled (k-1)-mers that found their bucket full (informational)
 } BgrBlobHeader;
+
+// ---- jump index (optional; staged one-word graphs without exception bases) ---------------------------------------------------
+// Property P: no (k-1)-mer at an interior offset 0 < t < len - (k-1) of any unitig, on either strand, is a key of the overlap key table
+// (true for the unitigs of a compacted de Bruijn graph, checked at build time for whatever the caller hands in).  Under P a read that
+// equals a unitig on some diagonal has its overlap keys exactly where the diagonal passes the unitig's ends, so ONE lookup that names the
+// unitig and the offset, plus a compare of the read with `seq`, settles all windows of the compared stretch (greedy_kernels.hip, the jump).
+// The index is a HINT -- everything it says is verified against `seq` -- and therefore lossy: a hash table over a SAMPLE of the (k-1)-mers of
+// every forward strand, keyed by the canonical (k-1)-mer through m = bgr_mix64 (the scan's hash).  The sample is chosen by the hash itself: one
+// (k-1)-mer in BGR_JUMP_STRIDE, those with bgr_jump_selects(m) (palindromes left out) -- so a read knows, without touching memory, which of its
+// windows can be in the index at all, and probes ONE of them per item (sampling every 4th offset instead costs four probes per item, each its own
+// cache line of a table far larger than the L2: measured, the probes then cost most of what the jump saves).  bucket = mulhi32(low word of m,
+// jump_buckets), tag = bgr_tab_fp(m).  A bucket is 16 bytes = two entries, one load per probe; an entry that finds its bucket full is dropped
+// (one bucket per sampled (k-1)-mer on average: about one in ten), and so is one whose offset does not fit its field.
+typedef struct {
+    uint32_t idc;     // unitig id | BGR_JUMP_FWD_CANON when the forward window is its own canonical form
+    uint32_t t_tag;   // t << 8 | tag (1..255); 0 = empty entry
+} BgrJumpEntry;       // 8 B
+#define BGR_JUMP_FWD_CANON 0x40000000u
+#define BGR_JUMP_MAX_T 0x00FFFFFFu
+#define BGR_JUMP_STRIDE 4u     /* a power of two */
+#define BGR_JUMP_WINDOWS 3u    /* the kernel hashes the first 4 x BGR_JUMP_WINDOWS windows of an item for one that is sampled (12: 97 in 100 have one) */
+// the index must stay resident in the device's last-level cache next to the rest of the graph and the reads in flight: a quarter of the
+// MI355X's 256 MiB Infinity Cache.  (E. coli scale: 18 MB.  The chr1-scale graph would need 900 MB -- its key table is not staged anyway.)
+#define BGR_JUMP_CAP_BYTES (64ull << 20)
 
 // What a kernel receives by value (pointers resolved against the device copy of the blob).  Kept small on
 // purpose: everything here lives in SGPRs for the whole kernel; what only rare paths need (exception planes,
 // fallback list, level table) is reached through `hdr`, the blob header in HBM.
 #define BGR_GF_HAS_EXC 1u
 #define BGR_GF_HAS_FALLBACK 2u
+#define BGR_GF_JUMP 4u  // the launch may use the blob's jump index (set for the staged sixteen-reads-per-wave greedy launch alone, capi.hip); the
+                        // kernel reaches the section through `hdr`: this struct must not grow, its fields live in SGPRs
 typedef struct {
     const uint32_t* table;   // n_buckets dwords: 4 one-byte fingerprints each (slot s = byte s), 0 = empty
     const BgrKeyEntry* keys; // n_keys entries
@@ -238,6 +270,7 @@ BGR_HD uint32_t bgr_mmx_of_key(uint64_t key, uint32_t K1) {  // key: K1 bases, r
 BGR_HD uint32_t bgr_mmx_block(uint32_t mh, uint32_t shift) { return (mh * 0x85EBCA6Bu) >> shift; }  // 2^(32 - shift) blocks
 BGR_HD uint32_t bgr_mmx_word(uint64_t m) { return (uint32_t)(m >> 8) & 15u; }                       // m = bgr_mix64(key)
 BGR_HD uint32_t bgr_mmx_bits(uint64_t m) { return (1u << ((uint32_t)(m >> 12) & 31u)) | (1u << ((uint32_t)(m >> 17) & 31u)); }
+BGR_HD bool bgr_jump_selects(uint64_t m) { return (((uint32_t)(m >> 40)) & (BGR_JUMP_STRIDE - 1u)) == 0; }  // (bits the bucket and the tag do not use)
 BGR_HD uint32_t bgr_tab_fp(uint64_t m) { const uint32_t f = (uint32_t)(m >> 32) & 0xFFu; return f ? f : 1u; }
 // bit 7 of every byte of x that is zero (exact: no borrow between bytes)
 BGR_HD uint32_t bgr_zero_bytes(uint32_t x) { return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }

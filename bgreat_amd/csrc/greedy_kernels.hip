@@ -225,6 +225,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
     const unsigned long long wt0 = wall_clock64();
     unsigned long long wt2 = 0;
     uint32_t dbg_steps = 0, dbg_items = 0, dbg_groups = 0;  // tools/scan_steps.py: scan steps, items scanned, groups of items taken
+    uint32_t dbg_jumped = 0, dbg_raised = 0;                // items the jump settled without a scan step, items whose resume position it raised
 #endif
     uint32_t ktab_words;
     const uint32_t* ktab = block_prologue<STAGE>(g, lds, &ktab_words);
@@ -346,10 +347,129 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             // still looks up 64 (k-1)-mers.
             // Per half, all uniform: the item's group hq, the step's first position hb and the item's npos hn (0: the half is idle).
             // `pend`: bit GL q = group q's item is still to be scanned (an item with nothing left to scan never gets there: no anchor).
-            const uint32_t g_from = st & G4_ST_POS_MASK;  // where the group's item resumes: the first position it may report
+            uint32_t g_from = st & G4_ST_POS_MASK;  // where the group's item resumes: the first position it may report
             uint32_t g_npos = L >= K1 ? L - K1 + 1 : 0;
             if (!prm.effort && g_npos > 1) g_npos = 1;
-            u64 pend = __ballot(act != 0 && sub == 0 && g_from < g_npos);
+            uint32_t to_scan = (act != 0 && g_from < g_npos) ? 1u : 0u;
+            // The jump (graph_layout.h, jump index): most positions a scan looks up are interior (k-1)-mers of the unitig the read lies on, and
+            // under property P none of those is a key.  For all sixteen items at once: the four lanes of an item hash the item's first
+            // 4 x BGR_JUMP_WINDOWS windows and the first window whose hash selects it (one in BGR_JUMP_STRIDE does, and only those are in the index)
+            // is probed -- ONE load per item; a hit names a unitig and an offset, i.e. a diagonal; the lanes compare the read with `seq` along it,
+            // from the resume position to the first mismatch (or the end of either).  Every window of that stretch is the unitig's own, so it
+            // is a key exactly where the diagonal passes a unitig end: the item's anchor -- or the fact that it has none -- is arithmetic, and an
+            // item the stretch does not settle resumes its scan behind it.  The index is only a hint: nothing is concluded from what was not
+            // compared, and an item without a hit (or whose stretch starts behind its resume position) is scanned as it always was.
+#ifdef BGR_PHASE_TIMING
+            if ((g.flags & BGR_GF_JUMP) && prm.debug_stop != 1) {  // (1 = stops behind the staging of the reads)
+#else
+            if (g.flags & BGR_GF_JUMP) {
+#endif
+                // (where the index and `meta` lie is read from the blob's header here, once per sixteen items, three scalar loads: as kernel
+                // arguments they would stay in SGPRs through the scan and the walks, which have none to spare)
+                const BgrBlobHeader* jh = g.hdr;
+                asm volatile("" : "+s"(jh));
+                const uint4* jtab = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(jh) + jh->off_jump);
+                const BgrUnitigMeta* jmeta = reinterpret_cast<const BgrUnitigMeta*>(reinterpret_cast<const char*>(jh) + jh->off_meta);
+                const uint32_t jnb = (uint32_t)jh->jump_buckets;
+                // lane `sub` looks at the positions g_from + sub + 4 j; my_rel: its first selected window, counted from g_from (none: 255), with
+                // the window's tag in bits 8-15 and "it is its own canonical form" in bit 31; my_bk: its bucket
+                uint32_t my_rel = 255u, my_bk = 0;
+#pragma unroll 1
+                for (uint32_t rel = sub; rel < GL * BGR_JUMP_WINDOWS; rel += GL) {
+                    if (to_scan && my_rel == 255u && g_from + rel < g_npos) {
+                        const u64 num = lds_win32(F, g_from + rel) >> (64 - 2 * K1);
+                        const u64 rcn = rcb_fast(num, K1);
+                        const u64 mx = bgr_mix64(num < rcn ? num : rcn);
+                        if (bgr_jump_selects(mx) && num != rcn) {
+                            my_rel = rel | (bgr_tab_fp(mx) << 8) | (num < rcn ? 0x80000000u : 0u);
+                            my_bk = __umulhi((uint32_t)mx, jnb);
+                        }
+                    }
+                }
+                uint32_t w_sub = my_rel & 255u;  // the quad's first selected window: its lane probes
+                { const uint32_t o = quad_xor1(w_sub); w_sub = o < w_sub ? o : w_sub; }
+                { const uint32_t o = quad_xor2(w_sub); w_sub = o < w_sub ? o : w_sub; }
+                uint32_t w_idc = 0, w_tt = 0;  // the entry; bit 31 of w_idc: the read's window is its own canonical form
+                if ((my_rel & 255u) == w_sub && w_sub != 255u) {
+                    const uint4 b = jtab[my_bk];
+                    const uint32_t tag = (my_rel >> 8) & 0xFFu;
+                    if ((b.y & 0xFFu) == tag) { w_idc = b.x; w_tt = b.y; }
+                    else if ((b.w & 0xFFu) == tag) { w_idc = b.z; w_tt = b.w; }
+                    if (w_tt) w_idc = (w_idc & 0x7FFFFFFFu) | (my_rel & 0x80000000u);
+                    else w_idc = 0;
+                }
+                w_tt |= quad_xor1(w_tt); w_tt |= quad_xor2(w_tt);      // (one lane of the quad holds it: into all four)
+                w_idc |= quad_xor1(w_idc); w_idc |= quad_xor2(w_idc);
+                // the diagonal: the read on strand rcs of the unitig (0: forward, 1: the copy at F + len), its base g_from at offset u0 of that strand
+                uint32_t live = 0, ulen = 0, rcs = 0, u0 = 0, rb = 0, re = 0, mfl = 0, hi_p = 0;
+                uint32_t sw = 0, ss = 0;  // base g_from of the read lies at bit ss of seq word sw (the store stays below 2^32 bytes)
+                if (w_tt) {
+                    const BgrUnitigMeta* mp = jmeta + (w_idc & BGR_SLOT_ID_MASK);
+                    const uint4 m0 = *reinterpret_cast<const uint4*>(mp);  // len, flags, rec_beg, rec_end
+                    const u64 Fm = mp->F;
+                    ulen = m0.x; mfl = m0.y; rb = m0.z; re = m0.w;
+                    const uint32_t t = w_tt >> 8;
+                    rcs = ((w_idc >> 31) ^ (w_idc >> 30)) & 1u;
+                    if (t + K1 <= ulen) {
+                        const uint32_t u = rcs ? ulen - K1 - t : t;  // the probed window's offset on that strand
+                        if (u >= w_sub) {                            // the stretch starts at the resume position (else: the plain scan)
+                            u0 = u - w_sub;
+                            const u64 sbase = Fm + (rcs ? ulen : 0u) + u0;
+                            sw = (uint32_t)(sbase >> 5);
+                            ss = 2u * ((uint32_t)sbase & 31u);
+                            const uint32_t room = ulen - u0;         // bases of the unitig from u0 on
+                            hi_p = L - g_from < room ? L : g_from + room;
+                            live = 1;
+                        }
+                    }
+                }
+                // compare: lane `sub` takes the 64-base chunks sub, sub + 4, ... of [g_from, hi_p) -- three words of either side, two windows --
+                // so reads of up to 256 bases behind g_from take one round; e = the first mismatch, or hi_p.  The third word is read only when
+                // the chunk's second half is needed: the read's row and `seq` hold it then (scan_take_word.h: a row has a word to spare;
+                // the store ends in two pad words).
+                uint32_t e = hi_p;
+                const uint32_t fs = 2u * (g_from & 31u);
+                for (uint32_t c0 = 0; __any(live != 0 && g_from + 64u * c0 < hi_p); c0 += GL) {
+                    const uint32_t rp = g_from + 64u * (c0 + sub);
+                    if (live && rp < hi_p) {
+                        const bool two = rp + 32u < hi_p;
+                        const u64* fp = F + (rp >> 5);
+                        const u64* sp = g.seq + sw + 2u * (c0 + sub);
+                        const u64 f0 = fp[0], f1 = fp[1], f2 = two ? fp[2] : 0;
+                        const u64 s0 = sp[0], s1 = sp[1], s2 = two ? sp[2] : 0;
+                        const u64 xa = ((f0 << fs) | ((f1 >> 1) >> (63 - fs))) ^ ((s0 << ss) | ((s1 >> 1) >> (63 - ss)));
+                        const u64 xb = two ? ((f1 << fs) | ((f2 >> 1) >> (63 - fs))) ^ ((s1 << ss) | ((s2 >> 1) >> (63 - ss))) : 0;
+                        const uint32_t q = xa ? rp + ((uint32_t)__builtin_clzll(xa) >> 1) : xb ? rp + 32u + ((uint32_t)__builtin_clzll(xb) >> 1) : e;
+                        e = q < e ? q : e;
+                    }
+                }
+                { const uint32_t o = quad_xor1(e); e = o < e ? o : e; }
+                { const uint32_t o = quad_xor2(e); e = o < e ? o : e; }
+                const int32_t last = (int32_t)e - (int32_t)K1;  // the last window of the compared stretch
+                uint32_t jumped = 0, raised = 0;
+                if (live && last >= (int32_t)g_from) {
+                    // windows g_from .. last are the strand's (k-1)-mers u0 .. u0 + last - g_from: keys at offset 0 and at ulen - (k-1), nowhere else
+                    const uint32_t p1 = g_from + (ulen - K1 - u0);
+                    uint32_t found = 0, at_end = 0;
+                    if (u0 == 0) found = 1;
+                    else if ((int32_t)p1 <= last && p1 < g_npos) { found = 1; at_end = 1; }
+                    if (found) {
+                        a_pos = at_end ? p1 : g_from;
+                        // strand offset 0 is the unitig's beg forward and rc(end) on the other strand; the far end the other way round
+                        const uint32_t cbit = at_end ? (rcs ? BGR_META_CANON_RCBEG : BGR_META_CANON_END) : (rcs ? BGR_META_CANON_RCEND : BGR_META_CANON_BEG);
+                        a_rec = ((at_end ^ rcs) ? re : rb) | ((mfl & cbit) ? G4_CANON : 0u);
+                        to_scan = 0;
+                        jumped = 1;
+                    } else if (last >= (int32_t)g_npos - 1) { to_scan = 0; jumped = 1; }  // every position compared, no end passed: no anchor
+                    else { g_from = (uint32_t)last + 1; raised = 1; }
+                }
+#ifdef BGR_PHASE_TIMING
+                dbg_jumped += (uint32_t)__popcll(__ballot(jumped != 0 && sub == 0));
+                dbg_raised += (uint32_t)__popcll(__ballot(raised != 0 && sub == 0));
+#endif
+                (void)jumped; (void)raised;
+            }
+            u64 pend = __ballot(to_scan != 0 && sub == 0);
 #ifdef BGR_PHASE_TIMING
             if (prm.debug_stop == 1) pend = 0;  // 1 = stops behind the staging of the reads
             dbg_items += (uint32_t)__popcll(pend);
@@ -608,7 +728,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         w[0] = wt0; w[1] = wt1; w[2] = wt2; w[3] = wall_clock64();
         // behind the time stamps of all waves: the wave's scan counts (two-scanner instances; 0 steps for the others)
         unsigned long long* c = io.wave_times + 4ull * (gridDim.x * waves) + 4ull * (blockIdx.x * waves + wave);
-        c[0] = dbg_steps; c[1] = dbg_items; c[2] = dbg_groups; c[3] = 0;
+        c[0] = dbg_steps; c[1] = dbg_items; c[2] = dbg_groups; c[3] = (unsigned long long)dbg_jumped | ((unsigned long long)dbg_raised << 32);
     }
 #endif
     __syncthreads();

@@ -30,6 +30,8 @@ inline Option* option_table(size_t* n) {
         {"huge_pinned", {1}, 0, 1, "bgr_host_alloc: buffers of 2 MB and more from huge-page mappings registered with the runtime"},
         {"exh_filter", {1}, 0, 1, "exhaustive mode probes large key tables through the minimizer filter"},
         {"build_filter", {-1}, -1, 2, "index build: filter in front of the key table: -1 by table size, 0 none, 1 one hash, 2 minimizer-blocked (forced onto small graphs by tests)"},
+        {"build_jump", {1}, 0, 1, "index build: the jump index of the greedy anchor scan (graph_layout.h) where a graph qualifies: 1 = build it, 0 = none"},
+        {"test.jump_drop", {0}, 0, INT64_MAX, "test hook: index build: every N-th sampled (k-1)-mer is left out of the jump index (the index is a hint: results must not change)"},
         {"poison_device_buffers", {0}, 0, 1, "diagnostic: every new device buffer is filled with a pattern (a kernel that reads what nothing wrote shows in any run)"},
         {"test.bases_cap", {0}, 0, INT64_MAX, "test hook: bases per batch of bgr_align_all (walks the cut of large batches with small inputs)"},
         {"test.lanes_on_one_device", {0}, 0, 1, "test hook: every lane of a split run / every device of --gpus N is device 0 (a one-GPU box walks the N-device code)"},

@@ -70,7 +70,17 @@ typedef struct {
     uint64_t total_bases, blob_bytes, mphf_bytes, max_unitig_len;      /* mphf_bytes: size of the overlap key table */
     uint32_t has_exceptions, has_anchors; /* has_anchors: built with BGR_BUILD_ANCHORS (needed by BGR_MODE_ANCHORS) */
     double gamma;  /* key table slots per key */
+    uint64_t jump_entries, jump_bytes; /* the jump index of the greedy anchor scan: entries placed, bytes of the section (0: the graph has none) */
+    uint32_t jump_stride;              /* it samples every jump_stride-th (k-1)-mer of a unitig */
+    uint32_t jump_absent;              /* why the graph has none: BGR_JUMP_* (0: it has one) */
+    uint32_t jump_dropped_x1000, jump_reserved; /* 1000 x the share of the sampled (k-1)-mers that found no place in the table */
 } bgr_graph_info_t;
+#define BGR_JUMP_PRESENT 0u
+#define BGR_JUMP_WIDE_KEYS 1u     /* two-word overlap keys (k > 32) */
+#define BGR_JUMP_EXCEPTIONS 2u    /* unitig bases outside ACGT */
+#define BGR_JUMP_NOT_STAGED 3u    /* the key table is too large to be staged in LDS: the kernel that jumps never runs */
+#define BGR_JUMP_OVER_CAP 4u      /* the index would not stay resident in the last-level cache */
+#define BGR_JUMP_NOT_COMPACTED 5u /* an interior (k-1)-mer of a unitig is an overlap key (or the index was built with build_jump = 0) */
 
 const char* bgr_last_error(void);
 
@@ -127,6 +137,10 @@ int bgr_graph_key_lookup_wide(const bgr_graph* g, uint64_t key_hi, uint64_t key_
 const void* bgr_graph_blob(const bgr_graph* g, uint64_t* bytes);
 int bgr_graph_from_blob(const void* blob, uint64_t bytes, bgr_graph** out); /* copies the blob */
 int bgr_graph_info(const bgr_graph* g, bgr_graph_info_t* out);
+/* The jump index of a graph built here (graph_layout.h: buckets of two 8-byte entries), or NULL.  It is NOT part of bgr_graph_blob's bytes -- those
+ * are what they always were -- but lies behind them in the graph's storage and in every device copy that bgr_graph_upload / bgr_devices_init make;
+ * a graph made from a blob (bgr_graph_from_blob, bgr_graph_adopt_device_blob) has none unless the blob's header names one. */
+const void* bgr_graph_jump_index(const bgr_graph* g, uint64_t* bytes);
 /* The unitig characters as they were handed to bgr_graph_build (offsets[n+1]; unitig id i is row i-1), the
  * reference's `vector<string> unitigs` (aligner.h:70).  Only graphs built from sequences carry them (not blobs). */
 int bgr_graph_unitigs(const bgr_graph* g, const char** seqs, const uint64_t** offsets, uint64_t* n);
@@ -476,7 +490,9 @@ int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blo
  *                              a tiny cap pushes most reads through the later passes
  *   BGR_KNOB_EXH_SEARCH        0 = choose per graph and budget, 1 = depth-first search, 2 = level search
  *   BGR_KNOB_BATCH_SPLIT_LIMIT bgr_align_batch maps a batch in pieces beyond this many path-arena ints, 0 = default (~2^32)
- *   BGR_KNOB_DEBUG_STOP        diagnostic builds (-DBGR_PHASE_TIMING) only: 1 = stop after packing, 2 = after the position scan */
+ *   BGR_KNOB_DEBUG_STOP        diagnostic builds (-DBGR_PHASE_TIMING) only: 1 = stop after packing, 2 = after the position scan
+ *   BGR_KNOB_GREEDY_JUMP       greedy mode: 1 = the anchor scan ignores the graph's jump index (bgr_graph_info: jump_entries), 0 = it uses it (default);
+ *                              the results are the same either way */
 #define BGR_KNOB_EXH_FRAME_CAP 1u
 #define BGR_KNOB_EXH_SEARCH 2u
 #define BGR_KNOB_BATCH_SPLIT_LIMIT 3u
@@ -493,6 +509,7 @@ int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blo
                                       (32-bit counters in each workgroup's LDS, flushed once); same table either way */
 #define BGR_KNOB_LINKS_FORM 13u /* the links kernel (bgr_aligner_links_enable): 0 = choose per graph, 1 = form A (every traversal is an insert into the table in device memory), 2 = form B (a table of 2048 links per
                                   workgroup in LDS, flushed once; what finds no place in it goes the way of form A); same counts either way */
+#define BGR_KNOB_GREEDY_JUMP 15u /* greedy mode, sixteen-reads-per-wave pass with the key table in LDS: 0 = the anchor scan jumps over verified unitig interiors when the graph has a jump index (bgr_graph_info: jump_entries; default), 1 = it ignores the index (same results: the index is a hint) */
 #define BGR_KNOB_GREEDY_FAST 5u /* greedy mode: 0 = sixteen-reads-per-wave pass + general kernel for the rest (default), 1 = general kernel only */
 #define BGR_KNOB_DEVICE_OVERLAP 14u /* consecutive bgr_align_device launches (greedy / anchors mode) that nobody waited for: 0 = they take turns on two streams with two sets of
                                        launch buffers, so that one starts on the CU slots the one before frees (default), 1 = every launch on the aligner's own stream and buffers */

@@ -645,12 +645,12 @@ class Graph:
 
     def bubbles(self):
         """bgr_graph_bubbles: the bubbles of the last align_all with the switch on -> array of BUBBLE_DTYPE, ordered by (|source|, source < 0)."""
-        return _fetch_bubbles(lambda out, cap, n: lib().bgr_graph_bubbles(self.h, out, cap, n))
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_bubbles(self.h, out, cap, n), BUBBLE_DTYPE)
 
     def links(self):
         """bgr_graph_links: the links of the last align_all with the switch on -> array of LINK_DTYPE (from, to, count), canonical, sorted by key.
         Raises BgrError when there are none."""
-        return _fetch_links(lib().bgr_graph_links, self.h)
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_links(self.h, out, cap, n), LINK_DTYPE)
 
     def pileup_enable(self, on=True):
         """bgr_graph_pileup_enable: sticky -- every later align_all on this graph counts unitig abundance and the per-base pileup."""
@@ -686,7 +686,7 @@ class Graph:
     def variants(self):
         """bgr_graph_variants: the sites of the last align_all with the switch on -> array of VARIANT_DTYPE (unitig, pos, depth, a, c, g, t, n) in
         (unitig, pos) order.  Raises BgrError when there are none."""
-        return _fetch_sites(lambda out, cap, n: lib().bgr_graph_variants(self.h, out, cap, n))
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_variants(self.h, out, cap, n), VARIANT_DTYPE)
 
     def variants_params(self):
         """bgr_graph_variants_params: (min_depth, min_alt, min_af_ppm) the sites of Graph.variants() were called with."""
@@ -727,7 +727,7 @@ class Graph:
 
     def variant_strand_sites(self):
         """bgr_graph_variant_strand_sites: the sites of the last align_all with variants_strands_enable on -> array of VARIANT_STRAND_DTYPE."""
-        return _fetch_sites(lambda out, cap, n: lib().bgr_graph_variant_strand_sites(self.h, out, cap, n), VARIANT_STRAND_DTYPE)
+        return _fetch_records(lambda out, cap, n: lib().bgr_graph_variant_strand_sites(self.h, out, cap, n), VARIANT_STRAND_DTYPE)
 
     def write_vcf_strands(self, path, sites, params):
         """bgr_write_vcf_strands: `sites` (VARIANT_STRAND_DTYPE) called with params = (min_depth, min_alt, min_af_ppm, min_alt_strand) as VCF 4.2 with ADF / ADR."""
@@ -986,12 +986,12 @@ class Aligner:
 
     def links(self):
         """bgr_aligner_links -> array of LINK_DTYPE (from, to, count) since enable / reset: canonical links, sorted by key."""
-        return _fetch_links(lib().bgr_aligner_links, self.h)
+        return _fetch_records(lambda out, cap, n: lib().bgr_aligner_links(self.h, out, cap, n), LINK_DTYPE)
 
     def bubbles(self, min_link=1):
         """bgr_aligner_bubbles: the bubbles of the aligner's table of links as it stands, called on the device -> array of BUBBLE_DTYPE, ordered by
         (|source|, source < 0)."""
-        return _fetch_bubbles(lambda out, cap, n: lib().bgr_aligner_bubbles(self.h, int(min_link), out, cap, n))
+        return _fetch_records(lambda out, cap, n: lib().bgr_aligner_bubbles(self.h, int(min_link), out, cap, n), BUBBLE_DTYPE)
 
     def bubbles_times(self):
         """bgr_aligner_bubbles_times -> the last bubbles() call's four launches in milliseconds (adjacency, count, scan, emit)."""
@@ -1048,7 +1048,7 @@ class Aligner:
         """bgr_aligner_pileup_sites -> array of VARIANT_DTYPE: the SNV sites of this aligner's pileup table, called on the device (five launches
         on the aligner's stream); only the records cross to the host."""
         prm = VariantParams(int(min_depth), int(min_alt), int(min_af_ppm))
-        return _fetch_sites(lambda out, cap, n: lib().bgr_aligner_pileup_sites(self.h, C.byref(prm), out, cap, n))
+        return _fetch_records(lambda out, cap, n: lib().bgr_aligner_pileup_sites(self.h, C.byref(prm), out, cap, n), VARIANT_DTYPE)
 
     def pileup_strands_enable(self, on=True):
         """bgr_aligner_pileup_strands_enable: the pileup kernel of every launch from now on also adds the forward observations to a second table
@@ -1062,7 +1062,7 @@ class Aligner:
     def pileup_strand_sites(self, min_depth=2, min_alt=2, min_af_ppm=200000, min_alt_strand=0):
         """bgr_aligner_pileup_strand_sites -> array of VARIANT_STRAND_DTYPE: pileup_sites under the strand filter, with the forward numbers."""
         prm = VariantStrandParams(int(min_depth), int(min_alt), int(min_af_ppm), int(min_alt_strand))
-        return _fetch_sites(lambda out, cap, n: lib().bgr_aligner_pileup_strand_sites(self.h, C.byref(prm), out, cap, n), VARIANT_STRAND_DTYPE)
+        return _fetch_records(lambda out, cap, n: lib().bgr_aligner_pileup_strand_sites(self.h, C.byref(prm), out, cap, n), VARIANT_STRAND_DTYPE)
 
     def pileup_sites_times(self):
         """bgr_aligner_pileup_sites_times -> the milliseconds of the last pileup_sites' five launches (tile sums, scan, classify, scan, emit)."""
@@ -1201,19 +1201,6 @@ def _fetch_forward(fn, obj):
     return out
 
 
-def _fetch_sites(fn, dtype=None):
-    """the two-call form of bgr_aligner_pileup_sites / bgr_graph_variants: the number first (BGR_E_CAPACITY), then the records"""
-    dtype = VARIANT_DTYPE if dtype is None else dtype
-    n = C.c_uint64(0)
-    rc = fn(None, 0, C.byref(n))
-    if rc != -4 or n.value == 0:
-        _check(rc)
-        return np.zeros(0, dtype=dtype)
-    out = np.zeros(n.value, dtype=dtype)
-    _check(fn(out.ctypes.data, n.value, C.byref(n)))
-    return out[: n.value]
-
-
 def parse_min_alt_strand(text):
     """bgr_parse_min_alt_strand: the CLI's --min-alt-strand parser; BgrError for anything but at most nine digits."""
     v = C.c_uint32(0)
@@ -1237,40 +1224,14 @@ def _fetch_pileup(fn, obj):
     return out, int(skipped.value)
 
 
-def _fetch_links(fn, handle):
-    """the two-call form of bgr_aligner_links / bgr_graph_links: the number first (BGR_E_CAPACITY), then the links"""
-    n = C.c_uint64(0)
-    rc = fn(handle, None, 0, C.byref(n))
-    if rc != -4:   # (BGR_E_CAPACITY with n set: there are links)
-        _check(rc)
-        return np.zeros(0, dtype=LINK_DTYPE)
-    if n.value == 0:   # (the table overflowed: the message says so)
-        _check(rc)
-    out = np.zeros(n.value, dtype=LINK_DTYPE)
-    assert LINK_DTYPE.itemsize == C.sizeof(Link) == 16
-    _check(fn(handle, out.ctypes.data, n.value, C.byref(n)))
-    return out[: n.value]
-
-
-def _fetch_bubbles(call):
-    """the two-call form of the bubble calls: the number first (BGR_E_CAPACITY with it), then the records"""
-    assert BUBBLE_DTYPE.itemsize == C.sizeof(Bubble) == 48
-    n = C.c_uint64(0)
-    rc = call(None, 0, C.byref(n))
-    if rc != -4 or n.value == 0:   # (no bubbles, or an error that is not "there are n of them")
-        _check(rc)
-        return np.zeros(0, dtype=BUBBLE_DTYPE)
-    out = np.zeros(n.value, dtype=BUBBLE_DTYPE)
-    _check(call(out.ctypes.data, n.value, C.byref(n)))
-    return out[: n.value]
-
-
 def _fetch_records(call, dtype):
-    """the two-call form of the triples and phase calls: the number first (BGR_E_CAPACITY with it), then the records"""
+    """the two-call form of the calls that deliver records (links, bubbles, triples, phase records, block entries, sites): the number first
+    (BGR_E_CAPACITY with it), then the records"""
+    assert LINK_DTYPE.itemsize == C.sizeof(Link) == 16 and BUBBLE_DTYPE.itemsize == C.sizeof(Bubble) == 48
     assert TRIPLE_DTYPE.itemsize == C.sizeof(Triple) == 24 and PHASE_DTYPE.itemsize == C.sizeof(Phase) == 64
     n = C.c_uint64(0)
     rc = call(None, 0, C.byref(n))
-    if rc != -4 or n.value == 0:   # (no records, or an error that is not "there are n of them": an overflowed table says so)
+    if rc != -4 or n.value == 0:   # (no records, or an error that is not "there are n of them": an overflowed table is BGR_E_CAPACITY with n = 0, and says so)
         _check(rc)
         return np.zeros(0, dtype=dtype)
     out = np.zeros(n.value, dtype=dtype)
@@ -1393,7 +1354,7 @@ def links_bubbles(links, n_unitigs, min_link=1, device=0):
     """bgr_links_bubbles: the bubbles of a list of links (an array of LINK_DTYPE, or (from, to, count) triples; canonical, strictly ascending by key,
     as Aligner.links() delivers them) on a graph of n_unitigs unitigs, called on `device` -> array of BUBBLE_DTYPE."""
     links = _as_links(links)
-    return _fetch_bubbles(lambda out, cap, n: lib().bgr_links_bubbles(int(device), links.ctypes.data, links.shape[0], int(n_unitigs), int(min_link), out, cap, n))
+    return _fetch_records(lambda out, cap, n: lib().bgr_links_bubbles(int(device), links.ctypes.data, links.shape[0], int(n_unitigs), int(min_link), out, cap, n), BUBBLE_DTYPE)
 
 
 def write_bubbles(path, graph, bubbles):

@@ -427,7 +427,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.release(); a->triples.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
+        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.buf.release(); a->triples.buf.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
                           &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
@@ -566,17 +566,17 @@ static int queue_counting(bgr_aligner* a, uint64_t arena_cap, const uint64_t* re
         HIP_TRY(mark("bgr_abundance_kernel"));
     }
     // Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
-    if (a->links_on) {
-        const bgr::LinksPlan lp = bgr::plan_links(a->links_bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
-        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->links_tab,
-                              a->links_cap, lp, a->stream);
+    if (a->links.on) {
+        const bgr::LinksPlan lp = bgr::plan_links(a->links.bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
+        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->links.tab,
+                              a->links.cap, lp, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_links_kernel"));
     }
     // Triples (bgr_aligner_triples_enable): likewise one kernel that adds every three consecutive ids of this launch's rows to the aligner's hash table.
-    if (a->triples_on) {
-        e = bgr::launch_triples(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->triples_tab,
-                                a->triples_cap, (uint32_t)a->num_cus, a->stream);
+    if (a->triples.on) {
+        e = bgr::launch_triples(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->triples.tab,
+                                a->triples.cap, (uint32_t)a->num_cus, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_triples_kernel): ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_triples_kernel"));
     }
@@ -605,9 +605,9 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
     if (a->abundance_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->links_on && p->mode == BGR_MODE_EXHAUSTIVE)
+    if (a->links.on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts links (bgr_aligner_links_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->triples_on && p->mode == BGR_MODE_EXHAUSTIVE)
+    if (a->triples.on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts triples (bgr_aligner_triples_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
@@ -854,8 +854,7 @@ static int twins_setup(bgr_aligner* a, unsigned n_twins) {
         prev = tw;
     }
     pileup_share(a);   // (one pileup table, one table of links and one of triples for the aligner and its twins: the atomics are device-scope)
-    links_share(a);
-    triples_share(a);
+    tables_share(a);
     return BGR_OK;
 }
 

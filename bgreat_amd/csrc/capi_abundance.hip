@@ -6,6 +6,9 @@
 
 #include "capi_internal.h"
 #include "run_counts.h"
+#pragma GCC visibility push(hidden)   // (the rules are no part of the interface; run_counts.h, above, is what pipeline.cpp shares)
+#include "run_stages.h"
+#pragma GCC visibility pop
 
 namespace {  // the totals of a run with bgr_run_options.abundance
 void graph_abundance_begin(bgr_graph* g) {  // a new run: the totals of the one before are gone, whatever becomes of this one
@@ -17,10 +20,11 @@ void graph_abundance_add(bgr_graph* g, const bgr_unitig_abundance* rows, uint64_
     std::lock_guard<std::mutex> l(g->abundance_m);
     for (uint64_t i = 0; i < n && i < g->abundance.size(); ++i) { g->abundance[i].reads += rows[i].reads; g->abundance[i].bases += rows[i].bases; g->abundance[i].kmers += rows[i].kmers; }
 }
-void graph_abundance_end(bgr_graph* g, bool ok) {  // totals only of a run that ended well
+int graph_abundance_end(bgr_graph* g, bool ok) {  // totals only of a run that ended well
     std::lock_guard<std::mutex> l(g->abundance_m);
     if (!ok) g->abundance.clear();
     g->abundance_valid = ok;
+    return BGR_OK;
 }
 }  // namespace
 
@@ -113,85 +117,52 @@ int bgr_write_abundance(const char* path, const bgr_graph* g, const bgr_unitig_a
     if (n_rows != g->header.n_unitigs) return fail(BGR_E_ARG, "bgr_write_abundance: n_rows is not the graph's number of unitigs");
     if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_write_abundance: the graph has no host blob (the unitig lengths are read from it)");
     const BgrUnitigMeta* meta = reinterpret_cast<const BgrUnitigMeta*>(g->host.base() + g->header.off_meta);
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_abundance: cannot open ") + path);
-    std::string buf = "#unitig\tlength\treads\tbases\tkmers\n";
-    bool ok = true;
-    for (uint64_t i = 0; i < n_rows && ok; ++i) {
-        buf += std::to_string(i + 1); buf += '\t';
-        buf += std::to_string(meta[i + 1].len); buf += '\t';
-        buf += std::to_string(rows[i].reads); buf += '\t';
-        buf += std::to_string(rows[i].bases); buf += '\t';
-        buf += std::to_string(rows[i].kmers); buf += '\n';
-        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
-    }
-    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_abundance: write to ") + path + " failed");
-    return BGR_OK;
+    return write_lines("bgr_write_abundance", path, "#unitig\tlength\treads\tbases\tkmers\n", n_rows, [&](uint64_t i, std::string* buf) {
+        for (uint64_t x : {i + 1, (uint64_t)meta[i + 1].len, rows[i].reads, rows[i].bases}) { *buf += std::to_string(x); *buf += '\t'; }
+        *buf += std::to_string(rows[i].kmers); *buf += '\n';
+    });
 }
 
 // ---- what a whole run calls (run_counts.h) -------------------------------------------------------------------------------------
-// The orders are kept here and nowhere else: an aligner's links and pileup are collected before its abundance (the pileup's snapshot reads the
-// aligner's abundance table, and the first aligner's pileup table leaves it there); the pileup ends behind the abundance, whose summed reads
-// column guards the summed depths.
+// The stages of a run (run_stages.h), and with them the two orders, kept here and nowhere else.
+// The table's order is the order in which an aligner is collected: its links and pileup before its abundance (the pileup's snapshot reads the aligner's
+// abundance table, and the first aligner's pileup table leaves it there).
+// The tiers are the order in which the run ends: the abundance totals; the merged tables of links and triples; then what is derived from totals, each
+// behind the one it reads -- the bubbles from the links, the phase from the bubbles and the triples, the blocks from the phase, the haplotypes from the
+// blocks; last the pileup, behind the abundance totals, whose summed reads column guards the summed depths.  (The message of a failed run stays: only
+// a refusal of a derived stage's or the pileup's end sets one.)
+static int abundance_enable(bgr_aligner* a, uint32_t) { return bgr_aligner_abundance_enable(a, 1); }
+static int links_enable(bgr_aligner* a, uint32_t) { return bgr_aligner_links_enable(a, 1); }
+static int triples_enable(bgr_aligner* a, uint32_t) { return bgr_aligner_triples_enable(a, 1); }
+static int pileup_enable(bgr_aligner* a, uint32_t what) { return what & bgr::kCountStrands ? bgr_aligner_pileup_strands_enable(a, 1) : bgr_aligner_pileup_enable(a, 1); }
+static const bgr::RunStage kStages[] = {
+    {bgr::kCountLinks, run_links_begin, links_enable, run_links_collect, run_links_end, bgr::kTierTables},
+    {bgr::kCountBubbles, run_bubbles_begin, nullptr, run_bubbles_collect, run_bubbles_end, bgr::kTierDerived},
+    {bgr::kCountTriples, run_triples_begin, triples_enable, run_triples_collect, run_triples_end, bgr::kTierTables},
+    {bgr::kCountPhase, run_phase_begin, nullptr, nullptr, run_phase_end, bgr::kTierDerived},
+    {bgr::kCountBlocks, run_blocks_begin, nullptr, nullptr, run_blocks_end, bgr::kTierDerived},
+    {bgr::kCountHaplotypes, run_haplotypes_begin, nullptr, nullptr, run_haplotypes_end, bgr::kTierDerived},
+    {bgr::kCountPileup, run_pileup_begin, pileup_enable, run_pileup_collect, run_pileup_end, bgr::kTierPileup},
+    {bgr::kCountAbundance, graph_abundance_begin, abundance_enable, run_abundance_collect, graph_abundance_end, bgr::kTierAbundance},
+};
+const int kNStages = sizeof(kStages) / sizeof(kStages[0]);
+
 static uint32_t run_counts_wanted(const bgr_graph* g) {
     if (!g) return 0;
-    uint32_t what = 0;
-    const bool blocks = g->blocks_on || g->haplotypes_on;   // (the haplotypes' switch implies the blocks')
-    const bool phase = g->phase_on || blocks;   // (the blocks' switch implies the phase's)
-    if (g->links_on || g->bubbles_on || phase) what |= bgr::kCountLinks;
-    if (g->bubbles_on || phase) what |= bgr::kCountBubbles;
-    if (g->triples_on || phase) what |= bgr::kCountTriples;
-    if (phase) what |= bgr::kCountPhase;
-    if (blocks) what |= bgr::kCountBlocks;
-    if (g->haplotypes_on) what |= bgr::kCountHaplotypes;
-    if (g->pileup_on || g->variants_on) what |= bgr::kCountPileup;
-    if (g->variants_on) what |= bgr::kCountVariants;
-    if ((g->pileup_on && g->pileup_strands_on) || (g->variants_on && g->variants_strands_on)) what |= bgr::kCountStrands;
-    return what ? what | bgr::kCountAbundance : 0;
+    return bgr::counts_wanted(bgr::RunSwitches{g->links.on, g->bubbles.on, g->triples.on, g->phase.on, g->blocks.on, g->haplotypes.on, g->pileup_on, g->variants_on, g->pileup_strands_on, g->variants_strands_on});
 }
 static void run_counts_begin(bgr_graph* g, uint32_t what) {
-    if (what & bgr::kCountAbundance) graph_abundance_begin(g);
-    if (what & bgr::kCountLinks) run_links_begin(g);
-    if (what & bgr::kCountBubbles) run_bubbles_begin(g);
-    if (what & bgr::kCountTriples) run_triples_begin(g);
-    if (what & bgr::kCountPhase) run_phase_begin(g);
-    if (what & bgr::kCountBlocks) run_blocks_begin(g);
-    if (what & bgr::kCountHaplotypes) run_haplotypes_begin(g);
-    if (what & bgr::kCountPileup) run_pileup_begin(g);
+    for (const bgr::RunStage& s : kStages) if (what & s.bit) s.begin(g);
 }
 static int run_counts_enable(bgr_aligner* a, uint32_t what) {   // every launch of the aligner is followed by the kernels of what the run counts
-    int rc = what & bgr::kCountAbundance ? bgr_aligner_abundance_enable(a, 1) : BGR_OK;
-    if (rc == BGR_OK && (what & bgr::kCountLinks)) rc = bgr_aligner_links_enable(a, 1);
-    if (rc == BGR_OK && (what & bgr::kCountTriples)) rc = bgr_aligner_triples_enable(a, 1);
-    if (rc == BGR_OK && (what & bgr::kCountPileup)) rc = what & bgr::kCountStrands ? bgr_aligner_pileup_strands_enable(a, 1) : bgr_aligner_pileup_enable(a, 1);
+    int rc = BGR_OK;
+    for (const bgr::RunStage& s : kStages) if (rc == BGR_OK && (what & s.bit) && s.enable) rc = s.enable(a, what);   // (the tables are independent: the order decides nothing)
     return rc;
 }
 static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
-    int rc = what & bgr::kCountLinks ? run_links_collect(g, a) : BGR_OK;
-    if (rc == BGR_OK && (what & bgr::kCountBubbles)) run_bubbles_collect(g, a);
-    if (rc == BGR_OK && (what & bgr::kCountTriples)) rc = run_triples_collect(g, a);
-    if (rc == BGR_OK && (what & bgr::kCountPileup)) rc = run_pileup_collect(g, a);
-    if (rc == BGR_OK && (what & bgr::kCountAbundance)) rc = run_abundance_collect(g, a);
+    int rc = BGR_OK;
+    for (const bgr::RunStage& s : kStages) if (rc == BGR_OK && (what & s.bit) && s.collect) rc = s.collect(g, a);
     return rc;
 }
-static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) {   // (the message of a failed run stays: only a refusal of the bubbles' or the pileup's end sets one)
-    if (what & bgr::kCountAbundance) graph_abundance_end(g, ok);
-    if (what & bgr::kCountLinks) run_links_end(g, ok);
-    if (what & bgr::kCountTriples) run_triples_end(g, ok);
-    int brc = what & bgr::kCountBubbles ? run_bubbles_end(g, ok) : BGR_OK;   // (behind the links' end: it reads the merged links)
-    if (brc == BGR_OK && (what & bgr::kCountPhase)) brc = run_phase_end(g, ok);   // (behind the bubbles' and the triples' end: it joins the two)
-    if (what & bgr::kCountBlocks) brc = brc == BGR_OK ? run_blocks_end(g, ok) : (run_blocks_end(g, false), brc);   // (behind the phase's end: it chains the records)
-    if (what & bgr::kCountHaplotypes) brc = brc == BGR_OK ? run_haplotypes_end(g, ok) : (run_haplotypes_end(g, false), brc);   // (behind the blocks' end: it spells the entries)
-    if (brc != BGR_OK) {   // (the run has failed after all: it leaves no totals)
-        graph_abundance_end(g, false); run_links_end(g, false);
-        if (what & bgr::kCountTriples) run_triples_end(g, false);
-        if (what & bgr::kCountPhase) (void)run_phase_end(g, false);
-        if (what & bgr::kCountBlocks) (void)run_blocks_end(g, false);
-        if (what & bgr::kCountHaplotypes) (void)run_haplotypes_end(g, false);
-    }
-    const int prc = what & bgr::kCountPileup ? run_pileup_end(g, ok && brc == BGR_OK) : BGR_OK;
-    return brc != BGR_OK ? brc : prc;
-}
+static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) { return bgr::end_stages(kStages, kNStages, g, what, ok); }
 static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end}, true);

@@ -35,34 +35,24 @@ static int blocks_call(int device, const bgr_bubble* bubbles, uint64_t n_bubbles
     }
     *n = n_bubbles;
     if (n_bubbles == 0) return BGR_OK;   // (no bubble, no block: no device work)
-    if (!vec && n_bubbles > cap) return fail(BGR_E_CAPACITY, w + ": " + std::to_string(n_bubbles) + " entries, room for " + std::to_string(cap));
+    if (!vec) if (const int rc = rows_refusal(n_bubbles, cap, n, who, "entries"); rc != BGR_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(device));
-    struct Res {
-        hipStream_t s = nullptr;
-        DevBuf in_b, in_p, scratch, outbuf;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Res() { in_b.release(); in_p.release(); scratch.release(); outbuf.release(); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (s) (void)hipStreamDestroy(s); }
-    } r;
-    HIP_TRY(hipStreamCreate(&r.s));
+    DeviceCall r;
+    if (const int rc = r.own_stream(); rc != BGR_OK) return rc;
+    DevBuf &in_b = r.buf[0], &in_p = r.buf[1], &scratch = r.buf[2], &outbuf = r.buf[3];
     const uint64_t bytes[4] = {n_bubbles * sizeof(bgr_bubble), n_phase * sizeof(bgr_phase), bgr::blocks_scratch_bytes(n_bubbles, n_unitigs), n_bubbles * sizeof(bgr_block_entry)};
-    DevBuf* const bufs[4] = {&r.in_b, &r.in_p, &r.scratch, &r.outbuf};
-    for (int i = 0; i < 4; ++i) {
-        if (bytes[i] == 0) continue;
-        const hipError_t e = bufs[i]->ensure(bytes[i]);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, w + ": " + std::to_string(bytes[i]) + " bytes on the device for " + std::to_string(n_bubbles) + " bubbles, " +
-                                                                                std::to_string(n_phase) + " phase records and " + std::to_string(n_unitigs) + " unitigs: " + hipGetErrorString(e));
-        }
-    }
-    for (hipEvent_t& e : r.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(r.in_b.p, bubbles, bytes[0], hipMemcpyHostToDevice, r.s));
-    if (n_phase) HIP_TRY(hipMemcpyAsync(r.in_p.p, phase, bytes[1], hipMemcpyHostToDevice, r.s));
-    const bgr::BlocksScratch sc(r.scratch.p, n_bubbles, n_unitigs);
-    const bgr_bubble* db = static_cast<const bgr_bubble*>(r.in_b.p);
+    for (int i = 0; i < 4; ++i)
+        if (bytes[i] && !r.room(r.buf[i], bytes[i], w + ": " + std::to_string(bytes[i]) + " bytes on the device for " + std::to_string(n_bubbles) + " bubbles, " + std::to_string(n_phase) +
+                                                        " phase records and " + std::to_string(n_unitigs) + " unitigs"))
+            return r.rc;
+    if (const int rc = r.events(4); rc != BGR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(in_b.p, bubbles, bytes[0], hipMemcpyHostToDevice, r.s));
+    if (n_phase) HIP_TRY(hipMemcpyAsync(in_p.p, phase, bytes[1], hipMemcpyHostToDevice, r.s));
+    const bgr::BlocksScratch sc(scratch.p, n_bubbles, n_unitigs);
+    const bgr_bubble* db = static_cast<const bgr_bubble*>(in_b.p);
     HIP_TRY(hipEventRecord(r.ev[0], r.s));
-    hipError_t e = bgr::launch_blocks_link(db, n_bubbles, static_cast<const bgr_phase*>(r.in_p.p), n_phase, n_unitigs, min_phase, r.scratch.p, r.s);
+    hipError_t e = bgr::launch_blocks_link(db, n_bubbles, static_cast<const bgr_phase*>(in_p.p), n_phase, n_unitigs, min_phase, scratch.p, r.s);
     if (e != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_index_kernel, bgr_blocks_link_kernel): " + hipGetErrorString(e));
     HIP_TRY(hipEventRecord(r.ev[1], r.s));
     uint32_t err = 0;
@@ -76,10 +66,10 @@ static int blocks_call(int device, const bgr_bubble* bubbles, uint64_t n_bubbles
                                                        : "two decided phase records leave or enter one bubble";
         return fail(BGR_E_ARG, w + ": " + m + " (error word " + std::to_string(err) + ")");
     }
-    if ((e = bgr::launch_blocks_rank(n_bubbles, n_unitigs, r.scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_rank_*_kernel): " + hipGetErrorString(e));
+    if ((e = bgr::launch_blocks_rank(n_bubbles, n_unitigs, scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_rank_*_kernel): " + hipGetErrorString(e));
     HIP_TRY(hipEventRecord(r.ev[2], r.s));
-    if ((e = bgr::launch_blocks_count(n_bubbles, n_unitigs, r.scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_heads_kernel): " + hipGetErrorString(e));
-    if ((e = bgr::launch_blocks_place(n_bubbles, n_unitigs, r.scratch.p, static_cast<bgr_block_entry*>(r.outbuf.p), r.s)) != hipSuccess)
+    if ((e = bgr::launch_blocks_count(n_bubbles, n_unitigs, scratch.p, r.s)) != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_heads_kernel): " + hipGetErrorString(e));
+    if ((e = bgr::launch_blocks_place(n_bubbles, n_unitigs, scratch.p, static_cast<bgr_block_entry*>(outbuf.p), r.s)) != hipSuccess)
         return fail(BGR_E_HIP, w + ": kernel launch (bgr_blocks_write_kernel): " + hipGetErrorString(e));
     HIP_TRY(hipEventRecord(r.ev[3], r.s));
     uint64_t total = 0;
@@ -88,7 +78,7 @@ static int blocks_call(int device, const bgr_bubble* bubbles, uint64_t n_bubbles
     HIP_TRY(hipStreamSynchronize(r.s));
     if (total != n_bubbles || err) return fail(BGR_E_INTERNAL, w + ": " + std::to_string(total) + " entries placed for " + std::to_string(n_bubbles) + " bubbles (error word " + std::to_string(err) + ")");
     if (vec) { vec->resize(n_bubbles); out = vec->data(); }
-    HIP_TRY(hipMemcpyAsync(out, r.outbuf.p, bytes[3], hipMemcpyDeviceToHost, r.s));   // (only now: a refused list copies nothing)
+    HIP_TRY(hipMemcpyAsync(out, outbuf.p, bytes[3], hipMemcpyDeviceToHost, r.s));   // (only now: a refused list copies nothing)
     HIP_TRY(hipStreamSynchronize(r.s));
     for (int i = 0; i < 3; ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, r.ev[i], r.ev[i + 1])); tl_blocks_ms[i] = f; }
     tl_blocks_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -111,54 +101,30 @@ int bgr_phase_blocks_times(double ms[4]) {
 // ---- what a whole run calls (run_counts.h, through capi_abundance.hip) ---------------------------------------------------------------------
 void run_blocks_begin(bgr_graph* g) {
     std::lock_guard<std::mutex> l(g->abundance_m);
-    g->blocks.clear();
-    g->blocks_valid = false;
+    g->blocks.forget();
 }
 int run_blocks_end(bgr_graph* g, bool ok) {   // behind run_phase_end: the run's bubbles and phase records uploaded once to the device the bubbles were called on
     std::lock_guard<std::mutex> l(g->abundance_m);
-    g->blocks.clear();
-    g->blocks_valid = false;
-    if (!ok) return BGR_OK;
-    int rc = BGR_OK;
-    uint64_t n = 0;
-    const uint64_t min_phase = g->blocks_on || !g->haplotypes_on ? g->blocks_min_phase : g->haplotypes_min_phase;   // (a run that only spells chains its blocks with the haplotypes' threshold)
-    if (!g->bubbles_valid || !g->phase_valid) rc = fail(BGR_E_INTERNAL, "bgr_align_all: blocks without the bubbles and the phase records they are chained from");
-    else if (!g->bubbles.empty()) {
-        if (g->bubbles_device < 0) rc = fail(BGR_E_INTERNAL, "bgr_align_all: bubbles, but no aligner of the run was collected");
-        else rc = blocks_call(g->bubbles_device, g->bubbles.data(), g->bubbles.size(), g->phase.data(), g->phase.size(), g->header.n_unitigs, min_phase, "bgr_align_all", &g->blocks,
-                              nullptr, 0, &n);
-    }
-    if (rc != BGR_OK) { g->blocks.clear(); g->blocks.shrink_to_fit(); }
-    g->blocks_valid = rc == BGR_OK;
-    return rc;
+    return chain_stage_end(g, g->blocks, ok, g->bubbles.valid && g->phase.valid, "blocks without the bubbles and the phase records they are chained from", !g->bubbles.rows.empty(), "bubbles", [&] {
+        uint64_t n = 0;
+        return blocks_call(g->bubbles.device, g->bubbles.rows.data(), g->bubbles.rows.size(), g->phase.rows.data(), g->phase.rows.size(), g->header.n_unitigs, run_thresholds(g).phase, "bgr_align_all",
+                           &g->blocks.rows, nullptr, 0, &n);
+    });
 }
 
 int bgr_graph_blocks_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64_t min_phase) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: null graph");
-    if (on) {
-        if (min_link == 0) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: min_link is at least 1");
-        if (min_phase == 0) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: min_phase is at least 1");
-        if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_blocks_enable: the graph has no host blob (the tables of links and triples are sized from it)");
-        if (g->header.has_exc)
-            return fail(BGR_E_ARG, "bgr_graph_blocks_enable: blocks (--blocks) chain phased bubbles, which need a graph of ACGT-only unitigs: on one with other characters a branch read backwards does not spell the reverse complement");
-        g->blocks_min_link = min_link;
-        g->blocks_min_phase = min_phase;
-    }
-    g->blocks_on = on != 0;
+    const ChainMins given = {min_link, min_phase, 1};
+    if (const int rc = chain_refusal(g, "bgr_graph_blocks_enable", on, given, "the tables of links and triples are sized from it",
+                                     "blocks (--blocks) chain phased bubbles, which need a graph of ACGT-only unitigs: on one with other characters a branch read backwards does not spell the reverse complement");
+        rc != BGR_OK)
+        return rc;
+    g->blocks.set(on, given);
     return BGR_OK;
 }
 
-int bgr_graph_blocks_enabled(const bgr_graph* g) { return g && g->blocks_on ? 1 : 0; }
+int bgr_graph_blocks_enabled(const bgr_graph* g) { return g && g->blocks.on ? 1 : 0; }
 
-int bgr_graph_blocks(const bgr_graph* g, bgr_block_entry* out, uint64_t cap, uint64_t* n) {
-    if (n) *n = 0;
-    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, "bgr_graph_blocks: null argument");
-    if (!g->blocks_valid) return fail(BGR_E_ARG, "bgr_graph_blocks: no entries -- they are those of the last successful bgr_align_all with bgr_graph_blocks_enable on");
-    *n = g->blocks.size();
-    if (g->blocks.size() > cap) return fail(BGR_E_CAPACITY, "bgr_graph_blocks: " + std::to_string(g->blocks.size()) + " entries, room for " + std::to_string(cap));
-    if (!g->blocks.empty()) memcpy(out, g->blocks.data(), g->blocks.size() * sizeof(bgr_block_entry));
-    return BGR_OK;
-}
+int bgr_graph_blocks(const bgr_graph* g, bgr_block_entry* out, uint64_t cap, uint64_t* n) { return graph_rows(g, &bgr_graph::blocks, out, cap, n, "bgr_graph_blocks", "entries", "entries"); }
 
 int bgr_write_blocks(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n) {
     if (!path || !g || (n_bubbles && !bubbles) || (n && !entries)) return fail(BGR_E_ARG, "bgr_write_blocks: null argument");
@@ -168,16 +134,5 @@ int bgr_write_blocks(const char* path, const bgr_graph* g, const bgr_bubble* bub
         for (int32_t x : {bubbles[i].source, bubbles[i].sink, bubbles[i].branch[0], bubbles[i].branch[1]})
             if (!bgr::blocks_id_ok(x, nu)) return fail(BGR_E_ARG, "bgr_write_blocks: bubble " + std::to_string(i) + " names a unitig the graph does not have");
     if (!bgr::blocks_entries_ok(entries, n, n_bubbles, &bad)) return fail(BGR_E_ARG, "bgr_write_blocks: entry " + std::to_string(bad) + " names no bubble of the list, or is none that bgr_phase_blocks makes");
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(BGR_E_IO, std::string("bgr_write_blocks: cannot open ") + path);
-    std::string buf = bgr::blocks_header();
-    bool ok = true;
-    for (uint64_t i = 0; i < n && ok; ++i) {
-        bgr::blocks_line(entries[i], bubbles[entries[i].bubble], &buf);
-        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
-    }
-    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    if (fclose(f) != 0) ok = false;
-    if (!ok) return fail(BGR_E_IO, std::string("bgr_write_blocks: write to ") + path + " failed");
-    return BGR_OK;
+    return write_lines("bgr_write_blocks", path, bgr::blocks_header(), n, [&](uint64_t i, std::string* buf) { bgr::blocks_line(entries[i], bubbles[entries[i].bubble], buf); });
 }

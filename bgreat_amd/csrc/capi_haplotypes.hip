@@ -43,33 +43,22 @@ static int haplotypes_call(const bgr_graph* g, int device, const bgr_bubble* bub
     HIP_TRY(hipSetDevice(device));
     BgrDeviceGraph dg;
     bgr::resolve_device_graph(&g->header, it->second.ptr, dg);
-    struct Res {
-        hipStream_t s = nullptr;
-        DevBuf in_b, in_e, scratch, recs, bytes;
-        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around items + scan; before the spell launch (behind the allocations), behind it, behind the records
-        ~Res() { if (s) (void)hipStreamSynchronize(s);   // (an early return may leave copies into the call's locals in flight)
-                 in_b.release(); in_e.release(); scratch.release(); recs.release(); bytes.release(); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (s) (void)hipStreamDestroy(s); }
-    } r;
-    HIP_TRY(hipStreamCreate(&r.s));
-    auto room = [&](DevBuf& b, uint64_t bytes, int* rc) {   // -> whether the device has `bytes` more
-        const hipError_t e = b.ensure(bytes);
-        if (e == hipSuccess) return true;
-        (void)hipGetLastError();
-        *rc = fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, w + ": " + std::to_string(bytes) + " bytes on the device for " + std::to_string(n_bubbles) + " bubbles and " +
-                                                                           std::to_string(n_entries) + " entries: " + hipGetErrorString(e));
-        return false;
+    DeviceCall r;   // r.ev: around items + scan; before the spell launch (behind the allocations), behind it, behind the records
+    if (const int rc = r.own_stream(); rc != BGR_OK) return rc;
+    DevBuf &in_b = r.buf[0], &in_e = r.buf[1], &scratch = r.buf[2], &recs = r.buf[3], &bytes = r.buf[4];
+    auto room = [&](DevBuf& b, uint64_t want) {   // -> whether the device has `want` more bytes
+        return r.room(b, want, w + ": " + std::to_string(want) + " bytes on the device for " + std::to_string(n_bubbles) + " bubbles and " + std::to_string(n_entries) + " entries");
     };
-    int rc = BGR_OK;
     const uint64_t in_bytes[2] = {n_bubbles * sizeof(bgr_bubble), n_entries * sizeof(bgr_block_entry)};
-    if (!room(r.in_b, in_bytes[0], &rc) || !room(r.in_e, in_bytes[1], &rc) || !room(r.scratch, bgr::hap_scratch_bytes(n_entries), &rc)) return rc;
-    for (hipEvent_t& e : r.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(r.in_b.p, bubbles, in_bytes[0], hipMemcpyHostToDevice, r.s));
-    HIP_TRY(hipMemcpyAsync(r.in_e.p, entries, in_bytes[1], hipMemcpyHostToDevice, r.s));
-    const bgr::HapScratch sc(r.scratch.p, n_entries);
-    const bgr_bubble* db = static_cast<const bgr_bubble*>(r.in_b.p);
-    const bgr_block_entry* de = static_cast<const bgr_block_entry*>(r.in_e.p);
+    if (!room(in_b, in_bytes[0]) || !room(in_e, in_bytes[1]) || !room(scratch, bgr::hap_scratch_bytes(n_entries))) return r.rc;
+    if (const int rc = r.events(5); rc != BGR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(in_b.p, bubbles, in_bytes[0], hipMemcpyHostToDevice, r.s));
+    HIP_TRY(hipMemcpyAsync(in_e.p, entries, in_bytes[1], hipMemcpyHostToDevice, r.s));
+    const bgr::HapScratch sc(scratch.p, n_entries);
+    const bgr_bubble* db = static_cast<const bgr_bubble*>(in_b.p);
+    const bgr_block_entry* de = static_cast<const bgr_block_entry*>(in_e.p);
     HIP_TRY(hipEventRecord(r.ev[0], r.s));
-    hipError_t e = bgr::launch_hap_items(dg, nu, g->header.total_bases, db, n_bubbles, de, n_entries, min_block, r.scratch.p, r.s);
+    hipError_t e = bgr::launch_hap_items(dg, nu, g->header.total_bases, db, n_bubbles, de, n_entries, min_block, scratch.p, r.s);
     if (e != hipSuccess) return fail(BGR_E_HIP, w + ": kernel launch (bgr_hap_items_kernel, bgr_hap_tiles_kernel, bgr_hap_tile_scan_kernel): " + hipGetErrorString(e));
     HIP_TRY(hipEventRecord(r.ev[1], r.s));
     uint64_t total = 0, blocks = 0, words[2] = {0, 0};
@@ -91,20 +80,20 @@ static int haplotypes_call(const bgr_graph* g, int device, const bgr_bubble* bub
         return fail(BGR_E_CAPACITY, w + ": " + std::to_string(2 * blocks) + " sequences of " + std::to_string(total) + " bytes, room for " + std::to_string(cap) + " and " + std::to_string(seq_cap));
     }
     if (blocks) {   // (every kept block has two sequences of at least k characters)
-        if (!room(r.recs, 2 * blocks * sizeof(bgr_haplotype), &rc) || !room(r.bytes, total, &rc)) return rc;
+        if (!room(recs, 2 * blocks * sizeof(bgr_haplotype)) || !room(bytes, total)) return r.rc;
         HIP_TRY(hipEventRecord(r.ev[2], r.s));   // (only here: the sizing copies, the wait and the two allocations above are no part of the spell stage)
-        if ((e = bgr::launch_hap_spell(dg, n_entries, total, r.scratch.p, static_cast<char*>(r.bytes.p), r.s)) != hipSuccess)
+        if ((e = bgr::launch_hap_spell(dg, n_entries, total, scratch.p, static_cast<char*>(bytes.p), r.s)) != hipSuccess)
             return fail(BGR_E_HIP, w + ": kernel launch (bgr_hap_spell_kernel): " + hipGetErrorString(e));
         HIP_TRY(hipEventRecord(r.ev[3], r.s));
-        if ((e = bgr::launch_hap_records(de, n_entries, min_block, r.scratch.p, static_cast<bgr_haplotype*>(r.recs.p), 2 * blocks, r.s)) != hipSuccess)
+        if ((e = bgr::launch_hap_records(de, n_entries, min_block, scratch.p, static_cast<bgr_haplotype*>(recs.p), 2 * blocks, r.s)) != hipSuccess)
             return fail(BGR_E_HIP, w + ": kernel launch (bgr_hap_records_kernel): " + hipGetErrorString(e));
         HIP_TRY(hipEventRecord(r.ev[4], r.s));
         HIP_TRY(hipMemcpyAsync(words, sc.words, 16, hipMemcpyDeviceToHost, r.s));
         HIP_TRY(hipStreamSynchronize(r.s));
         if ((uint32_t)words[1]) return fail(BGR_E_INTERNAL, w + ": a record beyond the " + std::to_string(2 * blocks) + " the scan counted (error word " + std::to_string((uint32_t)words[1]) + ")");
         if (vec) { vec->resize(2 * blocks); vseq->resize(total); out = vec->data(); seq = vseq->data(); }
-        HIP_TRY(hipMemcpyAsync(out, r.recs.p, 2 * blocks * sizeof(bgr_haplotype), hipMemcpyDeviceToHost, r.s));   // (only now: a refused call copies nothing)
-        HIP_TRY(hipMemcpyAsync(seq, r.bytes.p, total, hipMemcpyDeviceToHost, r.s));
+        HIP_TRY(hipMemcpyAsync(out, recs.p, 2 * blocks * sizeof(bgr_haplotype), hipMemcpyDeviceToHost, r.s));   // (only now: a refused call copies nothing)
+        HIP_TRY(hipMemcpyAsync(seq, bytes.p, total, hipMemcpyDeviceToHost, r.s));
         HIP_TRY(hipStreamSynchronize(r.s));
         for (int i = 1; i < 3; ++i) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, r.ev[i + 1], r.ev[i + 2])); tl_hap_ms[i] = f; }
     }
@@ -128,65 +117,48 @@ int bgr_blocks_haplotypes_times(double ms[4]) {
 }
 
 // ---- what a whole run calls (run_counts.h, through capi_abundance.hip) ---------------------------------------------------------------------
-static void haplotypes_forget(bgr_graph* g) {
-    g->haplotypes.clear(); g->haplotypes.shrink_to_fit();
-    g->haplotypes_seq.clear(); g->haplotypes_seq.shrink_to_fit();
-    g->haplotypes_valid = false;
-}
 void run_haplotypes_begin(bgr_graph* g) {
     std::lock_guard<std::mutex> l(g->abundance_m);
-    haplotypes_forget(g);
+    g->haplotypes.forget();
 }
 int run_haplotypes_end(bgr_graph* g, bool ok) {   // behind run_blocks_end: the run's bubbles and entries uploaded once to the device the bubbles were called on
     std::lock_guard<std::mutex> l(g->abundance_m);
-    haplotypes_forget(g);
-    if (!ok) return BGR_OK;
-    int rc = BGR_OK;
-    uint64_t n = 0, bytes = 0, bad = 0;
-    if (!g->bubbles_valid || !g->blocks_valid) rc = fail(BGR_E_INTERNAL, "bgr_align_all: haplotypes without the bubbles and the block entries they are spelled from");
-    else if (!g->blocks.empty()) {
-        if (g->bubbles_device < 0) rc = fail(BGR_E_INTERNAL, "bgr_align_all: block entries, but no aligner of the run was collected");
-        else rc = haplotypes_call(g, g->bubbles_device, g->bubbles.data(), g->bubbles.size(), g->blocks.data(), g->blocks.size(), g->haplotypes_min_block, "bgr_align_all", &g->haplotypes,
-                                  &g->haplotypes_seq, nullptr, 0, &n, nullptr, 0, &bytes, &bad);
-        if (rc == BGR_OK && bad)
-            rc = fail(BGR_E_INTERNAL, "bgr_align_all: " + std::to_string(bad) + " junctions of the run's haplotype walks do not overlap in k - 1 characters: the bubbles' links are none of this graph");
-    }
-    if (rc != BGR_OK) haplotypes_forget(g);
-    g->haplotypes_valid = rc == BGR_OK;
-    return rc;
+    return chain_stage_end(g, g->haplotypes, ok, g->bubbles.valid && g->blocks.valid, "haplotypes without the bubbles and the block entries they are spelled from", !g->blocks.rows.empty(),
+                           "block entries", [&] {
+        uint64_t n = 0, bytes = 0, bad = 0;
+        const int rc = haplotypes_call(g, g->bubbles.device, g->bubbles.rows.data(), g->bubbles.rows.size(), g->blocks.rows.data(), g->blocks.rows.size(), run_thresholds(g).block, "bgr_align_all",
+                                       &g->haplotypes.rows, &g->haplotypes.seq, nullptr, 0, &n, nullptr, 0, &bytes, &bad);
+        if (rc != BGR_OK || !bad) return rc;
+        return fail(BGR_E_INTERNAL, "bgr_align_all: " + std::to_string(bad) + " junctions of the run's haplotype walks do not overlap in k - 1 characters: the bubbles' links are none of this graph");
+    });
 }
 
 int bgr_graph_haplotypes_enable(bgr_graph* g, uint32_t on, uint64_t min_link, uint64_t min_phase, uint64_t min_block) {
-    if (!g) return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: null graph");
-    if (on) {
-        if (min_link == 0) return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: min_link is at least 1");
-        if (min_phase == 0) return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: min_phase is at least 1");
-        if (min_block == 0) return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: min_block is at least 1");
-        if (g->host.blob.empty()) return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: the graph has no host blob (the tables of links and triples are sized from it)");
-        if (g->header.has_exc)
-            return fail(BGR_E_ARG, "bgr_graph_haplotypes_enable: the haplotypes (--haplotypes) are spelled from the 2-bit store along phased bubbles, which needs a graph of ACGT-only unitigs");
-        g->haplotypes_min_link = min_link;
-        g->haplotypes_min_phase = min_phase;
-        g->haplotypes_min_block = min_block;
-    }
-    g->haplotypes_on = on != 0;
+    const ChainMins given = {min_link, min_phase, min_block};
+    if (const int rc = chain_refusal(g, "bgr_graph_haplotypes_enable", on, given, "the tables of links and triples are sized from it",
+                                     "the haplotypes (--haplotypes) are spelled from the 2-bit store along phased bubbles, which needs a graph of ACGT-only unitigs");
+        rc != BGR_OK)
+        return rc;
+    g->haplotypes.set(on, given);
     return BGR_OK;
 }
 
-int bgr_graph_haplotypes_enabled(const bgr_graph* g) { return g && g->haplotypes_on ? 1 : 0; }
+int bgr_graph_haplotypes_enabled(const bgr_graph* g) { return g && g->haplotypes.on ? 1 : 0; }
 
+// (two vectors with one refusal for both: the one getter that is not graph_rows)
 int bgr_graph_haplotypes(const bgr_graph* g, bgr_haplotype* out, uint64_t cap, uint64_t* n, char* seq, uint64_t seq_cap, uint64_t* seq_bytes) {
     if (n) *n = 0;
     if (seq_bytes) *seq_bytes = 0;
     if (!g || !n || !seq_bytes || (cap && !out) || (seq_cap && !seq)) return fail(BGR_E_ARG, "bgr_graph_haplotypes: null argument");
-    if (!g->haplotypes_valid) return fail(BGR_E_ARG, "bgr_graph_haplotypes: no sequences -- they are those of the last successful bgr_align_all with bgr_graph_haplotypes_enable on");
-    *n = g->haplotypes.size();
-    *seq_bytes = g->haplotypes_seq.size();
-    if (g->haplotypes.size() > cap || g->haplotypes_seq.size() > seq_cap)
-        return fail(BGR_E_CAPACITY, "bgr_graph_haplotypes: " + std::to_string(g->haplotypes.size()) + " sequences of " + std::to_string(g->haplotypes_seq.size()) + " bytes, room for " +
-                                        std::to_string(cap) + " and " + std::to_string(seq_cap));
-    if (!g->haplotypes.empty()) memcpy(out, g->haplotypes.data(), g->haplotypes.size() * sizeof(bgr_haplotype));
-    if (!g->haplotypes_seq.empty()) memcpy(seq, g->haplotypes_seq.data(), g->haplotypes_seq.size());
+    const bgr_graph::Haplotypes& h = g->haplotypes;
+    if (!h.valid) return fail(BGR_E_ARG, "bgr_graph_haplotypes: no sequences -- they are those of the last successful bgr_align_all with bgr_graph_haplotypes_enable on");
+    *n = h.rows.size();
+    *seq_bytes = h.seq.size();
+    if (h.rows.size() > cap || h.seq.size() > seq_cap)
+        return fail(BGR_E_CAPACITY, "bgr_graph_haplotypes: " + std::to_string(h.rows.size()) + " sequences of " + std::to_string(h.seq.size()) + " bytes, room for " + std::to_string(cap) + " and " +
+                                        std::to_string(seq_cap));
+    if (!h.rows.empty()) memcpy(out, h.rows.data(), h.rows.size() * sizeof(bgr_haplotype));
+    if (!h.seq.empty()) memcpy(seq, h.seq.data(), h.seq.size());
     return BGR_OK;
 }
 

@@ -1,11 +1,17 @@
-// capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; capi_abundance.hip,
-// capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip, capi_variants.hip: the counting features): the objects behind the opaque handles, the error channel, the
-// waits, and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or leaves the library.
+// capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; the counting features:
+// capi_abundance.hip with the table of a run's stages, capi_links.hip with the count tables of links and triples, capi_triples.hip with the phase,
+// capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip, capi_variants.hip): the objects behind the opaque handles, the error
+// channel, the waits, the helpers the counting features are written with (delivering rows, the chain's switches and thresholds, a file of lines,
+// a call's stream and buffers), and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or
+// leaves the library.
 #ifndef BGREAT_AMD_CAPI_INTERNAL_H
 #define BGREAT_AMD_CAPI_INTERNAL_H
 
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <cstdio>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -35,6 +41,27 @@ inline int fail(int code, const std::string& msg) { return bgr::set_error(code, 
 const int kTimerRing = 64;   // launches between two drains of the timers
 const int kTimerSlots = 8;   // kernels of one launch timed separately (pre-pass, passes)
 
+// What a counting feature keeps in the graph object: the rows of the last successful run.
+template <class Row>
+struct RunRows {
+    bool valid = false;
+    std::vector<Row> rows;
+    void forget() { std::vector<Row>().swap(rows); valid = false; }   // (nothing stays allocated)
+};
+// ... of a count table (links: W = 2, triples: W = 3): the key words, then the count
+template <size_t W>
+struct CountRows : RunRows<std::array<uint64_t, W>> {
+    bool on = false, bound_known = false;
+    uint64_t bound = 0;
+};
+// ... and the sticky switch of a feature of the chain bubbles -> phase -> blocks -> haplotypes with the thresholds it was given (1 where it takes none)
+struct ChainMins { uint64_t link = 1, phase = 1, block = 1; };
+struct ChainSwitch {
+    bool on = false;
+    ChainMins min;
+    void set(uint32_t on_, const ChainMins& given) { if (on_) min = given; on = on_ != 0; }
+};
+
 struct bgr_graph {
     bgr::HostGraph host;  // empty when adopted from a device blob
     std::vector<char> ascii;            // the unitig characters as given (only graphs built from sequences have them):
@@ -47,39 +74,22 @@ struct bgr_graph {
     std::vector<bgr_unitig_abundance> abundance;
     bool abundance_valid = false;
     std::mutex abundance_m;   // (the lanes of a split run end side by side)
-    // links (bgr_graph_links_enable): the sticky switch, the bound of distinct links (computed from the host blob the first time it is asked for),
-    // and the totals of the last bgr_align_all with the switch on: {key, count} as the aligners delivered them until the run ends, then merged and sorted
-    bool links_on = false, links_valid = false, links_bound_known = false;
-    uint64_t links_bound = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> links;
-    // bubbles (bgr_graph_bubbles_enable): the sticky switch with its threshold; the device of the first aligner a run collected (-1: none yet), where
-    // the run's merged links are called when it ends; the records of the last successful run and the threshold they were called with
-    bool bubbles_on = false, bubbles_valid = false;
-    uint64_t bubbles_min_link = 1, bubbles_called = 0;
-    int bubbles_device = -1;
-    std::vector<bgr_bubble> bubbles;
-    // triples (bgr_graph_triples_enable): as the links -- the sticky switch, the bound of distinct triples (from the host blob, the first time it is asked
-    // for), the totals of the last bgr_align_all with the switch on: {k0, k1, count} as the aligners delivered them until the run ends, then merged and sorted
-    struct TripleRow { uint64_t k0, k1, count; };
-    bool triples_on = false, triples_valid = false, triples_bound_known = false;
-    uint64_t triples_bound = 0;
-    std::vector<TripleRow> triples;
-    // phase (bgr_graph_phase_enable): the sticky switch with the threshold its bubbles are called with when the bubbles' own switch is off; the records
-    // of the last successful run
-    bool phase_on = false, phase_valid = false;
-    uint64_t phase_min_link = 1;
-    std::vector<bgr_phase> phase;
-    // blocks (bgr_graph_blocks_enable): the sticky switch with the threshold of a decided link, and the threshold the run's bubbles are called with when
-    // neither the bubbles' nor the phase's own switch is on; the entries of the last successful run
-    bool blocks_on = false, blocks_valid = false;
-    uint64_t blocks_min_link = 1, blocks_min_phase = 1;
-    std::vector<bgr_block_entry> blocks;
-    // haplotypes (bgr_graph_haplotypes_enable): the sticky switch with the smallest block that is spelled, and the thresholds the run's bubbles and blocks
-    // are called with when no switch before it in the chain (bubbles, phase, blocks) is on; the records and characters of the last successful run
-    bool haplotypes_on = false, haplotypes_valid = false;
-    uint64_t haplotypes_min_link = 1, haplotypes_min_phase = 1, haplotypes_min_block = 1;
-    std::vector<bgr_haplotype> haplotypes;
-    std::vector<char> haplotypes_seq;
+    // The counting features whose rows a run leaves here (RunRows above): `on` is the sticky switch, `rows` with `valid` those of the last successful
+    // bgr_align_all with the feature counted.  Every access is under abundance_m.
+    // links and triples (bgr_graph_links_enable, bgr_graph_triples_enable): {key, count} and {k0, k1, count} as the aligners delivered them until the run
+    // ends, then merged and sorted; the bound of distinct keys is computed from the host blob the first time it is asked for
+    CountRows<2> links;
+    CountRows<3> triples;
+    // bubbles, phase, blocks, haplotypes (bgr_graph_*_enable): each switch with the thresholds it was given (run_thresholds below says which of them a
+    // run uses).  bubbles.device: the device of the first aligner a run collected (-1: none yet), where the run's merged links are called when it ends
+    // and the later stages of the chain run; haplotypes.seq: the characters the records point into
+    struct Bubbles : ChainSwitch, RunRows<bgr_bubble> { int device = -1; } bubbles;
+    struct Phase : ChainSwitch, RunRows<bgr_phase> {} phase;
+    struct Blocks : ChainSwitch, RunRows<bgr_block_entry> {} blocks;
+    struct Haplotypes : ChainSwitch, RunRows<bgr_haplotype> {
+        std::vector<char> seq;
+        void forget() { RunRows<bgr_haplotype>::forget(); std::vector<char>().swap(seq); }
+    } haplotypes;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -189,14 +199,15 @@ struct bgr_aligner {
     bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel
     DevBuf abundance;               // u64[n_unitigs + 1][3], allocated and zeroed on the first enable
     uint32_t knob_links_form = 0;   // BGR_KNOB_LINKS_FORM
-    bool links_on = false;          // bgr_aligner_links_enable: every greedy / anchors launch is followed by the links kernel
-    DevBuf links;                   // {u64 key, u64 count}[links_cap] + the tail words (links_kernels.h), allocated and zeroed on the first enable
-    unsigned long long* links_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
-    uint64_t links_cap = 0, links_bound = 0;
-    bool triples_on = false;        // bgr_aligner_triples_enable: every greedy / anchors launch is followed by the triples kernel
-    DevBuf triples;                 // {u64 k0, u64 k1, u64 count}[triples_cap] + the tail words (triples_kernels.h), allocated and zeroed on the first enable
-    unsigned long long* triples_tab = nullptr;   // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
-    uint64_t triples_cap = 0, triples_bound = 0;
+    // links and triples (bgr_aligner_links_enable, bgr_aligner_triples_enable): every greedy / anchors launch is followed by the kernel that adds to the
+    // table.  buf: {key words, u64 count}[cap] + the tail words (links_kernels.h, triples_kernels.h), allocated and zeroed on the first enable; tab: the
+    // table this aligner's launches add to -- its own, or (a twin) the one of the aligner it belongs to
+    struct CountTable {
+        bool on = false;
+        DevBuf buf;
+        unsigned long long* tab = nullptr;
+        uint64_t cap = 0, bound = 0;
+    } links, triples;
     bool pileup_on = false;         // bgr_aligner_pileup_enable: every greedy / anchors launch is followed by the pileup kernel
     DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
     uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
@@ -240,33 +251,139 @@ inline int sync_all(bgr_aligner* a) {
 inline bgr_aligner* holder_of(bgr_aligner* a) { return a->holder ? a->holder : a; }
 inline const bgr_aligner* holder_of(const bgr_aligner* a) { return a->holder ? a->holder : a; }
 
+// ---- what the counting features' units share -----------------------------------------------------------------------------------------
+// *n = have; BGR_E_CAPACITY when `cap` has no room for them (the first call of a caller that asks for the number)
+inline int rows_refusal(uint64_t have, uint64_t cap, uint64_t* n, const char* who, const char* noun) {
+    *n = have;
+    if (have > cap) return fail(BGR_E_CAPACITY, std::string(who) + ": " + std::to_string(have) + " " + noun + ", room for " + std::to_string(cap));
+    return BGR_OK;
+}
+// `rows` into `out` when cap has room, each through `conv` (a row of a count table is no record of the interface)
+template <class Row, class Out, class Conv>
+int deliver_rows(const std::vector<Row>& rows, Out* out, uint64_t cap, uint64_t* n, const char* who, const char* noun, Conv conv) {
+    if (const int rc = rows_refusal(rows.size(), cap, n, who, noun); rc != BGR_OK) return rc;
+    for (size_t i = 0; i < rows.size(); ++i) out[i] = conv(rows[i]);
+    return BGR_OK;
+}
+template <class Row>
+int deliver_rows(const std::vector<Row>& rows, Row* out, uint64_t cap, uint64_t* n, const char* who, const char* noun) {
+    return deliver_rows(rows, out, cap, n, who, noun, [](const Row& r) { return r; });
+}
+// a bgr_graph_* getter: the rows the last successful run left in g->*f (`none`: what the message calls them when there are none)
+template <class F, class Out, class... Conv>
+int graph_rows(const bgr_graph* g, F bgr_graph::*f, Out* out, uint64_t cap, uint64_t* n, const char* who, const char* noun, const char* none, Conv... conv) {
+    if (n) *n = 0;
+    if (!g || !n || (cap && !out)) return fail(BGR_E_ARG, std::string(who) + ": null argument");
+    if (!(g->*f).valid) return fail(BGR_E_ARG, std::string(who) + ": no " + none + " -- they are those of the last successful bgr_align_all with " + who + "_enable on");
+    return deliver_rows((g->*f).rows, out, cap, n, who, noun, conv...);
+}
+
+// what bgr_graph_{bubbles,phase,blocks,haplotypes}_enable refuse: a null graph, and with `on` a threshold of 0, a graph without its host blob, one
+// whose unitigs are not ACGT only (`blob`, `acgt`: the feature's own words for the last two)
+inline int chain_refusal(const bgr_graph* g, const char* who, uint32_t on, const ChainMins& given, const char* blob, const char* acgt) {
+    const std::string w = who;
+    if (!g) return fail(BGR_E_ARG, w + ": null graph");
+    if (!on) return BGR_OK;
+    if (given.link == 0) return fail(BGR_E_ARG, w + ": min_link is at least 1");
+    if (given.phase == 0) return fail(BGR_E_ARG, w + ": min_phase is at least 1");
+    if (given.block == 0) return fail(BGR_E_ARG, w + ": min_block is at least 1");
+    if (g->host.blob.empty()) return fail(BGR_E_ARG, w + ": the graph has no host blob (" + blob + ")");
+    if (g->header.has_exc) return fail(BGR_E_ARG, w + ": " + acgt);
+    return BGR_OK;
+}
+// The thresholds a run uses (under abundance_m).  link, what its bubbles are called with: that of the first switch that is on in the order bubbles,
+// phase, blocks, haplotypes -- the others are on top of it -- and the bubbles' stored one when none is.  phase, what its blocks are chained with: the
+// blocks' when their switch is on or the haplotypes' is off, else the haplotypes'.  block, the smallest block that is spelled: the haplotypes'.
+inline ChainMins run_thresholds(const bgr_graph* g) {
+    ChainMins m = {g->bubbles.min.link, g->blocks.on || !g->haplotypes.on ? g->blocks.min.phase : g->haplotypes.min.phase, g->haplotypes.min.block};
+    const ChainSwitch* const chain[4] = {&g->haplotypes, &g->blocks, &g->phase, &g->bubbles};
+    for (const ChainSwitch* s : chain) if (s->on) m.link = s->min.link;
+    return m;
+}
+
+// a file of lines: the header, then line(i, &buf) for i < n, in pieces of a megabyte
+template <class Line>
+int write_lines(const char* who, const char* path, const char* header, uint64_t n, Line line) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(BGR_E_IO, std::string(who) + ": cannot open " + path);
+    std::string buf = header;
+    bool ok = true;
+    for (uint64_t i = 0; i < n && ok; ++i) {
+        line(i, &buf);
+        if (buf.size() > (1u << 20)) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
+    }
+    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(BGR_E_IO, std::string(who) + ": write to " + path + " failed");
+    return BGR_OK;
+}
+
+// What one call needs on a device and nowhere after it: a stream (its own, made on the current device, or a borrowed one), events, buffers.  The
+// destructor waits for the stream first -- an early return may leave a copy into the caller's locals in flight -- then frees: nothing stays allocated.
+struct DeviceCall {
+    hipStream_t s = nullptr;
+    bool owned = false;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf buf[5];
+    int rc = BGR_OK;   // what the last room() that returned false has set
+    explicit DeviceCall(hipStream_t borrowed = nullptr) : s(borrowed) {}
+    DeviceCall(const DeviceCall&) = delete;
+    int own_stream() { HIP_TRY(hipStreamCreate(&s)); owned = true; return BGR_OK; }
+    int events(int n) { for (int i = 0; i < n; ++i) HIP_TRY(hipEventCreate(&ev[i])); return BGR_OK; }
+    bool room(DevBuf& b, uint64_t bytes, const std::string& what) {   // -> whether the device has `bytes` for b; else rc = BGR_E_NOMEM / BGR_E_HIP, "`what`: the runtime's words"
+        const hipError_t e = b.ensure(bytes);
+        if (e == hipSuccess) return true;
+        (void)hipGetLastError();
+        rc = fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, what + ": " + hipGetErrorString(e));
+        return false;
+    }
+    ~DeviceCall() {
+        if (s) (void)hipStreamSynchronize(s);
+        for (DevBuf& b : buf) b.release();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (owned) (void)hipStreamDestroy(s);
+    }
+};
+
 // ---- the functions that cross units --------------------------------------------------------------------------------------------
 // capi_abundance.hip
 int abundance_set(bgr_aligner* a, bool on);   // this one aligner's (or twin's) switch; the table is allocated and zeroed the first time
 bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases);   // geometry and form of the abundance kernel behind a launch of this size
-// capi_links.hip
-void links_share(bgr_aligner* a);   // the twins add to the aligner's table of links: its fields copied to each of them
-int links_tail(bgr_aligner* a, const char* who, uint64_t* tail);   // the three words behind the aligner's table, every stream that adds to it waited for; BGR_E_ARG when links were never enabled, BGR_E_CAPACITY when the table has overflowed
-void run_links_begin(bgr_graph* g);                   // a whole run (run_counts.h): the totals of the run before are gone,
-int run_links_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's table joins the run's,
-void run_links_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
-// capi_triples.hip
-void triples_share(bgr_aligner* a);   // the twins add to the aligner's table of triples: its fields copied to each of them
-void run_triples_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
-int run_triples_collect(bgr_graph* g, bgr_aligner* a);  // ... an aligner's table joins the run's,
-void run_triples_end(bgr_graph* g, bool ok);            // ... sorted and merged; totals only of a run that ended well
-void run_phase_begin(bgr_graph* g);
-int run_phase_end(bgr_graph* g, bool ok);               // ... behind the bubbles' and the triples' end: the run's bubbles joined with its triples on the host
-// capi_blocks.hip
-void run_blocks_begin(bgr_graph* g);
-int run_blocks_end(bgr_graph* g, bool ok);              // ... behind the phase's end: the run's bubbles and phase records uploaded once, chained on the device, the entries kept
-// capi_haplotypes.hip
-void run_haplotypes_begin(bgr_graph* g);
-int run_haplotypes_end(bgr_graph* g, bool ok);          // ... behind the blocks' end: the run's bubbles and entries uploaded once, spelled from the resident graph, records and bytes kept
-// capi_bubbles.hip
-void run_bubbles_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
-void run_bubbles_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's links will be called,
-int run_bubbles_end(bgr_graph* g, bool ok);             // ... behind the links' end: the merged links uploaded once, the four passes, the records kept
+// capi_links.hip: the count tables, links and triples
+void tables_share(bgr_aligner* a);   // the twins add to the aligner's tables of links and triples: its fields copied to each of them
+int links_tail(bgr_aligner* a, const char* who, uint64_t* tail);   // the three words behind the aligner's table of links, every stream that adds to it waited for; BGR_E_ARG when links were never enabled, BGR_E_CAPACITY when the table has overflowed
+void triples_records(const std::vector<std::array<uint64_t, 3>>& rows, bgr_triple* out);   // the rows of a table of triples as the interface's records
+// A whole run (run_counts.h, through the table of stages in capi_abundance.hip).  begin: the totals of the run before are gone; collect: an aligner's
+// table joins the run's; end: totals only of a run that ended well -- the tables sorted and merged, every stage of the chain called from the totals of
+// the one it reads (all on bubbles.device), BGR_OK when ok is false
+void run_links_begin(bgr_graph* g);
+int run_links_collect(bgr_graph* g, bgr_aligner* a);
+int run_links_end(bgr_graph* g, bool ok);
+void run_triples_begin(bgr_graph* g);
+int run_triples_collect(bgr_graph* g, bgr_aligner* a);
+int run_triples_end(bgr_graph* g, bool ok);
+void run_bubbles_begin(bgr_graph* g);                    // capi_bubbles.hip
+int run_bubbles_collect(bgr_graph* g, bgr_aligner* a);   // ... the first aligner's device is where the run's links will be called
+int run_bubbles_end(bgr_graph* g, bool ok);              // ... behind the links' end
+void run_phase_begin(bgr_graph* g);                      // capi_triples.hip
+int run_phase_end(bgr_graph* g, bool ok);                // ... behind the bubbles' and the triples' end: the two joined on the host
+void run_blocks_begin(bgr_graph* g);                     // capi_blocks.hip
+int run_blocks_end(bgr_graph* g, bool ok);               // ... behind the phase's end
+void run_haplotypes_begin(bgr_graph* g);                 // capi_haplotypes.hip
+int run_haplotypes_end(bgr_graph* g, bool ok);           // ... behind the blocks' end: spelled from the resident graph
+// The end of a chain stage under abundance_m: what it kept is forgotten; with ok, `call` makes the new rows (BGR_OK, or what it refuses with) provided
+// the stages it reads (`inputs_valid`, else BGR_E_INTERNAL with `missing`) have theirs and, where there is something to call from, an aligner was collected
+template <class F, class Call>
+int chain_stage_end(bgr_graph* g, F& f, bool ok, bool inputs_valid, const char* missing, bool anything, const char* uncollected, Call call) {
+    f.forget();
+    if (!ok) return BGR_OK;
+    int rc = BGR_OK;
+    if (!inputs_valid) rc = fail(BGR_E_INTERNAL, std::string("bgr_align_all: ") + missing);
+    else if (anything) rc = g->bubbles.device < 0 ? fail(BGR_E_INTERNAL, std::string("bgr_align_all: ") + uncollected + ", but no aligner of the run was collected") : call();
+    if (rc != BGR_OK) f.forget();
+    f.valid = rc == BGR_OK;
+    return rc;
+}
 // capi_pileup.hip
 void pileup_share(bgr_aligner* a);   // the twins add to the aligner's pileup tables: its fields copied to each of them
 int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who);   // BGR_E_CAPACITY when a reads column reached 2^32: a depth may have wrapped

@@ -269,76 +269,65 @@ int main(int argc, char** argv) {
         std::vector<bgr_unitig_abundance> rows(gi.n_unitigs);
         if (bgr_graph_abundance(graph, rows.data(), gi.n_unitigs) != BGR_OK || bgr_write_abundance(abundanceFile.c_str(), graph, rows.data(), gi.n_unitigs) != BGR_OK) die("abundance");
     }
+    // the two-call fetch of a run's records: the number first (BGR_E_CAPACITY with it), then the records
+    auto fetch = [&](auto call, auto& rows, const char* what) {
+        uint64_t n = 0;
+        if (call(graph, nullptr, 0, &n) != BGR_OK && n == 0) die(what);
+        rows.resize(n);
+        if (n && call(graph, rows.data(), n, &n) != BGR_OK) die(what);
+    };
     if (!gfaFile.empty()) {  // (likewise)
         bgr_graph_info_t gi;
         if (bgr_graph_info(graph, &gi) != BGR_OK) die("gfa");
         std::vector<bgr_unitig_abundance> rows(gi.n_unitigs);
-        uint64_t n_links = 0;
+        std::vector<bgr_link> links;
         if (bgr_graph_abundance(graph, rows.data(), gi.n_unitigs) != BGR_OK) die("gfa");
-        if (bgr_graph_links(graph, nullptr, 0, &n_links) != BGR_OK && n_links == 0) die("gfa");   // (BGR_E_CAPACITY with the number of links)
-        std::vector<bgr_link> links(n_links);
-        if (n_links && bgr_graph_links(graph, links.data(), n_links, &n_links) != BGR_OK) die("gfa");
-        if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), n_links) != BGR_OK) die("gfa");
+        fetch(bgr_graph_links, links, "gfa");
+        if (bgr_write_gfa(gfaFile.c_str(), graph, rows.data(), gi.n_unitigs, links.data(), links.size()) != BGR_OK) die("gfa");
     }
-    if (!bubblesFile.empty()) {  // (the run has called them from its merged links)
-        uint64_t n_bubbles = 0;
-        if (bgr_graph_bubbles(graph, nullptr, 0, &n_bubbles) != BGR_OK && n_bubbles == 0) die("--bubbles");   // (BGR_E_CAPACITY with the number of bubbles)
-        std::vector<bgr_bubble> bubbles(n_bubbles);
-        if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--bubbles");
-        if (bgr_write_bubbles(bubblesFile.c_str(), graph, bubbles.data(), n_bubbles) != BGR_OK) die("--bubbles");
+    // the run's bubbles (called from its merged links) and block entries (chained from its phase records): fetched once, for the first file that names them
+    std::vector<bgr_bubble> bubbles;
+    std::vector<bgr_block_entry> entries;
+    bool have_bubbles = false, have_entries = false;
+    auto need_bubbles = [&](const char* what) { if (!have_bubbles) fetch(bgr_graph_bubbles, bubbles, what); have_bubbles = true; };
+    auto need_entries = [&](const char* what) { need_bubbles(what); if (!have_entries) fetch(bgr_graph_blocks, entries, what); have_entries = true; };
+    if (!bubblesFile.empty()) {
+        need_bubbles("--bubbles");
+        if (bgr_write_bubbles(bubblesFile.c_str(), graph, bubbles.data(), bubbles.size()) != BGR_OK) die("--bubbles");
     }
     if (!triplesFile.empty()) {  // (the run's aligners' tables, merged and sorted)
-        uint64_t n_triples = 0;
-        if (bgr_graph_triples(graph, nullptr, 0, &n_triples) != BGR_OK && n_triples == 0) die("--triples");   // (BGR_E_CAPACITY with the number of triples)
-        std::vector<bgr_triple> triples(n_triples);
-        if (n_triples && bgr_graph_triples(graph, triples.data(), n_triples, &n_triples) != BGR_OK) die("--triples");
-        if (bgr_write_triples(triplesFile.c_str(), graph, triples.data(), n_triples) != BGR_OK) die("--triples");
+        std::vector<bgr_triple> triples;
+        fetch(bgr_graph_triples, triples, "--triples");
+        if (bgr_write_triples(triplesFile.c_str(), graph, triples.data(), triples.size()) != BGR_OK) die("--triples");
     }
     if (!phaseFile.empty()) {  // (the run has joined its bubbles with its triples)
-        uint64_t n_phase = 0;
-        if (bgr_graph_phase(graph, nullptr, 0, &n_phase) != BGR_OK && n_phase == 0) die("--phase");   // (BGR_E_CAPACITY with the number of records)
-        std::vector<bgr_phase> recs(n_phase);
-        if (n_phase && bgr_graph_phase(graph, recs.data(), n_phase, &n_phase) != BGR_OK) die("--phase");
-        if (bgr_write_phase(phaseFile.c_str(), graph, recs.data(), n_phase) != BGR_OK) die("--phase");
+        std::vector<bgr_phase> recs;
+        fetch(bgr_graph_phase, recs, "--phase");
+        if (bgr_write_phase(phaseFile.c_str(), graph, recs.data(), recs.size()) != BGR_OK) die("--phase");
     }
-    if (!blocksFile.empty()) {  // (the run has chained its phase records; the lines name the run's bubbles)
-        uint64_t n_bubbles = 0, n_entries = 0;
-        if (bgr_graph_bubbles(graph, nullptr, 0, &n_bubbles) != BGR_OK && n_bubbles == 0) die("--blocks");   // (BGR_E_CAPACITY with the number of bubbles)
-        std::vector<bgr_bubble> bubbles(n_bubbles);
-        if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--blocks");
-        if (bgr_graph_blocks(graph, nullptr, 0, &n_entries) != BGR_OK && n_entries == 0) die("--blocks");
-        std::vector<bgr_block_entry> entries(n_entries);
-        if (n_entries && bgr_graph_blocks(graph, entries.data(), n_entries, &n_entries) != BGR_OK) die("--blocks");
-        if (bgr_write_blocks(blocksFile.c_str(), graph, bubbles.data(), n_bubbles, entries.data(), n_entries) != BGR_OK) die("--blocks");
+    if (!blocksFile.empty()) {  // (the lines name the run's bubbles)
+        need_entries("--blocks");
+        if (bgr_write_blocks(blocksFile.c_str(), graph, bubbles.data(), bubbles.size(), entries.data(), entries.size()) != BGR_OK) die("--blocks");
     }
     if (!haplotypesFile.empty()) {  // (the run has spelled its blocks; the header lines name the walks over the run's bubbles)
-        uint64_t n_bubbles = 0, n_entries = 0, n_haps = 0, seq_bytes = 0;
-        if (bgr_graph_bubbles(graph, nullptr, 0, &n_bubbles) != BGR_OK && n_bubbles == 0) die("--haplotypes");   // (BGR_E_CAPACITY with the number of bubbles)
-        std::vector<bgr_bubble> bubbles(n_bubbles);
-        if (n_bubbles && bgr_graph_bubbles(graph, bubbles.data(), n_bubbles, &n_bubbles) != BGR_OK) die("--haplotypes");
-        if (bgr_graph_blocks(graph, nullptr, 0, &n_entries) != BGR_OK && n_entries == 0) die("--haplotypes");
-        std::vector<bgr_block_entry> entries(n_entries);
-        if (n_entries && bgr_graph_blocks(graph, entries.data(), n_entries, &n_entries) != BGR_OK) die("--haplotypes");
+        need_entries("--haplotypes");
+        uint64_t n_haps = 0, seq_bytes = 0;
         if (bgr_graph_haplotypes(graph, nullptr, 0, &n_haps, nullptr, 0, &seq_bytes) != BGR_OK && n_haps == 0) die("--haplotypes");
         std::vector<bgr_haplotype> haps(n_haps);
         std::vector<char> seq(seq_bytes);
         if (n_haps && bgr_graph_haplotypes(graph, haps.data(), n_haps, &n_haps, seq.data(), seq_bytes, &seq_bytes) != BGR_OK) die("--haplotypes");
-        if (bgr_write_haplotypes(haplotypesFile.c_str(), graph, bubbles.data(), n_bubbles, entries.data(), n_entries, haps.data(), n_haps, seq.data(), seq_bytes) != BGR_OK) die("--haplotypes");
+        if (bgr_write_haplotypes(haplotypesFile.c_str(), graph, bubbles.data(), bubbles.size(), entries.data(), entries.size(), haps.data(), n_haps, seq.data(), seq_bytes) != BGR_OK) die("--haplotypes");
     }
     if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");
     if (!vcfFile.empty() && strands) {   // (the 64-byte records of a run that counted strands)
-        uint64_t n_sites = 0;
-        if (bgr_graph_variant_strand_sites(graph, nullptr, 0, &n_sites) != BGR_OK && n_sites == 0) die("--vcf");   // (BGR_E_CAPACITY with the number of sites)
-        std::vector<bgr_variant_strand_site> sites(n_sites);
-        if (n_sites && bgr_graph_variant_strand_sites(graph, sites.data(), n_sites, &n_sites) != BGR_OK) die("--vcf");
-        if (bgr_write_vcf_strands(vcfFile.c_str(), graph, &sprm, sites.data(), n_sites) != BGR_OK) die("--vcf");
+        std::vector<bgr_variant_strand_site> sites;
+        fetch(bgr_graph_variant_strand_sites, sites, "--vcf");
+        if (bgr_write_vcf_strands(vcfFile.c_str(), graph, &sprm, sites.data(), sites.size()) != BGR_OK) die("--vcf");
     } else if (!vcfFile.empty()) {   // (the run has called the sites: they, not the table, are what the graph keeps)
-        uint64_t n_sites = 0;
-        if (bgr_graph_variants(graph, nullptr, 0, &n_sites) != BGR_OK && n_sites == 0) die("--vcf");   // (BGR_E_CAPACITY with the number of sites)
-        std::vector<bgr_variant_site> sites(n_sites);
-        if (n_sites && bgr_graph_variants(graph, sites.data(), n_sites, &n_sites) != BGR_OK) die("--vcf");
-        if (bgr_write_vcf(vcfFile.c_str(), graph, &vprm, sites.data(), n_sites) != BGR_OK) die("--vcf");
+        std::vector<bgr_variant_site> sites;
+        fetch(bgr_graph_variants, sites, "--vcf");
+        if (bgr_write_vcf(vcfFile.c_str(), graph, &vprm, sites.data(), sites.size()) != BGR_OK) die("--vcf");
     }
     const uint64_t rn = tot[0], no = tot[1], ali = tot[2], na = tot[3];
     std::cout << "The End" << std::endl;  // aligner.cpp:588-596

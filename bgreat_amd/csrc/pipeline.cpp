@@ -1567,36 +1567,23 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
     // what the run counts (run_counts.h): the graph's sticky switches, which imply unitig abundance whatever bgr_run_options.abundance says, and that option
     const uint32_t counts = (bgr::g_run_counts.wanted ? bgr::g_run_counts.wanted(graph) : 0) | (opt->abundance ? bgr::kCountAbundance : 0);
-    if (counts & bgr::kCountPileup) {   // the graph's switch (bgr_graph_pileup_enable): per-base counts, defined on the rows of the greedy modes
-        if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountVariants
-                                                  ? "bgr_align_all: SNV sites (--vcf, bgr_graph_variants_enable) are called from the pileup, which is for the greedy modes; the rows of exhaustive mode (-b) have another layout"
-                                                  : "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
-    }
-    if (counts & bgr::kCountLinks) {   // the graph's switch (bgr_graph_links_enable): links and unitig abundance, both defined on the rows of the greedy modes
-        if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, counts & bgr::kCountHaplotypes
-                                                  ? "bgr_align_all: the haplotypes' sequences (--haplotypes, bgr_graph_haplotypes_enable) are spelled along phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
-                                                  : counts & bgr::kCountBlocks
-                                                  ? "bgr_align_all: haplotype blocks (--blocks, bgr_graph_blocks_enable) chain phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
-                                                  : counts & bgr::kCountPhase
-                                                  ? "bgr_align_all: phasing (--phase, bgr_graph_phase_enable) joins bubbles and triples, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"
-                                                  : counts & bgr::kCountBubbles
-                                                  ? "bgr_align_all: bubbles (--bubbles, bgr_graph_bubbles_enable) are called from the link counts, which are for the greedy modes; the rows of exhaustive mode (-b) have another layout"
-                                                  : "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
-    }
-    if (counts & bgr::kCountTriples) {   // the graph's switch (bgr_graph_triples_enable): triples and unitig abundance, defined on the rows of the greedy modes
-        if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, "bgr_align_all: triple counting (--triples, bgr_graph_triples_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
-    }
-    if (opt->abundance) {   // unitig abundance: defined on the rows of the greedy modes; refused before any device work
-        if (prm->mode == BGR_MODE_EXHAUSTIVE)
-            return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout");
-        if (!bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
-    }
+    // Everything that is counted is defined on the rows of the greedy modes, and refused before any device work: in the words of the most derived
+    // feature that asks for it (the pileup's family first, then the links' chain from its end, then the features that stand alone).
+    static const struct { uint32_t bit; const char* refusal; } kGreedyOnly[] = {
+        {bgr::kCountVariants, "bgr_align_all: SNV sites (--vcf, bgr_graph_variants_enable) are called from the pileup, which is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountPileup, "bgr_align_all: the pileup (--pileup, --depth, bgr_graph_pileup_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountHaplotypes, "bgr_align_all: the haplotypes' sequences (--haplotypes, bgr_graph_haplotypes_enable) are spelled along phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountBlocks, "bgr_align_all: haplotype blocks (--blocks, bgr_graph_blocks_enable) chain phased bubbles, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountPhase, "bgr_align_all: phasing (--phase, bgr_graph_phase_enable) joins bubbles and triples, which are counted on the rows of the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountBubbles, "bgr_align_all: bubbles (--bubbles, bgr_graph_bubbles_enable) are called from the link counts, which are for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountLinks, "bgr_align_all: link counting (--gfa, bgr_graph_links_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountTriples, "bgr_align_all: triple counting (--triples, bgr_graph_triples_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+        {bgr::kCountAbundance, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
+    };
+    if (prm->mode == BGR_MODE_EXHAUSTIVE)
+        for (const auto& r : kGreedyOnly)
+            if (counts & r.bit) return bgr::set_error(BGR_E_ARG, r.refusal);
+    if (counts && !bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");
     if (counts) bgr::g_run_counts.begin(graph, counts);
     int run_rc;
     if (opt->split_output && opt->n_gpus > 1 && !opt->fastq && !progress_blocks && !correction && !opt->gaf && !opt->no_overlap_file)

@@ -1,11 +1,12 @@
 // run_counts.h -- how a whole run (pipeline.cpp, host code that knows the device side only through the C-ABI) reaches what the counting
 // features keep: the graph's sticky switches, the aligners' tables on the device and the run's totals in the graph object (unitig abundance,
-// links and their bubbles, triples and the bubbles' phase, blocks and haplotypes, the pileup with its SNV sites and strands: capi_abundance.hip, capi_links.hip, capi_triples.hip, capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip,
-// capi_variants.hip).  One unit of the
-// library (capi_abundance.hip) fills the table below when the library is loaded; pipeline.cpp calls through it, so it needs no symbol beyond
-// the ones it already used -- a build of pipeline.cpp against another implementation of the C-ABI (tests/sanitize_pipeline.cpp,
-// tools/pipeline_bench.cpp) links as before, sees the table all null, counts nothing and refuses a run with bgr_run_options.abundance = 1.
-// The orders in which the features are collected and ended live behind `collect` and `end`, next to the code they protect.
+// links and their bubbles, triples and the bubbles' phase, blocks and haplotypes, the pileup with its SNV sites and strands: capi_abundance.hip,
+// capi_links.hip (both count tables), capi_triples.hip (phase), capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip,
+// capi_variants.hip).  One unit of the library (capi_abundance.hip) fills the table below when the library is loaded; pipeline.cpp calls through
+// it, so it needs no symbol beyond the ones it already used -- a build of pipeline.cpp against another implementation of the C-ABI
+// (tests/sanitize_pipeline.cpp, tools/pipeline_bench.cpp) links as before, sees the table all null, counts nothing and refuses a run with
+// bgr_run_options.abundance = 1.  Behind the five entries is one table of stages (capi_abundance.hip); the rules that walk it -- which switch
+// implies which, in which order the stages end, what a failure does -- are run_stages.h's, plain C++ that tests/test_run_stages_host.py drives.
 #ifndef BGREAT_AMD_RUN_COUNTS_H
 #define BGREAT_AMD_RUN_COUNTS_H
 

@@ -237,3 +237,43 @@ def test_align_all_keeps_the_blocks_in_the_graph(synth_files, tmp_path):
         B.align_all(g, str(tmp_path / "missing.fa"), PF, NF)
     with pytest.raises(B.BgrError):
         g.blocks()
+
+
+def test_a_run_takes_each_threshold_from_the_first_switch_that_is_on(tmp_path):
+    """several switches of the chain with different thresholds: the run's bubbles are called with the min_link of the first switch that is on in the
+    order bubbles, phase, blocks, haplotypes; its blocks are chained with the blocks' min_phase, or with the haplotypes' when only that switch is on.
+    Every run against the bubbles and blocks recomputed from its own links and phase records with the expected thresholds.  The reads are those of two
+    planted haplotypes at a depth of four each (the synthetic files' links all have counts beyond 10: no threshold of 1 .. 3 tells on them), where
+    min_link 1, 2 and 3 call 55, 37 and 18 bubbles and min_phase 1 and 2 chain different blocks (counted on the CPU, and asserted below)"""
+    import bubbles_ref as BR
+    from test_gpu_haplotypes import planted
+    haps, unitigs, reads = planted(2, coverage=8, genome_len=9000, n_sites=60)
+    uf, rf, PF, NF = (str(tmp_path / x) for x in ("u.fa", "r.fa", "p", "n"))
+    open(uf, "w").write("".join(">u%d\n%s\n" % (i, u) for i, u in enumerate(unitigs)))
+    open(rf, "w").write("".join(">r%d\n%s\n" % (i, r) for i, r in enumerate(reads)))
+    runs = [   # the switches of the run, the min_link and the min_phase (None: the run chains no blocks) it has to use
+        (dict(bubbles=dict(min_link=1), haplotypes=dict(min_link=3, min_phase=2)), 1, 2),
+        (dict(phase=dict(min_link=2), blocks=dict(min_link=3)), 2, 1),
+        (dict(blocks=dict(min_link=2, min_phase=1), haplotypes=dict(min_link=9, min_phase=2)), 2, 1),
+        (dict(haplotypes=dict(min_link=2, min_phase=2)), 2, 2),
+        (dict(bubbles=dict(min_link=3), phase=dict(min_link=1)), 3, None),
+        (dict(phase=dict(min_link=3)), 3, None),
+    ]
+    seen = {}
+    for switches, min_link, min_phase in runs:
+        g = B.Graph.from_fasta(uf, 31)
+        for name, kw in switches.items():
+            getattr(g, name + "_enable")(**kw)
+        B.align_all(g, rf, PF, NF, m=2, effort=2, threads=2)
+        bubbles, phase = BR.as_tuples(g.bubbles()), P.as_tuples(g.phase())
+        seen[min_link] = BR.as_tuples(B.links_bubbles(g.links(), len(unitigs), min_link=min_link))
+        assert bubbles == seen[min_link], (switches, min_link)
+        if min_phase is None:
+            with pytest.raises(B.BgrError):
+                g.blocks()
+        else:
+            want = R.blocks_of(bubbles, phase, min_phase)
+            assert R.as_tuples(g.blocks()) == want, (switches, min_phase)
+            assert want != R.blocks_of(bubbles, phase, 3 - min_phase), "min_phase 1 and 2 chain the same blocks: the run cannot tell the rules apart"
+        g.close()
+    assert [len(seen[m]) for m in (1, 2, 3)] == [55, 37, 18], "min_link 1, 2 and 3 have to call three different lists of bubbles"

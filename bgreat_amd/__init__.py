@@ -44,6 +44,7 @@ SYMBOLS = [
     "bgr_bubbles_phase", "bgr_graph_phase_enable", "bgr_graph_phase_enabled", "bgr_graph_phase", "bgr_write_phase",
     "bgr_phase_blocks", "bgr_phase_blocks_times", "bgr_graph_blocks_enable", "bgr_graph_blocks_enabled", "bgr_graph_blocks", "bgr_write_blocks",
     "bgr_blocks_haplotypes", "bgr_blocks_haplotypes_times", "bgr_graph_haplotypes_enable", "bgr_graph_haplotypes_enabled", "bgr_graph_haplotypes", "bgr_write_haplotypes",
+    "bgr_blocks_tag_table", "bgr_read_blocks_tags", "bgr_aligner_haplotag_enable", "bgr_aligner_haplotags", "bgr_graph_haplotag_enable", "bgr_graph_haplotag_enabled",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -350,6 +351,12 @@ def lib():
     L.bgr_graph_haplotypes_enabled.argtypes = [vp]
     L.bgr_graph_haplotypes.argtypes = [vp, vp, u64, vp, vp, u64, vp]
     L.bgr_write_haplotypes.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, u64, vp, u64]
+    L.bgr_blocks_tag_table.argtypes = [vp, u64, vp, u64, u64, u64, vp, vp]
+    L.bgr_read_blocks_tags.argtypes = [C.c_char_p, u64, vp, vp]
+    L.bgr_aligner_haplotag_enable.argtypes = [vp, vp, u64]
+    L.bgr_aligner_haplotags.argtypes = [vp, u64, vp]
+    L.bgr_graph_haplotag_enable.argtypes = [vp, vp, u64]
+    L.bgr_graph_haplotag_enabled.argtypes = [vp]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -792,6 +799,19 @@ class Graph:
         the characters as one uint8 array the records point into)."""
         return _fetch_haplotypes(lambda out, cap, n, seq, seq_cap, seq_bytes: lib().bgr_graph_haplotypes(self.h, out, cap, n, seq, seq_cap, seq_bytes))
 
+    def haplotag_enable(self, table):
+        """bgr_graph_haplotag_enable: sticky -- every later align_all with gaf on this graph tags its lines from `table` (n_unitigs + 1 uint32, as
+        blocks_tag_table / read_blocks_tags make it; the graph keeps a copy); None switches it off."""
+        if table is None:
+            _check(lib().bgr_graph_haplotag_enable(self.h, None, 0))
+            return
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        _check(lib().bgr_graph_haplotag_enable(self.h, table.ctypes.data, table.shape[0]))
+
+    def haplotag_enabled(self):
+        """bgr_graph_haplotag_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_haplotag_enabled(self.h))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -957,6 +977,21 @@ class Aligner:
         out = np.zeros(n, dtype=np.dtype([("path_len", np.uint64), ("path_start", np.uint64), ("aligned", np.uint32), ("mismatches", np.uint32)]))
         assert out.dtype.itemsize == C.sizeof(PathStat)
         _check(lib().bgr_aligner_path_stats(self.h, d_reads_ptr, d_offsets_ptr, n, out.ctypes.data))
+        return out
+
+    def haplotag_enable(self, table):
+        """bgr_aligner_haplotag_enable: `table` (n_unitigs + 1 uint32) onto the aligner's device -- haplotags() and the GAF lines of align_fasta_text
+        are tagged from it; None switches it off and frees the copy."""
+        if table is None:
+            _check(lib().bgr_aligner_haplotag_enable(self.h, None, 0))
+            return
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        _check(lib().bgr_aligner_haplotag_enable(self.h, table.ctypes.data, table.shape[0]))
+
+    def haplotags(self, n):
+        """bgr_aligner_haplotags over the rows of the last launch -> array of READ_TAG_DTYPE, n rows (zeros for an unmapped read)."""
+        out = np.zeros(n, dtype=READ_TAG_DTYPE)
+        _check(lib().bgr_aligner_haplotags(self.h, n, out.ctypes.data if n else None))
         return out
 
     def abundance_enable(self, on=True):
@@ -1298,6 +1333,27 @@ def write_blocks(path, graph, bubbles, entries):
     bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
     entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
     _check(lib().bgr_write_blocks(path.encode(), graph.h, bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0]))
+
+
+READ_TAG_DTYPE = np.dtype([("block", np.uint32), ("a", np.uint32), ("b", np.uint32), ("others", np.uint32)])   # an array of bgr_read_tag
+
+
+def blocks_tag_table(bubbles, entries, n_unitigs, min_block=1):
+    """bgr_blocks_tag_table: the tag table of the blocks of at least min_block bubbles, from `bubbles` (BUBBLE_DTYPE) and `entries` (BLOCK_DTYPE)
+    -> (uint32 array of n_unitigs + 1: block << 1 | hap per branch unitig, else 0; the number of tagged unitigs)."""
+    bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+    entries = np.ascontiguousarray(entries, dtype=BLOCK_DTYPE)
+    table, n = np.zeros(int(n_unitigs) + 1, dtype=np.uint32), C.c_uint64(0)
+    _check(lib().bgr_blocks_tag_table(bubbles.ctypes.data if len(bubbles) else None, bubbles.shape[0], entries.ctypes.data if len(entries) else None, entries.shape[0], int(n_unitigs),
+                                      int(min_block), table.ctypes.data, C.byref(n)))
+    return table, int(n.value)
+
+
+def read_blocks_tags(path, n_unitigs):
+    """bgr_read_blocks_tags: the tag table from a --blocks file (every block of it tags) -> (uint32 array of n_unitigs + 1, the number of tagged unitigs)."""
+    table, n = np.zeros(int(n_unitigs) + 1, dtype=np.uint32), C.c_uint64(0)
+    _check(lib().bgr_read_blocks_tags(str(path).encode(), int(n_unitigs), table.ctypes.data, C.byref(n)))
+    return table, int(n.value)
 
 
 def _fetch_haplotypes(call):

@@ -429,7 +429,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
         a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.buf.release(); a->triples.buf.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
         for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
-                          &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats}) b->release();
+                          &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats, &a->haplotag, &a->haplotag_out, &a->tx_tags}) b->release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
         if (a->ev_wait) (void)hipEventDestroy(a->ev_wait);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -973,7 +973,8 @@ static int fetch_text_impl(bgr_aligner* a, bgr_text_batch* b) {
         ? bgr::launch_text_gaf_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
                                      static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
                                      static_cast<const uint32_t*>(a->tx_noff.p), static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_idx.p),
-                                     static_cast<const uint4*>(a->tx_gaf.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p), a->stream)
+                                     static_cast<const uint4*>(a->tx_gaf.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p),
+                                     a->tx_tagged ? static_cast<const uint4*>(a->tx_tags.p) : nullptr, a->stream)
         : a->tx_want == 2
         ? bgr::launch_text_correct_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
                                          static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
@@ -1186,10 +1187,13 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     // 4. sizes of the records, stream offsets, the bytes
     if (b->want_output == 3) {  // (tx_idx is free again behind the compaction: it takes the lengths of the names)
         HIP_TRY(a->tx_gaf.ensure(((uint64_t)n_acc + 1) * 16));
+        a->tx_tagged = a->haplotag.p != nullptr;   // (an aligner with a tag table: the tagged instances of both GAF kernels)
+        if (a->tx_tagged) HIP_TRY(a->tx_tags.ensure(((uint64_t)n_acc + 1) * 16));
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
         e = bgr::launch_text_gaf_sizes(a->dg, text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
                                        static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, static_cast<uint32_t*>(a->tx_psz.p), static_cast<uint32_t*>(a->tx_nsz.p),
-                                       static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint4*>(a->tx_gaf.p), info + TXT_INFO_BUG, a->stream);
+                                       static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint4*>(a->tx_gaf.p), info + TXT_INFO_BUG,
+                                       a->tx_tagged ? static_cast<const uint32_t*>(a->haplotag.p) : nullptr, static_cast<uint4*>(a->tx_tags.p), a->stream);
     } else if (b->want_output == 2) {  // (tx_idx is free again behind the compaction: it takes the corrected reads' lengths)
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
         e = bgr::launch_text_correct_sizes(a->dg, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),

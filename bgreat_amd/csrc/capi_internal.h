@@ -1,6 +1,6 @@
 // capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; the counting features:
 // capi_abundance.hip with the table of a run's stages, capi_links.hip with the count tables of links and triples, capi_triples.hip with the phase,
-// capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_pileup.hip, capi_variants.hip): the objects behind the opaque handles, the error
+// capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_haplotag.hip, capi_pileup.hip, capi_variants.hip): the objects behind the opaque handles, the error
 // channel, the waits, the helpers the counting features are written with (delivering rows, the chain's switches and thresholds, a file of lines,
 // a call's stream and buffers), and the few functions that cross units.  Nothing in here is part of the interface (include/bgreat_gpu.h) or
 // leaves the library.
@@ -83,6 +83,9 @@ struct bgr_graph {
     // bubbles, phase, blocks, haplotypes (bgr_graph_*_enable): each switch with the thresholds it was given (run_thresholds below says which of them a
     // run uses).  bubbles.device: the device of the first aligner a run collected (-1: none yet), where the run's merged links are called when it ends
     // and the later stages of the chain run; haplotypes.seq: the characters the records point into
+    // haplotags (bgr_graph_haplotag_enable): the sticky switch and the graph's copy of the tag table, n_unitigs + 1 words
+    bool haplotag_on = false;
+    std::vector<uint32_t> haplotag;
     struct Bubbles : ChainSwitch, RunRows<bgr_bubble> { int device = -1; } bubbles;
     struct Phase : ChainSwitch, RunRows<bgr_phase> {} phase;
     struct Blocks : ChainSwitch, RunRows<bgr_block_entry> {} blocks;
@@ -215,6 +218,10 @@ struct bgr_aligner {
     bool strands_on = false;        // bgr_aligner_pileup_strands_enable: the pileup kernel also adds the forward observations to a second table
     DevBuf pileup_fwd;              // that table: the layout of `pileup`, its tail stays 0
     uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
+    // haplotags (bgr_aligner_haplotag_enable): the tag table on the device (null: off), the tags of the last call of bgr_aligner_haplotags; the text
+    // route's tags per accepted read next to tx_gaf, and whether the sizes launch of the piece in the buffers was a tagged one (the write launch follows it)
+    DevBuf haplotag, haplotag_out, tx_tags;
+    bool tx_tagged = false;
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
@@ -384,6 +391,9 @@ int chain_stage_end(bgr_graph* g, F& f, bool ok, bool inputs_valid, const char* 
     f.valid = rc == BGR_OK;
     return rc;
 }
+// capi_haplotag.hip: the graph's tag table while its switch is on (else null), and the table onto an aligner's device (run_counts.h)
+const uint32_t* run_haplotag_table(const bgr_graph* g, uint64_t* n_rows);
+int run_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
 // capi_pileup.hip
 void pileup_share(bgr_aligner* a);   // the twins add to the aligner's pileup tables: its fields copied to each of them
 int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who);   // BGR_E_CAPACITY when a reads column reached 2^32: a depth may have wrapped

@@ -52,6 +52,10 @@
 //                                                               the device from the graph's 2-bit store: per sequence a line ">block<b>_<A|B> bubbles= length= ring= walk=" and
 //                                                               the sequence on one line; blocks of fewer than N (1) bubbles are left out; counts, calls and chains what
 //                                                               --blocks does: include/bgreat_gpu.h)
+//                                                   --haplotag BLOCKS_FILE (with --gaf: tag every read with the haplotype it lies on -- BLOCKS_FILE is the --blocks file of an earlier run on the same
+//                                                               unitig file, of these reads or of others; a line whose path crosses a branch of a block gains
+//                                                               PS:i:<block> HP:i:<0|1|2> ha:i: hb:i: ho:i: (votes for haplotype A, for B, for other blocks), computed on the
+//                                                               device where the line is formatted; not with -b: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -73,7 +77,7 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile, haplotypesFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile, haplotypesFile, haplotagFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
     bool vprm_given = false, strands = false, strand_given = false;
@@ -97,6 +101,7 @@ int main(int argc, char** argv) {
                                 {"triples", required_argument, nullptr, 1021}, {"phase", required_argument, nullptr, 1022},
                                 {"blocks", required_argument, nullptr, 1023}, {"min-phase", required_argument, nullptr, 1024},
                                 {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
+                                {"haplotag", required_argument, nullptr, 1027},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -192,6 +197,7 @@ int main(int argc, char** argv) {
                 min_block_given = true;
                 break;
             }
+            case 1027: haplotagFile = optarg; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -209,12 +215,20 @@ int main(int argc, char** argv) {
     if (min_link_given && bubblesFile.empty() && phaseFile.empty() && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE, --phase FILE, --blocks FILE and --haplotypes FILE\n"); return 2; }
     if (min_phase_given && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-phase is the threshold of --blocks FILE and --haplotypes FILE\n"); return 2; }
     if (min_block_given && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-block is the threshold of --haplotypes FILE\n"); return 2; }
+    if (!haplotagFile.empty() && !gaf) { fprintf(stderr, "bgreat: --haplotag BLOCKS_FILE adds its fields to the lines of --gaf\n"); return 2; }
+    if (!haplotagFile.empty() && brute) { fprintf(stderr, "bgreat: --haplotag tags GAF lines, which are for the greedy modes; exhaustive mode (-b) writes no paths\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
     bgr_graph* graph = nullptr;
     bgr_set_build_threads((uint32_t)std::max(1, threads));
     if (bgr_graph_build_from_fasta_ex(unitigs.c_str(), (uint32_t)ka, 0.0, dog ? BGR_BUILD_ANCHORS : 0u, &graph) != BGR_OK) die("index");
+    if (!haplotagFile.empty()) {   // (before anything is mapped: a file that does not parse ends the run here, with the line named)
+        bgr_graph_info_t gi;
+        if (bgr_graph_info(graph, &gi) != BGR_OK) die("--haplotag");
+        std::vector<uint32_t> table(gi.n_unitigs + 1);
+        if (bgr_read_blocks_tags(haplotagFile.c_str(), gi.n_unitigs, table.data(), nullptr) != BGR_OK || bgr_graph_haplotag_enable(graph, table.data(), table.size()) != BGR_OK) die("--haplotag");
+    }
     // one host -> device copy, then device to device over xGMI (RCCL broadcast, or peer copies): include/bgreat_gpu.h
     int64_t one_device = 0, timing = 0;  // (test hook: every lane on device 0)
     (void)bgr_get_option("test.lanes_on_one_device", &one_device);

@@ -36,13 +36,14 @@
 #include "../../include/bgreat_gpu.h"
 #include "fastx.h"
 #include "file_image.h"
+#include "haplotag_host.h"
 #include "read_pack.h"
 #include "options.h"
 #include "run_counts.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip
-RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
+RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
 }
 
 namespace {
@@ -444,8 +445,9 @@ void format_range(const Batch& b, uint64_t lo, uint64_t hi, std::string& pbuf, s
 // Returns false on the reference's "bug compaction" condition (aligner.cpp:280-283: it prints "bug compaction", the walk
 // so far and the unitig that does not continue it, and exits); the buffers then hold the records BEFORE that read and
 // `bug` the two strings the reference prints.
+// tag_table (n_unitigs + 1 words, or null): a GAF line gains the fields of its read's haplotag (haplotag_host.h), computed from the path ints held here.
 bool format_range_ext(const Batch& b, uint64_t lo, uint64_t hi, const Unitigs* correct, bool gaf, bool split_no_overlap, std::string& pbuf,
-                      std::string& nbuf, std::string& obuf, std::string& bug) {
+                      std::string& nbuf, std::string& obuf, std::string& bug, const uint32_t* tag_table = nullptr, uint64_t tag_rows = 0) {
     const int32_t* paths = static_cast<const int32_t*>(b.pin->paths.p);
     const uint64_t* poffs = static_cast<const uint64_t*>(b.pin->poffs.p);
     const uint8_t* status = static_cast<const uint8_t*>(b.pin->status.p);
@@ -460,6 +462,10 @@ bool format_range_ext(const Batch& b, uint64_t lo, uint64_t hi, const Unitigs* c
             if (np < 2 || !gaf_line(*correct, paths + poffs[i], np, r.h, r.hl, r.s, r.sl, (status[i] & BGR_ST_RC) != 0, pbuf, walk, tmp, rc, fwd)) {
                 bug = walk + " " + tmp;
                 return false;
+            }
+            if (tag_table) {
+                const bgr_read_tag tag = bgr::haplotag_row(tag_table, tag_rows - 1, paths + poffs[i] + 1, np - 1);
+                if (tag.block) { pbuf.pop_back(); bgr::haplotag_suffix(tag, &pbuf); pbuf.push_back('\n'); }
             }
         } else if (np) {
             if (correct && (np < 2 || !recover_path(*correct, paths + poffs[i], np, r.sl, walk, tmp, rc))) {
@@ -558,6 +564,10 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
     const bool writes = prm->mode != BGR_MODE_EXHAUSTIVE || opt->write_exhaustive;
     const bool correction = opt->correction && prm->mode != BGR_MODE_EXHAUSTIVE;  // alignPartExhaustive ignores -c
     const bool gaf = opt->gaf != 0;  // (bgr_align_all has refused it in exhaustive mode, with -c and on a graph with exception planes)
+    // haplotags (bgr_graph_haplotag_enable; bgr_align_all has refused a run without gaf): the graph's table goes onto every aligner's device, and the
+    // host formatter tags from the same words
+    uint64_t tag_rows = 0;
+    const uint32_t* tag_table = gaf && bgr::g_run_counts.haplotag_table ? bgr::g_run_counts.haplotag_table(graph, &tag_rows) : nullptr;
     const bool progress_blocks = opt->echo_files && prm->mode == BGR_MODE_EXHAUSTIVE;
     // Text route: the device parses, packs, maps and formats (bgr_align_fasta_text); the host only moves bytes.  FASTA, the
     // reference's two output files and no -b progress blocks (those count getReads() calls, which only the host parser tracks).
@@ -618,6 +628,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             // (nobody reads bgr_aligner_kernel_times here: no events around the kernels -- they cost a 262 144-read piece's mapping launch a tenth of its time)
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
             if (counts) rc = bgr::g_run_counts.enable(a, counts);  // every launch of the run is followed by the kernels of what it counts (bgr_align_all has checked the table)
+            if (rc == BGR_OK && tag_table) rc = bgr::g_run_counts.haplotag_enable(a, tag_table, tag_rows);
             aligners.push_back(a);
             if (rc != BGR_OK) {
                 for (auto* x : aligners) bgr_aligner_destroy(x);
@@ -1368,7 +1379,7 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
                     uint64_t lo = t * per, hi = std::min<uint64_t>(cp->n, lo + per);
                     if (lo >= hi) return;
                     if (!extended) format_range(*cp, lo, hi, pb[t], nb[t]);
-                    else okv[t] = format_range_ext(*cp, lo, hi, (correction || gaf) ? &unitigs : nullptr, gaf, ovlF != nullptr, pb[t], nb[t], ob[t], bugv[t]) ? 1 : 0;
+                    else okv[t] = format_range_ext(*cp, lo, hi, (correction || gaf) ? &unitigs : nullptr, gaf, ovlF != nullptr, pb[t], nb[t], ob[t], bugv[t], tag_table, tag_rows) ? 1 : 0;
                 }, 3);
                 // "bug compaction": like the reference, everything before the offending read is written, nothing after it
                 unsigned t_stop = threads;
@@ -1563,6 +1574,11 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) and correction (-c) both claim the paths file; choose one");
         if (gi.has_exceptions)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) needs a graph of ACGT-only unitigs: on one with other characters a path read backwards does not spell the reverse complement");
+    }
+    if (!opt->gaf && bgr::g_run_counts.haplotag_table) {   // tags are fields of GAF lines: a run with the switch on and no GAF output has nowhere to put them
+        uint64_t tag_rows = 0;
+        if (bgr::g_run_counts.haplotag_table(graph, &tag_rows))
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: haplotags (--haplotag, bgr_graph_haplotag_enable) are fields of GAF lines; the run needs bgr_run_options.gaf (--gaf)");
     }
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
     // what the run counts (run_counts.h): the graph's sticky switches, which imply unitig abundance whatever bgr_run_options.abundance says, and that option

@@ -21,6 +21,10 @@ struct RunCounts {
     int (*enable)(bgr_aligner* a, uint32_t what);                  // every launch of this aligner counts
     int (*collect)(bgr_graph* g, bgr_aligner* a, uint32_t what);   // the aligner's tables (its streams waited for) join the run's totals: links, triples, pileup (+ variants), abundance, in that order
     int (*end)(bgr_graph* g, uint32_t what, bool ok);              // totals only of a run that ended well: abundance, links, triples, the bubbles behind the links, the phase behind both, the blocks behind the phase, the haplotypes behind the blocks, then the pileup behind the abundance totals (BGR_E_CAPACITY when a depth may have wrapped)
+    // haplotags count nothing and are no stage of the run: the graph's tag table while bgr_graph_haplotag_enable is on (else null), and the call that puts
+    // it on an aligner's device, whose GAF lines are tagged from then on; a run's host formatter tags from the same table (haplotag_host.h)
+    const uint32_t* (*haplotag_table)(const bgr_graph* g, uint64_t* n_rows);
+    int (*haplotag_enable)(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
 };
 extern RunCounts g_run_counts;   // pipeline.cpp; all null until the library's C-ABI units have registered
 

@@ -53,10 +53,10 @@ hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* tex
 // matches, NM (text_kernels.hip).  Sizes (psz / nsz, scanned by launch_scan2_u32), then the bytes; nlen (characters of the name), rows ({walk size low, high,
 // characters covered, NM} per accepted read) and psz pass from the first to the second.  *bug as launch_text_correct_sizes sets it.
 hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, hipStream_t stream);
+                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream);
 hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                  const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
-                                 hipStream_t stream);
+                                 const uint4* tags, hipStream_t stream);   // tag_table / tags (bgr_read_tag per read) null: the untagged kernels; else the tagged instances (haplotag_device.h)
 // bgr_aligner_path_stats: per read of a bgr_align_device launch six words {walk size low, high, path start low, high, characters covered, NM | 1 << 31 "spells no walk"}
 hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out,
                              hipStream_t stream);

@@ -11,6 +11,7 @@
 #include "device_common.h"
 #include "text_kernels.h"
 #include "walk_lanes.h"
+#include "haplotag_device.h"
 
 #ifdef BGR_X_TIMES
 __device__ unsigned long long bgr_x_times[4 * 16];
@@ -119,14 +120,6 @@ __global__ void __launch_bounds__(kTxtThreads) bgr_scan2_apply(const uint32_t* i
 // bit 7 of every byte of x that equals the byte replicated in `pat`
 __device__ __forceinline__ uint32_t eq_bytes(uint32_t x, uint32_t pat) { return bgr_zero_bytes(x ^ pat); }
 
-// min over the 16 lanes of a row, result in every lane
-__device__ __forceinline__ uint32_t row16_min(uint32_t x) {
-    uint32_t o = quad_xor1(x); x = o < x ? o : x;
-    o = quad_xor2(x); x = o < x ? o : x;
-    o = half_row_mirror(x); x = o < x ? o : x;
-    o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true); x = o < x ? o : x;  // row_mirror
-    return x;
-}
 // 16 bytes from `p` (any alignment; bytes at or beyond `end` read as zero)
 __device__ __forceinline__ void load16(const uint8_t* text, uint32_t p, uint32_t end, uint32_t w[4]) {
     w[0] = w[1] = w[2] = w[3] = 0;
@@ -922,6 +915,7 @@ struct GafStat {
     uint32_t cl = 0, nm = 0, segbytes = 0;   // segbytes: characters of the segment column ('>' or '<' and the id, per unitig)
     uint32_t obits = 0;                      // bit i: unitig i of the path (the first 32) was glued on in its forward strand
     bool bad = false;                        // the path spells no walk (the -c kernels' bug-compaction condition)
+    int32_t sid0 = 0;                        // this lane's path int of the first pass (0 behind the path's end): what the tagged instances vote with
 };
 __device__ __forceinline__ uint32_t dec_digits(u64 u) {   // characters of to_string(u)
     uint32_t n = 1;
@@ -964,6 +958,7 @@ __device__ __forceinline__ GafStat gaf_stat(const BgrDeviceGraph& g, const int32
         if (!walk_pass<WIDE>(g, path, nu, u0, sub, carry, w)) { s.bad = true; return s; }
         const uint32_t u = u0 + sub, id = w.id, len = w.len, st = w.st, last = w.last;
         const bool on = w.on;
+        if (u0 == 0) s.sid0 = w.sid;
         const u64 F = w.F, start = w.start, end = w.end, total = w.pass_start, pass_end = w.pass_end;
         s.segbytes += row16_sum(on ? 1u + dec_digits(id) : 0u);
         s.obits |= row16_sum(on && u < 32 && st == 0 ? 1u << u : 0u);
@@ -1021,9 +1016,14 @@ __device__ __forceinline__ uint32_t gaf_fixed_bytes(uint32_t L, uint32_t qs, uin
 // 2^32 bases): the write kernel walks the path itself}, nlen = characters of the name.  (Measured: with the write kernel walking every path for the
 // orientations, as -c's does for the bases, it took 150 us per 262 144 reads, of which the walk's dependent loads were two thirds.)
 // *bug as correct_sizes sets it.
-template <bool WIDE>
+// TAG (the aligner has a tag table, bgr_aligner_haplotag_enable): the read's tag is computed here, where the walk holds the path's first sixteen ids in
+// its lanes, kept in tags[a] next to the row, and the bytes of its five fields are part of the line's size.
+__device__ __forceinline__ uint32_t gaf_tag_bytes(const bgr_read_tag& t) {   // "\tPS:i:" and its four siblings, HP's one digit, four numbers
+    return t.block ? 31 + dec_digits(t.block) + dec_digits(t.a) + dec_digits(t.b) + dec_digits(t.others) : 0u;
+}
+template <bool WIDE, bool TAG>
 __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
+                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n_acc) return;
     const uint2 res = results[a];
@@ -1031,16 +1031,21 @@ __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t
     const uint32_t np = res.y & 0xFFFFFFu, L = r.w & 0x7FFFFFFFu;
     uint32_t ps = 0, ns = 0, nl = 0;
     uint4 row = make_uint4(0, 0, 0, 0);
+    bgr_read_tag tag = {0, 0, 0, 0};
     if (np) {
         const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
         const GafStat s = gaf_stat<WIDE, true>(g, arena + res.x, np, text + r.z, L, rc, sub);
         if (s.bad) { if (sub == 0) atomicMin(bug, a); }
         else {
+            if (TAG) {   // (np >= 2 here; every lane of the group is: s.bad is the same in all sixteen)
+                const uint32_t n_unitigs = (uint32_t)g.hdr->n_unitigs;
+                tag = haplotag_group(tag_table, n_unitigs, arena + res.x + 1, np - 1, haplotag_vote(tag_table, n_unitigs, s.sid0), sub);
+            }
             nl = gaf_name_len(text, r.x, r.y, sub);
             uint32_t qs, qe;
             u64 pstart;
             gaf_intervals(rc, L, (u64)arena[res.x], s.plen, s.cl, qs, qe, pstart);
-            ps = (nl ? nl : 1u) + s.segbytes + gaf_fixed_bytes(L, qs, qe, s.plen, pstart, s.cl, s.nm);
+            ps = (nl ? nl : 1u) + s.segbytes + gaf_fixed_bytes(L, qs, qe, s.plen, pstart, s.cl, s.nm) + (TAG ? gaf_tag_bytes(tag) : 0u);
             const bool again = np - 1 > 32 || (s.plen >> 32) != 0;   // (more than the row holds: the write kernel walks the path itself)
             row = make_uint4((uint32_t)s.plen, s.obits, s.cl, s.nm | (again ? 0x80000000u : 0u));
         }
@@ -1048,14 +1053,21 @@ __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t
         ns = r.y + L + 2;
     }
     if (sub == 0) { psz[a] = ps; nsz[a] = ns; nlen[a] = nl; rows[a] = row; }
+    if (TAG && sub == 1) tags[a] = make_uint4(tag.block, tag.a, tag.b, tag.others);
 }
 __global__ void __launch_bounds__(256) bgr_text_gaf_sizes_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
                                                                  const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
-    gaf_sizes<false>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
+    gaf_sizes<false, false>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, nullptr, nullptr);
 }
 __global__ void __launch_bounds__(256) bgr_text_gaf_sizes_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
                                                                       const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
-    gaf_sizes<true>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
+    gaf_sizes<true, false>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, nullptr, nullptr);
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(256) bgr_text_gaf_sizes_tag_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                     const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug,
+                                                                     const uint32_t* tag_table, uint4* tags) {
+    gaf_sizes<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
 }
 
 // lead + to_string(v) at d[pos ...] by the lane whose turn it is -> the position behind it (every lane keeps count)
@@ -1064,12 +1076,18 @@ __device__ __forceinline__ uint32_t gaf_put(uint8_t* d, uint32_t pos, u64 v, boo
     if (mine) { d[pos] = lead; put_dec(d + end, v); }
     return end;
 }
+// "\t" c0 c1 ":i:" to_string(v) at d[pos ...] by the lane whose turn it is -> the position behind it
+__device__ __forceinline__ uint32_t gaf_put_tag(uint8_t* d, uint32_t pos, uint8_t c0, uint8_t c1, uint32_t v, bool mine) {
+    const uint32_t end = pos + 6 + dec_digits(v);
+    if (mine) { d[pos] = '\t'; d[pos + 1] = c0; d[pos + 2] = c1; d[pos + 3] = ':'; d[pos + 4] = 'i'; d[pos + 5] = ':'; put_dec(d + end, v); }
+    return end;
+}
 // one 16-lane group per accepted read: a mapped read's line at its offset (the numbers by one lane each, the segments by the lanes in turn),
-// the others into the notAligned stream as correct_write sends them
-template <bool WIDE>
+// the others into the notAligned stream as correct_write sends them.  TAG: the five fields of tags[a] behind NM, by the lanes 12 .. 15 and 0
+template <bool WIDE, bool TAG>
 __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
                                           uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows,
-                                          uint8_t* pout, uint8_t* nout) {
+                                          uint8_t* pout, uint8_t* nout, const uint4* tags) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n_acc) return;
     const uint2 res = results[a];
@@ -1100,7 +1118,9 @@ __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t
     u64 pstart;
     gaf_intervals(rc, L, off, plen, cl, qs, qe, pstart);
     const uint32_t name = nl ? nl : 1u;
-    const uint32_t segbytes = line - name - gaf_fixed_bytes(L, qs, qe, plen, pstart, cl, nm);
+    bgr_read_tag tag = {0, 0, 0, 0};
+    if (TAG) { const uint4 t = tags[a]; tag.block = t.x; tag.a = t.y; tag.b = t.z; tag.others = t.w; }
+    const uint32_t segbytes = line - name - gaf_fixed_bytes(L, qs, qe, plen, pstart, cl, nm) - (TAG ? gaf_tag_bytes(tag) : 0u);
     if (nl) group_copy(d, text + r.x + 1, nl, sub);
     else if (sub == 0) d[0] = '*';
     uint32_t pos = name;
@@ -1117,7 +1137,14 @@ __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t
     pos = gaf_put(d, pos, cl, sub == 9);
     if (sub == 10) { d[pos] = '\t'; d[pos + 1] = '2'; d[pos + 2] = '5'; d[pos + 3] = '5'; d[pos + 4] = '\t'; d[pos + 5] = 'N'; d[pos + 6] = 'M'; d[pos + 7] = ':'; d[pos + 8] = 'i'; }
     pos = gaf_put(d, pos + 9, nm, sub == 11, ':');
-    if (sub == 12) d[pos] = '\n';
+    if (TAG && tag.block) {
+        pos = gaf_put_tag(d, pos, 'P', 'S', tag.block, sub == 12);
+        pos = gaf_put_tag(d, pos, 'H', 'P', tag.a > tag.b ? 1u : tag.b > tag.a ? 2u : 0u, sub == 13);
+        pos = gaf_put_tag(d, pos, 'h', 'a', tag.a, sub == 14);
+        pos = gaf_put_tag(d, pos, 'h', 'b', tag.b, sub == 15);
+        pos = gaf_put_tag(d, pos, 'h', 'o', tag.others, sub == 0);
+        if (sub == 0) d[pos] = '\n';
+    } else if (sub == 12) d[pos] = '\n';
     // the segments: lane (i - 1) mod 16 writes unitig i -- from the front, or on the rc from the back with its orientation flipped
     if (!again) {
         uint32_t acc = 0;
@@ -1157,12 +1184,18 @@ __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t
 __global__ void __launch_bounds__(256) bgr_text_gaf_write_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
                                                                  const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
                                                                  const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout) {
-    gaf_write<false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
+    gaf_write<false, false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, nullptr);
 }
 __global__ void __launch_bounds__(256) bgr_text_gaf_write_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
                                                                       const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
                                                                       const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout) {
-    gaf_write<true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
+    gaf_write<true, false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, nullptr);
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(256) bgr_text_gaf_write_tag_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                     const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
+                                                                     const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout, const uint4* tags) {
+    gaf_write<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
 }
 
 // bgr_aligner_path_stats: the same per-read function over the results of a bgr_align_device launch, the reads where the caller keeps them
@@ -1270,8 +1303,13 @@ hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* tex
 }
 
 hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, hipStream_t stream) {
+                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
+    if (tag_table) {   // the tagged instances: only an aligner with a tag table launches them
+        if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
+        else hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
+        return hipGetLastError();
+    }
     if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_sizes_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
     else hipLaunchKernelGGL(bgr_text_gaf_sizes_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
     return hipGetLastError();
@@ -1279,8 +1317,13 @@ hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, c
 
 hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                  const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
-                                 hipStream_t stream) {
+                                 const uint4* tags, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
+    if (tags) {
+        if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
+        else hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
+        return hipGetLastError();
+    }
     if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_write_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
     else hipLaunchKernelGGL(bgr_text_gaf_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
     return hipGetLastError();

@@ -876,6 +876,46 @@ int bgr_graph_haplotypes(const bgr_graph* g, bgr_haplotype* out, uint64_t cap, u
 int bgr_write_haplotypes(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n_entries,
                          const bgr_haplotype* haps, uint64_t n, const char* seq, uint64_t seq_bytes);
 
+/* Haplotags: which haplotype of which block a READ lies on, from blocks that are given -- the --blocks file of an earlier run on the same unitig
+ * file, or its structs -- so the reads tagged need not be the reads the blocks were phased from.  All integers, every result deterministic.
+ * The tag table: uint32_t table[n_unitigs + 1], table[0] = 0; table[u] = block << 1 | hap with block >= 1 when unitig u is the branch of a bubble
+ * that lies on haplotype A (hap 0) or B (hap 1) of that block, 0 when it is no branch of a tagged block.  Orientation never enters.
+ *   bgr_blocks_tag_table: for every entry e of a block with size >= min_block, with r = bubbles[e.bubble] and h = (e.flags >> 1) & 1
+ *   (BGR_BLOCK_HAP): |r.branch[h]| gets e.block << 1, |r.branch[1 - h]| gets e.block << 1 | 1; BGR_BLOCK_REVERSED and the ring flags do not matter.
+ *   bgr_read_blocks_tags: per line of the file |hapA| gets block << 1 and |hapB| block << 1 | 1; every block of the file tags.
+ *   Both write n_unitigs + 1 words to table_out and the number of non-zero entries to *n_tagged_out (may be null).  BGR_E_ARG with a message (the
+ *   file form names the line) for: an id that is 0 or beyond n_unitigs; a block that is 0 or >= 2^31; |hapA| == |hapB|; a unitig that would receive
+ *   two different tags (on lists from a run it cannot: a branch has one way in and one way out); an entry that names no bubble; a first line that is
+ *   not exactly the header bgr_write_blocks writes; a line without ten tab-separated fields; a block, hapA or hapB that is not a decimal integer
+ *   (an optional '-', then digits).  The last line may lack its newline; a file of the header alone tags nothing.  BGR_E_IO for a file that cannot
+ *   be read.
+ * The tag of a read: for a mapped row [off, id_1 .. id_n] the VOTES are table[|id_j|] for every j whose |id_j| (taken in 64 bits: INT32_MIN is
+ * merely out of range) lies in 1 .. n_unitigs and whose entry is not 0.  No votes: all zeros.  Else block = the smallest block number among the
+ * votes (independent of the strand), a and b = the votes of that block for A and for B, others = the votes for any other block.  An unmapped read,
+ * and a row that is not wholly inside the launch's arena (results[i][0] + ints > bgr_aligner_arena_ints), give zeros.
+ * bgr_aligner_haplotag_enable(a, table, n_rows) uploads the table to the aligner's device (n_rows must be n_unitigs + 1: BGR_E_ARG; BGR_E_NOMEM
+ * with nothing left allocated); a null table switches the feature off and frees the copy.  An internal twin is BGR_E_ARG.
+ * bgr_aligner_haplotags(a, n_reads, out): one kernel over the rows of the aligner's last launch (greedy or anchors mode), on the stream and the
+ * buffers that ran it, and one copy; it blocks.  A 16-lane group per read: lane i takes id i of a pass of sixteen, one 4-byte gather per id, the
+ * minimum and the three counts by reductions inside the sixteen lanes; no atomics, no LDS (bgreat_amd/csrc/haplotag_device.h).  BGR_E_ARG when no
+ * table is enabled, after an exhaustive launch, when n_reads is not the launch's, for an internal twin.
+ * GAF: with a table enabled, bgr_align_fasta_text with want_output 3 runs tagged instances of the GAF kernels; the line of a read with
+ * block != 0 gains, behind NM:i:<n> and in front of the newline,
+ *   \tPS:i:<block>\tHP:i:<h>\tha:i:<a>\thb:i:<b>\tho:i:<others>        h = 1 when a > b, 2 when b > a, 0 when they are equal
+ * and a read with block == 0 keeps the exact line it has without a table.  Without a table the kernels launched are the untagged ones.
+ * bgr_graph_haplotag_enable(g, table, n_rows) is sticky: the graph keeps a copy, null switches it off.  A bgr_align_all with the switch on is
+ * BGR_E_ARG without bgr_run_options.gaf; with it every aligner of the run gets the table on its device and both routes write tagged lines (pieces
+ * formatted on the host are tagged there, from the path ints the formatter holds).  notAligned, the counters and stdout do not change; the
+ * refusals are those of gaf. */
+typedef struct { uint32_t block, a, b, others; } bgr_read_tag;   /* 16 bytes */
+int bgr_blocks_tag_table(const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n_entries, uint64_t n_unitigs, uint64_t min_block,
+                         uint32_t* table_out, uint64_t* n_tagged_out);
+int bgr_read_blocks_tags(const char* path, uint64_t n_unitigs, uint32_t* table_out, uint64_t* n_tagged_out);
+int bgr_aligner_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
+int bgr_aligner_haplotags(bgr_aligner* a, uint64_t n_reads, bgr_read_tag* out);
+int bgr_graph_haplotag_enable(bgr_graph* g, const uint32_t* table, uint64_t n_rows);
+int bgr_graph_haplotag_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+
 /* The pileup of a whole run (bgr_pileup_base above).  The switch is the graph's, as bgr_graph_links_enable is: bgr_graph_pileup_enable(g, 1) is
  * sticky (BGR_E_ARG on a graph with non-ACGT unitig characters or without a host blob), and every later bgr_align_all on the graph counts unitig
  * abundance and the pileup in every aligner of the run; the tables of all aligners and devices are summed (mod 2^32: the differences commute) when

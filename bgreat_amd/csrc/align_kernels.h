@@ -172,8 +172,9 @@ uint32_t resident_waves_per_cu(KernelId k);
 
 // (results, arena) of the last mapping launch -> input-ordered CSR on the device.  phase 0: block_sums[ceil(n/4096)] and
 // *total (all path ints); phase 1: path_offsets[n+1], paths[total] (nothing is stored past paths_cap), status[n].
+// arena_ints: the ints of the launch's arena; a row that does not lie wholly inside them is an empty row in both phases (its status byte as stored).
 hipError_t launch_csr(const uint2* results, const int32_t* arena, uint32_t n, uint32_t* block_sums, unsigned long long* total,
-                      unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap, int phase, hipStream_t stream);
+                      unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap, int phase, uint64_t arena_ints, hipStream_t stream);
 
 // ASCII reads (ACGTN) -> the 2-bit planes the mapping kernels read.  `hasn` (ceil(n/32) words) must be zero on entry;
 // planes need (total_bytes >> 5) + n + 2 words each.

@@ -110,12 +110,18 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* l
     return before + inc - v;
 }
 
-__global__ void __launch_bounds__(kCsrThreads) bgr_csr_block_sums(const uint2* results, uint32_t n, uint32_t* block_sums) {
+// ints of a row: its count -- 0 for a row that does not lie wholly inside the launch's arena (compared in 64 bits: x + count may pass 2^32)
+__device__ __forceinline__ uint32_t csr_row_ints(uint2 r, unsigned long long arena_ints) {
+    const uint32_t len = r.y & 0xFFFFFFu;
+    return (unsigned long long)r.x + len > arena_ints ? 0u : len;
+}
+
+__global__ void __launch_bounds__(kCsrThreads) bgr_csr_block_sums(const uint2* results, uint32_t n, uint32_t* block_sums, unsigned long long arena_ints) {
     __shared__ uint32_t lw[16];
     const uint32_t base = blockIdx.x * kCsrTile + threadIdx.x * kCsrItems;
     uint32_t s = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kCsrItems; ++j) if (base + j < n) s += results[base + j].y & 0xFFFFFFu;
+    for (uint32_t j = 0; j < kCsrItems; ++j) if (base + j < n) s += csr_row_ints(results[base + j], arena_ints);
     uint32_t total;
     (void)block_exclusive_scan(s, lw, &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
@@ -142,7 +148,8 @@ __global__ void __launch_bounds__(kCsrThreads) bgr_csr_scan_sums(uint32_t* block
 }
 
 __global__ void __launch_bounds__(kCsrThreads) bgr_csr_gather(const uint2* results, const int32_t* arena, uint32_t n, const uint32_t* block_offs,
-                                                             unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap) {
+                                                             unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap,
+                                                             unsigned long long arena_ints) {
     __shared__ uint32_t lw[16];
     const uint32_t base = blockIdx.x * kCsrTile + threadIdx.x * kCsrItems;
     uint2 r[kCsrItems];
@@ -150,7 +157,7 @@ __global__ void __launch_bounds__(kCsrThreads) bgr_csr_gather(const uint2* resul
 #pragma unroll
     for (uint32_t j = 0; j < kCsrItems; ++j) {
         r[j] = base + j < n ? results[base + j] : make_uint2(0, 0);
-        s += r[j].y & 0xFFFFFFu;
+        s += csr_row_ints(r[j], arena_ints);
     }
     uint32_t total;
     uint32_t w = block_offs[blockIdx.x] + block_exclusive_scan(s, lw, &total);
@@ -158,7 +165,7 @@ __global__ void __launch_bounds__(kCsrThreads) bgr_csr_gather(const uint2* resul
 #pragma unroll
     for (uint32_t j = 0; j < kCsrItems; ++j) {
         if (base + j >= n) break;
-        const uint32_t len = r[j].y & 0xFFFFFFu;
+        const uint32_t len = csr_row_ints(r[j], arena_ints);
         if (w + len <= paths_cap)
             for (uint32_t q = 0; q < len; ++q) paths[w + q] = arena[r[j].x + q];
         w += len;
@@ -168,13 +175,13 @@ __global__ void __launch_bounds__(kCsrThreads) bgr_csr_gather(const uint2* resul
 }
 
 hipError_t launch_csr(const uint2* results, const int32_t* arena, uint32_t n, uint32_t* block_sums, unsigned long long* total,
-                      unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap, int phase, hipStream_t stream) {
+                      unsigned long long* path_offsets, int32_t* paths, uint8_t* status, uint32_t paths_cap, int phase, uint64_t arena_ints, hipStream_t stream) {
     const uint32_t nb = (n + kCsrTile - 1) / kCsrTile;
     if (phase == 0) {  // lengths -> tile offsets + total
-        hipLaunchKernelGGL(bgr_csr_block_sums, dim3(nb), dim3(kCsrThreads), 0, stream, results, n, block_sums);
+        hipLaunchKernelGGL(bgr_csr_block_sums, dim3(nb), dim3(kCsrThreads), 0, stream, results, n, block_sums, (unsigned long long)arena_ints);
         hipLaunchKernelGGL(bgr_csr_scan_sums, dim3(1), dim3(kCsrThreads), 0, stream, block_sums, nb, total);
     } else {           // gather (the caller has sized `paths` from the total)
-        hipLaunchKernelGGL(bgr_csr_gather, dim3(nb), dim3(kCsrThreads), 0, stream, results, arena, n, block_sums, path_offsets, paths, status, paths_cap);
+        hipLaunchKernelGGL(bgr_csr_gather, dim3(nb), dim3(kCsrThreads), 0, stream, results, arena, n, block_sums, path_offsets, paths, status, paths_cap, (unsigned long long)arena_ints);
     }
     return hipGetLastError();
 }

@@ -637,8 +637,14 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     if (P.error) return fail(BGR_E_ARG, P.error);
     const bgr::Pass& first = P.pass[0];
     if (P.deep_scratch_bytes) HIP_TRY(a->deepbuf.ensure(P.deep_scratch_bytes));
+    // test hook (option test.keep_rows): everything of this launch but its mapping passes -- (a->results, a->arena) keep the rows a test wrote there behind
+    // a first launch of the same reads, and the counting kernels and the text call's format launches read those.  Only over buffers that launch sized.
+    const bool keep_rows = bgr::opt("test.keep_rows") != 0;
+    if (keep_rows && (a->sized_n != n_reads || a->last_arena_cap != P.arena_cap))
+        return fail(BGR_E_ARG, "bgr_align_device: option test.keep_rows needs the launch before on this aligner to have had the same n_reads and the same arena");
     HIP_TRY(a->arena.ensure(P.arena_cap * 4));
     a->last_arena_cap = P.arena_cap; a->last_total_bases = total_bases;
+    a->sized_n = n_reads;
     for (uint32_t i = 0; i < P.n_passes; ++i) {  // the lists the passes leave each other, and the rings of follow-up items of the sixteen-reads-per-wave kernel
         const bgr::Pass& ps = P.pass[i];
         if (ps.appends != bgr::List::kNone) HIP_TRY(list_buf(a, ps.appends)->ensure(n_reads * 4));
@@ -714,7 +720,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
     // The passes, back to back on the stream.  A pass behind a list maps what an earlier pass listed; with an empty list its waves exit at once
     // (no host round trip in between).  The sixteen-reads-per-wave kernel works off the follow-up items of its reads (the next anchors of a read whose
     // first ones failed, then its reverse complement: alignerGreedy.cpp:41-56) in its own per-wave queues, inside the launch.
-    for (uint32_t i = 0; i < P.n_passes; ++i) {
+    for (uint32_t i = 0; i < (keep_rows ? 0u : P.n_passes); ++i) {
         const bgr::Pass& ps = P.pass[i];
         bgr::BatchIO pio = io;
         pio.words_per_read = ps.words;
@@ -1282,7 +1288,7 @@ static int fetch_total(bgr_aligner* a, uint64_t n, uint64_t* total_out) {
     HIP_TRY(a->csr_status.ensure(n));
     unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallCsrTotal);
     hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
-                                   static_cast<uint32_t*>(a->csr_sums.p), d_total, nullptr, nullptr, nullptr, 0, 0, a->stream);
+                                   static_cast<uint32_t*>(a->csr_sums.p), d_total, nullptr, nullptr, nullptr, 0, 0, a->last_arena_cap, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("csr launch: ") + hipGetErrorString(e));
     uint64_t hs[bgr::kSmallCsrTotal / 8 + 1];  // the cursor block at the start, the path-int total at the end
     HIP_TRY(hipMemcpyAsync(hs, a->small.p, sizeof(hs), hipMemcpyDeviceToHost, a->stream));
@@ -1297,7 +1303,7 @@ static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths
     HIP_TRY(a->csr_paths.ensure(total * 4 + 16));
     hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
                                    static_cast<uint32_t*>(a->csr_sums.p), d_total, static_cast<unsigned long long*>(a->csr_poffs.p),
-                                   static_cast<int32_t*>(a->csr_paths.p), static_cast<uint8_t*>(a->csr_status.p), (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull), 1, a->stream);
+                                   static_cast<int32_t*>(a->csr_paths.p), static_cast<uint8_t*>(a->csr_status.p), (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull), 1, a->last_arena_cap, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("csr launch: ") + hipGetErrorString(e));
     // (with_end = false: entry n, the end of the last read, is left to the caller -- it is the first entry of the next piece)
     HIP_TRY(hipMemcpyAsync(path_offsets, a->csr_poffs.p, (n + (with_end ? 1 : 0)) * 8, hipMemcpyDeviceToHost, a->stream));
@@ -1319,7 +1325,7 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
     static_assert(sizeof(bgr_path_stat) == 24, "six words per read, as the kernel writes them");
     HIP_TRY(a->path_stats.ensure(n * sizeof(bgr_path_stat)));
     hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->results.p),
-                                          static_cast<const int32_t*>(a->arena.p), (uint32_t)n, static_cast<uint32_t*>(a->path_stats.p), a->stream);
+                                          static_cast<const int32_t*>(a->arena.p), a->last_arena_cap, (uint32_t)n, static_cast<uint32_t*>(a->path_stats.p), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path stats launch: ") + hipGetErrorString(e));
     if (bgr::opt("test.count_with_path_stats")) {   // test hook: the counting kernels once over the rows the buffers hold now, the reads' characters from the caller's buffer
         bgr::PileupReads pr;

@@ -185,6 +185,7 @@ struct bgr_aligner {
     uint64_t last_n = 0;
     uint32_t last_mode = 0;       // mode of the last mapping launch (bgr_aligner_path_stats)
     uint64_t last_arena_cap = 0, last_total_bases = 0;   // its arena's ints and its reads' bases (the counting kernels behind bgr_aligner_path_stats: test.count_with_path_stats)
+    uint64_t sized_n = 0;         // reads of the last launch that sized the buffers (forget_launch leaves it: option test.keep_rows asks for the same launch again)
     DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
     uint64_t wave_times_n = 0;
     uint64_t ticket_serial = 0;       // bgr_align_batch_begin: tickets handed out; the batch of the last one is in flight until its wait

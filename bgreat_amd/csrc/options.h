@@ -40,6 +40,7 @@ inline Option* option_table(size_t* n) {
         {"test.triples_capacity", {0}, 0, INT64_MAX, "test hook: slots of the table of triples an aligner allocates when triple counting is enabled (0 = from the graph's bound): a table that can fill"},
         {"test.variants_stage_bytes", {0}, 0, 64 << 20, "test hook: bytes of the staging piece through which one pileup table is added into another (0 = one kernel on one device, 64 MiB pieces across devices); any value takes the staged way on one device too"},
         {"test.count_with_path_stats", {0}, 0, 1, "test hook: bgr_aligner_path_stats also queues every enabled counting kernel (abundance, links, triples, pileup) once over the rows the result buffers hold at that time, the read characters from its reads buffer: rows a test wrote there itself"},
+        {"test.keep_rows", {0}, 0, 1, "test hook: a mapping launch (every route) sizes its buffers, makes its planes, queues the counting kernels and formats its text as ever, but runs none of the mapping passes: the result buffers keep the rows they hold, which a test wrote there itself behind a first launch of the same reads (another n_reads or arena size: BGR_E_ARG)"},
         {"test.text_epoch", {0}, 0, 0x3FFFFF, "test hook: the epoch the text form's chains start from when their state is (re)allocated (walks the 22-bit wrap with a few pieces)"},
     };
     *n = sizeof(t) / sizeof(t[0]);

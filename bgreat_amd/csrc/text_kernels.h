@@ -58,8 +58,9 @@ hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, c
                                  const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
                                  const uint4* tags, hipStream_t stream);   // tag_table / tags (bgr_read_tag per read) null: the untagged kernels; else the tagged instances (haplotag_device.h)
 // bgr_aligner_path_stats: per read of a bgr_align_device launch six words {walk size low, high, path start low, high, characters covered, NM | 1 << 31 "spells no walk"}
-hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out,
-                             hipStream_t stream);
+// (zeros for an unmapped read, and for a row that does not lie wholly inside the launch's arena_ints)
+hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
+                             uint32_t* out, hipStream_t stream);
 // the pre-pass (batch_kernels.hip) over reads that lie scattered in a text: read r's characters start at reads + src_off[r]
 hipError_t launch_pack_reads_at(const uint8_t* text, const uint32_t* src_off, const uint64_t* read_offs, uint32_t n, uint64_t text_bytes, uint64_t total_bases,
                                 uint64_t* fw3, uint64_t* nmw, uint32_t* hasn, hipStream_t stream);

@@ -1199,16 +1199,17 @@ __global__ void __launch_bounds__(256) bgr_text_gaf_write_tag_kernel(BgrDeviceGr
 }
 
 // bgr_aligner_path_stats: the same per-read function over the results of a bgr_align_device launch, the reads where the caller keeps them
-// (their buffer is not padded).  out[i] = {plen low, plen high, path start low, path start high, cl, NM | no-walk flag}; zeros for an unmapped read.
+// (their buffer is not padded).  out[i] = {plen low, plen high, path start low, path start high, cl, NM | no-walk flag}; zeros for an unmapped read
+// and for a row that does not lie wholly inside the launch's arena_ints (an empty row, as the counting kernels take it).
 template <bool WIDE>
-__device__ __forceinline__ void path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out) {
+__device__ __forceinline__ void path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n) return;
     const uint2 res = results[a];
     const uint32_t np = res.y & 0xFFFFFFu;
     u64 plen = 0, pstart = 0;
     uint32_t cl = 0, nm = 0;
-    if (np) {
+    if (np && (u64)res.x + np <= arena_ints) {
         const u64 o0 = offs[a];
         const uint32_t L = (uint32_t)(offs[a + 1] - o0);
         const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
@@ -1225,11 +1226,11 @@ __device__ __forceinline__ void path_stats(const BgrDeviceGraph& g, const uint8_
         out[6ull * a + sub] = v;
     }
 }
-__global__ void __launch_bounds__(256) bgr_path_stats_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out) {
-    path_stats<false>(g, reads, offs, results, arena, n, out);
+__global__ void __launch_bounds__(256) bgr_path_stats_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
+    path_stats<false>(g, reads, offs, results, arena, arena_ints, n, out);
 }
-__global__ void __launch_bounds__(256) bgr_path_stats_wide_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out) {
-    path_stats<true>(g, reads, offs, results, arena, n, out);
+__global__ void __launch_bounds__(256) bgr_path_stats_wide_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
+    path_stats<true>(g, reads, offs, results, arena, arena_ints, n, out);
 }
 
 }  // namespace
@@ -1329,12 +1330,12 @@ hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, c
     return hipGetLastError();
 }
 
-hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint32_t n, uint32_t* out,
-                             hipStream_t stream) {
+hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
+                             uint32_t* out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const u64* offs = reinterpret_cast<const u64*>(read_offs);
-    if (g.k > 33) hipLaunchKernelGGL(bgr_path_stats_wide_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, n, out);
-    else hipLaunchKernelGGL(bgr_path_stats_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, n, out);
+    if (g.k > 33) hipLaunchKernelGGL(bgr_path_stats_wide_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
+    else hipLaunchKernelGGL(bgr_path_stats_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
     return hipGetLastError();
 }
 

@@ -304,7 +304,11 @@ int bgr_aligner_sync(bgr_aligner* a);
  * Row i of the result = arena[results[i][0] .. + (results[i][1] & 0xFFFFFF)].
  * The pointers are those of the LAST launch: behind un-waited consecutive launches (see bgr_align_device) they may differ from those of the launch
  * before, whose results lie in the other set of buffers until the next launch but one.  Like this call, bgr_aligner_fetch, bgr_aligner_path_stats,
- * bgr_aligner_arena_ints, bgr_aligner_pass_counts, bgr_aligner_launch_info and bgr_aligner_last_pass_runs describe the last launch. */
+ * bgr_aligner_arena_ints, bgr_aligner_pass_counts, bgr_aligner_launch_info and bgr_aligner_last_pass_runs describe the last launch.
+ * A caller may write rows of its own there.  One rule for every reader: a row with results[i][0] + (results[i][1] & 0xFFFFFF) > the arena ints
+ * of the launch (bgr_aligner_arena_ints; the sum taken in 64 bits) reads as an EMPTY row.  The counting kernels (abundance, links, triples,
+ * pileup, haplotags) skip it -- the pileup does not count it as skipped --, bgr_aligner_path_stats reports zeros as for an unmapped read, and
+ * bgr_aligner_fetch delivers an empty path with the status byte as stored. */
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor);
 /* Ints of that arena as the last launch planned it (0 before any launch): a row lies in the arena when results[i][0] + its ints is at most this,
  * and the counting kernels skip a row that does not. */

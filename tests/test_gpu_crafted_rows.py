@@ -11,10 +11,12 @@ Everything is compared exactly with the plain-Python definitions (gaf_ref, pileu
 The graph: a random genome cut into some sixty unitigs of k .. k + 6 characters that overlap by k - 1 (test_gpu_variants.chain), written in shuffled
 order with every third one as its reverse complement -- so the path along the genome has mixed signs -- plus one unitig that glues to nothing.
 
-Known limits.  The pileup reads the characters as ASCII (the caller's reads buffer) through this seam: its plane and text sources are not reached.
-Every crafted row lies wholly inside the arena, below the 2 (total_bases + 8 n) ints every launch plan gives it: the path-stats kernel and the CSR
-gather do not check that bound, so a row outside it would be an out-of-bounds read, and the counting kernels' "row not in the arena" skip stays
-untested on purpose."""
+Known limits.  The pileup reads the characters as ASCII (the caller's reads buffer) through this seam; its plane and text sources, the text call's
+record, GAF and correction kernels and their "bug compaction" exit see these rows in test_gpu_crafted_row_routes.py (option test.keep_rows).
+Every crafted row here lies wholly inside the arena, below the 2 (total_bases + 8 n) ints every launch plan gives it.  A row that does not is an
+empty row to the counting kernels, the path-stats kernel and the CSR gather (include/bgreat_gpu.h, bgr_aligner_device_results): that file tests
+it, with rows at, across and behind the arena's logical end inside an allocation made large enough first.  Still not covered anywhere: offsets
+that point outside the arena's allocation (a test must not read there), and the text-route kernels on rows outside the arena (they do not check)."""
 import functools
 import itertools
 import random

@@ -23,6 +23,11 @@ struct bgr_graph { uint32_t k; };
 struct bgr_aligner { int device = 0; uint64_t counters[5] = {0, 0, 0, 0, 0}; std::string ps, ns; /* text form: the last call's streams, for bgr_aligner_fetch_text */ };
 static thread_local std::string tl_err;
 namespace bgr { int set_error(int code, const std::string& msg) { tl_err = msg; return code; } }
+// The failure switch: the mapping call (bgr_align_batch_packed or bgr_align_fasta_text, counted together from 0) that finds the countdown at 0 fails
+// with BGR_E_HIP and a message of its own; negative = off.
+static std::atomic<long> g_fail_countdown{-1};
+static const char* const kInjected = "stand-in: injected failure of a mapping call";
+static bool injected_failure() { return g_fail_countdown.load() >= 0 && g_fail_countdown.fetch_sub(1) == 0; }
 extern "C" {
 const char* bgr_last_error(void) { return tl_err.c_str(); }
 int bgr_graph_info(const bgr_graph* g, bgr_graph_info_t* o) { memset(o, 0, sizeof(*o)); o->k = g->k; return BGR_OK; }
@@ -38,6 +43,7 @@ int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]) { memcpy(out, a->count
 int bgr_aligner_fetch(bgr_aligner*, uint64_t, int32_t*, uint64_t, uint64_t*, uint8_t*) { return BGR_E_INTERNAL; }
 int bgr_align_batch_packed(bgr_aligner* a, const bgr_params*, const bgr_packed_reads* pk, uint64_t n, int32_t* paths, uint64_t cap,
                            uint64_t* poffs, uint8_t* status) {
+    if (injected_failure()) return bgr::set_error(BGR_E_HIP, kInjected);
     const uint64_t* offs = pk->read_offsets;
     for (uint64_t i = 0; i < n; ++i) {  // the packed plane must spell the read: check the first base of every read's first word
         const uint64_t len = offs[i + 1] - offs[i];
@@ -88,6 +94,7 @@ extern "C" int bgr_aligner_fetch_text(bgr_aligner* a, bgr_text_batch* b) {
 }
 extern "C" int bgr_align_fasta_text(bgr_aligner* a, const bgr_params*, bgr_text_batch* b) {
     b->irregular = 0; b->n_records = b->n_accepted = b->paths_bytes = b->notaligned_bytes = 0;
+    if (injected_failure()) return bgr::set_error(BGR_E_HIP, kInjected);
     if (b->stage && b->stage->device != a->device) return bgr::set_error(BGR_E_ARG, "stand-in: the stage lives on another device");  // (as the real call)
     if (b->stage && (b->stage->copy.size() != b->text_bytes || (b->text && b->text_bytes && memcmp(b->stage->copy.data(), b->text, b->text_bytes) != 0))) return BGR_E_INTERNAL;  // the staged piece is this piece
     if (!b->stage && !b->text) return BGR_E_ARG;
@@ -259,20 +266,21 @@ int main(int argc, char** argv) {
         }
         printf("%s ok\n", c.file);
     }
+    // (shared by the split-run and the failure sections: the per-batch index blanked, the 40 000-record file)
+    auto blank = [](const std::string& gp) {
+        std::string out; out.reserve(gp.size());
+        std::istringstream ss(gp); std::string line; bool header = true;
+        while (std::getline(ss, line)) {
+            if (!header) { size_t a = line.find('.'), b = line.find('.', a + 1); if (a != std::string::npos && b != std::string::npos) line = line.substr(0, a + 1) + "#" + line.substr(b); }
+            out += line + "\n"; header = !header;
+        }
+        return out;
+    };
+    const std::string big = tmp + "/lanes.fa";
     // ---- split runs (bgr_run_options.split_output): one pipeline per stand-in device over contiguous shares of the input; the pairs
     // concatenated in device order must be the bytes of the single pipeline, whatever the lane count, route and batch size (the stand-in
     // numbers reads within a device batch: blanked as above; FASTA only -- other runs ignore the flag and write the single pair)
     {
-        auto blank = [](const std::string& gp) {
-            std::string out; out.reserve(gp.size());
-            std::istringstream ss(gp); std::string line; bool header = true;
-            while (std::getline(ss, line)) {
-                if (!header) { size_t a = line.find('.'), b = line.find('.', a + 1); if (a != std::string::npos && b != std::string::npos) line = line.substr(0, a + 1) + "#" + line.substr(b); }
-                out += line + "\n"; header = !header;
-            }
-            return out;
-        };
-        const std::string big = tmp + "/lanes.fa";
         {
             std::ofstream o(big, std::ios::binary);
             const char* al = "ACGT";
@@ -320,6 +328,49 @@ int main(int argc, char** argv) {
             if (rc != BGR_E_IO) { printf("FAIL lanes error path: rc %d %s\n", rc, bgr_last_error()); return 1; }
         }
         printf("split runs ok\n");
+    }
+    // ---- a mapping call that fails in the middle of a run: every thread winds down (a hang is the test's timeout), the call returns the
+    // failing call's code and message, and what reached the two files is a strict prefix of the fault-free run's bytes (whole batches in input
+    // order, nothing behind the batch that failed).  lanes.fa with 997-read batches is nine pieces / batches on either route.
+    {
+        bgr_graph g{5u};
+        bgr_params prm = {BGR_MODE_GREEDY, 2, 2, 0};
+        for (uint32_t route : {0u, 1u}) {
+            for (unsigned threads : {1u, 6u}) {
+                bgr_run_options opt;
+                memset(&opt, 0, sizeof(opt));
+                opt.struct_size = sizeof(opt);
+                opt.n_gpus = 2; opt.threads = threads; opt.batch_reads = 997; opt.chunk_bytes = 900; opt.route = route;
+                uint64_t tot[5]; double secs;
+                if (bgr_align_all(&g, &prm, &opt, big.c_str(), (tmp + "/pw").c_str(), (tmp + "/nw").c_str(), tot, &secs) != BGR_OK) { printf("FAIL failures reference run: %s\n", bgr_last_error()); return 1; }
+                const std::string want_p = blank(slurp(tmp + "/pw")), want_n = slurp(tmp + "/nw");
+                for (long at : {0L, 3L, 6L}) {
+                    g_fail_countdown.store(at);
+                    const int rc = bgr_align_all(&g, &prm, &opt, big.c_str(), (tmp + "/pf").c_str(), (tmp + "/nf").c_str(), tot, &secs);
+                    const bool fired = g_fail_countdown.exchange(-1) < 0;
+                    const std::string msg = bgr_last_error();
+                    const std::string gp = blank(slurp(tmp + "/pf")), gn = slurp(tmp + "/nf");
+                    if (!fired || rc != BGR_E_HIP || msg != kInjected || gp.size() >= want_p.size() || gn.size() >= want_n.size() || want_p.compare(0, gp.size(), gp) != 0 ||
+                        want_n.compare(0, gn.size(), gn) != 0) {
+                        printf("FAIL failure on call %ld route=%u threads=%u: fired %d rc %d '%s' paths %zu/%zu notAligned %zu/%zu\n", at, route, threads, (int)fired, rc, msg.c_str(), gp.size(),
+                               want_p.size(), gn.size(), want_n.size());
+                        return 1;
+                    }
+                }
+            }
+            for (long at : {0L, 5L}) {  // a split run: the failing lane's code and message, not the "stopped" of the lanes it stopped
+                bgr_run_options opt;
+                memset(&opt, 0, sizeof(opt));
+                opt.struct_size = sizeof(opt);
+                opt.n_gpus = 3; opt.split_output = 1; opt.threads = 6; opt.batch_reads = 997; opt.chunk_bytes = 900; opt.route = route;
+                uint64_t tot[5]; double secs;
+                g_fail_countdown.store(at);
+                const int rc = bgr_align_all(&g, &prm, &opt, big.c_str(), (tmp + "/pf").c_str(), (tmp + "/nf").c_str(), tot, &secs);
+                const bool fired = g_fail_countdown.exchange(-1) < 0;
+                if (!fired || rc != BGR_E_HIP || std::string(bgr_last_error()) != kInjected) { printf("FAIL failure on call %ld of a split run, route=%u: fired %d rc %d '%s'\n", at, route, (int)fired, rc, bgr_last_error()); return 1; }
+            }
+        }
+        printf("failures ok\n");
     }
     // ---- what the reference prints while it maps (file names; in exhaustive mode the block after every tenth getReads()
     // call, alignerExhaustive.cpp:306-316): it must come out of the ordered writer between the right reads, whatever the

@@ -4,7 +4,7 @@
 // [off, off + cl) that lies on unitig j.  No read characters, no strand, no key compare: the kernel needs the path ints, the read's length
 // and the unitig lengths of BgrUnitigMeta, so one kernel serves every k.
 //
-// Geometry as gaf_stat's (text_kernels.hip): sixteen lanes share a read, lane i takes unitig i of a pass of sixteen, a prefix sum by shuffles
+// Geometry as gaf_stat's (text_gaf.hip): sixteen lanes share a read, lane i takes unitig i of a pass of sixteen, a prefix sum by shuffles
 // places every unitig in the walk (e_j = e_{j-1} - (k-1) + len_j); a path of any length takes ceil(n / 16) passes with the walk's size so far
 // carried from one to the next.  With e_j <= plen the covered stretch needs no second pass for plen:
 //     o_j = max(0, min(off + cl, e_j) - max(off, s_j)) = max(0, min(off + L, e_j) - max(off, s_j))      (cl = max(0, min(L, plen - off)))

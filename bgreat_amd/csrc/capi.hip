@@ -1,5 +1,5 @@
-// capi.hip -- implementation of the C-ABI declared in include/bgreat_gpu.h: index, distribution, mapping, text route, batches, the
-// asynchronous form, host buffers and readsets (the counting features have their own units: capi_abundance.hip, capi_links.hip, capi_triples.hip,
+// capi.hip -- implementation of the C-ABI declared in include/bgreat_gpu.h: index, distribution, mapping, batches, the
+// asynchronous form, host buffers and readsets (the text route and the counting features have their own units: capi_text.hip, capi_abundance.hip, capi_links.hip, capi_triples.hip,
 // capi_pileup.hip, capi_variants.hip; capi_internal.h has what they share).  Thin: argument checks, HIP memory
 // and stream management, launch geometry; the algorithm lives in graph_build.cpp (index) and
 // the *_kernels.hip files (mapping; launch interface align_kernels.h).  There is no CPU mapping path in this library.
@@ -8,7 +8,6 @@
 #include <dlfcn.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -60,10 +59,10 @@ int drain_timers(bgr_aligner* a) {
     return BGR_OK;
 }
 
+}  // namespace
+
 // No single launch whose results could be read again (a batch mapped in pieces, a text piece, a batch in flight): bgr_aligner_fetch finds n = 0, on the aligner itself
 void forget_launch(bgr_aligner* a) { a->last_n = 0; a->holder = nullptr; }
-
-}  // namespace
 
 extern "C" {
 
@@ -420,16 +419,15 @@ int bgr_aligner_create(bgr_graph* g, int device, bgr_aligner** out) {
 
 void bgr_aligner_destroy(bgr_aligner* a) {
     if (!a) return;
-    if (a->tx_phase_s[4] > 0 && bgr::opt("timing"))
-        fprintf(stderr, "bgreat: text calls %.0f on device %d: to record count %.3f s, records %.3f s, mapping + sizes %.3f s, streams out %.3f s\n", a->tx_phase_s[4], a->device,
-                a->tx_phase_s[0], a->tx_phase_s[1], a->tx_phase_s[2], a->tx_phase_s[3]);
+    if (a->text.phase_s[4] > 0 && bgr::opt("timing"))
+        fprintf(stderr, "bgreat: text calls %.0f on device %d: to record count %.3f s, records %.3f s, mapping + sizes %.3f s, streams out %.3f s\n", a->text.phase_s[4], a->device,
+                a->text.phase_s[0], a->text.phase_s[1], a->text.phase_s[2], a->text.phase_s[3]);
     if (a->twin) { bgr_aligner_destroy(a->twin); a->twin = nullptr; }
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
         a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.buf.release(); a->triples.buf.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
-        for (DevBuf* b : {&a->tx_in, &a->tx_sums, &a->tx_state, &a->tx_rec, &a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_offs,
-                          &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff, &a->tx_pout, &a->tx_nout, &a->tx_info, &a->tx_gaf, &a->path_stats, &a->haplotag, &a->haplotag_out, &a->tx_tags}) b->release();
+        a->text.release(); a->path_stats.release(); a->haplotag.release(); a->haplotag_out.release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
         if (a->ev_wait) (void)hipEventDestroy(a->ev_wait);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -594,7 +592,7 @@ static int queue_counting(bgr_aligner* a, uint64_t arena_cap, const uint64_t* re
 // buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
 // (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
 // d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
-static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
+int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
                              uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
                              bool cursor_is_zero = false) {
     if (!a || !p) return fail(BGR_E_ARG, "bgr_align_device: null argument");
@@ -783,7 +781,7 @@ static int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_
 // exhaustive mode the last pass may have handed reads back whose table of remembered calls filled up (exh_memo, exhaustive_kernels.hip):
 // those run again -- the last pass only, over that list -- with a table sixteen times as large and as few waves as the list has reads, until
 // none is left.  A search visits at most positions x halves x 2 nodes, so this ends; what can end it early is the device's memory.
-static int settle_launch(bgr_aligner* a, uint32_t* cur) {
+int settle_launch(bgr_aligner* a, uint32_t* cur) {
     if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
     if (!a->deep.open) return BGR_OK;
     const uint32_t kRetry = bgr::list_word(bgr::List::kRetry);
@@ -963,290 +961,6 @@ int bgr_align_batch_packed(bgr_aligner* a, const bgr_params* p, const bgr_packed
     int rc = align_device_impl(a, p, nullptr, a->in_offs.p, n, total, max_len, true);
     if (rc != BGR_OK) return rc;
     return bgr_aligner_fetch(a, n, paths_out, paths_cap, path_offsets, status);
-}
-
-// ---- text form: FASTA bytes in, record bytes out (text_kernels.hip) -------------------------------------------------------------
-static int fetch_text_impl(bgr_aligner* a, bgr_text_batch* b) {
-    b->paths_bytes = a->tx_pbytes;
-    b->notaligned_bytes = a->tx_nbytes;
-    if (!b->want_output || a->tx_n_acc == 0) return BGR_OK;
-    if (a->tx_pbytes > b->paths_cap || a->tx_nbytes > b->notaligned_cap || (a->tx_pbytes && !b->paths_out) || (a->tx_nbytes && !b->notaligned_out))
-        return fail(BGR_E_CAPACITY, "bgr_align_fasta_text: output buffer too small (paths_bytes / notaligned_bytes say what is needed; bgr_aligner_fetch_text)");
-    if (!a->tx_written) {   // (correction mode; streams larger than the buffers the format launch wrote into; a second fetch)
-    HIP_TRY(a->tx_pout.ensure(a->tx_pbytes + 64));
-    HIP_TRY(a->tx_nout.ensure(a->tx_nbytes + 64));
-    hipError_t e = a->tx_want == 3
-        ? bgr::launch_text_gaf_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
-                                     static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
-                                     static_cast<const uint32_t*>(a->tx_noff.p), static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_idx.p),
-                                     static_cast<const uint4*>(a->tx_gaf.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p),
-                                     a->tx_tagged ? static_cast<const uint4*>(a->tx_tags.p) : nullptr, a->stream)
-        : a->tx_want == 2
-        ? bgr::launch_text_correct_write(a->dg, a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
-                                         static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc, static_cast<const uint32_t*>(a->tx_poff.p),
-                                         static_cast<const uint32_t*>(a->tx_noff.p), static_cast<const uint32_t*>(a->tx_idx.p), static_cast<uint8_t*>(a->tx_pout.p),
-                                         static_cast<uint8_t*>(a->tx_nout.p), a->stream)
-        : bgr::launch_text_write(a->tx_text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
-                                 static_cast<const uint4*>(a->tx_rec.p), static_cast<const uint32_t*>(a->tx_accrec.p), (uint32_t)a->tx_n_acc,
-                                 static_cast<const uint32_t*>(a->tx_poff.p), static_cast<const uint32_t*>(a->tx_noff.p), static_cast<uint8_t*>(a->tx_pout.p),
-                                 static_cast<uint8_t*>(a->tx_nout.p), a->stream);
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text write launch: ") + hipGetErrorString(e));
-    a->tx_written = true;
-    }
-    if (a->tx_pbytes) HIP_TRY(hipMemcpyAsync(b->paths_out, a->tx_pout.p, a->tx_pbytes, hipMemcpyDeviceToHost, a->stream));
-    if (a->tx_nbytes) HIP_TRY(hipMemcpyAsync(b->notaligned_out, a->tx_nout.p, a->tx_nbytes, hipMemcpyDeviceToHost, a->stream));
-    HIP_TRY(wait_stream(a));
-    return BGR_OK;
-}
-
-int bgr_aligner_fetch_text(bgr_aligner* a, bgr_text_batch* b) {
-    if (!a || !b) return fail(BGR_E_ARG, "bgr_aligner_fetch_text: null argument");
-    if (b->struct_size != sizeof(bgr_text_batch)) return fail(BGR_E_ARG, "bgr_aligner_fetch_text: bgr_text_batch.struct_size is not this library's sizeof(bgr_text_batch)");
-    HIP_TRY(hipSetDevice(a->device));
-    return fetch_text_impl(a, b);
-}
-
-int bgr_text_stage_create(int device, bgr_text_stage** out) {
-    if (!out) return fail(BGR_E_ARG, "bgr_text_stage_create: null argument");
-    HIP_TRY(hipSetDevice(device));
-    bgr_text_stage* s = new bgr_text_stage();
-    s->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    s->timing = bgr::opt("timing") != 0;
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev, s->timing ? hipEventDefault : hipEventDisableTiming);
-    if (e == hipSuccess && s->timing) e = hipEventCreate(&s->ev0);
-    if (e != hipSuccess) { bgr_text_stage_destroy(s); return fail(BGR_E_HIP, std::string("bgr_text_stage_create: ") + hipGetErrorString(e)); }
-    *out = s;
-    return BGR_OK;
-}
-
-void bgr_text_stage_destroy(bgr_text_stage* s) {
-    if (!s) return;
-    if (hipSetDevice(s->device) == hipSuccess) {
-        if (s->stream) { (void)hipStreamSynchronize(s->stream); s->settle(); (void)hipStreamDestroy(s->stream); }
-        if (s->timing && s->copy_ms > 0) fprintf(stderr, "bgreat: stage on device %d: %.0f MB up in %.3f s of copies = %.1f GB/s\n", s->device, s->copy_bytes / 1e6, s->copy_ms / 1e3, s->copy_bytes / s->copy_ms / 1e6);
-        if (s->ev) (void)hipEventDestroy(s->ev);
-        if (s->ev0) (void)hipEventDestroy(s->ev0);
-        s->buf.release();
-    }
-    delete s;
-}
-
-int bgr_text_stage_device(const bgr_text_stage* s) { return s ? s->device : -1; }
-
-int bgr_text_stage_upload(bgr_text_stage* s, const char* text, uint64_t bytes) {
-    if (!s || (bytes && !text)) return fail(BGR_E_ARG, "bgr_text_stage_upload: null argument");
-    if (bytes >= (1ull << 31)) return fail(BGR_E_ARG, "bgr_text_stage_upload: piece of 2 GiB or more; cut it");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));  // (a piece still on its way: the buffer may grow, i.e. move)
-    s->settle();
-    HIP_TRY(s->buf.ensure(bytes + 128));
-    if (s->timing) { HIP_TRY(hipEventRecord(s->ev0, s->stream)); s->pending = true; }
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(s->buf.p) + (bytes & ~63ull), 0, 128, s->stream));   // (from an aligned address: one fill; the copies below lay the text over its start)
-    if (bytes) HIP_TRY(hipMemcpyAsync(s->buf.p, text, bytes, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipEventRecord(s->ev, s->stream));
-    s->bytes = bytes;
-    return BGR_OK;
-}
-
-int bgr_text_stage_upload_parts(bgr_text_stage* s, uint32_t n_parts, const char* const* parts, const uint64_t* part_bytes) {
-    if (!s || (n_parts && (!parts || !part_bytes))) return fail(BGR_E_ARG, "bgr_text_stage_upload_parts: null argument");
-    uint64_t bytes = 0;
-    for (uint32_t i = 0; i < n_parts; ++i) { if (part_bytes[i] && !parts[i]) return fail(BGR_E_ARG, "bgr_text_stage_upload_parts: null part"); bytes += part_bytes[i]; }
-    if (bytes >= (1ull << 31)) return fail(BGR_E_ARG, "bgr_text_stage_upload_parts: piece of 2 GiB or more; cut it");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));  // (a piece still on its way: the buffer may grow, i.e. move)
-    s->settle();
-    HIP_TRY(s->buf.ensure(bytes + 128));
-    if (s->timing) { HIP_TRY(hipEventRecord(s->ev0, s->stream)); s->pending = true; }
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(s->buf.p) + (bytes & ~63ull), 0, 128, s->stream));   // (from an aligned address: one fill; the copies below lay the text over its start)
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n_parts; ++i) {
-        if (part_bytes[i]) HIP_TRY(hipMemcpyAsync(static_cast<char*>(s->buf.p) + at, parts[i], part_bytes[i], hipMemcpyHostToDevice, s->stream));
-        at += part_bytes[i];
-    }
-    HIP_TRY(hipEventRecord(s->ev, s->stream));
-    s->bytes = bytes;
-    return BGR_OK;
-}
-
-static double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b) {
-    if (!a || !p || !b) return fail(BGR_E_ARG, "bgr_align_fasta_text: null argument");
-    if (b->struct_size != sizeof(bgr_text_batch)) return fail(BGR_E_ARG, "bgr_align_fasta_text: bgr_text_batch.struct_size is not this library's sizeof(bgr_text_batch): the caller was built against another header (zero the struct, set struct_size)");
-    if (b->text_bytes && !b->text && !b->stage) return fail(BGR_E_ARG, "bgr_align_fasta_text: null argument");
-    if (b->record_info_out && b->text_bytes >= (1ull << 30)) return fail(BGR_E_ARG, "bgr_align_fasta_text: record_info_out holds a read's length in 30 bits: pieces below 2^30 bytes");
-    double tw = wall_now();
-    auto lap = [&](int i) { const double t = wall_now(); a->tx_phase_s[i] += t - tw; tw = t; };
-    if (b->text_bytes >= (1ull << 31)) return fail(BGR_E_ARG, "bgr_align_fasta_text: piece of 2 GiB or more; cut it");
-    if (b->want_output > 3) return fail(BGR_E_ARG, "bgr_align_fasta_text: want_output must be 0, 1, 2 or 3");
-    if (b->fastq > 2) return fail(BGR_E_ARG, "bgr_align_fasta_text: fastq must be 0, 1 (four-line records) or 2 (header and read lines only)");
-    const uint32_t rec_lines = b->fastq == 2 ? 2u : b->fastq ? 4u : 0u;  // lines per record of a FASTQ piece (0: FASTA, records start at '>' lines)
-    if (b->fastq && b->text_bytes && b->text && b->text[b->text_bytes - 1] != '\n' && !b->stage)
-        return fail(BGR_E_ARG, "bgr_align_fasta_text: a FASTQ piece holds whole four-line records and ends with a newline");
-    if (b->want_output == 2 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
-        return fail(BGR_E_ARG, "bgr_align_fasta_text: correction on the device needs a graph of ACGT-only unitigs and greedy mode (format such a run on the host)");
-    if (b->want_output == 3 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
-        return fail(BGR_E_ARG, "bgr_align_fasta_text: GAF output needs a graph of ACGT-only unitigs (a path read backwards does not spell the reverse complement on one with other characters) and a greedy mode");
-    if (b->record_info_out && (b->want_output >= 2 || b->record_info_cap < b->text_bytes / 24 + 1024))
-        return fail(BGR_E_ARG, "bgr_align_fasta_text: record_info_out needs room for text_bytes / 24 + 1024 words and is not available in correction mode or with GAF output");
-    a->tx_want = b->want_output;
-    b->irregular = 0;
-    b->n_records = b->n_accepted = b->paths_bytes = b->notaligned_bytes = 0;
-    forget_launch(a);
-    a->tx_n_acc = a->tx_pbytes = a->tx_nbytes = 0;
-    if (b->text_bytes == 0) return BGR_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    const uint32_t nbytes = (uint32_t)b->text_bytes;
-    const uint8_t* text = nullptr;
-    // 1. the piece in HBM (zero padded): uploaded ahead of this call by a stage (bgr_text_stage_upload, a copy stream of its own), or copied now
-    if (b->stage) {
-        if (b->stage->device != a->device || b->stage->bytes != b->text_bytes) return fail(BGR_E_ARG, "bgr_align_fasta_text: the stage holds another piece / lives on another device");
-        HIP_TRY(hipStreamWaitEvent(a->stream, b->stage->ev, 0));
-        text = static_cast<const uint8_t*>(b->stage->buf.p);
-    } else {
-        if (!b->text) return fail(BGR_E_ARG, "bgr_align_fasta_text: null text");
-        HIP_TRY(a->tx_in.ensure((uint64_t)nbytes + 128));
-        text = static_cast<const uint8_t*>(a->tx_in.p);
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(a->tx_in.p) + (nbytes & ~63ull), 0, 128, a->stream));   // (64 zero bytes behind the piece at least; from an aligned address: ONE fill, and the copy below lays the text over its start)
-        HIP_TRY(hipMemcpyAsync(a->tx_in.p, b->text, nbytes, hipMemcpyHostToDevice, a->stream));
-    }
-    a->tx_text = text;
-    // 2. records: starts, extents, shape, accept test; accepted records compacted in input order.  Room for one record per 24 bytes of
-    // text (a sequencing read with its header is several times that): a piece with more record starts goes to the host parser.
-    const uint32_t R_cap = nbytes / 24 + 1024;
-    // (tickets and chains of the two one-launch kernels, text_kernels.hip: never cleared between launches -- every launch gets a fresh epoch)
-    {
-        const uint64_t chain_words = std::max<uint64_t>(3ull * bgr::text_tiles(nbytes), 2ull * bgr::format_tiles(R_cap));
-        const size_t had = a->tx_state.cap;
-        HIP_TRY(a->tx_state.ensure(64 + chain_words * 8));
-        if (a->tx_state.cap != had || a->tx_epoch + 2 > BGR_TEXT_EPOCH_MAX) {
-            const bool fresh = a->tx_state.cap != had;
-            HIP_TRY(hipMemsetAsync(a->tx_state.p, 0, a->tx_state.cap, a->stream));
-            a->tx_epoch = fresh ? (uint32_t)bgr::opt("test.text_epoch") : 0u;   // (0 but for the test hook)
-            a->tx_ticket[0] = a->tx_ticket[1] = 0;
-        }
-    }
-    uint32_t* tickets = static_cast<uint32_t*>(a->tx_state.p);
-    uint64_t* chains = reinterpret_cast<uint64_t*>(static_cast<char*>(a->tx_state.p) + 64);
-    HIP_TRY(a->tx_sums.ensure((2ull * bgr::scan_tiles(R_cap) + 16) * 4));   // (correction mode's scans)
-    for (DevBuf* d : {&a->tx_idx, &a->tx_accrec, &a->tx_accsrc, &a->tx_psz, &a->tx_nsz, &a->tx_poff, &a->tx_noff})
-        HIP_TRY(d->ensure(((uint64_t)R_cap + 4) * 4));
-    HIP_TRY(a->tx_rec.ensure(((uint64_t)R_cap + 1) * 16));
-    HIP_TRY(a->tx_offs.ensure(((uint64_t)R_cap + 2) * 8));
-    uint32_t* sums2 = static_cast<uint32_t*>(a->tx_sums.p);
-    // TXT_INFO_WORDS u32 behind cursor / counters / CSR total -- two such blocks, taken in turn: a piece's parse launch clears the block of the NEXT piece (and the
-    // mapping launch's cursor), so that no fill stands in front of either (the blocks start zero: bgr_aligner_create)
-    a->tx_flip ^= 1u;   // (here, behind everything that can fail before the launch: a block is cleared by the launch in front of the one that uses it)
-    uint32_t* info = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * a->tx_flip);
-    uint32_t* info_next = reinterpret_cast<uint32_t*>(static_cast<char*>(a->small.p) + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * (a->tx_flip ^ 1u));
-    static_assert(TXT_INFO_WORDS * 4 == bgr::kSmallTextInfoBytes, "two info blocks at small + kSmallTextInfo");
-    hipError_t e = bgr::launch_text_parse(text, nbytes, rec_lines, a->dg.k, tickets, a->tx_ticket[0], ++a->tx_epoch, chains, static_cast<uint4*>(a->tx_rec.p),
-                                          static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint32_t*>(a->tx_accrec.p), static_cast<uint32_t*>(a->tx_accsrc.p),
-                                          static_cast<uint64_t*>(a->tx_offs.p), info, R_cap, static_cast<uint32_t*>(a->small.p), bgr::kCurWords, info_next, TXT_INFO_WORDS, a->stream);
-    if (e == hipSuccess) a->tx_ticket[0] += bgr::text_tiles(nbytes);   // (as many tickets as workgroups will take)
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text record launches: ") + hipGetErrorString(e));
-    uint32_t h[TXT_INFO_WORDS];
-    HIP_TRY(hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, a->stream));
-    HIP_TRY(wait_stream(a));
-    lap(0);
-    const uint32_t R = h[TXT_INFO_N_REC];
-    b->n_records = R;
-    if (R == 0 || R > R_cap) { b->irregular = 1; return BGR_OK; }  // no record start in the bytes, or far more than a read file has: the host parser decides
-    lap(1);
-    if (h[TXT_INFO_IRREGULAR]) { b->irregular = 1; return BGR_OK; }
-    const uint32_t n_acc = h[TXT_INFO_N_ACC], bases = h[TXT_INFO_BASES], max_len = h[TXT_INFO_MAX_LEN];
-    b->n_accepted = n_acc;
-    if (n_acc == 0) {
-        if (b->record_info_out) memset(b->record_info_out, 0, (size_t)R * 4);  // (nothing kept: every record a dropped one)
-        return BGR_OK;
-    }
-    // 3. the mapping launch, its reads where they lie in the text (planes by the pre-pass, or -- greedy mode -- staged by the mapping kernels themselves)
-    int rc = align_device_impl(a, p, text, a->tx_offs.p, n_acc, bases, max_len, false, a->tx_accsrc.p, nbytes, true);
-    if (rc != BGR_OK) return rc;
-    forget_launch(a);  // (bgr_aligner_fetch has no host read_offsets to pair its rows with: the text form hands out text)
-    a->tx_n_acc = n_acc;
-    // Everything behind the mapping launch reads its results.  In exhaustive mode those are final only once the launch is settled (reads the last pass
-    // handed back for a larger table are mapped again: settle_launch) -- which hardly ever happens: so the kernels below are enqueued at once, the
-    // cursor comes back with the wait this call makes anyway, and only a launch that did hand reads back is settled and the kernels enqueued AGAIN
-    // (a wait between the mapping launch and them cost -b a fifth of its end-to-end rate)
-    uint64_t pcap_dev = 0, ncap_dev = 0;
-    a->tx_written = false;
-    for (int again = 0; again < 2; ++again) {
-    if (b->record_info_out) {  // what became of every record (the -b progress blocks of the caller), on its way to the host behind the mapping launch
-        HIP_TRY(a->tx_info.ensure((uint64_t)R * 4));
-        e = bgr::launch_text_record_info(static_cast<const uint4*>(a->tx_rec.p), static_cast<const uint32_t*>(a->tx_idx.p), static_cast<const uint2*>(a->results.p), R,
-                                         static_cast<uint32_t*>(a->tx_info.p), a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("record info launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(b->record_info_out, a->tx_info.p, (size_t)R * 4, hipMemcpyDeviceToHost, a->stream));
-    }
-    if (!b->want_output) {  // counters only: the launch still has to be settled (arena flag; exhaustive mode: reads the last pass handed back)
-        uint32_t cur[bgr::kCurWords];
-        HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
-        HIP_TRY(wait_stream(a));
-        const bool handed_back = a->deep.open && cur[bgr::list_word(bgr::List::kRetry)] != 0;
-        rc = settle_launch(a, cur);
-        if (rc != BGR_OK || !handed_back || !b->record_info_out) return rc;
-        continue;  // (the record info was made from results that were not final)
-    }
-    // 4. sizes of the records, stream offsets, the bytes
-    if (b->want_output == 3) {  // (tx_idx is free again behind the compaction: it takes the lengths of the names)
-        HIP_TRY(a->tx_gaf.ensure(((uint64_t)n_acc + 1) * 16));
-        a->tx_tagged = a->haplotag.p != nullptr;   // (an aligner with a tag table: the tagged instances of both GAF kernels)
-        if (a->tx_tagged) HIP_TRY(a->tx_tags.ensure(((uint64_t)n_acc + 1) * 16));
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
-        e = bgr::launch_text_gaf_sizes(a->dg, text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
-                                       static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, static_cast<uint32_t*>(a->tx_psz.p), static_cast<uint32_t*>(a->tx_nsz.p),
-                                       static_cast<uint32_t*>(a->tx_idx.p), static_cast<uint4*>(a->tx_gaf.p), info + TXT_INFO_BUG,
-                                       a->tx_tagged ? static_cast<const uint32_t*>(a->haplotag.p) : nullptr, static_cast<uint4*>(a->tx_tags.p), a->stream);
-    } else if (b->want_output == 2) {  // (tx_idx is free again behind the compaction: it takes the corrected reads' lengths)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info + TXT_INFO_BUG), -1, 1, a->stream));
-        e = bgr::launch_text_correct_sizes(a->dg, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
-                                           static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, static_cast<uint32_t*>(a->tx_psz.p), static_cast<uint32_t*>(a->tx_nsz.p),
-                                           static_cast<uint32_t*>(a->tx_idx.p), info + TXT_INFO_BUG, a->stream);
-    } else {
-        // sizes, offsets and bytes in one launch, into device buffers of the caller's capacities (at most twice the piece + 1 MB each: a piece whose
-        // streams need more -- paths of very many unitigs -- is written by bgr_text_write_kernel from the offsets once the totals are known)
-        pcap_dev = b->paths_out ? std::min<uint64_t>(b->paths_cap, 2ull * nbytes + (1ull << 20)) : 0;
-        ncap_dev = b->notaligned_out ? std::min<uint64_t>(b->notaligned_cap, 2ull * nbytes + (1ull << 20)) : 0;
-        HIP_TRY(a->tx_pout.ensure(pcap_dev + 64));
-        HIP_TRY(a->tx_nout.ensure(ncap_dev + 64));
-        e = bgr::launch_text_format(text, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), static_cast<const uint4*>(a->tx_rec.p),
-                                    static_cast<const uint32_t*>(a->tx_accrec.p), n_acc, tickets + 1, a->tx_ticket[1], ++a->tx_epoch, chains, static_cast<uint32_t*>(a->tx_poff.p),
-                                    static_cast<uint32_t*>(a->tx_noff.p), static_cast<uint8_t*>(a->tx_pout.p), static_cast<uint8_t*>(a->tx_nout.p), pcap_dev, ncap_dev, info, a->stream);
-        if (n_acc && e == hipSuccess) a->tx_ticket[1] += bgr::format_tiles(n_acc);   // (as many tickets as workgroups ran: launch_text_format launches nothing for zero reads)
-    }
-    if (e == hipSuccess && b->want_output >= 2) e = bgr::launch_scan2_u32(static_cast<const uint32_t*>(a->tx_psz.p), static_cast<const uint32_t*>(a->tx_nsz.p), static_cast<uint32_t*>(a->tx_poff.p),
-                                                   static_cast<uint32_t*>(a->tx_noff.p), n_acc, nullptr, sums2, info + TXT_INFO_PBYTES, info + TXT_INFO_NBYTES, a->stream);
-    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("text size launches: ") + hipGetErrorString(e));
-    uint32_t all[bgr::kSmallBytes / 4], h2[bgr::kCurWords];   // the cursor block and the info block lie in the same `small` buffer: one copy
-    HIP_TRY(hipMemcpyAsync(all, a->small.p, sizeof(all), hipMemcpyDeviceToHost, a->stream));
-    HIP_TRY(wait_stream(a));
-    memcpy(h2, all, sizeof(h2));
-    memcpy(h, all + (info - static_cast<const uint32_t*>(a->small.p)), sizeof(h));
-    lap(2);
-    if (h2[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
-    if (a->deep.open) {
-        const bool handed_back = h2[bgr::list_word(bgr::List::kRetry)] != 0;
-        rc = settle_launch(a, h2);
-        if (rc != BGR_OK) return rc;
-        if (handed_back) continue;  // sizes and offsets once more, from the final results
-    }
-    break;
-    }
-    if (b->want_output >= 2 && h[TXT_INFO_BUG] != 0xFFFFFFFFu) {  // a path that does not spell a walk: the reference prints "bug compaction" and exits
-        b->irregular = 2;                                          // (aligner.cpp:280-283); the caller reproduces that on the host
-        a->tx_n_acc = 0;
-        return BGR_OK;
-    }
-    a->tx_pbytes = h[TXT_INFO_PBYTES];
-    a->tx_nbytes = h[TXT_INFO_NBYTES];
-    a->tx_written = b->want_output == 1 && a->tx_pbytes <= pcap_dev && a->tx_nbytes <= ncap_dev;   // (every workgroup's stretch ended below the capacities)
-    const int frc = fetch_text_impl(a, b);
-    lap(3);
-    a->tx_phase_s[4] += 1;
-    return frc;
 }
 
 int bgr_aligner_sync(bgr_aligner* a) {

@@ -1,4 +1,4 @@
-// capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, text route, batches; the counting features:
+// capi_internal.h -- what the units of the C-ABI share (capi.hip: index, distribution, mapping, batches; capi_text.hip: the text route; the counting features:
 // capi_abundance.hip with the table of a run's stages, capi_links.hip with the count tables of links and triples, capi_triples.hip with the phase,
 // capi_bubbles.hip, capi_blocks.hip, capi_haplotypes.hip, capi_haplotag.hip, capi_pileup.hip, capi_variants.hip): the objects behind the opaque handles, the error
 // channel, the waits, the helpers the counting features are written with (delivering rows, the chain's switches and thresholds, a file of lines,
@@ -24,6 +24,7 @@
 #include "graph_build.h"
 #include "launch_plan.h"
 #include "options.h"
+#include "text_epochs.h"
 
 namespace bgr {
 int set_error(int code, const std::string& msg);  // capi.hip: the one definition, with the thread's message that bgr_last_error returns (pipeline.cpp calls it too)
@@ -129,6 +130,7 @@ struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }   // the buffer as an array of T
 };
 
 struct VariantsRun {   // the pileup table of a run with bgr_graph_variants_enable while its aligners are collected (bgr_graph has the rest)
@@ -154,22 +156,31 @@ struct bgr_text_stage {  // one piece of text on its way to / resident in a devi
     }
 };
 
+// The text route's state in an aligner (capi_text.hip: bgr_align_fasta_text, bgr_aligner_fetch_text): the piece, its records, the formatted streams
+struct TextRoute {
+    DevBuf in, sums, state, rec, idx, accrec, accsrc, offs, psz, nsz, poff, noff, pout, nout, info, gaf;
+    DevBuf tags;                    // GAF output of an aligner with a tag table: the tags per accepted read, next to gaf
+    uint64_t n_acc = 0, pbytes = 0, nbytes = 0;
+    const uint8_t* text = nullptr;  // where the last call's piece lies in HBM (in, or the caller's stage)
+    bgr::TextEpochs epochs;         // the one-launch kernels' chains (epoch of the last launch, tickets earlier launches took) and which of the two info blocks a piece uses
+    bool written = false;           // the streams lie in pout / nout (the format launch wrote them: every stretch ended below the capacities)
+    uint32_t want = 0;              // the piece's want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
+    bool tagged = false;            // the sizes launch of the piece in the buffers was a tagged one (the write launch follows it)
+    double phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
+    void release() {
+        for (DevBuf* b : {&in, &sums, &state, &rec, &idx, &accrec, &accsrc, &offs, &psz, &nsz, &poff, &noff, &pout, &nout, &info, &gaf, &tags}) b->release();
+    }
+};
+
 struct bgr_aligner {
     bgr_graph* graph = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
     BgrDeviceGraph dg;
-    // the text route (bgr_align_fasta_text): the piece, its records, the formatted streams
-    DevBuf tx_in, tx_sums, tx_state, tx_rec, tx_idx, tx_accrec, tx_accsrc, tx_offs, tx_psz, tx_nsz, tx_poff, tx_noff, tx_pout, tx_nout, tx_info, tx_gaf, path_stats;
-    uint64_t tx_n_acc = 0, tx_pbytes = 0, tx_nbytes = 0;
+    TextRoute text;
+    DevBuf path_stats;
     bool blocking_sync = bgr::opt("blocking_sync") != 0;
     hipEvent_t ev_wait = nullptr;
-    const uint8_t* tx_text = nullptr;  // where the last call's piece lies in HBM (tx_in, or the caller's stage)
-    uint32_t tx_flip = 0;              // which of the two info blocks the current piece uses
-    uint32_t tx_epoch = 0, tx_ticket[2] = {0, 0};   // the one-launch kernels' chains: epoch of the last launch; tickets earlier launches took (parse, format)
-    bool tx_written = false;           // the streams lie in tx_pout / tx_nout (the format launch wrote them: every stretch ended below the capacities)
-    uint32_t tx_want = 0;              // its want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
-    double tx_phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
 
     DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: kSmall* (align_kernels.h)
     struct DeepRun {  // the last pass of the exhaustive launch in flight, as enqueued: settle_launch runs it again for reads whose table filled up
@@ -219,10 +230,8 @@ struct bgr_aligner {
     bool strands_on = false;        // bgr_aligner_pileup_strands_enable: the pileup kernel also adds the forward observations to a second table
     DevBuf pileup_fwd;              // that table: the layout of `pileup`, its tail stays 0
     uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
-    // haplotags (bgr_aligner_haplotag_enable): the tag table on the device (null: off), the tags of the last call of bgr_aligner_haplotags; the text
-    // route's tags per accepted read next to tx_gaf, and whether the sizes launch of the piece in the buffers was a tagged one (the write launch follows it)
-    DevBuf haplotag, haplotag_out, tx_tags;
-    bool tx_tagged = false;
+    // haplotags (bgr_aligner_haplotag_enable): the tag table on the device (null: off), the tags of the last call of bgr_aligner_haplotags
+    DevBuf haplotag, haplotag_out;
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
@@ -354,6 +363,13 @@ struct DeviceCall {
 };
 
 // ---- the functions that cross units --------------------------------------------------------------------------------------------
+// capi.hip, for the text route (capi_text.hip)
+void forget_launch(bgr_aligner* a);   // no single launch whose results could be read again: bgr_aligner_fetch finds n = 0, on the aligner itself
+extern "C" {   // (defined among the functions of the interface)
+int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads, uint64_t total_bases, uint32_t max_read_len,
+                      bool planes_ready, const void* d_src_off, uint64_t reads_bytes, bool cursor_is_zero);   // the mapping launch of one batch (see there)
+int settle_launch(bgr_aligner* a, uint32_t* cur);   // behind a mapping launch, its stream waited for and the cursor block in `cur`: the arena flag; exhaustive mode: reads handed back are mapped
+}
 // capi_abundance.hip
 int abundance_set(bgr_aligner* a, bool on);   // this one aligner's (or twin's) switch; the table is allocated and zeroed the first time
 bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases);   // geometry and form of the abundance kernel behind a launch of this size

@@ -675,6 +675,17 @@ __device__ __forceinline__ uint32_t row_ror4(uint32_t x) { return (uint32_t)__bu
 __device__ __forceinline__ uint32_t half_row_mirror(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true); }
 __device__ __forceinline__ uint32_t row_ror8(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, true); }
 __device__ __forceinline__ uint32_t lane_get(uint32_t v, uint32_t src_lane) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v); }
+// min over the 16 lanes of a row, result in every lane
+__device__ __forceinline__ uint32_t row16_min(uint32_t x) {
+    uint32_t o = quad_xor1(x); x = o < x ? o : x;
+    o = quad_xor2(x); x = o < x ? o : x;
+    o = half_row_mirror(x); x = o < x ? o : x;
+    o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true); x = o < x ? o : x;  // row_mirror
+    return x;
+}
+// bits 7, 15, 23, 31 of h -> bits 0..3 (one multiply: the four shifted copies do not meet)
+__device__ __forceinline__ uint32_t nibble_of(uint32_t h) { return (((h >> 7) * 0x00204081u) >> 21) & 0xFu; }
+typedef uint32_t __attribute__((ext_vector_type(4), aligned(1))) u32x4_unaligned;   // 16 bytes at any alignment (the text kernels, walk_lanes.h)
 
 // record index | canonical << 28 (| fits << 29 | found << 30 in a step result) as the several-reads-per-wave kernels pass it around
 #define G4_REC_MASK 0x0FFFFFFFu

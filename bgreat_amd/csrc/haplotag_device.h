@@ -1,5 +1,5 @@
 // haplotag_device.h -- the tag of one mapped read's row (bgr_read_tag, include/bgreat_gpu.h) by the sixteen lanes of a group, shared by the
-// stand-alone kernel behind bgr_aligner_haplotags (haplotag_kernels.hip) and the tagged instances of the GAF formatter (text_kernels.hip).
+// stand-alone kernel behind bgr_aligner_haplotags (haplotag_kernels.hip) and the tagged instances of the GAF formatter (text_gaf.hip).
 // haplotag_host.h has the plain C++ twin, tests/haplotag_ref.py the definition.  Included behind device_common.h by .hip files only.
 //
 // Lane i takes id i of a pass of sixteen: one 4-byte gather from the table per id.  The smallest block among the votes is a min-reduction over

@@ -1,6 +1,6 @@
 // haplotag_kernels.h -- launch interface of haplotag_kernels.hip: the tags (bgr_read_tag in include/bgreat_gpu.h has the definition) of the rows
 // of a greedy or anchors launch, from a tag table resident on the device.  The per-row function is haplotag_device.h's, which the tagged GAF
-// kernels (text_kernels.hip) share.
+// kernels (text_gaf.hip) share.
 #ifndef BGREAT_AMD_HAPLOTAG_KERNELS_H
 #define BGREAT_AMD_HAPLOTAG_KERNELS_H
 

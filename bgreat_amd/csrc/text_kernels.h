@@ -1,4 +1,5 @@
-// text_kernels.h -- launch interface of text_kernels.hip (FASTA text in, formatted records out; see there).
+// text_kernels.h -- launch interface of the text route's kernels (FASTA text in, formatted records out): text_kernels.hip (the streaming kernels: scan,
+// parse, record info, write, format), text_correct.hip (correction mode), text_gaf.hip (GAF lines, path stats); see there.
 #ifndef BGREAT_AMD_TEXT_KERNELS_H
 #define BGREAT_AMD_TEXT_KERNELS_H
 
@@ -17,7 +18,7 @@
 #define TXT_INFO_NBYTES 6     /* bytes of the notAligned stream */
 #define TXT_INFO_BUG 7        /* correction mode: the first accepted read whose path does not spell a walk ("bug compaction"), else ~0 */
 #define TXT_INFO_WORDS 8
-#define BGR_TEXT_EPOCH_MAX 0x3FFFFFu /* epochs of the chains: 22 bits, 0 = never written */
+#include "text_epochs.h" /* BGR_TEXT_EPOCH_MAX, and the host's book of the epochs */
 
 namespace bgr {
 
@@ -30,8 +31,8 @@ uint32_t format_tiles(uint32_t n_acc);   // ... of the format launch
 // The piece in one launch: info[N_REC, N_ACC, BASES, MAX_LEN, IRREGULAR]; rec[0 .. min(N_REC, rec_cap)); the accepted records compacted in input order: acc_rec (which
 // record), acc_src (where its read starts in the text), read_offs (base offsets, N_ACC + 1 of them); acc_idx[j] = a for accepted record j.
 // fastq_lines: 0 FASTA, else lines per FASTQ record (4, 2).  Running totals pass between the launch's workgroups through `chains` (3 * text_tiles(n) u64), tagged
-// with `epoch` (1 .. kTextEpochMax, a fresh one per launch; the chains are zero before epoch 1 is used), the workgroups numbered by *ticket - ticket_base (*ticket
-// grows by text_tiles(n) per launch).  words_a words at zero_a and words_b at zero_b (at most 1024 each) are cleared: words only later launches read.
+// with `epoch` (1 .. BGR_TEXT_EPOCH_MAX, a fresh one per launch; the chains are zero before epoch 1 is used; any other value: hipErrorInvalidValue and no launch -- the
+// kernels would wait for ever), the workgroups numbered by *ticket - ticket_base (*ticket grows by text_tiles(n) per launch).  words_a words at zero_a and words_b at zero_b (at most 1024 each) are cleared: words only later launches read.
 hipError_t launch_text_parse(const uint8_t* text, uint32_t n, uint32_t fastq_lines, uint32_t k, uint32_t* ticket, uint32_t ticket_base, uint32_t epoch, uint64_t* chains,
                              uint4* rec, uint32_t* acc_idx, uint32_t* acc_rec, uint32_t* acc_src, uint64_t* read_offs, uint32_t* info, uint32_t rec_cap, uint32_t* zero_a,
                              uint32_t words_a, uint32_t* zero_b, uint32_t words_b, hipStream_t stream);
@@ -50,7 +51,7 @@ hipError_t launch_text_correct_sizes(const BgrDeviceGraph& g, const uint2* resul
 hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                      const uint32_t* poff, const uint32_t* noff, const uint32_t* clen, uint8_t* pout, uint8_t* nout, hipStream_t stream);
 // GAF output (--gaf, want_output 3): a mapped read's record is one GAF line -- name, query interval, the path's segments with their orientations, path interval,
-// matches, NM (text_kernels.hip).  Sizes (psz / nsz, scanned by launch_scan2_u32), then the bytes; nlen (characters of the name), rows ({walk size low, high,
+// matches, NM (text_gaf.hip).  Sizes (psz / nsz, scanned by launch_scan2_u32), then the bytes; nlen (characters of the name), rows ({walk size low, high,
 // characters covered, NM} per accepted read) and psz pass from the first to the second.  *bug as launch_text_correct_sizes sets it.
 hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                  uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream);

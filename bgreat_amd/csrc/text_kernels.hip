@@ -7,11 +7,11 @@
 //   out  the records as the reference writes them: mapped -> header '\n' printPath (aligner.cpp:600-609: to_string(int) + '.')
 //        '\n' (alignerGreedy.cpp:406-411), the others -> header '\n' read '\n' (alignerGreedy.cpp:421-427), each stream in input
 //        order at offsets from a device-wide scan.
-// Streaming byte work: HBM-bound by design, no MFMA.
+// Streaming byte work: HBM-bound by design, no MFMA.  These are the kernels that never read the graph -- scan, parse, record info, write, format --
+// with their launchers; the ones that walk paths through it are text_correct.hip (-c) and text_gaf.hip (--gaf, path stats); text_device.h has what they share.
 #include "device_common.h"
 #include "text_kernels.h"
-#include "walk_lanes.h"
-#include "haplotag_device.h"
+#include "text_device.h"
 
 #ifdef BGR_X_TIMES
 __device__ unsigned long long bgr_x_times[4 * 16];
@@ -25,39 +25,6 @@ namespace bgr {
 namespace {
 
 constexpr uint32_t kTxtThreads = 1024;
-
-// inclusive scan over the 64 lanes of a wave without LDS: four row_shr steps scan each row of 16, row_bcast:15 carries row 0 into row 1 and row 2 into row 3,
-// row_bcast:31 carries rows 0..1 into rows 2..3 (a lane whose source lies outside its row, or whose row is masked out, adds the 0 given as `old`)
-#define BGR_DPP0(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), ctrl, rows, 0xF, false))
-__device__ __forceinline__ uint32_t wave_inclusive_scan32(uint32_t x) {
-    x += BGR_DPP0(x, 0x111, 0xF); x += BGR_DPP0(x, 0x112, 0xF); x += BGR_DPP0(x, 0x114, 0xF); x += BGR_DPP0(x, 0x118, 0xF);
-    x += BGR_DPP0(x, 0x142, 0xA);
-    x += BGR_DPP0(x, 0x143, 0xC);
-    return x;
-}
-#define BGR_DPP0_64(x, ctrl, rows) (((u64)BGR_DPP0((uint32_t)((x) >> 32), ctrl, rows) << 32) | BGR_DPP0((uint32_t)(x), ctrl, rows))
-__device__ __forceinline__ u64 wave_inclusive_scan64(u64 x) {
-    x += BGR_DPP0_64(x, 0x111, 0xF); x += BGR_DPP0_64(x, 0x112, 0xF); x += BGR_DPP0_64(x, 0x114, 0xF); x += BGR_DPP0_64(x, 0x118, 0xF);
-    x += BGR_DPP0_64(x, 0x142, 0xA);
-    x += BGR_DPP0_64(x, 0x143, 0xC);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t block_exclusive_scan32(uint32_t v, uint32_t* lds_waves, uint32_t* block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;   // (up to 16 waves)
-    const uint32_t inc = wave_inclusive_scan32(v);
-    if (lane == 63) lds_waves[wave] = inc;
-    __syncthreads();
-    // every wave scans the (at most 16) wave totals itself: one LDS read, four shuffles (a loop over them waits for LDS sixteen times)
-    const uint32_t t = lane < nw ? lds_waves[lane] : 0u;
-    uint32_t ti = t;
-    ti += BGR_DPP0(ti, 0x111, 0xF); ti += BGR_DPP0(ti, 0x112, 0xF); ti += BGR_DPP0(ti, 0x114, 0xF); ti += BGR_DPP0(ti, 0x118, 0xF);   // (row 0 holds them)
-    const uint32_t before = (uint32_t)__shfl((int)(ti - t), wave, 64);
-    *block_total = (uint32_t)__shfl((int)ti, 15, 64);
-    __syncthreads();
-    return before + inc - v;
-}
-
 constexpr uint32_t kScanItems = 4, kScanTile = kTxtThreads * kScanItems;
 
 // ---- device-wide exclusive scan of TWO u32 arrays of equal length in one go (4096 items per workgroup; sums, one-workgroup scan of the sums, apply),
@@ -115,33 +82,6 @@ __global__ void __launch_bounds__(kTxtThreads) bgr_scan2_apply(const uint32_t* i
         if (base + j < n) { outA[base + j] = wa; outB[base + j] = wb; }
         wa += va[j]; wb += vb[j];
     }
-}
-
-// bit 7 of every byte of x that equals the byte replicated in `pat`
-__device__ __forceinline__ uint32_t eq_bytes(uint32_t x, uint32_t pat) { return bgr_zero_bytes(x ^ pat); }
-
-// 16 bytes from `p` (any alignment; bytes at or beyond `end` read as zero)
-__device__ __forceinline__ void load16(const uint8_t* text, uint32_t p, uint32_t end, uint32_t w[4]) {
-    w[0] = w[1] = w[2] = w[3] = 0;
-    if (p >= end) return;
-    const u32x4_unaligned v = *reinterpret_cast<const u32x4_unaligned*>(text + p);  // (the buffer is padded by 32 bytes)
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    const uint32_t valid = end - p;
-    if (valid < 16) {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const uint32_t lo = 4u * d;
-            if (valid <= lo) w[d] = 0;
-            else if (valid < lo + 4) w[d] &= 0xFFFFFFFFu >> (8 * (lo + 4 - valid));
-        }
-    }
-}
-// bit i (0..15) = byte i of the 16 loaded equals c
-__device__ __forceinline__ uint32_t mask16(const uint32_t w[4], uint32_t pat) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) m |= nibble_of(eq_bytes(w[d], pat)) << (4 * d);
-    return m;
 }
 
 // ---- a running total handed from tile to tile inside ONE launch (decoupled look-back) ----------------------------------------------------------
@@ -203,32 +143,6 @@ __device__ __forceinline__ u64 chain_lookback(u64* st, uint32_t vt, uint32_t epo
     return chain_walk(st, vt, epoch, own);
 }
 
-__device__ __forceinline__ u64 shfl64(u64 x, int l) { return ((u64)(uint32_t)__shfl((int)(uint32_t)(x >> 32), l, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)x, l, 64); }
-// exclusive scans of N 64-bit values per thread over the workgroup, array after array (value n of thread t comes behind value n - 1 of every thread): one pair
-// of barriers for all of them.  ex[n] = what lies in front of v[n]; *total = everything.  (fields packed in a value must not carry into each other)
-template <int N>
-__device__ __forceinline__ void block_exclusive_scan64xN(const u64 (&v)[N], u64* lds_waves /* N * 16 */, u64 (&ex)[N], u64* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    u64 inc[N];
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        inc[n] = wave_inclusive_scan64(v[n]);
-        if (lane == 63) lds_waves[n * 16 + wave] = inc[n];
-    }
-    __syncthreads();
-    u64 run = 0;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const u64 t = lane < nw ? lds_waves[n * 16 + lane] : 0ull;
-        u64 ti = t;
-        ti += BGR_DPP0_64(ti, 0x111, 0xF); ti += BGR_DPP0_64(ti, 0x112, 0xF); ti += BGR_DPP0_64(ti, 0x114, 0xF); ti += BGR_DPP0_64(ti, 0x118, 0xF);
-        ex[n] = run + shfl64(ti - t, wave) + inc[n] - v[n];
-        run += shfl64(ti, 15);
-    }
-    *total = run;
-    __syncthreads();
-}
-
 // ---- the piece in ONE pass: record starts, extents, shape, accept test, accepted records compacted in input order --------------------------------
 // (round 4/5: eight launches -- two marking passes and a scan for the record starts, a 16-lane group per record reading the text a third time,
 //  three launches of scans, a compaction; 230 us per 44 MB piece.)  A workgroup takes 96 KB of text as three stretches of 32 KB, 32 bytes per thread
@@ -243,7 +157,6 @@ __device__ __forceinline__ void block_exclusive_scan64xN(const u64 (&v)[N], u64*
 constexpr uint32_t kParseThreads = 1024, kParseStretch = kParseThreads * 32, kParseStretches = 3, kParseTile = kParseStretch * kParseStretches;
 constexpr uint32_t kParseHaloWords = 32, kParseWords = kParseThreads + kParseHaloWords, kParseWindow = kParseWords * 32;
 constexpr uint32_t kParseMaxLocal = kParseThreads;   // record starts per stretch (a record of 32 bytes is hardly a read: such a piece goes to the host)
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t next_set(const uint32_t* bits, uint32_t from) {   // first set bit at or behind `from` in the window, or kNone
     if (from >= kParseWindow) return kNone;
@@ -520,27 +433,7 @@ __global__ void __launch_bounds__(256) bgr_text_record_info_kernel(const uint4* 
     out[j] = v;
 }
 
-// ---- out: sizes of the formatted records -----------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dec_len(int32_t v) {  // characters of to_string(v) + '.'
-    uint32_t u = (uint32_t)v, len = 1;
-    if (v < 0) { u = 0u - u; len = 2; }
-    len += u < 10 ? 1 : u < 100 ? 2 : u < 1000 ? 3 : u < 10000 ? 4 : u < 100000 ? 5 : u < 1000000 ? 6 : u < 10000000 ? 7 : u < 100000000 ? 8 : u < 1000000000 ? 9 : 10;
-    return len;
-}
-// the first min(m, 16) bytes of v to dst (any alignment)
-__device__ __forceinline__ void store_upto16(uint8_t* dst, const u32x4_unaligned v, uint32_t m) {
-    if (m >= 16) { *reinterpret_cast<u32x4_unaligned*>(dst) = v; return; }
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};   // (the last bytes: byte stores out of registers -- a loop of byte loads and stores waits for memory once per byte)
-#pragma unroll
-    for (uint32_t i = 0; i < 15; ++i) if (i < m) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-}
-// n bytes from src to dst by the 16 lanes of a group (any alignment on both sides; the SOURCE may be read up to 15 bytes past its end: the text is padded)
-__device__ __forceinline__ void group_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t sub) {
-    for (uint32_t b = 16 * sub; b < n; b += 256) {
-        store_upto16(dst + b, *reinterpret_cast<const u32x4_unaligned*>(src + b), n - b);
-    }
-}
-
+// ---- out: the formatted records ---------------------------------------------------------------------------------------------
 // one accepted read's record by the 16 lanes of a group: into the paths stream (d_p) or the notAligned stream (d_n), whichever is not null
 __device__ __forceinline__ void write_record(const uint8_t* text, const uint2 res, const uint4 r, const int32_t* arena, uint8_t* d_p, uint8_t* d_n, uint32_t sub) {
     const uint32_t np = res.y & 0xFFFFFFu, hl = r.y;
@@ -754,485 +647,6 @@ __global__ void __launch_bounds__(kFmtThreads, 8) bgr_text_format_kernel(const u
     }
 }
 
-// ---- correction mode (-c) on the device: the read as spelled by its path ----------------------------------------------------------
-// recoverPath (aligner.cpp:270-290): walk = getUnitig(path[1]); for every further int: compactionEnd(walk, getUnitig(path[i]), k-1)
-// (utils.cpp:171-179) glues the unitig on when the walk's last k-1 characters equal its first k-1 -- as oriented by its sign or,
-// failing that, reverse complemented -- else "bug compaction"; then walk.substr(path[0], read size), reverse complemented when the
-// path was found on the read's reverse complement (alignerGreedy.cpp:394-404).  Graphs without exception planes only (every unitig
-// character is one of ACGT, so the 2-bit store spells it); the caller formats such a batch on the host otherwise.
-// WIDE (k > 33: a (k-1)-mer is longer than one word): the overlap compare takes a second window for the bases behind the first 32.
-template <bool WIDE>
-struct WalkIter {   // the oriented unitigs of a path, one after the other
-    const BgrDeviceGraph& g;
-    const int32_t* path;
-    uint32_t np, K1;
-    uint32_t i = 1;          // path int of the current unitig
-    u64 base = 0;            // where its oriented bases start in seq
-    uint32_t len = 0, skip = 0;  // its length; bases of it that belong to the overlap with its predecessor (0 for the first, else k-1)
-    bool bad = false;
-    __device__ WalkIter(const BgrDeviceGraph& g_, const int32_t* p, uint32_t n) : g(g_), path(p), np(n), K1(g_.k - 1) {}
-    __device__ u64 kmer_at(u64 b) const { return win32(g.seq, b) >> (64 - 2 * (WIDE ? 32 : K1)); }
-    __device__ bool kmer_eq(u64 b, u64 t, u64 t2) const { return kmer_at(b) == t && (!WIDE || win32(g.seq, b + 32) >> (128 - 2 * K1) == t2); }
-    __device__ bool load() {  // unitig i as its sign orients it; false when the id is out of range (getUnitig of a bad int)
-        const int32_t s = path[i];
-        const uint32_t id = (uint32_t)(s < 0 ? -(int64_t)s : (int64_t)s);
-        if (id == 0 || id > (uint32_t)g.hdr->n_unitigs) return false;
-        const BgrUnitigMeta m = g.meta[id];
-        len = m.len;
-        base = m.F + (s < 0 ? m.len : 0);
-        return true;
-    }
-    __device__ bool first() { skip = 0; i = 1; if (np < 2 || !load()) { bad = true; return false; } return true; }
-    __device__ bool next() {   // false: no further unitig (or bad set: bug compaction)
-        if (i + 1 >= np) return false;
-        const u64 tail = kmer_at(base + len - K1), tail2 = WIDE ? win32(g.seq, base + len - K1 + 32) >> (128 - 2 * K1) : 0;
-        ++i;
-        if (!load()) { bad = true; return false; }
-        if (!kmer_eq(base, tail, tail2)) {  // compactionEnd's second try: the reverse complement (the other strand of the store)
-            const int32_t s = path[i];
-            const uint32_t id = (uint32_t)(s < 0 ? -(int64_t)s : (int64_t)s);
-            const BgrUnitigMeta m = g.meta[id];
-            const u64 other = m.F + (s < 0 ? 0 : m.len);
-            if (!kmer_eq(other, tail, tail2)) { bad = true; return false; }
-            base = other;
-        }
-        skip = K1;
-        return true;
-    }
-};
-
-// sizes: mapped read -> header + '\n' + min(read size, walk size - offset) + '\n' in the paths stream; *bug (atomicMin) = the first
-// accepted read whose path does not spell a walk
-template <bool WIDE>
-__device__ __forceinline__ void correct_sizes(const BgrDeviceGraph& g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                              uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
-    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n_acc) return;
-    const uint2 res = results[a];
-    const uint4 r = rec[acc_rec[a]];
-    const uint32_t np = res.y & 0xFFFFFFu, L = r.w & 0x7FFFFFFFu;
-    uint32_t ps = 0, ns = 0, cl = 0;
-    if (np) {
-        WalkIter<WIDE> w(g, arena + res.x, np);
-        u64 total = 0;
-        if (w.first()) { total = w.len; while (w.next()) total += w.len - w.skip; }
-        const int32_t off = arena[res.x];
-        if (w.bad || off < 0 || (u64)off > total) atomicMin(bug, a);
-        else {
-            const u64 left = total - (u64)off;
-            cl = left < L ? (uint32_t)left : L;
-        }
-        ps = r.y + 2 + cl;
-    } else {
-        ns = r.y + L + 2;
-    }
-    psz[a] = ps;
-    nsz[a] = ns;
-    clen[a] = cl;
-}
-__global__ void __launch_bounds__(256) bgr_text_correct_sizes_kernel(BgrDeviceGraph g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                                                     uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
-    correct_sizes<false>(g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
-}
-__global__ void __launch_bounds__(256) bgr_text_correct_sizes_wide_kernel(BgrDeviceGraph g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* clen, uint32_t* bug) {
-    correct_sizes<true>(g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
-}
-
-__device__ __forceinline__ uint8_t base_char(uint32_t code) { return (uint8_t)((0x54474341u >> (8 * code)) & 0xFF); }  // "ACGT"
-
-// one 16-lane group per accepted read; a mapped read's record is header + '\n' + the corrected read + '\n'
-template <bool WIDE>
-__device__ __forceinline__ void correct_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                              const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
-                                              uint8_t* pout, uint8_t* nout) {
-    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    if (a >= n_acc) return;
-    const uint2 res = results[a];
-    const uint4 r = rec[acc_rec[a]];
-    const uint32_t np = res.y & 0xFFFFFFu, hl = r.y;
-    if (!np) {   // alignerGreedy.cpp:421-427: header + '\n' + read + '\n'
-        uint8_t* d = nout + noff[a];
-        const uint32_t L = r.w & 0x7FFFFFFFu;
-        group_copy(d, text + r.x, hl, sub);
-        if (sub == 0) d[hl] = '\n';
-        group_copy(d + hl + 1, text + r.z, L, sub);
-        if (sub == 0) d[hl + 1 + L] = '\n';
-        return;
-    }
-    uint8_t* d = pout + poff[a];
-    group_copy(d, text + r.x, hl, sub);
-    if (sub == 0) d[hl] = '\n';
-    const uint32_t cl = clen[a];
-    uint8_t* o = d + hl + 1;
-    if (sub == 0) o[cl] = '\n';
-    const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
-    // every lane walks the path (a handful of unitigs) and spells the characters j = sub, sub + 16, ... of walk[off, off + cl)
-    const uint32_t off = (uint32_t)arena[res.x];
-    WalkIter<WIDE> w(g, arena + res.x, np);
-    if (!w.first()) return;
-    u64 start = 0;  // walk position of the current unitig's first NEW base (behind the overlap)
-    for (;;) {
-        const u64 new_len = w.len - w.skip, end = start + new_len;   // walk positions [start, end) come from this unitig at oriented offsets skip + (p - start)
-        // walk positions wanted: off + j, j < cl
-        if (end > off && start < (u64)off + cl) {
-            const u64 lo = start > off ? start : off, hi = end < (u64)off + cl ? end : (u64)off + cl;
-            // j with off + j in [lo, hi), j = sub mod 16
-            uint32_t j = (uint32_t)(lo - off);
-            j += (sub + 16 - (j & 15)) & 15;
-            for (; (u64)off + j < hi; j += 16) {
-                const u64 p = w.base + w.skip + ((u64)off + j - start);
-                const uint32_t code = (uint32_t)(g.seq[p >> 5] >> (62 - 2 * (p & 31))) & 3u;
-                if (!rc) o[j] = base_char(code);
-                else o[cl - 1 - j] = base_char(3u - code);  // reverseComplements(corrected) (utils.cpp:66-73; ACGT only here)
-            }
-        }
-        start = end;
-        if (start >= (u64)off + cl) break;
-        if (!w.next()) break;
-    }
-}
-__global__ void __launch_bounds__(256) bgr_text_correct_write_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                     const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
-                                                                     uint8_t* pout, uint8_t* nout) {
-    correct_write<false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
-}
-__global__ void __launch_bounds__(256) bgr_text_correct_write_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                          const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* clen,
-                                                                          uint8_t* pout, uint8_t* nout) {
-    correct_write<true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
-}
-
-// ---- GAF output (--gaf, want_output 3): one line per mapped read -- strand, coordinates and mismatches -------------------------------------
-// The walk is the one -c spells (WalkIter), the line describes the read as it stands in the input: a read mapped on its reverse complement
-// (BGR_ST_RC) has its path written reversed with every orientation flipped.  With walk offset off = path[0], read size L, plen = size of
-// the walk, cl = min(L, plen - off):   forward: query [0, cl), path [off, off + cl);   on the rc: query [L - cl, L), path [plen - off - cl, plen - off).
-// NM counts the positions where the read's characters differ from what the path spells there (an N always differs).  Graphs without
-// exception planes only, as -c on the device.  A 16-lane group per read: the unitigs of the path are spread over the lanes (gaf_stat), then the compare,
-// 16 characters per lane-step -- characters by one 16-byte load, bases by one 64-bit window of the 2-bit store.
-struct GafStat {
-    u64 plen = 0;
-    uint32_t cl = 0, nm = 0, segbytes = 0;   // segbytes: characters of the segment column ('>' or '<' and the id, per unitig)
-    uint32_t obits = 0;                      // bit i: unitig i of the path (the first 32) was glued on in its forward strand
-    bool bad = false;                        // the path spells no walk (the -c kernels' bug-compaction condition)
-    int32_t sid0 = 0;                        // this lane's path int of the first pass (0 behind the path's end): what the tagged instances vote with
-};
-__device__ __forceinline__ uint32_t dec_digits(u64 u) {   // characters of to_string(u)
-    uint32_t n = 1;
-    for (u64 p = 10; n < 20 && u >= p; p *= 10) ++n;
-    return n;
-}
-// to_string(u) ending in front of e
-__device__ __forceinline__ void put_dec(uint8_t* e, u64 u) {
-    if (u <= 0xFFFFFFFFull) { uint32_t v = (uint32_t)u; do { const uint32_t q = v / 10; *--e = (uint8_t)('0' + (v - q * 10)); v = q; } while (v); }
-    else do { const u64 q = u / 10; *--e = (uint8_t)('0' + (uint32_t)(u - q * 10)); u = q; } while (u);
-}
-// the header's name: its characters behind the first one ('>' or '@') up to the first space or tab -> their number (0: the line gets '*')
-__device__ __forceinline__ uint32_t gaf_name_len(const uint8_t* text, uint32_t p, uint32_t hl, uint32_t sub) {
-    if (hl < 2) return 0;
-    const uint32_t s = p + 1, e = p + hl;
-    for (uint32_t base = s; base < e; base += 256) {
-        uint32_t w[4];
-        const uint32_t at = base + 16 * sub;
-        load16(text, at, e, w);
-        const uint32_t m = mask16(w, 0x20202020u) | mask16(w, 0x09090909u);
-        const uint32_t first = row16_min(m ? at + (uint32_t)__ffs((int)m) - 1 : kNone);
-        if (first != kNone) return first - s;
-    }
-    return e - s;
-}
-// The walk of one mapped read's path (np >= 1 ints) and the compare of the read with it, by the 16 lanes of a group; the results in every lane.
-// read: its L characters as they stand in the input.  The walk itself -- lane i takes unitig i of a pass of sixteen -- is walk_pass (walk_lanes.h);
-// then lane c takes the read's characters [16 c, 16 c + 16) and compares them with the one or two unitigs that lie under them.
-template <bool WIDE, bool PADDED>
-__device__ __forceinline__ GafStat gaf_stat(const BgrDeviceGraph& g, const int32_t* path, uint32_t np, const uint8_t* read, uint32_t L, bool rc, uint32_t sub) {
-    GafStat s;
-    const int32_t off_s = path[0];
-    if (np < 2 || off_s < 0) { s.bad = true; return s; }
-    const u64 off = (u64)off_s;
-    const uint32_t nu = np - 1, K1 = g.k - 1;
-    WalkCarry carry;
-    uint32_t nm = 0;
-    for (uint32_t u0 = 0; u0 < nu; u0 += 16) {
-        WalkLane w;
-        if (!walk_pass<WIDE>(g, path, nu, u0, sub, carry, w)) { s.bad = true; return s; }
-        const uint32_t u = u0 + sub, id = w.id, len = w.len, st = w.st, last = w.last;
-        const bool on = w.on;
-        if (u0 == 0) s.sid0 = w.sid;
-        const u64 F = w.F, start = w.start, end = w.end, total = w.pass_start, pass_end = w.pass_end;
-        s.segbytes += row16_sum(on ? 1u + dec_digits(id) : 0u);
-        s.obits |= row16_sum(on && u < 32 && st == 0 ? 1u << u : 0u);
-        // read position t faces base t + cst of the store: forward the strand it was glued on in; on the rc the read runs against the walk, i.e. along
-        // the unitig's OTHER strand (the store holds both)
-        const u64 skip = u == 0 ? 0u : K1;
-        const int64_t cst = !rc ? (int64_t)(F + (st ? len : 0u) + skip) + (int64_t)off - (int64_t)start
-                                : (int64_t)(F + (st ? 0u : len) + len - skip) + (int64_t)start - (int64_t)off - (int64_t)L;
-        const u64 lo = total > off ? total : off, hi = pass_end < off + L ? pass_end : off + L;   // walk positions of this pass that lie under the read
-        if (lo < hi) {
-            const uint32_t tlo = !rc ? (uint32_t)(lo - off) : L - (uint32_t)(hi - off), thi = !rc ? (uint32_t)(hi - off) : L - (uint32_t)(lo - off);
-            const uint32_t cnt = last + 1;
-            for (uint32_t c0 = tlo >> 4; 16 * (u64)c0 < thi; c0 += 16) {   // (every lane takes every turn: the shuffles below need them all)
-                const uint32_t t0 = 16 * (c0 + sub);
-                const bool mine = t0 < thi;
-                const uint32_t ca = tlo > t0 ? tlo : t0, cb = thi < t0 + 16 ? thi : t0 + 16;   // the read positions [ca, cb) of these 16
-                uint32_t ch[4] = {0, 0, 0, 0};
-                if (mine) load16p<PADDED>(read + t0, L - t0, ch);
-                for (uint32_t v = 0; v < cnt; ++v) {
-                    const u64 sv = grp_get64(start, v), ev = grp_get64(end, v);
-                    const int64_t cv = (int64_t)grp_get64((u64)cst, v);
-                    // unitig v's new bases [sv, ev) of the walk in read positions
-                    const int64_t va = !rc ? (int64_t)sv - (int64_t)off : (int64_t)L - ((int64_t)ev - (int64_t)off);
-                    const int64_t vb = !rc ? (int64_t)ev - (int64_t)off : (int64_t)L - ((int64_t)sv - (int64_t)off);
-                    const int64_t xa = va > (int64_t)ca ? va : (int64_t)ca, xb = vb < (int64_t)cb ? vb : (int64_t)cb;
-                    if (mine && xa < xb) {
-                        const uint32_t a = (uint32_t)xa - t0, b = (uint32_t)xb - t0;
-                        const uint32_t codes = (uint32_t)(win32(g.seq, (u64)(xa + cv)) >> 32) >> (2 * a);   // base of character i at bits 31 - 2 i, 30 - 2 i
-                        const uint32_t eq = eq16_acgt(ch, codes);
-                        nm += (uint32_t)__popc(~eq & ((1u << b) - 1u) & ~((1u << a) - 1u));
-                    }
-                }
-            }
-        }
-    }
-    const u64 total = carry.total;
-    if (off > total) { s.bad = true; return s; }
-    s.plen = total;
-    s.cl = total - off < L ? (uint32_t)(total - off) : L;
-    s.nm = row16_sum(nm);
-    return s;
-}
-// where the line's intervals lie (see above)
-__device__ __forceinline__ void gaf_intervals(bool rc, uint32_t L, u64 off, u64 plen, uint32_t cl, uint32_t& qs, uint32_t& qe, u64& pstart) {
-    if (!rc) { qs = 0; qe = cl; pstart = off; }
-    else { qs = L - cl; qe = L; pstart = plen - (off + cl); }
-}
-// the line without its name and its segment column: 9 numbers, 12 tabs, '+', "255", "NM:i:", '\n'
-__device__ __forceinline__ uint32_t gaf_fixed_bytes(uint32_t L, uint32_t qs, uint32_t qe, u64 plen, u64 pstart, uint32_t cl, uint32_t nm) {
-    return 22 + dec_digits(L) + dec_digits(qs) + dec_digits(qe) + dec_digits(plen) + dec_digits(pstart) + dec_digits(pstart + cl) + dec_digits(cl - nm) + dec_digits(cl) + dec_digits(nm);
-}
-
-// sizes: a mapped read's line in the paths stream, the others' header + '\n' + read + '\n' in the notAligned stream; what the write kernel needs
-// again is kept per read: row = {plen, strand bits of the first 32 unitigs, cl, NM | bit 31: the row does not hold it all (a longer path, a walk of
-// 2^32 bases): the write kernel walks the path itself}, nlen = characters of the name.  (Measured: with the write kernel walking every path for the
-// orientations, as -c's does for the bases, it took 150 us per 262 144 reads, of which the walk's dependent loads were two thirds.)
-// *bug as correct_sizes sets it.
-// TAG (the aligner has a tag table, bgr_aligner_haplotag_enable): the read's tag is computed here, where the walk holds the path's first sixteen ids in
-// its lanes, kept in tags[a] next to the row, and the bytes of its five fields are part of the line's size.
-__device__ __forceinline__ uint32_t gaf_tag_bytes(const bgr_read_tag& t) {   // "\tPS:i:" and its four siblings, HP's one digit, four numbers
-    return t.block ? 31 + dec_digits(t.block) + dec_digits(t.a) + dec_digits(t.b) + dec_digits(t.others) : 0u;
-}
-template <bool WIDE, bool TAG>
-__device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags) {
-    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    if (a >= n_acc) return;
-    const uint2 res = results[a];
-    const uint4 r = rec[acc_rec[a]];
-    const uint32_t np = res.y & 0xFFFFFFu, L = r.w & 0x7FFFFFFFu;
-    uint32_t ps = 0, ns = 0, nl = 0;
-    uint4 row = make_uint4(0, 0, 0, 0);
-    bgr_read_tag tag = {0, 0, 0, 0};
-    if (np) {
-        const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
-        const GafStat s = gaf_stat<WIDE, true>(g, arena + res.x, np, text + r.z, L, rc, sub);
-        if (s.bad) { if (sub == 0) atomicMin(bug, a); }
-        else {
-            if (TAG) {   // (np >= 2 here; every lane of the group is: s.bad is the same in all sixteen)
-                const uint32_t n_unitigs = (uint32_t)g.hdr->n_unitigs;
-                tag = haplotag_group(tag_table, n_unitigs, arena + res.x + 1, np - 1, haplotag_vote(tag_table, n_unitigs, s.sid0), sub);
-            }
-            nl = gaf_name_len(text, r.x, r.y, sub);
-            uint32_t qs, qe;
-            u64 pstart;
-            gaf_intervals(rc, L, (u64)arena[res.x], s.plen, s.cl, qs, qe, pstart);
-            ps = (nl ? nl : 1u) + s.segbytes + gaf_fixed_bytes(L, qs, qe, s.plen, pstart, s.cl, s.nm) + (TAG ? gaf_tag_bytes(tag) : 0u);
-            const bool again = np - 1 > 32 || (s.plen >> 32) != 0;   // (more than the row holds: the write kernel walks the path itself)
-            row = make_uint4((uint32_t)s.plen, s.obits, s.cl, s.nm | (again ? 0x80000000u : 0u));
-        }
-    } else {
-        ns = r.y + L + 2;
-    }
-    if (sub == 0) { psz[a] = ps; nsz[a] = ns; nlen[a] = nl; rows[a] = row; }
-    if (TAG && sub == 1) tags[a] = make_uint4(tag.block, tag.a, tag.b, tag.others);
-}
-__global__ void __launch_bounds__(256) bgr_text_gaf_sizes_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                 const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
-    gaf_sizes<false, false>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, nullptr, nullptr);
-}
-__global__ void __launch_bounds__(256) bgr_text_gaf_sizes_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                      const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
-    gaf_sizes<true, false>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, nullptr, nullptr);
-}
-template <bool WIDE>
-__global__ void __launch_bounds__(256) bgr_text_gaf_sizes_tag_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                     const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug,
-                                                                     const uint32_t* tag_table, uint4* tags) {
-    gaf_sizes<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
-}
-
-// lead + to_string(v) at d[pos ...] by the lane whose turn it is -> the position behind it (every lane keeps count)
-__device__ __forceinline__ uint32_t gaf_put(uint8_t* d, uint32_t pos, u64 v, bool mine, uint8_t lead = '\t') {
-    const uint32_t end = pos + 1 + dec_digits(v);
-    if (mine) { d[pos] = lead; put_dec(d + end, v); }
-    return end;
-}
-// "\t" c0 c1 ":i:" to_string(v) at d[pos ...] by the lane whose turn it is -> the position behind it
-__device__ __forceinline__ uint32_t gaf_put_tag(uint8_t* d, uint32_t pos, uint8_t c0, uint8_t c1, uint32_t v, bool mine) {
-    const uint32_t end = pos + 6 + dec_digits(v);
-    if (mine) { d[pos] = '\t'; d[pos + 1] = c0; d[pos + 2] = c1; d[pos + 3] = ':'; d[pos + 4] = 'i'; d[pos + 5] = ':'; put_dec(d + end, v); }
-    return end;
-}
-// one 16-lane group per accepted read: a mapped read's line at its offset (the numbers by one lane each, the segments by the lanes in turn),
-// the others into the notAligned stream as correct_write sends them.  TAG: the five fields of tags[a] behind NM, by the lanes 12 .. 15 and 0
-template <bool WIDE, bool TAG>
-__device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                          uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows,
-                                          uint8_t* pout, uint8_t* nout, const uint4* tags) {
-    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    if (a >= n_acc) return;
-    const uint2 res = results[a];
-    const uint4 r = rec[acc_rec[a]];
-    const uint32_t np = res.y & 0xFFFFFFu, hl = r.y, L = r.w & 0x7FFFFFFFu;
-    if (!np) {   // alignerGreedy.cpp:421-427: header + '\n' + read + '\n'
-        uint8_t* d = nout + noff[a];
-        group_copy(d, text + r.x, hl, sub);
-        if (sub == 0) d[hl] = '\n';
-        group_copy(d + hl + 1, text + r.z, L, sub);
-        if (sub == 0) d[hl + 1 + L] = '\n';
-        return;
-    }
-    uint8_t* d = pout + poff[a];
-    const uint4 row = rows[a];
-    const uint32_t nl = nlen[a], line = psz[a], cl = row.z, nm = row.w & 0x7FFFFFFFu;
-    if (!line) return;   // (a path that spells no walk: the call ends without this stream)
-    const bool again = (row.w >> 31) != 0;
-    const u64 off = (u64)arena[res.x];
-    u64 plen = row.x;
-    if (again) {
-        WalkIter<WIDE> w0(g, arena + res.x, np);
-        plen = 0;
-        if (w0.first()) { plen = w0.len; while (w0.next()) plen += w0.len - w0.skip; }
-    }
-    const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
-    uint32_t qs, qe;
-    u64 pstart;
-    gaf_intervals(rc, L, off, plen, cl, qs, qe, pstart);
-    const uint32_t name = nl ? nl : 1u;
-    bgr_read_tag tag = {0, 0, 0, 0};
-    if (TAG) { const uint4 t = tags[a]; tag.block = t.x; tag.a = t.y; tag.b = t.z; tag.others = t.w; }
-    const uint32_t segbytes = line - name - gaf_fixed_bytes(L, qs, qe, plen, pstart, cl, nm) - (TAG ? gaf_tag_bytes(tag) : 0u);
-    if (nl) group_copy(d, text + r.x + 1, nl, sub);
-    else if (sub == 0) d[0] = '*';
-    uint32_t pos = name;
-    pos = gaf_put(d, pos, L, sub == 1);
-    pos = gaf_put(d, pos, qs, sub == 2);
-    pos = gaf_put(d, pos, qe, sub == 3);
-    if (sub == 4) { d[pos] = '\t'; d[pos + 1] = '+'; d[pos + 2] = '\t'; }
-    const uint32_t seg0 = pos + 3;
-    pos = seg0 + segbytes;
-    pos = gaf_put(d, pos, plen, sub == 5);
-    pos = gaf_put(d, pos, pstart, sub == 6);
-    pos = gaf_put(d, pos, pstart + cl, sub == 7);
-    pos = gaf_put(d, pos, cl - nm, sub == 8);
-    pos = gaf_put(d, pos, cl, sub == 9);
-    if (sub == 10) { d[pos] = '\t'; d[pos + 1] = '2'; d[pos + 2] = '5'; d[pos + 3] = '5'; d[pos + 4] = '\t'; d[pos + 5] = 'N'; d[pos + 6] = 'M'; d[pos + 7] = ':'; d[pos + 8] = 'i'; }
-    pos = gaf_put(d, pos + 9, nm, sub == 11, ':');
-    if (TAG && tag.block) {
-        pos = gaf_put_tag(d, pos, 'P', 'S', tag.block, sub == 12);
-        pos = gaf_put_tag(d, pos, 'H', 'P', tag.a > tag.b ? 1u : tag.b > tag.a ? 2u : 0u, sub == 13);
-        pos = gaf_put_tag(d, pos, 'h', 'a', tag.a, sub == 14);
-        pos = gaf_put_tag(d, pos, 'h', 'b', tag.b, sub == 15);
-        pos = gaf_put_tag(d, pos, 'h', 'o', tag.others, sub == 0);
-        if (sub == 0) d[pos] = '\n';
-    } else if (sub == 12) d[pos] = '\n';
-    // the segments: lane (i - 1) mod 16 writes unitig i -- from the front, or on the rc from the back with its orientation flipped
-    if (!again) {
-        uint32_t acc = 0;
-        for (uint32_t i = 1; i < np; ++i) {
-            const int32_t sid = arena[res.x + i];
-            const uint32_t id = (uint32_t)(sid < 0 ? -(int64_t)sid : (int64_t)sid);
-            const uint32_t len = 1 + dec_digits(id);
-            if (acc + len > segbytes) break;
-            if (((i - 1) & 15u) == sub) {
-                const bool fwd = ((row.y >> (i - 1)) & 1u) != 0;
-                uint8_t* p = d + seg0 + (rc ? segbytes - acc - len : acc);
-                *p = fwd != rc ? '>' : '<';
-                put_dec(p + len, id);
-            }
-            acc += len;
-        }
-        return;
-    }
-    WalkIter<WIDE> w(g, arena + res.x, np);   // (every lane walks the path)
-    if (!w.first()) return;
-    uint32_t acc = 0;
-    for (;;) {
-        const int32_t sid = arena[res.x + w.i];
-        const uint32_t id = (uint32_t)(sid < 0 ? -(int64_t)sid : (int64_t)sid);
-        const uint32_t len = 1 + dec_digits(id);
-        if (acc + len > segbytes) break;
-        if (((w.i - 1) & 15u) == sub) {
-            const bool fwd = w.base == g.meta[id].F;
-            uint8_t* p = d + seg0 + (rc ? segbytes - acc - len : acc);
-            *p = fwd != rc ? '>' : '<';
-            put_dec(p + len, id);
-        }
-        acc += len;
-        if (!w.next()) break;
-    }
-}
-__global__ void __launch_bounds__(256) bgr_text_gaf_write_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                 const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
-                                                                 const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout) {
-    gaf_write<false, false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, nullptr);
-}
-__global__ void __launch_bounds__(256) bgr_text_gaf_write_wide_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                      const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
-                                                                      const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout) {
-    gaf_write<true, false>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, nullptr);
-}
-template <bool WIDE>
-__global__ void __launch_bounds__(256) bgr_text_gaf_write_tag_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
-                                                                     const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
-                                                                     const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout, const uint4* tags) {
-    gaf_write<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
-}
-
-// bgr_aligner_path_stats: the same per-read function over the results of a bgr_align_device launch, the reads where the caller keeps them
-// (their buffer is not padded).  out[i] = {plen low, plen high, path start low, path start high, cl, NM | no-walk flag}; zeros for an unmapped read
-// and for a row that does not lie wholly inside the launch's arena_ints (an empty row, as the counting kernels take it).
-template <bool WIDE>
-__device__ __forceinline__ void path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
-    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    if (a >= n) return;
-    const uint2 res = results[a];
-    const uint32_t np = res.y & 0xFFFFFFu;
-    u64 plen = 0, pstart = 0;
-    uint32_t cl = 0, nm = 0;
-    if (np && (u64)res.x + np <= arena_ints) {
-        const u64 o0 = offs[a];
-        const uint32_t L = (uint32_t)(offs[a + 1] - o0);
-        const bool rc = ((res.y >> 24) & BGR_ST_RC) != 0;
-        const GafStat s = gaf_stat<WIDE, false>(g, arena + res.x, np, reads + o0, L, rc, sub);
-        if (s.bad) nm = 0x80000000u;
-        else {
-            uint32_t qs, qe;
-            gaf_intervals(rc, L, (u64)arena[res.x], s.plen, s.cl, qs, qe, pstart);
-            plen = s.plen; cl = s.cl; nm = s.nm;
-        }
-    }
-    if (sub < 6) {
-        const uint32_t v = sub == 0 ? (uint32_t)plen : sub == 1 ? (uint32_t)(plen >> 32) : sub == 2 ? (uint32_t)pstart : sub == 3 ? (uint32_t)(pstart >> 32) : sub == 4 ? cl : nm;
-        out[6ull * a + sub] = v;
-    }
-}
-__global__ void __launch_bounds__(256) bgr_path_stats_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
-    path_stats<false>(g, reads, offs, results, arena, arena_ints, n, out);
-}
-__global__ void __launch_bounds__(256) bgr_path_stats_wide_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints, uint32_t n, uint32_t* out) {
-    path_stats<true>(g, reads, offs, results, arena, arena_ints, n, out);
-}
-
 }  // namespace
 
 hipError_t launch_scan2_u32(const uint32_t* inA, const uint32_t* inB, uint32_t* outA, uint32_t* outB, uint32_t n, const uint32_t* n_dev, uint32_t* sums, uint32_t* totalA,
@@ -1250,6 +664,7 @@ uint32_t format_tiles(uint32_t n_acc) { return std::max<uint32_t>(1, (n_acc + kF
 hipError_t launch_text_parse(const uint8_t* text, uint32_t n, uint32_t fastq_lines, uint32_t k, uint32_t* ticket, uint32_t ticket_base, uint32_t epoch, uint64_t* chains,
                              uint4* rec, uint32_t* acc_idx, uint32_t* acc_rec, uint32_t* acc_src, uint64_t* read_offs, uint32_t* info, uint32_t rec_cap, uint32_t* zero_a,
                              uint32_t words_a, uint32_t* zero_b, uint32_t words_b, hipStream_t stream) {
+    if (epoch == 0 || epoch > BGR_TEXT_EPOCH_MAX) return hipErrorInvalidValue;   // (chain_word has 22 bits for it: an epoch outside them is never matched, and the tiles behind the first would wait for ever)
     const uint32_t nt = text_tiles(n);
     u64* cA = reinterpret_cast<u64*>(chains);
     u64* cB = cA + nt;
@@ -1266,6 +681,7 @@ hipError_t launch_text_parse(const uint8_t* text, uint32_t n, uint32_t fastq_lin
 hipError_t launch_text_format(const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc, uint32_t* ticket,
                               uint32_t ticket_base, uint32_t epoch, uint64_t* chains, uint32_t* poff, uint32_t* noff, uint8_t* pout, uint8_t* nout, uint64_t pcap, uint64_t ncap,
                               uint32_t* info, hipStream_t stream) {
+    if (epoch == 0 || epoch > BGR_TEXT_EPOCH_MAX) return hipErrorInvalidValue;   // (as launch_text_parse)
     if (n_acc == 0) return hipSuccess;
     const uint32_t nt = format_tiles(n_acc);
     u64* cP = reinterpret_cast<u64*>(chains);
@@ -1284,58 +700,6 @@ hipError_t launch_text_write(const uint8_t* text, const uint2* results, const in
                              const uint32_t* poff, const uint32_t* noff, uint8_t* pout, uint8_t* nout, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
     hipLaunchKernelGGL(bgr_text_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, text, results, arena, rec, acc_rec, n_acc, poff, noff, pout, nout);
-    return hipGetLastError();
-}
-
-hipError_t launch_text_correct_sizes(const BgrDeviceGraph& g, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz,
-                                     uint32_t* nsz, uint32_t* clen, uint32_t* bug, hipStream_t stream) {
-    if (n_acc == 0) return hipSuccess;
-    if (g.k > 33) hipLaunchKernelGGL(bgr_text_correct_sizes_wide_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, stream, g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
-    else hipLaunchKernelGGL(bgr_text_correct_sizes_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, stream, g, results, arena, rec, acc_rec, n_acc, psz, nsz, clen, bug);
-    return hipGetLastError();
-}
-
-hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                     const uint32_t* poff, const uint32_t* noff, const uint32_t* clen, uint8_t* pout, uint8_t* nout, hipStream_t stream) {
-    if (n_acc == 0) return hipSuccess;
-    if (g.k > 33) hipLaunchKernelGGL(bgr_text_correct_write_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
-    else hipLaunchKernelGGL(bgr_text_correct_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, clen, pout, nout);
-    return hipGetLastError();
-}
-
-hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream) {
-    if (n_acc == 0) return hipSuccess;
-    if (tag_table) {   // the tagged instances: only an aligner with a tag table launches them
-        if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
-        else hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
-        return hipGetLastError();
-    }
-    if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_sizes_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
-    else hipLaunchKernelGGL(bgr_text_gaf_sizes_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug);
-    return hipGetLastError();
-}
-
-hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
-                                 const uint4* tags, hipStream_t stream) {
-    if (n_acc == 0) return hipSuccess;
-    if (tags) {
-        if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
-        else hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
-        return hipGetLastError();
-    }
-    if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_write_wide_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
-    else hipLaunchKernelGGL(bgr_text_gaf_write_kernel, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout);
-    return hipGetLastError();
-}
-
-hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
-                             uint32_t* out, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const u64* offs = reinterpret_cast<const u64*>(read_offs);
-    if (g.k > 33) hipLaunchKernelGGL(bgr_path_stats_wide_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
-    else hipLaunchKernelGGL(bgr_path_stats_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // walk_lanes.h -- the walk of a mapped read's path by the sixteen lanes of a group, shared by the kernels that need to know where every unitig of
-// a path lies in the walk and on which strand it was glued on: gaf_stat (text_kernels.hip: GAF lines, path stats) and the pileup kernel
+// a path lies in the walk and on which strand it was glued on: gaf_stat (text_gaf.hip: GAF lines, path stats) and the pileup kernel
 // (pileup_kernels.hip).  Included behind device_common.h by .hip files only.
 //
 // A serial walk costs three dependent loads per unitig (path int -> meta -> bases) in every lane; here lane i takes unitig i of a pass of sixteen:
@@ -15,20 +15,6 @@
 
 namespace bgr {
 namespace {
-
-// bits 7, 15, 23, 31 of h -> bits 0..3 (one multiply: the four shifted copies do not meet)
-__device__ __forceinline__ uint32_t nibble_of(uint32_t h) { return (((h >> 7) * 0x00204081u) >> 21) & 0xFu; }
-
-// min over the 16 lanes of a row, result in every lane
-__device__ __forceinline__ uint32_t row16_min(uint32_t x) {
-    uint32_t o = quad_xor1(x); x = o < x ? o : x;
-    o = quad_xor2(x); x = o < x ? o : x;
-    o = half_row_mirror(x); x = o < x ? o : x;
-    o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true); x = o < x ? o : x;  // row_mirror
-    return x;
-}
-
-typedef uint32_t __attribute__((ext_vector_type(4), aligned(1))) u32x4_unaligned;
 
 // 16 bytes at p of which `valid` (>= 1) belong to the buffer; PADDED: the buffer may be read 15 bytes past its end (the text is)
 template <bool PADDED>

@@ -443,3 +443,47 @@ def test_the_chains_of_the_text_kernels_across_the_wrap_of_their_epoch(tmp_path)
             else:
                 assert want_p.startswith(got_p) and want_n.startswith(got_n) and 0 < len(got_p) < len(want_p), i
         al.close()
+
+
+@pytest.fixture(scope="module")
+def padded_soup(tmp_path_factory):
+    """tests/util.py homopolymer_soup as one FASTA piece, its reads in the middle of cheap ones (substrings of the soup's random unitigs) -- enough of them that the
+    piece spans two tiles of the parse launch and two of the format launch; and what the host route makes of it, computed once: both streams and the record info."""
+    from util import homopolymer_soup
+    k, (seqs, offs), (sr, so), (lr, lo) = homopolymer_soup()
+    soup = [bytes(sr[int(so[i]):int(so[i + 1])]) for i in range(len(so) - 1)] + [bytes(lr[int(lo[i]):int(lo[i + 1])]) for i in range(len(lo) - 1)]
+    units = [bytes(seqs[int(offs[i]):int(offs[i + 1])]) for i in range(7, 27)]   # the twenty random 40-mers
+    pad = [units[i % 20][(i // 20) % 11:][:30] for i in range(2700)]
+    reads = pad[:1350] + soup + pad[1350:]
+    text = b"".join(b">q%d\n%s\n" % (i, r) for i, r in enumerate(reads))
+    g = B.Graph.build(k, seqs, offs)
+    al = B.Aligner(g, 0)
+    d = tmp_path_factory.mktemp("padded_soup")
+    want_p, want_n, n = _host_route(al, text, k, d, m=2, mode=B.MODE_EXHAUSTIVE)
+    assert n == len(reads) and len(want_p) > 0 and len(want_n) > 0   # (every record is kept: ACGT only, longer than k)
+    mapped = {h[1:] for h in want_p.split(b"\n")[0::2] if h}
+    want_info = np.array([0x80000000 | (0x40000000 if b"q%d" % i in mapped else 0) | len(r) for i, r in enumerate(reads)], dtype=np.uint32)
+    al.close()
+    return dict(k=k, graph=g, text=text, n=n, want_p=want_p, want_n=want_n, want_info=want_info)
+
+
+@pytest.mark.parametrize("epoch", [0x3FFFFF - 3, 0x3FFFFF - 2, 0x3FFFFF - 1, 0x3FFFFF])
+def test_the_epoch_wrap_inside_a_call_that_formats_twice(epoch, padded_soup):
+    """A default-output call whose exhaustive last pass hands reads back (BGR_KNOB_EXH_MEMO_CAP 8) runs three launches that take an epoch: parse, format, and format
+    again behind the settled launch.  With the chains' state freshly allocated at the top of the 22 bits (the hook applies to a new aligner), the call either fits its
+    three epochs below the end exactly (MAX - 3: MAX - 2, MAX - 1, MAX) or starts over from 1 -- and the call behind it on the same piece wraps or goes on; each
+    time the same bytes and the same record info as the host route.  The piece spans two tiles of both launches, so that tiles behind the first really read chain
+    words: a parse tile is 98 304 bytes of text (1024 threads x 32 bytes x 3 stretches), a format tile 1024 accepted reads.
+    The aligner is new and its buffers are poisoned: the last pass writes no row for a read it hands back, and the first format launch runs before the launch is
+    settled -- the rows of handed-back reads must read as "no path" until then, never as what the result buffer held."""
+    s = padded_soup
+    assert len(s["text"]) > 98304 and s["n"] > 1024
+    with B.options(**{"test.text_epoch": epoch, "poison_device_buffers": 1}):
+        al = B.Aligner(s["graph"], 0)
+        al.set_knob(B.KNOB_EXH_MEMO_CAP, 8)
+        for call in range(2):
+            p, n, info = al.align_fasta_text(s["text"], m=2, mode=B.MODE_EXHAUSTIVE, want_output=True, record_info=True)
+            assert not info["irregular"] and info["n_accepted"] == s["n"] and p == s["want_p"] and n == s["want_n"], call
+            assert np.array_equal(info["records"], s["want_info"]), call
+            assert al.last_pass_runs()[0] >= 2, call   # (reads were handed back: the three-epoch path was taken)
+        al.close()

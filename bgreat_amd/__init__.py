@@ -45,6 +45,7 @@ SYMBOLS = [
     "bgr_phase_blocks", "bgr_phase_blocks_times", "bgr_graph_blocks_enable", "bgr_graph_blocks_enabled", "bgr_graph_blocks", "bgr_write_blocks",
     "bgr_blocks_haplotypes", "bgr_blocks_haplotypes_times", "bgr_graph_haplotypes_enable", "bgr_graph_haplotypes_enabled", "bgr_graph_haplotypes", "bgr_write_haplotypes",
     "bgr_blocks_tag_table", "bgr_read_blocks_tags", "bgr_aligner_haplotag_enable", "bgr_aligner_haplotags", "bgr_graph_haplotag_enable", "bgr_graph_haplotag_enabled",
+    "bgr_aligner_path_diffs", "bgr_aligner_gaf_cs_enable", "bgr_graph_gaf_cs_enable", "bgr_graph_gaf_cs_enabled",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
     "bgr_write_pileup", "bgr_write_depth",
     "bgr_aligner_pileup_sites", "bgr_aligner_pileup_sites_times", "bgr_aligner_pileup_add", "bgr_graph_variants_enable", "bgr_graph_variants_enabled", "bgr_graph_variants",
@@ -157,6 +158,7 @@ class PathStat(C.Structure):  # bgr_path_stat
 
 
 PATH_STAT_NO_WALK = 0x80000000
+PATH_DIFF_DTYPE = np.dtype([("read_pos", np.uint32), ("path_base", np.uint8), ("read_base", np.uint8), ("reserved", np.uint16)])   # an array of bgr_path_diff
 
 
 class Ticket(C.Structure):
@@ -357,6 +359,10 @@ def lib():
     L.bgr_aligner_haplotags.argtypes = [vp, u64, vp]
     L.bgr_graph_haplotag_enable.argtypes = [vp, vp, u64]
     L.bgr_graph_haplotag_enabled.argtypes = [vp]
+    L.bgr_aligner_path_diffs.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
+    L.bgr_aligner_gaf_cs_enable.argtypes = [vp, C.c_int]
+    L.bgr_graph_gaf_cs_enable.argtypes = [vp, C.c_int]
+    L.bgr_graph_gaf_cs_enabled.argtypes = [vp]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -812,6 +818,14 @@ class Graph:
         """bgr_graph_haplotag_enabled: the switch as it stands."""
         return bool(lib().bgr_graph_haplotag_enabled(self.h))
 
+    def gaf_cs_enable(self, on=True):
+        """bgr_graph_gaf_cs_enable: sticky -- the GAF lines of every later align_all with gaf on this graph end in the cs:Z: field."""
+        _check(lib().bgr_graph_gaf_cs_enable(self.h, int(bool(on))))
+
+    def gaf_cs_enabled(self):
+        """bgr_graph_gaf_cs_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_gaf_cs_enabled(self.h))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -978,6 +992,23 @@ class Aligner:
         assert out.dtype.itemsize == C.sizeof(PathStat)
         _check(lib().bgr_aligner_path_stats(self.h, d_reads_ptr, d_offsets_ptr, n, out.ctypes.data))
         return out
+
+    def path_diffs(self, d_reads_ptr, d_offsets_ptr, n):
+        """bgr_aligner_path_diffs over the last align_device launch (the same device reads again) -> (uint64 offsets, n + 1 of them; array of
+        PATH_DIFF_DTYPE): the differences of read i are rows offsets[i] .. offsets[i + 1], ascending read_pos.  The two-call form: the count first."""
+        assert PATH_DIFF_DTYPE.itemsize == 8
+        offs, total = np.zeros(n + 1, dtype=np.uint64), C.c_uint64(0)
+        rc = lib().bgr_aligner_path_diffs(self.h, d_reads_ptr, d_offsets_ptr, n, offs.ctypes.data, None, 0, C.byref(total))
+        if rc != -4:   # (no difference at all, or an error that is not "there are *n of them")
+            _check(rc)
+            return offs, np.zeros(0, dtype=PATH_DIFF_DTYPE)
+        out = np.zeros(total.value, dtype=PATH_DIFF_DTYPE)
+        _check(lib().bgr_aligner_path_diffs(self.h, d_reads_ptr, d_offsets_ptr, n, offs.ctypes.data, out.ctypes.data, len(out), C.byref(total)))
+        return offs, out
+
+    def gaf_cs_enable(self, on=True):
+        """bgr_aligner_gaf_cs_enable: the GAF lines of align_fasta_text (want_output=3) end in the cs:Z: field from now on."""
+        _check(lib().bgr_aligner_gaf_cs_enable(self.h, int(bool(on))))
 
     def haplotag_enable(self, table):
         """bgr_aligner_haplotag_enable: `table` (n_unitigs + 1 uint32) onto the aligner's device -- haplotags() and the GAF lines of align_fasta_text

@@ -427,7 +427,7 @@ void bgr_aligner_destroy(bgr_aligner* a) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
         a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.buf.release(); a->triples.buf.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
-        a->text.release(); a->path_stats.release(); a->haplotag.release(); a->haplotag_out.release();
+        a->text.release(); a->path_stats.release(); a->path_diffs.release(); a->haplotag.release(); a->haplotag_out.release();
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
         if (a->ev_wait) (void)hipEventDestroy(a->ev_wait);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -1049,6 +1049,48 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
         if (crc != BGR_OK) return crc;
     }
     HIP_TRY(hipMemcpyAsync(out, a->path_stats.p, n * sizeof(bgr_path_stat), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(wait_stream(a));
+    return BGR_OK;
+}
+
+// bgr_aligner_path_diffs: count, scan, fill (text_gaf.hip); the refusals are bgr_aligner_path_stats's
+int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n, uint64_t* diff_offsets, bgr_path_diff* out, uint64_t cap, uint64_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (!a || !diff_offsets || !n_out || (cap && !out) || (n && (!d_reads || !d_read_offsets))) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: null argument");
+    a = holder_of(a);   // (the rows of the last launch, on the stream that ran it)
+    if (a->graph->header.has_exc)
+        return fail(BGR_E_ARG, "bgr_aligner_path_diffs: needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
+    if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: n_reads differs from the last bgr_align_device call");
+    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: the last launch was exhaustive; paths of the greedy modes only");
+    diff_offsets[0] = 0;
+    if (n == 0) return BGR_OK;
+    if (a->last_total_bases >= (1ull << 32)) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: launches of fewer than 2^32 bases (a read has at most one difference per base, and their offsets are scanned in 32 bits)");
+    HIP_TRY(hipSetDevice(a->device));
+    static_assert(sizeof(bgr_path_diff) == 8, "two words per difference, as the kernel writes them");
+    // counts | offsets | offsets' unused twin (launch_scan2_u32 scans two arrays) | the scan's tile sums and the total
+    const uint64_t words = n + 4, sums = 2ull * bgr::scan_tiles((uint32_t)n) + 16;
+    HIP_TRY(a->path_diffs.ensure((3 * words + sums + 4) * 4));
+    uint32_t* cnt = a->path_diffs.as<uint32_t>();
+    uint32_t *doff = cnt + words, *twin = doff + words, *tile = twin + words, *total = tile + sums;
+    const uint8_t* reads = static_cast<const uint8_t*>(d_reads);
+    const uint64_t* offs = static_cast<const uint64_t*>(d_read_offsets);
+    hipError_t e = bgr::launch_path_diffs_count(a->dg, reads, offs, a->results.as<uint2>(), a->arena.as<int32_t>(), a->last_arena_cap, (uint32_t)n, cnt, a->stream);
+    if (e == hipSuccess) e = bgr::launch_scan2_u32(cnt, cnt, doff, twin, (uint32_t)n, nullptr, tile, total, total + 1, a->stream);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs launches: ") + hipGetErrorString(e));
+    std::vector<uint32_t> h(n + 1);
+    HIP_TRY(hipMemcpyAsync(h.data(), doff, n * 4, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(h.data() + n, total, 4, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(wait_stream(a));
+    for (uint64_t i = 0; i <= n; ++i) diff_offsets[i] = h[i];
+    const uint64_t all = h[n];
+    *n_out = all;
+    if (all > cap) return fail(BGR_E_CAPACITY, "bgr_aligner_path_diffs: out holds fewer differences than the launch has (*n says how many; the offsets are set)");
+    if (all == 0) return BGR_OK;
+    DevBuf& buf = a->path_stats;   // (the records: the buffer of bgr_aligner_path_stats' rows is free between calls)
+    HIP_TRY(buf.ensure(all * sizeof(bgr_path_diff)));
+    e = bgr::launch_path_diffs_fill(a->dg, reads, offs, a->results.as<uint2>(), a->arena.as<int32_t>(), (uint32_t)n, cnt, doff, buf.as<uint2>(), a->stream);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs fill launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(out, buf.p, all * sizeof(bgr_path_diff), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return BGR_OK;
 }

@@ -86,6 +86,7 @@ struct bgr_graph {
     // and the later stages of the chain run; haplotypes.seq: the characters the records point into
     // haplotags (bgr_graph_haplotag_enable): the sticky switch and the graph's copy of the tag table, n_unitigs + 1 words
     bool haplotag_on = false;
+    bool gaf_cs_on = false;   // bgr_graph_gaf_cs_enable: sticky -- the GAF lines of every later bgr_align_all end in the cs:Z: field
     std::vector<uint32_t> haplotag;
     struct Bubbles : ChainSwitch, RunRows<bgr_bubble> { int device = -1; } bubbles;
     struct Phase : ChainSwitch, RunRows<bgr_phase> {} phase;
@@ -160,15 +161,17 @@ struct bgr_text_stage {  // one piece of text on its way to / resident in a devi
 struct TextRoute {
     DevBuf in, sums, state, rec, idx, accrec, accsrc, offs, psz, nsz, poff, noff, pout, nout, info, gaf;
     DevBuf tags;                    // GAF output of an aligner with a tag table: the tags per accepted read, next to gaf
+    DevBuf cs;                      // GAF output with the cs:Z: field (bgr_aligner_gaf_cs_enable): the bytes of its ops per accepted read, next to gaf
     uint64_t n_acc = 0, pbytes = 0, nbytes = 0;
     const uint8_t* text = nullptr;  // where the last call's piece lies in HBM (in, or the caller's stage)
     bgr::TextEpochs epochs;         // the one-launch kernels' chains (epoch of the last launch, tickets earlier launches took) and which of the two info blocks a piece uses
     bool written = false;           // the streams lie in pout / nout (the format launch wrote them: every stretch ended below the capacities)
     uint32_t want = 0;              // the piece's want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
     bool tagged = false;            // the sizes launch of the piece in the buffers was a tagged one (the write launch follows it)
+    bool with_cs = false;           // ... was one of the instances that carry the cs:Z: field (the same)
     double phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
     void release() {
-        for (DevBuf* b : {&in, &sums, &state, &rec, &idx, &accrec, &accsrc, &offs, &psz, &nsz, &poff, &noff, &pout, &nout, &info, &gaf, &tags}) b->release();
+        for (DevBuf* b : {&in, &sums, &state, &rec, &idx, &accrec, &accsrc, &offs, &psz, &nsz, &poff, &noff, &pout, &nout, &info, &gaf, &tags, &cs}) b->release();
     }
 };
 
@@ -179,6 +182,8 @@ struct bgr_aligner {
     BgrDeviceGraph dg;
     TextRoute text;
     DevBuf path_stats;
+    DevBuf path_diffs;            // bgr_aligner_path_diffs: counts and offsets (two arrays of n + 1 words each way), then the differences
+    bool gaf_cs = false;          // bgr_aligner_gaf_cs_enable: the GAF lines of bgr_align_fasta_text end in the cs:Z: field
     bool blocking_sync = bgr::opt("blocking_sync") != 0;
     hipEvent_t ev_wait = nullptr;
 
@@ -411,6 +416,9 @@ int chain_stage_end(bgr_graph* g, F& f, bool ok, bool inputs_valid, const char* 
 // capi_haplotag.hip: the graph's tag table while its switch is on (else null), and the table onto an aligner's device (run_counts.h)
 const uint32_t* run_haplotag_table(const bgr_graph* g, uint64_t* n_rows);
 int run_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
+// capi_text.hip: the graph's cs:Z: switch, and the switch of an aligner (run_counts.h)
+int run_gaf_cs_wanted(const bgr_graph* g);
+int run_gaf_cs_enable(bgr_aligner* a, int on);
 // capi_pileup.hip
 void pileup_share(bgr_aligner* a);   // the twins add to the aligner's pileup tables: its fields copied to each of them
 int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who);   // BGR_E_CAPACITY when a reads column reached 2^32: a depth may have wrapped

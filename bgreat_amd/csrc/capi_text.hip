@@ -1,7 +1,7 @@
 // capi_text.hip -- the C-ABI's text route: FASTA / FASTQ bytes in, record bytes out (text_kernels.h has the kernels' launch interface, text_epochs.h
 // the book of their epochs, tickets and info blocks; the state is TextRoute in capi_internal.h).  bgr_align_fasta_text as a row of named steps,
 // bgr_aligner_fetch_text, and the stages through which a caller uploads the next piece ahead of its call (bgr_text_stage_*).  What the CLI runs for
-// every piece of every read file: default output, -c, --gaf, --haplotag.
+// every piece of every read file: default output, -c, --gaf, --haplotag, --cs (the switches of the cs:Z: field are here too).
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -46,7 +46,7 @@ uint64_t* chains_of(const TextRoute& t) { return reinterpret_cast<uint64_t*>(t.s
 hipError_t write_gaf(const bgr_aligner* a, const TextRoute& t) {
     return bgr::launch_text_gaf_write(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
                                       t.noff.as<uint32_t>(), t.psz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), t.pout.as<uint8_t>(), t.nout.as<uint8_t>(),
-                                      t.tagged ? t.tags.as<uint4>() : nullptr, a->stream);
+                                      t.tagged ? t.tags.as<uint4>() : nullptr, t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream);
 }
 hipError_t write_corrected(const bgr_aligner* a, const TextRoute& t) {
     return bgr::launch_text_correct_write(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc,
@@ -206,10 +206,12 @@ int gaf_sizes(TextCall& c) {
     HIP_TRY(t.gaf.ensure(((uint64_t)c.n_acc + 1) * 16));
     t.tagged = a->haplotag.p != nullptr;   // (an aligner with a tag table: the tagged instances of both GAF kernels)
     if (t.tagged) HIP_TRY(t.tags.ensure(((uint64_t)c.n_acc + 1) * 16));
+    t.with_cs = a->gaf_cs;                 // (bgr_aligner_gaf_cs_enable: the instances whose lines end in the cs:Z: field)
+    if (t.with_cs) HIP_TRY(t.cs.ensure(((uint64_t)c.n_acc + 1) * 4));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.info + TXT_INFO_BUG), -1, 1, a->stream));
     return launched(bgr::launch_text_gaf_sizes(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
                                                t.nsz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), c.info + TXT_INFO_BUG, t.tagged ? a->haplotag.as<uint32_t>() : nullptr,
-                                               t.tags.as<uint4>(), a->stream),
+                                               t.tags.as<uint4>(), t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream),
                     "text size launches");
 }
 int correct_sizes(TextCall& c) {
@@ -306,6 +308,26 @@ int finish_text_call(TextCall& c) {
 }
 
 }  // namespace
+
+int bgr_aligner_gaf_cs_enable(bgr_aligner* a, int on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_gaf_cs_enable: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_gaf_cs_enable: an internal twin (the switch belongs to the aligner it was made for)");
+    a->gaf_cs = on != 0;   // (read when a piece's sizes are launched; the write launch follows what that launch was)
+    return BGR_OK;
+}
+
+int bgr_graph_gaf_cs_enable(bgr_graph* g, int on) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_gaf_cs_enable: null graph");
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->gaf_cs_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_gaf_cs_enabled(const bgr_graph* g) { return g && g->gaf_cs_on ? 1 : 0; }
+
+// what a whole run calls (run_counts.h, registered by capi_abundance.hip)
+int run_gaf_cs_wanted(const bgr_graph* g) { return bgr_graph_gaf_cs_enabled(g); }
+int run_gaf_cs_enable(bgr_aligner* a, int on) { return bgr_aligner_gaf_cs_enable(a, on); }
 
 int bgr_aligner_fetch_text(bgr_aligner* a, bgr_text_batch* b) {
     if (!a || !b) return fail(BGR_E_ARG, "bgr_aligner_fetch_text: null argument");

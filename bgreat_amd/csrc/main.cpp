@@ -56,6 +56,9 @@
 //                                                               unitig file, of these reads or of others; a line whose path crosses a branch of a block gains
 //                                                               PS:i:<block> HP:i:<0|1|2> ha:i: hb:i: ho:i: (votes for haplotype A, for B, for other blocks), computed on the
 //                                                               device where the line is formatted; not with -b: include/bgreat_gpu.h)
+//                                                   --cs (with --gaf: every line ends in cs:Z:, minimap2's short difference string -- ":<n>" per run of equal characters, "*<path base><read
+//                                                               base>" per difference, in the read's direction, behind NM:i: and the --haplotag fields; computed on the device
+//                                                               where the line is formatted; runs with everything --gaf runs with: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -89,7 +92,7 @@ int main(int argc, char** argv) {
     uint64_t min_block = 1;        // --min-block
     bool min_block_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
-    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false;
+    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
@@ -101,7 +104,7 @@ int main(int argc, char** argv) {
                                 {"triples", required_argument, nullptr, 1021}, {"phase", required_argument, nullptr, 1022},
                                 {"blocks", required_argument, nullptr, 1023}, {"min-phase", required_argument, nullptr, 1024},
                                 {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
-                                {"haplotag", required_argument, nullptr, 1027},
+                                {"haplotag", required_argument, nullptr, 1027}, {"cs", no_argument, nullptr, 1028},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -198,6 +201,7 @@ int main(int argc, char** argv) {
                 break;
             }
             case 1027: haplotagFile = optarg; break;
+            case 1028: gaf_cs = true; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -217,6 +221,7 @@ int main(int argc, char** argv) {
     if (min_block_given && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-block is the threshold of --haplotypes FILE\n"); return 2; }
     if (!haplotagFile.empty() && !gaf) { fprintf(stderr, "bgreat: --haplotag BLOCKS_FILE adds its fields to the lines of --gaf\n"); return 2; }
     if (!haplotagFile.empty() && brute) { fprintf(stderr, "bgreat: --haplotag tags GAF lines, which are for the greedy modes; exhaustive mode (-b) writes no paths\n"); return 2; }
+    if (gaf_cs && !gaf) { fprintf(stderr, "bgreat: --cs adds the cs:Z: field to the lines of --gaf\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -229,6 +234,7 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> table(gi.n_unitigs + 1);
         if (bgr_read_blocks_tags(haplotagFile.c_str(), gi.n_unitigs, table.data(), nullptr) != BGR_OK || bgr_graph_haplotag_enable(graph, table.data(), table.size()) != BGR_OK) die("--haplotag");
     }
+    if (gaf_cs && bgr_graph_gaf_cs_enable(graph, 1) != BGR_OK) die("--cs");
     // one host -> device copy, then device to device over xGMI (RCCL broadcast, or peer copies): include/bgreat_gpu.h
     int64_t one_device = 0, timing = 0;  // (test hook: every lane on device 0)
     (void)bgr_get_option("test.lanes_on_one_device", &one_device);

@@ -23,7 +23,7 @@
 #include "pipeline_stages.h"
 
 namespace bgr {
-RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
+RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
 }
 
 extern "C" void bgr_host_cache_release(void) {
@@ -224,6 +224,8 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
         if (bgr::g_run_counts.haplotag_table(graph, &tag_rows))
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: haplotags (--haplotag, bgr_graph_haplotag_enable) are fields of GAF lines; the run needs bgr_run_options.gaf (--gaf)");
     }
+    if (!opt->gaf && bgr::g_run_counts.gaf_cs_wanted && bgr::g_run_counts.gaf_cs_wanted(graph))   // the same for the cs:Z: field
+        return bgr::set_error(BGR_E_ARG, "bgr_align_all: the cs:Z: field (--cs, bgr_graph_gaf_cs_enable) is a field of GAF lines; the run needs bgr_run_options.gaf (--gaf)");
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
     // what the run counts (run_counts.h): the graph's sticky switches, which imply unitig abundance whatever bgr_run_options.abundance says, and that option
     const uint32_t counts = (bgr::g_run_counts.wanted ? bgr::g_run_counts.wanted(graph) : 0) | (opt->abundance ? bgr::kCountAbundance : 0);

@@ -173,6 +173,7 @@ struct RunShape {
     Unitigs unitigs;                     // -c and --gaf: the host formatter spells walks
     const uint32_t* tag_table = nullptr; // haplotags (bgr_graph_haplotag_enable; bgr_align_all has refused a run without gaf): the graph's table goes onto every
     uint64_t tag_rows = 0;               // aligner's device, and the host formatter tags from the same words
+    bool gaf_cs = false;                 // the cs:Z: field (bgr_graph_gaf_cs_enable; the same refusal): every aligner's switch is set, the host formatter writes it too
     int device_of(unsigned g) const { return (int)(one_device ? first_device : first_device + g); }
 };
 
@@ -210,6 +211,7 @@ int plan_run(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt
         s.unitigs.k = gi.k;
     }
     if (s.gaf && bgr::g_run_counts.haplotag_table) s.tag_table = bgr::g_run_counts.haplotag_table(graph, &s.tag_rows);
+    if (s.gaf && bgr::g_run_counts.gaf_cs_wanted) s.gaf_cs = bgr::g_run_counts.gaf_cs_wanted(graph) != 0;
     // two aligners (streams) per device so that consecutive batches overlap copy and compute (text route: the piece is already on its
     // way to the device when a worker takes the batch; measured 185 / 163 / 149 Mreads/s end to end with 2 / 3 / 4 workers per device)
     if (const int64_t w = bgr::opt("workers_per_device")) s.per_dev = (unsigned)w;  // (tuning / experiments)
@@ -259,6 +261,7 @@ int make_aligners(bgr_graph* graph, const RunShape& s, uint32_t counts, std::vec
             (void)bgr_aligner_set_knob(a, BGR_KNOB_KERNEL_EVENTS, 0);
             if (counts) rc = bgr::g_run_counts.enable(a, counts);  // every launch of the run is followed by the kernels of what it counts (bgr_align_all has checked the table)
             if (rc == BGR_OK && s.tag_table) rc = bgr::g_run_counts.haplotag_enable(a, s.tag_table, s.tag_rows);
+            if (rc == BGR_OK && s.gaf_cs) rc = bgr::g_run_counts.gaf_cs_enable(a, 1);
             if (rc != BGR_OK) return rc;
         }
     }
@@ -967,7 +970,7 @@ struct OrderedWriter {
             if (lo >= hi) return;
             if (!s.extended) format_range(cur.recs.data(), paths, poffs, lo, hi, o.pb[t], o.nb[t]);
             else okv[t] = format_range_ext(cur.recs.data(), paths, poffs, status, lo, hi, (s.correction || s.gaf) ? &s.unitigs : nullptr, s.gaf, s.split_no_overlap, o.pb[t], o.nb[t],
-                                           o.ob[t], bugv[t], s.tag_table, s.tag_rows) ? 1 : 0;
+                                           o.ob[t], bugv[t], s.tag_table, s.tag_rows, s.gaf_cs) ? 1 : 0;
         }, 3);
         unsigned t_stop = threads;
         for (unsigned t = 0; t < threads; ++t)

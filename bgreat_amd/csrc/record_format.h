@@ -86,10 +86,26 @@ inline void put_u64(std::string& o, uint64_t v) {
     do { *--w = (char)('0' + v % 10); v /= 10; } while (v);
     o.append(w, (size_t)(e - w));
 }
+// The value of the cs:Z: field (minimap2's short form, substitutions only: include/bgreat_gpu.h): walk[off ...] under the read's first cl characters,
+// or -- on_rc -- its reverse complement under the read's last cl.  ":<n>" per maximal run of equal characters, "*<path><read>" in lower case per
+// difference, 'n' for a read character outside ACGT.
+inline void append_cs_ops(const std::string& walk, uint64_t off, uint32_t cl, const char* read, uint32_t L, bool on_rc, std::string& out) {
+    uint32_t run = 0;
+    for (uint32_t j = 0; j < cl; ++j) {
+        const char p = on_rc ? rc_char(walk[off + cl - 1 - j]) : walk[off + j], r = on_rc ? read[L - cl + j] : read[j];
+        if (p == r) { ++run; continue; }
+        if (run) { out.push_back(':'); put_u64(out, run); run = 0; }
+        out.push_back('*');
+        out.push_back((char)(p | 0x20));
+        out.push_back(r == 'A' || r == 'C' || r == 'G' || r == 'T' ? (char)(r | 0x20) : 'n');
+    }
+    if (run) { out.push_back(':'); put_u64(out, run); }
+}
 // Appends the line of one mapped read (path of n >= 2 ints) to `out`.  The walk is recover_path's, with the orientation each unitig was glued
 // on in kept in `fwd`; false = the path spells no walk (walk / tmp then hold what the reference prints behind "bug compaction").
+// tail (or null): what goes between NM:i: and the newline, made from the walk while it is at hand -- the cs:Z: field.
 bool gaf_line(const Unitigs& u, const int32_t* path, uint64_t n, const char* h, uint32_t hl, const char* read, uint32_t L, bool on_rc, std::string& out,
-              std::string& walk, std::string& tmp, std::string& rc, std::vector<uint8_t>& fwd) {
+              std::string& walk, std::string& tmp, std::string& rc, std::vector<uint8_t>& fwd, std::string* tail = nullptr) {
     const uint32_t K1 = u.k - 1;
     oriented_unitig(u, path[1], walk);
     tmp.clear();
@@ -132,6 +148,7 @@ bool gaf_line(const Unitigs& u, const int32_t* path, uint64_t n, const char* h, 
     out.push_back('\t'); put_u64(out, cl);
     out.append("\t255\tNM:i:"); put_u64(out, nm);
     out.push_back('\n');
+    if (tail) { tail->assign("\tcs:Z:"); append_cs_ops(walk, off, cl, read, L, on_rc, *tail); }
     return true;
 }
 
@@ -173,17 +190,19 @@ void format_range(const RecSlice* recs, const int32_t* paths, const uint64_t* po
 // so far and the unitig that does not continue it, and exits); the buffers then hold the records BEFORE that read and
 // `bug` the two strings the reference prints.
 // tag_table (n_unitigs + 1 words, or null): a GAF line gains the fields of its read's haplotag (haplotag_host.h), computed from the path ints held here.
+// gaf_cs: a GAF line ends in the cs:Z: field, behind the tags.
 bool format_range_ext(const RecSlice* recs, const int32_t* paths, const uint64_t* poffs, const uint8_t* status, uint64_t lo, uint64_t hi, const Unitigs* correct, bool gaf,
-                      bool split_no_overlap, std::string& pbuf, std::string& nbuf, std::string& obuf, std::string& bug, const uint32_t* tag_table = nullptr, uint64_t tag_rows = 0) {
+                      bool split_no_overlap, std::string& pbuf, std::string& nbuf, std::string& obuf, std::string& bug, const uint32_t* tag_table = nullptr, uint64_t tag_rows = 0,
+                      bool gaf_cs = false) {
     pbuf.clear(); nbuf.clear(); obuf.clear();
-    std::string walk, tmp, rc;
+    std::string walk, tmp, rc, cs;
     std::vector<uint8_t> fwd;
     for (uint64_t i = lo; i < hi; ++i) {
         const RecSlice& r = recs[i];
         const uint64_t np = poffs[i + 1] - poffs[i];
         if (np && gaf) {
             if (np < 2) { walk.clear(); tmp.clear(); }
-            if (np < 2 || !gaf_line(*correct, paths + poffs[i], np, r.h, r.hl, r.s, r.sl, (status[i] & BGR_ST_RC) != 0, pbuf, walk, tmp, rc, fwd)) {
+            if (np < 2 || !gaf_line(*correct, paths + poffs[i], np, r.h, r.hl, r.s, r.sl, (status[i] & BGR_ST_RC) != 0, pbuf, walk, tmp, rc, fwd, gaf_cs ? &cs : nullptr)) {
                 bug = walk + " " + tmp;
                 return false;
             }
@@ -191,6 +210,7 @@ bool format_range_ext(const RecSlice* recs, const int32_t* paths, const uint64_t
                 const bgr_read_tag tag = bgr::haplotag_row(tag_table, tag_rows - 1, paths + poffs[i] + 1, np - 1);
                 if (tag.block) { pbuf.pop_back(); bgr::haplotag_suffix(tag, &pbuf); pbuf.push_back('\n'); }
             }
+            if (gaf_cs) { pbuf.pop_back(); pbuf.append(cs); pbuf.push_back('\n'); }
         } else if (np) {
             if (correct && (np < 2 || !recover_path(*correct, paths + poffs[i], np, r.sl, walk, tmp, rc))) {
                 bug = walk + " " + tmp;

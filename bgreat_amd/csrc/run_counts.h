@@ -25,6 +25,10 @@ struct RunCounts {
     // it on an aligner's device, whose GAF lines are tagged from then on; a run's host formatter tags from the same table (haplotag_host.h)
     const uint32_t* (*haplotag_table)(const bgr_graph* g, uint64_t* n_rows);
     int (*haplotag_enable)(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
+    // the cs:Z: field of GAF lines, the same way: the graph's switch (bgr_graph_gaf_cs_enable) as 1 or 0, and the call that sets an aligner's; the host
+    // formatter writes the same bytes (record_format.h)
+    int (*gaf_cs_wanted)(const bgr_graph* g);
+    int (*gaf_cs_enable)(bgr_aligner* a, int on);
 };
 extern RunCounts g_run_counts;   // pipeline.cpp; all null until the library's C-ABI units have registered
 

@@ -12,6 +12,7 @@
 #include "text_device.h"
 #include "walk_lanes.h"
 #include "haplotag_device.h"
+#include "gaf_cs_device.h"
 
 namespace bgr {
 namespace {
@@ -114,18 +115,21 @@ __device__ __forceinline__ uint32_t gaf_fixed_bytes(uint32_t L, uint32_t qs, uin
 // *bug as correct_sizes sets it.
 // TAG (the aligner has a tag table, bgr_aligner_haplotag_enable): the read's tag is computed here, where the walk holds the path's first sixteen ids in
 // its lanes, kept in tags[a] next to the row, and the bytes of its five fields are part of the line's size.
+// CS (bgr_aligner_gaf_cs_enable): the line ends in "\tcs:Z:" + the ops of gaf_cs_device.h; their bytes are part of the line's size and kept in csb[a].
+// A read without a difference -- most are -- has the one run ":<cl>" and is not compared again.
 __device__ __forceinline__ uint32_t gaf_tag_bytes(const bgr_read_tag& t) {   // "\tPS:i:" and its four siblings, HP's one digit, four numbers
     return t.block ? 31 + dec_digits(t.block) + dec_digits(t.a) + dec_digits(t.b) + dec_digits(t.others) : 0u;
 }
-template <bool WIDE, bool TAG>
+template <bool WIDE, bool TAG, bool CS = false>
 __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
-                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags) {
+                                          uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags,
+                                          uint32_t* csb = nullptr) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n_acc) return;
     const uint2 res = results[a];
     const uint4 r = rec[acc_rec[a]];
     const uint32_t np = res.y & 0xFFFFFFu, L = r.w & 0x7FFFFFFFu;
-    uint32_t ps = 0, ns = 0, nl = 0;
+    uint32_t ps = 0, ns = 0, nl = 0, cs = 0;
     uint4 row = make_uint4(0, 0, 0, 0);
     bgr_read_tag tag = {0, 0, 0, 0};
     if (np) {
@@ -142,6 +146,10 @@ __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t
             u64 pstart;
             gaf_intervals(rc, L, (u64)arena[res.x], s.plen, s.cl, qs, qe, pstart);
             ps = (nl ? nl : 1u) + s.segbytes + gaf_fixed_bytes(L, qs, qe, s.plen, pstart, s.cl, s.nm) + (TAG ? gaf_tag_bytes(tag) : 0u);
+            if (CS) {   // (s.nm is the same in all sixteen)
+                cs = s.nm == 0 ? cs_run_bytes(s.cl) : cs_ops<WIDE, true, false>(g, arena + res.x, np, text + r.z, L, rc, sub, nullptr);
+                ps += 6 + cs;
+            }
             const bool again = np - 1 > 32 || (s.plen >> 32) != 0;   // (more than the row holds: the write kernel walks the path itself)
             row = make_uint4((uint32_t)s.plen, s.obits, s.cl, s.nm | (again ? 0x80000000u : 0u));
         }
@@ -150,6 +158,7 @@ __device__ __forceinline__ void gaf_sizes(const BgrDeviceGraph& g, const uint8_t
     }
     if (sub == 0) { psz[a] = ps; nsz[a] = ns; nlen[a] = nl; rows[a] = row; }
     if (TAG && sub == 1) tags[a] = make_uint4(tag.block, tag.a, tag.b, tag.others);
+    if (CS && sub == 2) csb[a] = cs;
 }
 __global__ void __launch_bounds__(256) bgr_text_gaf_sizes_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
                                                                  const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug) {
@@ -165,6 +174,12 @@ __global__ void __launch_bounds__(256) bgr_text_gaf_sizes_tag_kernel(BgrDeviceGr
                                                                      const uint32_t* tag_table, uint4* tags) {
     gaf_sizes<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
 }
+template <bool WIDE, bool TAG>
+__global__ void __launch_bounds__(256) bgr_text_gaf_sizes_cs_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                    const uint32_t* acc_rec, uint32_t n_acc, uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug,
+                                                                    const uint32_t* tag_table, uint4* tags, uint32_t* csb) {
+    gaf_sizes<WIDE, TAG, true>(g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags, csb);
+}
 
 // lead + to_string(v) at d[pos ...] by the lane whose turn it is -> the position behind it (every lane keeps count)
 __device__ __forceinline__ uint32_t gaf_put(uint8_t* d, uint32_t pos, u64 v, bool mine, uint8_t lead = '\t') {
@@ -179,11 +194,12 @@ __device__ __forceinline__ uint32_t gaf_put_tag(uint8_t* d, uint32_t pos, uint8_
     return end;
 }
 // one 16-lane group per accepted read: a mapped read's line at its offset (the numbers by one lane each, the segments by the lanes in turn),
-// the others into the notAligned stream as correct_write sends them.  TAG: the five fields of tags[a] behind NM, by the lanes 12 .. 15 and 0
-template <bool WIDE, bool TAG>
+// the others into the notAligned stream as correct_write sends them.  TAG: the five fields of tags[a] behind NM, by the lanes 12 .. 15 and 0.
+// CS: "\tcs:Z:" and the csb[a] bytes of the ops behind everything else, the ops by the lanes that hold the differences (gaf_cs_device.h)
+template <bool WIDE, bool TAG, bool CS = false>
 __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec,
                                           uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows,
-                                          uint8_t* pout, uint8_t* nout, const uint4* tags) {
+                                          uint8_t* pout, uint8_t* nout, const uint4* tags, const uint32_t* csb = nullptr) {
     const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
     if (a >= n_acc) return;
     const uint2 res = results[a];
@@ -216,7 +232,8 @@ __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t
     const uint32_t name = nl ? nl : 1u;
     bgr_read_tag tag = {0, 0, 0, 0};
     if (TAG) { const uint4 t = tags[a]; tag.block = t.x; tag.a = t.y; tag.b = t.z; tag.others = t.w; }
-    const uint32_t segbytes = line - name - gaf_fixed_bytes(L, qs, qe, plen, pstart, cl, nm) - (TAG ? gaf_tag_bytes(tag) : 0u);
+    const uint32_t csbytes = CS ? csb[a] : 0u;
+    const uint32_t segbytes = line - name - gaf_fixed_bytes(L, qs, qe, plen, pstart, cl, nm) - (TAG ? gaf_tag_bytes(tag) : 0u) - (CS ? 6u + csbytes : 0u);
     if (nl) group_copy(d, text + r.x + 1, nl, sub);
     else if (sub == 0) d[0] = '*';
     uint32_t pos = name;
@@ -239,8 +256,15 @@ __device__ __forceinline__ void gaf_write(const BgrDeviceGraph& g, const uint8_t
         pos = gaf_put_tag(d, pos, 'h', 'a', tag.a, sub == 14);
         pos = gaf_put_tag(d, pos, 'h', 'b', tag.b, sub == 15);
         pos = gaf_put_tag(d, pos, 'h', 'o', tag.others, sub == 0);
-        if (sub == 0) d[pos] = '\n';
-    } else if (sub == 12) d[pos] = '\n';
+        if (!CS && sub == 0) d[pos] = '\n';
+    } else if (!CS && sub == 12) d[pos] = '\n';
+    if (CS) {
+        uint8_t* o = d + pos + 6;
+        if (sub == 1) { d[pos] = '\t'; d[pos + 1] = 'c'; d[pos + 2] = 's'; d[pos + 3] = ':'; d[pos + 4] = 'Z'; d[pos + 5] = ':'; }
+        if (nm == 0) { if (sub == 2 && cl) cs_put_run(o, 0, cl); }
+        else cs_ops<WIDE, true, true>(g, arena + res.x, np, text + r.z, L, rc, sub, o);
+        if (sub == 3) o[csbytes] = '\n';
+    }
     // the segments: lane (i - 1) mod 16 writes unitig i -- from the front, or on the rc from the back with its orientation flipped
     if (!again) {
         uint32_t acc = 0;
@@ -293,6 +317,12 @@ __global__ void __launch_bounds__(256) bgr_text_gaf_write_tag_kernel(BgrDeviceGr
                                                                      const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout, const uint4* tags) {
     gaf_write<WIDE, true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
 }
+template <bool WIDE, bool TAG>
+__global__ void __launch_bounds__(256) bgr_text_gaf_write_cs_kernel(BgrDeviceGraph g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec,
+                                                                    const uint32_t* acc_rec, uint32_t n_acc, const uint32_t* poff, const uint32_t* noff, const uint32_t* psz,
+                                                                    const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout, const uint4* tags, const uint32_t* csb) {
+    gaf_write<WIDE, TAG, true>(g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags, csb);
+}
 
 // bgr_aligner_path_stats: the same per-read function over the results of a bgr_align_device launch, the reads where the caller keeps them
 // (their buffer is not padded).  out[i] = {plen low, plen high, path start low, path start high, cl, NM | no-walk flag}; zeros for an unmapped read
@@ -329,11 +359,51 @@ __global__ void __launch_bounds__(256) bgr_path_stats_wide_kernel(BgrDeviceGraph
     path_stats<true>(g, reads, offs, results, arena, arena_ints, n, out);
 }
 
+
+// bgr_aligner_path_diffs: the differences of every read of a bgr_align_device launch as structs.  Count (gaf_stat's NM per read; nothing for an
+// unmapped read, a row not wholly inside the arena, a path that spells no walk), the scan of launch_scan2_u32, fill (cs_diffs, the function under
+// the cs:Z: ops, at the read's offset; the caller has checked that all of them fit).
+template <bool WIDE>
+__global__ void __launch_bounds__(256) bgr_path_diffs_count_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, u64 arena_ints,
+                                                                   uint32_t n, uint32_t* cnt) {
+    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
+    if (a >= n) return;
+    const uint2 res = results[a];
+    const uint32_t np = res.y & 0xFFFFFFu;
+    uint32_t nm = 0;
+    if (np && (u64)res.x + np <= arena_ints) {
+        const u64 o0 = offs[a];
+        const GafStat s = gaf_stat<WIDE, false>(g, arena + res.x, np, reads + o0, (uint32_t)(offs[a + 1] - o0), ((res.y >> 24) & BGR_ST_RC) != 0, sub);
+        if (!s.bad) nm = s.nm;
+    }
+    if (sub == 0) cnt[a] = nm;
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(256) bgr_path_diffs_fill_kernel(BgrDeviceGraph g, const uint8_t* reads, const u64* offs, const uint2* results, const int32_t* arena, uint32_t n,
+                                                                  const uint32_t* cnt, const uint32_t* doff, uint2* out) {
+    const uint32_t a = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
+    if (a >= n || cnt[a] == 0) return;   // (a row that counted differences lies inside the arena and spells a walk)
+    const uint2 res = results[a];
+    const u64 o0 = offs[a];
+    cs_diffs<WIDE, false>(g, arena + res.x, res.y & 0xFFFFFFu, reads + o0, (uint32_t)(offs[a + 1] - o0), ((res.y >> 24) & BGR_ST_RC) != 0, sub, out + doff[a]);
+}
+
 }  // namespace
 
 hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream) {
+                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, uint32_t* csb, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
+    if (csb) {   // the instances that carry the cs:Z: field: only an aligner with that switch on launches them
+        const dim3 grid((n_acc + 15) / 16), block(256);
+        if (tag_table) {
+            if (g.k > 33) hipLaunchKernelGGL((bgr_text_gaf_sizes_cs_kernel<true, true>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags, csb);
+            else hipLaunchKernelGGL((bgr_text_gaf_sizes_cs_kernel<false, true>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags, csb);
+        } else {
+            if (g.k > 33) hipLaunchKernelGGL((bgr_text_gaf_sizes_cs_kernel<true, false>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags, csb);
+            else hipLaunchKernelGGL((bgr_text_gaf_sizes_cs_kernel<false, false>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags, csb);
+        }
+        return hipGetLastError();
+    }
     if (tag_table) {   // the tagged instances: only an aligner with a tag table launches them
         if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
         else hipLaunchKernelGGL(bgr_text_gaf_sizes_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, psz, nsz, nlen, rows, bug, tag_table, tags);
@@ -346,8 +416,19 @@ hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, c
 
 hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                  const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
-                                 const uint4* tags, hipStream_t stream) {
+                                 const uint4* tags, const uint32_t* csb, hipStream_t stream) {
     if (n_acc == 0) return hipSuccess;
+    if (csb) {
+        const dim3 grid((n_acc + 15) / 16), block(256);
+        if (tags) {
+            if (g.k > 33) hipLaunchKernelGGL((bgr_text_gaf_write_cs_kernel<true, true>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags, csb);
+            else hipLaunchKernelGGL((bgr_text_gaf_write_cs_kernel<false, true>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags, csb);
+        } else {
+            if (g.k > 33) hipLaunchKernelGGL((bgr_text_gaf_write_cs_kernel<true, false>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags, csb);
+            else hipLaunchKernelGGL((bgr_text_gaf_write_cs_kernel<false, false>), grid, block, 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags, csb);
+        }
+        return hipGetLastError();
+    }
     if (tags) {
         if (g.k > 33) hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<true>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
         else hipLaunchKernelGGL(bgr_text_gaf_write_tag_kernel<false>, dim3((n_acc + 15) / 16), dim3(256), 0, stream, g, text, results, arena, rec, acc_rec, n_acc, poff, noff, psz, nlen, rows, pout, nout, tags);
@@ -364,6 +445,24 @@ hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, cons
     const u64* offs = reinterpret_cast<const u64*>(read_offs);
     if (g.k > 33) hipLaunchKernelGGL(bgr_path_stats_wide_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
     else hipLaunchKernelGGL(bgr_path_stats_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_diffs_count(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
+                                   uint32_t* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const u64* offs = reinterpret_cast<const u64*>(read_offs);
+    if (g.k > 33) hipLaunchKernelGGL(bgr_path_diffs_count_kernel<true>, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, cnt);
+    else hipLaunchKernelGGL(bgr_path_diffs_count_kernel<false>, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, (u64)arena_ints, n, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_diffs_fill(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint32_t n, const uint32_t* cnt,
+                                  const uint32_t* doff, uint2* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const u64* offs = reinterpret_cast<const u64*>(read_offs);
+    if (g.k > 33) hipLaunchKernelGGL(bgr_path_diffs_fill_kernel<true>, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, n, cnt, doff, out);
+    else hipLaunchKernelGGL(bgr_path_diffs_fill_kernel<false>, dim3((n + 15) / 16), dim3(256), 0, stream, g, reads, offs, results, arena, n, cnt, doff, out);
     return hipGetLastError();
 }
 

@@ -54,14 +54,21 @@ hipError_t launch_text_correct_write(const BgrDeviceGraph& g, const uint8_t* tex
 // matches, NM (text_gaf.hip).  Sizes (psz / nsz, scanned by launch_scan2_u32), then the bytes; nlen (characters of the name), rows ({walk size low, high,
 // characters covered, NM} per accepted read) and psz pass from the first to the second.  *bug as launch_text_correct_sizes sets it.
 hipError_t launch_text_gaf_sizes(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
-                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, hipStream_t stream);
+                                 uint32_t* psz, uint32_t* nsz, uint32_t* nlen, uint4* rows, uint32_t* bug, const uint32_t* tag_table, uint4* tags, uint32_t* csb, hipStream_t stream);
 hipError_t launch_text_gaf_write(const BgrDeviceGraph& g, const uint8_t* text, const uint2* results, const int32_t* arena, const uint4* rec, const uint32_t* acc_rec, uint32_t n_acc,
                                  const uint32_t* poff, const uint32_t* noff, const uint32_t* psz, const uint32_t* nlen, const uint4* rows, uint8_t* pout, uint8_t* nout,
-                                 const uint4* tags, hipStream_t stream);   // tag_table / tags (bgr_read_tag per read) null: the untagged kernels; else the tagged instances (haplotag_device.h)
+                                 const uint4* tags, const uint32_t* csb, hipStream_t stream);   // tag_table / tags (bgr_read_tag per read) null: the untagged kernels; else the tagged instances (haplotag_device.h)
+// csb (a word per accepted read: the bytes of its cs:Z: ops) null: the kernels as ever; else the instances whose lines end in that field (gaf_cs_device.h)
 // bgr_aligner_path_stats: per read of a bgr_align_device launch six words {walk size low, high, path start low, high, characters covered, NM | 1 << 31 "spells no walk"}
 // (zeros for an unmapped read, and for a row that does not lie wholly inside the launch's arena_ints)
 hipError_t launch_path_stats(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
                              uint32_t* out, hipStream_t stream);
+// bgr_aligner_path_diffs: cnt[r] = the differences of read r (what path stats reports as NM; 0 for a row it reports zeros or "no walk" for); then, with doff the
+// exclusive scan of cnt, the differences themselves at out[doff[r] ...], two words each (bgr_path_diff), ascending read position
+hipError_t launch_path_diffs_count(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint64_t arena_ints, uint32_t n,
+                                   uint32_t* cnt, hipStream_t stream);
+hipError_t launch_path_diffs_fill(const BgrDeviceGraph& g, const uint8_t* reads, const uint64_t* read_offs, const uint2* results, const int32_t* arena, uint32_t n, const uint32_t* cnt,
+                                  const uint32_t* doff, uint2* out, hipStream_t stream);
 // the pre-pass (batch_kernels.hip) over reads that lie scattered in a text: read r's characters start at reads + src_off[r]
 hipError_t launch_pack_reads_at(const uint8_t* text, const uint32_t* src_off, const uint64_t* read_offs, uint32_t n, uint64_t text_bytes, uint64_t total_bases,
                                 uint64_t* fw3, uint64_t* nmw, uint32_t* hasn, hipStream_t stream);

@@ -325,6 +325,32 @@ typedef struct {
 } bgr_path_stat;
 #define BGR_PATH_STAT_NO_WALK 0x80000000u
 int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n_reads, bgr_path_stat* out);
+/* WHICH characters differ, where bgr_path_stat says how many: the differences of read i at out[diff_offsets[i] .. diff_offsets[i + 1]), ascending
+ * read_pos (a position of the read as the caller holds it), path_base = what the path spells there in the read's direction (for a read mapped on its
+ * reverse complement: the complement), read_base = the read's character.  These are the "*" ops of the cs:Z: field below, as structs.  Nothing for an
+ * unmapped read, for a row that does not lie wholly inside the arena and for a path that spells no walk -- so a read has as many entries as
+ * bgr_path_stat.mismatches says, 0 where that is BGR_PATH_STAT_NO_WALK.  Three launches on the aligner's stream: count, a scan, fill; blocking.
+ * diff_offsets has n_reads + 1 entries; *n = the differences of the launch.  BGR_E_CAPACITY, with *n and the offsets set and `out` untouched, when
+ * cap < *n: call again with room.  The refusals are bgr_aligner_path_stats's, and BGR_E_ARG for a launch of 2^32 bases or more. */
+typedef struct {
+    uint32_t read_pos;
+    uint8_t path_base;   /* 0..3 = ACGT, in the read's direction */
+    uint8_t read_base;   /* 0..3 = ACGT, 4 = a character outside ACGT */
+    uint16_t reserved;   /* 0 */
+} bgr_path_diff;
+int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n_reads, uint64_t* diff_offsets, bgr_path_diff* out, uint64_t cap,
+                           uint64_t* n);
+/* The cs:Z: field of GAF lines (--cs): "\tcs:Z:<ops>" as the LAST field of every line, behind NM:i: and behind the haplotag fields of a line that has
+ * them.  The ops are minimap2's short form with substitutions only (a path and its read have no gaps between them): over the aligned characters in
+ * the read's direction, ":<n>" per maximal run of n equal characters and "*<path base><read base>" in lower case per difference, "n" for a read
+ * character outside ACGT; no aligned character: the empty value.  So the number of "*" is NM, and the run lengths plus NM are column 11.
+ * bgr_aligner_gaf_cs_enable(a, on): the GAF lines of bgr_align_fasta_text (want_output = 3) of this aligner end in the field; the sizes and write
+ * kernels then launched are instances of their own (bgreat_amd/csrc/gaf_cs_device.h), an aligner with the switch off launches the kernels it always did
+ * and writes the bytes it always did.  bgr_graph_gaf_cs_enable(g, on) is sticky, for whole runs: every later bgr_align_all with bgr_run_options.gaf
+ * writes the field, on every route (the host formatter writes the same bytes); BGR_E_ARG from a bgr_align_all with the switch on and gaf off. */
+int bgr_aligner_gaf_cs_enable(bgr_aligner* a, int on);
+int bgr_graph_gaf_cs_enable(bgr_graph* g, int on);
+int bgr_graph_gaf_cs_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n_reads, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status);
 

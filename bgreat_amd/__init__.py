@@ -52,6 +52,8 @@ SYMBOLS = [
     "bgr_graph_variants_params", "bgr_write_vcf", "bgr_parse_af_ppm",
     "bgr_aligner_pileup_strands_enable", "bgr_aligner_pileup_forward", "bgr_aligner_pileup_strand_sites", "bgr_graph_pileup_strands_enable", "bgr_graph_pileup_strands_enabled",
     "bgr_graph_pileup_forward", "bgr_graph_variants_strands_enable", "bgr_graph_variant_strand_sites", "bgr_write_pileup_strands", "bgr_write_vcf_strands", "bgr_parse_min_alt_strand",
+    "bgr_graph_inside_build", "bgr_graph_inside_info", "bgr_graph_inside_lookup", "bgr_aligner_inside_enable", "bgr_aligner_inside_count",
+    "bgr_graph_inside_enable", "bgr_graph_inside_enabled", "bgr_graph_inside_count",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
@@ -159,6 +161,10 @@ class PathStat(C.Structure):  # bgr_path_stat
 
 PATH_STAT_NO_WALK = 0x80000000
 PATH_DIFF_DTYPE = np.dtype([("read_pos", np.uint32), ("path_base", np.uint8), ("read_base", np.uint8), ("reserved", np.uint16)])   # an array of bgr_path_diff
+
+
+class InsideInfo(C.Structure):  # bgr_inside_info
+    _fields_ = [("entries", C.c_uint64), ("slots", C.c_uint64), ("bytes", C.c_uint64), ("build_seconds", C.c_double)]
 
 
 class Ticket(C.Structure):
@@ -363,6 +369,14 @@ def lib():
     L.bgr_aligner_gaf_cs_enable.argtypes = [vp, C.c_int]
     L.bgr_graph_gaf_cs_enable.argtypes = [vp, C.c_int]
     L.bgr_graph_gaf_cs_enabled.argtypes = [vp]
+    L.bgr_graph_inside_build.argtypes = [vp]
+    L.bgr_graph_inside_info.argtypes = [vp, C.POINTER(InsideInfo)]
+    L.bgr_graph_inside_lookup.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.bgr_aligner_inside_enable.argtypes = [vp, C.c_int]
+    L.bgr_aligner_inside_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.bgr_graph_inside_enable.argtypes = [vp, C.c_int]
+    L.bgr_graph_inside_enabled.argtypes = [vp]
+    L.bgr_graph_inside_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.bgr_aligner_pileup_enable.argtypes = [vp, u32]
     L.bgr_aligner_pileup.argtypes = [vp, vp, u64, vp]
     L.bgr_aligner_reset_pileup.argtypes = [vp]
@@ -620,6 +634,35 @@ class Graph:
         d = {f[0]: getattr(gi, f[0]) for f in GraphInfo._fields_ if f[0].startswith("jump_")}
         d["jump_absent_why"] = JUMP_ABSENT[gi.jump_absent]
         return d
+
+    def inside_build(self):
+        """bgr_graph_inside_build: the inside index (an exact table over a sample of the unitigs' k-mers) on the host; sticky."""
+        _check(lib().bgr_graph_inside_build(self.h))
+
+    def inside_info(self):
+        """bgr_graph_inside_info -> {entries, slots, bytes, build_seconds}; zeroes before inside_build()."""
+        o = InsideInfo()
+        _check(lib().bgr_graph_inside_info(self.h, C.byref(o)))
+        return {f[0]: getattr(o, f[0]) for f in InsideInfo._fields_}
+
+    def inside_lookup(self, kmer):
+        """bgr_graph_inside_lookup: the entry of a k-mer word (either strand) -> (unitig id, offset, forward window is canonical), or None."""
+        u, j, fc, found = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().bgr_graph_inside_lookup(self.h, int(kmer), C.byref(u), C.byref(j), C.byref(fc), C.byref(found)))
+        return (int(u.value), int(j.value), bool(fc.value)) if found.value else None
+
+    def inside_enable(self, on=True):
+        """bgr_graph_inside_enable: sticky -- every aligner of a later align_all on this graph runs the inside pass."""
+        _check(lib().bgr_graph_inside_enable(self.h, int(bool(on))))
+
+    def inside_enabled(self):
+        return bool(lib().bgr_graph_inside_enabled(self.h))
+
+    def inside_count(self):
+        """bgr_graph_inside_count: reads the last align_all with the switch on mapped inside a unitig."""
+        n = C.c_uint64(0)
+        _check(lib().bgr_graph_inside_count(self.h, C.byref(n)))
+        return int(n.value)
 
     def upload(self, device=0):
         _check(lib().bgr_graph_upload(self.h, device))
@@ -1005,6 +1048,16 @@ class Aligner:
         out = np.zeros(total.value, dtype=PATH_DIFF_DTYPE)
         _check(lib().bgr_aligner_path_diffs(self.h, d_reads_ptr, d_offsets_ptr, n, offs.ctypes.data, out.ctypes.data, len(out), C.byref(total)))
         return offs, out
+
+    def inside_enable(self, on=True):
+        """bgr_aligner_inside_enable: every greedy / anchors launch is followed by the inside pass from now on (the graph needs inside_build())."""
+        _check(lib().bgr_aligner_inside_enable(self.h, int(bool(on))))
+
+    def inside_count(self):
+        """bgr_aligner_inside_count: reads the inside pass has mapped on this aligner."""
+        n = C.c_uint64(0)
+        _check(lib().bgr_aligner_inside_count(self.h, C.byref(n)))
+        return int(n.value)
 
     def gaf_cs_enable(self, on=True):
         """bgr_aligner_gaf_cs_enable: the GAF lines of align_fasta_text (want_output=3) end in the cs:Z: field from now on."""

@@ -68,6 +68,8 @@ enum class List : uint32_t {
 constexpr uint32_t list_word(List l) { return static_cast<uint32_t>(l); }
 // The rest of `small` (bytes): the counters, the CSR total, the text route's two info blocks (TXT_INFO_WORDS u32 each, text_kernels.h)
 constexpr uint32_t kSmallCounters = 4 * kCurCounters, kSmallCsrTotal = 128, kSmallTextInfo = 192, kSmallTextInfoBytes = 32, kSmallBytes = 256;
+constexpr uint32_t kSmallInside = kSmallCounters + 8 * kCounters;  // one u64 behind the counters: reads the inside pass mapped (bgr_aligner_inside_count)
+static_assert(kSmallInside % 8 == 0 && kSmallInside + 8 <= kSmallCsrTotal, "the inside count lies between the counters and the CSR total");
 constexpr bool distinct_words(std::initializer_list<uint32_t> w) {
     uint32_t seen = 0;
     for (uint32_t x : w) {

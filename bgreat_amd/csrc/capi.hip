@@ -34,6 +34,7 @@
 #include "text_kernels.h"
 #include "options.h"
 #include "capi_internal.h"
+#include "inside_kernels.h"
 
 namespace bgr {
 static thread_local std::string tl_err;
@@ -217,6 +218,7 @@ void bgr_graph_destroy(bgr_graph* g) {
         }
     }
     variants_run_free(g);
+    inside_free_devices(g);
     delete g;
 }
 
@@ -609,6 +611,10 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts triples (bgr_aligner_triples_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
     if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->inside_tab && p->mode == BGR_MODE_EXHAUSTIVE)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner runs the inside pass (bgr_aligner_inside_enable), which writes rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->inside_tab && n_reads && max_read_len > bgr::kInsideMaxReadLen)
+        return fail(BGR_E_ARG, "bgr_align_device: this aligner runs the inside pass (bgr_aligner_inside_enable), which takes reads of at most 32 000 characters");
     a->holder = nullptr;   // (a launch on the aligner's own stream and buffers; bgr_align_device names the twin behind this call when that took it)
     a->last_n = n_reads;
     a->last_mode = p->mode;
@@ -631,6 +637,7 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
     bgr::PlanBatch pb;
     pb.mode = p->mode; pb.max_mismatch = p->max_mismatch; pb.partial = p->partial; pb.max_read_len = max_read_len;
     pb.n_reads = n_reads; pb.total_bases = total_bases;
+    pb.inside = a->inside_tab != nullptr;   // (2 more arena ints per read: the rows of the inside pass)
     const bgr::LaunchPlan P = bgr::plan_launch(plan_graph_of(a->graph->header), a->plan_dev, plan_tuning_of(a), pb);
     if (P.error) return fail(BGR_E_ARG, P.error);
     const bgr::Pass& first = P.pass[0];
@@ -761,12 +768,20 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
             a->deep.runs = 1;
         }
     }
-    // The counting kernels behind the last pass.  The pileup reads the read characters where this launch has them: the ASCII bytes when the mapping
-    // kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
+    // Behind the last pass: the inside pass (bgr_aligner_inside_enable) over the reads the passes left without an anchor, then the counting kernels -- in
+    // stream order in front of everything that reads the rows.  Both read the read characters where this launch has them: the ASCII bytes when the
+    // mapping kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
     {
         bgr::PileupReads pr;
         if (inline_pack) { pr.ascii = static_cast<const uint8_t*>(d_reads); pr.src_off = static_cast<const uint32_t*>(d_src_off); pr.ascii_bytes = reads_bytes; }
         else { pr.fw3 = io.fw3; pr.nmw = io.nmw; pr.hasn = io.hasn; }
+        if (a->inside_tab && !keep_rows) {
+            bgr::InsideLaunch il{io.results, io.arena, io.cursor, io.arena_cap, io.arena_own, io.read_offs, io.n_reads, max_read_len, p->max_mismatch, pr};
+            e = bgr::launch_inside(a->dg, a->inside_tab, a->inside_slots, il, reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallInside),
+                                   (uint32_t)a->num_cus, a->stream);
+            if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_align_inside_kernel): ") + hipGetErrorString(e));
+            HIP_TRY(mark("bgr_align_inside_kernel"));
+        }
         const int crc = queue_counting(a, P.arena_cap, io.read_offs, n_reads, total_bases, pr, mark);
         if (crc != BGR_OK) return crc;
     }
@@ -854,6 +869,7 @@ static int twins_setup(bgr_aligner* a, unsigned n_twins) {
         tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events; tw->knob_no_jump = a->knob_no_jump;
         tw->knob_abundance_form = a->knob_abundance_form;
         tw->knob_links_form = a->knob_links_form;
+        tw->inside_tab = a->inside_tab; tw->inside_slots = a->inside_slots;
         if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
         prev = tw;
     }
@@ -1310,10 +1326,10 @@ int bgr_aligner_reset_counters(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_counters: null aligner");
     HIP_TRY(hipSetDevice(a->device));
     // (on the aligner's own stream: a fill on the null stream is not ordered with a non-blocking stream's kernels)
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(a->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8, a->stream));
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(a->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8 + 8, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(tw->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8, tw->stream));
+        HIP_TRY(hipMemsetAsync(static_cast<char*>(tw->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8 + 8, tw->stream));
         HIP_TRY(hipStreamSynchronize(tw->stream));
     }
     return BGR_OK;

@@ -165,4 +165,4 @@ static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
     return rc;
 }
 static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) { return bgr::end_stages(kStages, kNStages, g, what, ok); }
-static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, run_haplotag_enable, run_gaf_cs_wanted, run_gaf_cs_enable}, true);
+static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, run_haplotag_enable, run_gaf_cs_wanted, run_gaf_cs_enable, run_inside_wanted, run_inside_begin, run_inside_enable, run_inside_collect}, true);

@@ -22,6 +22,7 @@
 #include "abundance_kernels.h"
 #include "align_kernels.h"
 #include "graph_build.h"
+#include "inside_index.h"
 #include "launch_plan.h"
 #include "options.h"
 #include "text_epochs.h"
@@ -113,6 +114,13 @@ struct bgr_graph {
     uint32_t variants_min_alt_strand = 0, variants_called_strand = 0;
     std::vector<uint32_t> pileup_fwd_words;
     std::vector<bgr_variant_strand_site> variants_strand_sites;
+    // the inside index (bgr_graph_inside_build; inside_index.h): a buffer of its own on the host and, uploaded once per device that an aligner with the
+    // pass enabled lives on, in HBM (inside_dev, under abundance_m) -- never part of the blob.  inside_on: the sticky switch of whole runs,
+    // inside_run: what the aligners of the last bgr_align_all mapped inside
+    bgr::InsideIndex inside;
+    std::map<int, void*> inside_dev;
+    bool inside_on = false;
+    uint64_t inside_run = 0;
 };
 
 struct DevBuf {
@@ -240,6 +248,10 @@ struct bgr_aligner {
     DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
     double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
     double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
+    // the inside pass (bgr_aligner_inside_enable): every greedy / anchors launch is followed, in front of the counting kernels, by bgr_align_inside_kernel
+    // over the graph's inside index on this device (inside_tab: null = off); what it mapped is counted at kSmallInside of `small`
+    const BgrInsideEntry* inside_tab = nullptr;
+    uint64_t inside_slots = 0;
     bgr_aligner* twin = nullptr;    // second stream + buffers: the overlapped form of bgr_align_batch, un-waited consecutive bgr_align_device launches (created on first use)
     bool is_twin = false;
     uint32_t knob_device_overlap = 0;   // BGR_KNOB_DEVICE_OVERLAP
@@ -428,6 +440,12 @@ int pileup_refusal(const bgr_graph* g, const char* who);   // BGR_E_ARG on a gra
 void run_pileup_begin(bgr_graph* g);                   // a whole run (run_counts.h), as the links';
 int run_pileup_collect(bgr_graph* g, bgr_aligner* a);  // ... the pileup switch gathers on the host, the variants switch on a device
 int run_pileup_end(bgr_graph* g, bool ok);             // ... behind the abundance's end: BGR_E_CAPACITY when a depth may have wrapped
+// capi_inside.hip
+void inside_free_devices(bgr_graph* g);                // the device copies of the graph's inside index released (bgr_graph_destroy)
+int run_inside_wanted(const bgr_graph* g);             // the graph's switch for whole runs (run_counts.h)
+void run_inside_begin(bgr_graph* g);                   // ... a new run: its count starts at 0
+int run_inside_enable(bgr_aligner* a, int on);         // ... onto an aligner of the run
+int run_inside_collect(bgr_graph* g, bgr_aligner* a);  // ... the aligner's count (its streams waited for) joins the run's
 // capi_variants.hip
 int variants_collect(bgr_graph* g, bgr_aligner* a);   // a run's aligner: the first one's tables become the run's (g->variants_run), the others' are added
 int variants_end(bgr_graph* g, bool ok);              // the run's end: the sites called once from the run's table, which is freed whatever happens

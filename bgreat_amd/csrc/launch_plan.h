@@ -40,6 +40,7 @@ struct PlanTuning {   // bgr_aligner_configure / bgr_aligner_set_knob
 struct PlanBatch {
     uint32_t mode = 0, max_mismatch = 0, partial = 0, max_read_len = 0;
     uint64_t n_reads = 0, total_bases = 0;
+    bool inside = false;  // the launch is followed by the inside pass (inside_kernels.h), which takes a row of 2 ints per read it maps from the arena
 };
 
 // One kernel launch of a mapping launch
@@ -264,7 +265,7 @@ inline LaunchPlan plan_launch(const PlanGraph& g, const PlanDevice& d, const Pla
     // Path arena: every path int consumes at least one read base (+8 per read for offsets / short reads), plus what the passes take beyond that.
     // A chunk is at least twice the longest possible path, so an abandoned chunk is more than half used.
     P.arena_chunk = std::max<uint32_t>(256, 2 * P.path_cap);
-    P.arena_cap = 2 * (b.total_bases + 8 * n_reads);
+    P.arena_cap = 2 * (b.total_bases + 8 * n_reads) + (b.inside ? 2 * n_reads : 0);
     for (uint32_t i = 0; i < P.n_passes; ++i) {
         const Pass& ps = P.pass[i];
         // the sixteen-reads-per-wave greedy and the four-reads-per-wave anchors kernels write a read's path ints where they are found, into the read's own

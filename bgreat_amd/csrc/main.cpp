@@ -59,6 +59,10 @@
 //                                                   --cs (with --gaf: every line ends in cs:Z:, minimap2's short difference string -- ":<n>" per run of equal characters, "*<path base><read
 //                                                               base>" per difference, in the read's direction, behind NM:i: and the --haplotag fields; computed on the device
 //                                                               where the line is formatted; runs with everything --gaf runs with: include/bgreat_gpu.h)
+//                                                   --inside (greedy and -G: reads that lie wholly inside one unitig hold no overlap (k-1)-mer and stay unmapped; a pass behind the mapping
+//                                                               looks up a sample of their k-mers in an exact index of the unitigs' k-mers and maps them as [offset, +-unitig], so
+//                                                               they reach `paths` and every counting flag instead of notAligned.fa; one last line on stdout counts them; not with
+//                                                               -b, k > 32 or non-ACGT unitig characters: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -92,7 +96,7 @@ int main(int argc, char** argv) {
     uint64_t min_block = 1;        // --min-block
     bool min_block_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
-    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false;
+    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false, inside = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
@@ -104,7 +108,7 @@ int main(int argc, char** argv) {
                                 {"triples", required_argument, nullptr, 1021}, {"phase", required_argument, nullptr, 1022},
                                 {"blocks", required_argument, nullptr, 1023}, {"min-phase", required_argument, nullptr, 1024},
                                 {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
-                                {"haplotag", required_argument, nullptr, 1027}, {"cs", no_argument, nullptr, 1028},
+                                {"haplotag", required_argument, nullptr, 1027}, {"cs", no_argument, nullptr, 1028}, {"inside", no_argument, nullptr, 1029},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -202,6 +206,7 @@ int main(int argc, char** argv) {
             }
             case 1027: haplotagFile = optarg; break;
             case 1028: gaf_cs = true; break;
+            case 1029: inside = true; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -222,6 +227,8 @@ int main(int argc, char** argv) {
     if (!haplotagFile.empty() && !gaf) { fprintf(stderr, "bgreat: --haplotag BLOCKS_FILE adds its fields to the lines of --gaf\n"); return 2; }
     if (!haplotagFile.empty() && brute) { fprintf(stderr, "bgreat: --haplotag tags GAF lines, which are for the greedy modes; exhaustive mode (-b) writes no paths\n"); return 2; }
     if (gaf_cs && !gaf) { fprintf(stderr, "bgreat: --cs adds the cs:Z: field to the lines of --gaf\n"); return 2; }
+    if (inside && brute) { fprintf(stderr, "bgreat: --inside maps the reads greedy mode leaves without an anchor; exhaustive mode (-b) is refused\n"); return 2; }
+    if (inside && ka > 32) { fprintf(stderr, "bgreat: --inside indexes one-word k-mers: k <= 32\n"); return 2; }
     if (gpus < 1 || batch < 0) { fprintf(stderr, "bgreat: --gpus and --batch must be positive\n"); return 2; }
 
     auto t0 = std::chrono::system_clock::now();
@@ -235,6 +242,7 @@ int main(int argc, char** argv) {
         if (bgr_read_blocks_tags(haplotagFile.c_str(), gi.n_unitigs, table.data(), nullptr) != BGR_OK || bgr_graph_haplotag_enable(graph, table.data(), table.size()) != BGR_OK) die("--haplotag");
     }
     if (gaf_cs && bgr_graph_gaf_cs_enable(graph, 1) != BGR_OK) die("--cs");
+    if (inside && (bgr_graph_inside_build(graph) != BGR_OK || bgr_graph_inside_enable(graph, 1) != BGR_OK)) die("--inside");   // (k > 32, non-ACGT unitig characters: refused here, status 2)
     // one host -> device copy, then device to device over xGMI (RCCL broadcast, or peer copies): include/bgreat_gpu.h
     int64_t one_device = 0, timing = 0;  // (test hook: every lane on device 0)
     (void)bgr_get_option("test.lanes_on_one_device", &one_device);
@@ -360,6 +368,11 @@ int main(int argc, char** argv) {
     auto secs = std::chrono::duration_cast<std::chrono::seconds>(end - start).count();
     std::cout << "Reads/seconds : " << rn / (uint64_t)(secs + 1) << std::endl;
     std::cout << "Mapping in seconds : " << secs << std::endl;
+    if (inside) {   // (one more line, the last: the lines above are the reference's)
+        uint64_t ni = 0;
+        if (bgr_graph_inside_count(graph, &ni) != BGR_OK) die("--inside");
+        std::cout << "Mapped inside a unitig : " << ni << std::endl;
+    }
     if (timing) fprintf(stderr, "bgreat: mapping %.3f s, %.3f Mreads/s end to end\n", map_secs, map_secs > 0 ? rn / map_secs / 1e6 : 0.0);
     bgr_host_cache_release();  // the pipeline's page-locked staging sets (kept for a next run of the process): freed while the HIP runtime is up
     bgr_graph_destroy(graph);

@@ -74,6 +74,10 @@ int align_all_impl(bgr_graph* graph, const bgr_params* prm, const bgr_run_option
             const int crc = bgr::g_run_counts.collect(graph, a.get(), counts);
             if (crc != BGR_OK) r.fail(crc, bgr_last_error());
         }
+        if (!r.failed && shape.inside) {  // and what it mapped inside
+            const int irc = bgr::g_run_counts.inside_collect(graph, a.get());
+            if (irc != BGR_OK) r.fail(irc, bgr_last_error());
+        }
         a.reset();
     }
     if (counters_out) memcpy(counters_out, tot, sizeof(tot));
@@ -226,6 +230,10 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
     }
     if (!opt->gaf && bgr::g_run_counts.gaf_cs_wanted && bgr::g_run_counts.gaf_cs_wanted(graph))   // the same for the cs:Z: field
         return bgr::set_error(BGR_E_ARG, "bgr_align_all: the cs:Z: field (--cs, bgr_graph_gaf_cs_enable) is a field of GAF lines; the run needs bgr_run_options.gaf (--gaf)");
+    const bool inside = bgr::g_run_counts.inside_wanted && bgr::g_run_counts.inside_wanted(graph);
+    if (inside && prm->mode == BGR_MODE_EXHAUSTIVE)
+        return bgr::set_error(BGR_E_ARG, "bgr_align_all: the inside pass (--inside, bgr_graph_inside_enable) writes rows of the greedy modes; exhaustive mode (-b) is refused");
+    if (inside) bgr::g_run_counts.inside_begin(graph);
     if (opt->abundance > 1) return bgr::set_error(BGR_E_ARG, "bgr_align_all: bgr_run_options.abundance is 0 or 1");
     // what the run counts (run_counts.h): the graph's sticky switches, which imply unitig abundance whatever bgr_run_options.abundance says, and that option
     const uint32_t counts = (bgr::g_run_counts.wanted ? bgr::g_run_counts.wanted(graph) : 0) | (opt->abundance ? bgr::kCountAbundance : 0);

@@ -174,6 +174,7 @@ struct RunShape {
     const uint32_t* tag_table = nullptr; // haplotags (bgr_graph_haplotag_enable; bgr_align_all has refused a run without gaf): the graph's table goes onto every
     uint64_t tag_rows = 0;               // aligner's device, and the host formatter tags from the same words
     bool gaf_cs = false;                 // the cs:Z: field (bgr_graph_gaf_cs_enable; the same refusal): every aligner's switch is set, the host formatter writes it too
+    bool inside = false;                 // the inside pass (bgr_graph_inside_enable; bgr_align_all has refused it in exhaustive mode): every aligner's switch is set
     int device_of(unsigned g) const { return (int)(one_device ? first_device : first_device + g); }
 };
 
@@ -212,6 +213,7 @@ int plan_run(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt
     }
     if (s.gaf && bgr::g_run_counts.haplotag_table) s.tag_table = bgr::g_run_counts.haplotag_table(graph, &s.tag_rows);
     if (s.gaf && bgr::g_run_counts.gaf_cs_wanted) s.gaf_cs = bgr::g_run_counts.gaf_cs_wanted(graph) != 0;
+    if (bgr::g_run_counts.inside_wanted) s.inside = bgr::g_run_counts.inside_wanted(graph) != 0;
     // two aligners (streams) per device so that consecutive batches overlap copy and compute (text route: the piece is already on its
     // way to the device when a worker takes the batch; measured 185 / 163 / 149 Mreads/s end to end with 2 / 3 / 4 workers per device)
     if (const int64_t w = bgr::opt("workers_per_device")) s.per_dev = (unsigned)w;  // (tuning / experiments)
@@ -262,6 +264,7 @@ int make_aligners(bgr_graph* graph, const RunShape& s, uint32_t counts, std::vec
             if (counts) rc = bgr::g_run_counts.enable(a, counts);  // every launch of the run is followed by the kernels of what it counts (bgr_align_all has checked the table)
             if (rc == BGR_OK && s.tag_table) rc = bgr::g_run_counts.haplotag_enable(a, s.tag_table, s.tag_rows);
             if (rc == BGR_OK && s.gaf_cs) rc = bgr::g_run_counts.gaf_cs_enable(a, 1);
+            if (rc == BGR_OK && s.inside) rc = bgr::g_run_counts.inside_enable(a, 1);
             if (rc != BGR_OK) return rc;
         }
     }

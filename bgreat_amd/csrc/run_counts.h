@@ -29,6 +29,12 @@ struct RunCounts {
     // formatter writes the same bytes (record_format.h)
     int (*gaf_cs_wanted)(const bgr_graph* g);
     int (*gaf_cs_enable)(bgr_aligner* a, int on);
+    // the inside pass (bgr_graph_inside_enable), the same way: the graph's switch as 1 or 0, the start of a run's count, the call that sets an
+    // aligner's switch (the index goes onto its device), and the call that adds a finished aligner's count to the run's
+    int (*inside_wanted)(const bgr_graph* g);
+    void (*inside_begin)(bgr_graph* g);
+    int (*inside_enable)(bgr_aligner* a, int on);
+    int (*inside_collect)(bgr_graph* g, bgr_aligner* a);
 };
 extern RunCounts g_run_counts;   // pipeline.cpp; all null until the library's C-ABI units have registered
 

@@ -354,6 +354,48 @@ int bgr_graph_gaf_cs_enabled(const bgr_graph* g);   /* the switch as it stands: 
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n_reads, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status);
 
+/* Reads that lie inside one unitig (--inside).  Greedy mode anchors a read on overlap (k-1)-mers, which sit at unitig ends: a read that lies wholly
+ * inside one unitig has none, gets BGR_ST_NOANCHOR and reaches no output.  The inside pass maps these reads in a pass of its own behind the mapping
+ * passes.  The definition (tests/inside_ref.py restates it in plain Python):
+ *   k-mer word: the 2k-bit word of the graph's 2-bit code, first base most significant, k <= 32; canonical = the smaller of the word and the word of
+ *   its reverse complement; a k-mer equal to its own reverse complement is never indexed; a k-mer is SELECTED when the jump index's rule holds for the hash of
+ *   its canonical form (bgr_jump_selects over bgr_mix64, bgreat_amd/csrc/graph_layout.h: one in four, a function of the k-mer alone).
+ *   The inside index holds, for every unitig id and offset 0 <= j <= len - k whose k-mer is selected, canonical -> (id, j, whether the forward window
+ *   is the canonical one); of a k-mer that occurs more than once the smallest (id, j).  It is exact: membership is decided by comparing the key.
+ *   The pass, over a read R of L >= k characters whose status & BGR_ST_MASK is BGR_ST_NOANCHOR, for i = 0 .. L - k in order: the window R[i, i + k) is
+ *   skipped if it holds a character outside ACGT, is not selected or is not in the index; else with its entry (id, j): if the window equals the
+ *   unitig's at j the read lies forward on it from s = j - i, else on its reverse complement from s = (len - k - j) - i, counted there.  The candidate
+ *   is valid when 0 <= s, s + L <= len and R differs from the oriented unitig's [s, s + L) in at most max_mismatch characters (a read character
+ *   outside ACGT always differs).  The FIRST valid candidate decides: the row becomes [s, +id] or [s, -id] (two ints; the sign is the strand) and the
+ *   status BGR_ST_ALIGNED without BGR_ST_RC.  No valid candidate: nothing about the read changes.  effort does not enter.  Reads shorter than k,
+ *   BGR_ST_FAILED reads and reads that hang over a unitig's end stay as they are.  The result is a function of the read, the graph and max_mismatch
+ *   alone, whatever the batching, route, stream or device.
+ * bgr_graph_inside_build builds the index on the host (bgr_set_build_threads threads) from the graph's host blob; sticky, a second call does nothing.
+ * BGR_E_ARG for k > 32, a graph with non-ACGT unitig characters and one without a host blob; BGR_E_NOMEM, with nothing left allocated, when the table
+ * cannot be had.  The table -- open addressing, load at most 0.5, 16-byte entries: 32 bytes per selected k-mer, at most 8 bytes per graph base -- is NOT part of bgr_graph_blob's bytes: it
+ * lives in a buffer of its own and is copied once to each device on which an aligner enables the pass.  bgr_graph_inside_info: its numbers (zeroes
+ * before a build).  bgr_graph_inside_lookup (diagnostic, the CPU tests pin the table with it): the entry of a k-mer word given on either strand.
+ * bgr_aligner_inside_enable(a, on): while on, every greedy / anchors launch of the aligner, through every entry point, is followed on its stream -- in
+ * front of the counting kernels, the text formatter and everything else that reads rows -- by one kernel ("bgr_align_inside_kernel" in
+ * bgr_aligner_kernel_times); the launch's arena is planned with 2 more ints per read.  BGR_E_ARG when the graph has no index; an exhaustive launch
+ * of an enabled aligner, and one with a read beyond 32 000 characters, is refused with BGR_E_ARG.  bgr_aligner_inside_count: reads the pass has
+ * mapped since the aligner was made or bgr_aligner_reset_counters; the five counters of bgr_aligner_counters keep their meaning -- no_overlap counts
+ * the reads without an anchor, those mapped inside included.
+ * bgr_graph_inside_enable(g, on) is sticky, for whole runs: every aligner of a later bgr_align_all runs the pass (both routes, every device, split
+ * output); BGR_E_ARG from a run in exhaustive mode.  bgr_graph_inside_count: what the last such run mapped inside. */
+typedef struct {
+    uint64_t entries, slots, bytes;   /* distinct k-mers held, slots of the table, its bytes (16 per slot) */
+    double build_seconds;
+} bgr_inside_info;
+int bgr_graph_inside_build(bgr_graph* g);
+int bgr_graph_inside_info(const bgr_graph* g, bgr_inside_info* out);
+int bgr_graph_inside_lookup(const bgr_graph* g, uint64_t kmer, uint32_t* unitig, uint32_t* offset, uint32_t* forward_canonical, uint32_t* found);
+int bgr_aligner_inside_enable(bgr_aligner* a, int on);
+int bgr_aligner_inside_count(bgr_aligner* a, uint64_t* n);
+int bgr_graph_inside_enable(bgr_graph* g, int on);
+int bgr_graph_inside_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_inside_count(const bgr_graph* g, uint64_t* n);
+
 /* Per-unitig abundance, counted on the device behind every mapping launch (the definition: bgr_run_options.abundance below).  Off unless enabled;
  * while enabled every greedy / anchors launch of the aligner -- through bgr_align_device, bgr_align_batch and its split and overlapped forms, the
  * packed form, begin / wait, the text form -- is followed on its stream by one kernel ("bgr_abundance_kernel" in bgr_aligner_kernel_times) that adds

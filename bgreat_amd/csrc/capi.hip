@@ -394,6 +394,7 @@ int bgr_aligner_create(bgr_graph* g, int device, bgr_aligner** out) {
     bgr_aligner* a = new bgr_aligner();
     a->graph = g;
     a->device = device;
+    a->sh = new AlignerShared();   // (a twin gives its own up for its owner's: twins_setup)
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) { delete a; return fail(BGR_E_HIP, hipGetErrorString(e)); }
@@ -401,18 +402,13 @@ int bgr_aligner_create(bgr_graph* g, int device, bgr_aligner** out) {
     a->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : 65536;
     e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete a; return fail(BGR_E_HIP, hipGetErrorString(e)); }
-    for (int i = 0; i < kTimerRing; ++i) {
-        for (int j = 0; j <= kTimerSlots; ++j) {
-            if (hipEventCreate(&a->ev[i][j]) != hipSuccess) {
-                delete a;
-                return fail(BGR_E_HIP, "hipEventCreate failed");
-            }
-        }
-    }
+    for (auto& launch : a->ev)
+        for (hipEvent_t& ev : launch)
+            if (hipEventCreate(&ev) != hipSuccess) { delete a; return fail(BGR_E_HIP, "hipEventCreate failed"); }
     if (a->blocking_sync && hipEventCreateWithFlags(&a->ev_wait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) a->blocking_sync = false;
     bgr::resolve_device_graph(&g->header, g->dev[device].ptr, a->dg);
-    e = a->small.ensure(bgr::kSmallBytes);
-    if (e == hipSuccess) e = hipMemset(a->small.p, 0, a->small.cap);
+    e = a->launch.small.ensure(bgr::kSmallBytes);
+    if (e == hipSuccess) e = hipMemset(a->launch.small.p, 0, a->launch.small.cap);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the fill runs on the null stream, which the aligner's non-blocking stream does not wait for)
     if (e != hipSuccess) { delete a; return fail(BGR_E_HIP, hipGetErrorString(e)); }
     *out = a;
@@ -427,9 +423,8 @@ void bgr_aligner_destroy(bgr_aligner* a) {
     if (a->twin) { bgr_aligner_destroy(a->twin); a->twin = nullptr; }
     if (hipSetDevice(a->device) == hipSuccess) {
         if (a->stream) (void)hipStreamSynchronize(a->stream);
-        a->in_reads.release(); a->in_offs.release(); a->pk_fw3.release(); a->pk_nm.release(); a->pk_hasn.release(); a->results.release(); a->arena.release(); a->ovf.release(); a->ovf2.release(); a->lst.release(); a->deepbuf.release(); a->retry.release(); a->retry2.release(); a->small.release();
-        a->csr_sums.release(); a->csr_poffs.release(); a->csr_status.release(); a->csr_paths.release(); a->wave_times.release(); a->abundance.release(); a->links.buf.release(); a->triples.buf.release(); a->pileup.release(); a->pileup_offs.release(); a->pileup_fwd.release(); a->var_scratch.release(); a->var_out.release(); a->var_stage.release();
-        a->text.release(); a->path_stats.release(); a->path_diffs.release(); a->haplotag.release(); a->haplotag_out.release();
+        a->launch.release(); a->fetch.release(); a->text.release(); a->tag.release(); a->var.release(); a->abundance.release();
+        if (!a->is_twin) a->sh->release();   // (the tables every stream added to: the twins' streams are gone)
         for (int i = 0; i < kTimerRing; ++i) for (int j = 0; j <= kTimerSlots; ++j) (void)hipEventDestroy(a->ev[i][j]);
         if (a->ev_wait) (void)hipEventDestroy(a->ev_wait);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -439,31 +434,44 @@ void bgr_aligner_destroy(bgr_aligner* a) {
 
 int bgr_aligner_configure(bgr_aligner* a, uint32_t waves_per_block, uint32_t blocks_per_cu, uint32_t lds_mphf) {
     if (!a || waves_per_block > 16 || lds_mphf > 2) return fail(BGR_E_ARG, "bgr_aligner_configure: bad argument");
-    a->cfg_waves = waves_per_block;
-    a->cfg_blocks_per_cu = blocks_per_cu;
-    a->cfg_lds_mphf = lds_mphf;
+    a->sh->cfg_waves = waves_per_block;
+    a->sh->cfg_blocks_per_cu = blocks_per_cu;
+    a->sh->cfg_lds_mphf = lds_mphf;
     return BGR_OK;
 }
 
+// The knobs: where each is kept and what becomes of a value beyond its limit -- refused, the limit instead, or its bits under the limit (the knobs
+// without a limit of their own keep 32 bits); `inverted`: kept as "off"
+enum class Over { kReject, kClamp, kMask };
+struct KnobRule { uint32_t id; uint64_t limit; Over over; uint64_t AlignerShared::*dst; bool inverted; };
+static const KnobRule kKnobs[] = {
+    {BGR_KNOB_EXH_FRAME_CAP, 1u << 20, Over::kClamp, &AlignerShared::knob_frame_cap, false},
+    {BGR_KNOB_EXH_SEARCH, 2, Over::kReject, &AlignerShared::knob_search, false},
+    {BGR_KNOB_BATCH_SPLIT_LIMIT, ~0ull, Over::kMask, &AlignerShared::knob_split_limit, false},
+    {BGR_KNOB_DEBUG_STOP, 0xFFFFFFFFull, Over::kMask, &AlignerShared::knob_debug_stop, false},
+    {BGR_KNOB_BATCH_OVERLAP, 0xFFFFFFFFull, Over::kMask, &AlignerShared::knob_overlap, false},
+    {BGR_KNOB_DEVICE_OVERLAP, 0xFFFFFFFFull, Over::kMask, &AlignerShared::knob_device_overlap, false},
+    {BGR_KNOB_GREEDY_FAST, 1, Over::kReject, &AlignerShared::knob_greedy_fast, false},
+    {BGR_KNOB_EXH_FAST, 1, Over::kReject, &AlignerShared::knob_exh_fast, false},
+    {BGR_KNOB_ANCHORS_FAST, 1, Over::kReject, &AlignerShared::knob_anc_fast, false},
+    {BGR_KNOB_GREEDY_PREPASS, 1, Over::kReject, &AlignerShared::knob_prepass, false},
+    {BGR_KNOB_GREEDY_JUMP, 1, Over::kReject, &AlignerShared::knob_no_jump, false},
+    {BGR_KNOB_KERNEL_EVENTS, 1, Over::kReject, &AlignerShared::knob_no_events, true},
+    {BGR_KNOB_ABUNDANCE_FORM, 2, Over::kReject, &AlignerShared::knob_abundance_form, false},
+    {BGR_KNOB_LINKS_FORM, 2, Over::kReject, &AlignerShared::knob_links_form, false},
+    {BGR_KNOB_EXH_MEMO_CAP, 1u << 24, Over::kClamp, &AlignerShared::knob_memo_cap, false},
+};
+
 int bgr_aligner_set_knob(bgr_aligner* a, uint32_t knob, uint64_t value) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_set_knob: null aligner");
-    switch (knob) {
-        case BGR_KNOB_EXH_FRAME_CAP: a->knob_frame_cap = (uint32_t)std::min<uint64_t>(value, 1u << 20); return BGR_OK;
-        case BGR_KNOB_EXH_SEARCH: if (value > 2) break; a->knob_search = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_BATCH_SPLIT_LIMIT: a->knob_split_limit = value; return BGR_OK;
-        case BGR_KNOB_DEBUG_STOP: a->knob_debug_stop = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_BATCH_OVERLAP: a->knob_overlap = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_DEVICE_OVERLAP: a->knob_device_overlap = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_GREEDY_FAST: if (value > 1) break; a->knob_greedy_fast = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_EXH_FAST: if (value > 1) break; a->knob_exh_fast = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_ANCHORS_FAST: if (value > 1) break; a->knob_anc_fast = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_GREEDY_PREPASS: if (value > 1) break; a->knob_prepass = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_GREEDY_JUMP: if (value > 1) break; a->knob_no_jump = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_no_jump = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_KERNEL_EVENTS: if (value > 1) break; a->knob_no_events = value ? 0u : 1u; return BGR_OK;
-        case BGR_KNOB_ABUNDANCE_FORM: if (value > 2) break; a->knob_abundance_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_abundance_form = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_LINKS_FORM: if (value > 2) break; a->knob_links_form = (uint32_t)value; for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) tw->knob_links_form = (uint32_t)value; return BGR_OK;
-        case BGR_KNOB_EXH_MEMO_CAP: a->knob_memo_cap = (uint32_t)std::min<uint64_t>(value, 1u << 24); return BGR_OK;
-        default: break;
+    for (const KnobRule& r : kKnobs) {
+        if (r.id != knob) continue;
+        if (value > r.limit) {
+            if (r.over == Over::kReject) break;
+            value = r.over == Over::kClamp ? r.limit : value & r.limit;
+        }
+        a->sh->*r.dst = r.inverted ? (value ? 0u : 1u) : value;
+        return BGR_OK;
     }
     return fail(BGR_E_ARG, "bgr_aligner_set_knob: unknown knob or value out of range");
 }
@@ -478,9 +486,9 @@ static bgr::PlanGraph plan_graph_of(const BgrBlobHeader& h) {
 }
 static bgr::PlanTuning plan_tuning_of(const bgr_aligner* a) {
     bgr::PlanTuning t;
-    t.cfg_waves = a->cfg_waves; t.cfg_blocks_per_cu = a->cfg_blocks_per_cu; t.cfg_lds_mphf = a->cfg_lds_mphf;
-    t.frame_cap = a->knob_frame_cap; t.search = a->knob_search; t.memo_cap = a->knob_memo_cap;
-    t.no_greedy_fast = a->knob_greedy_fast != 0; t.no_exh_fast = a->knob_exh_fast != 0; t.no_anc_fast = a->knob_anc_fast != 0;
+    t.cfg_waves = a->sh->cfg_waves; t.cfg_blocks_per_cu = a->sh->cfg_blocks_per_cu; t.cfg_lds_mphf = a->sh->cfg_lds_mphf;
+    t.frame_cap = a->sh->knob_frame_cap; t.search = a->sh->knob_search; t.memo_cap = a->sh->knob_memo_cap;
+    t.no_greedy_fast = a->sh->knob_greedy_fast != 0; t.no_exh_fast = a->sh->knob_exh_fast != 0; t.no_anc_fast = a->sh->knob_anc_fast != 0;
     return t;
 }
 
@@ -528,10 +536,10 @@ extern "C" int bgr_plan_launch(const bgr_plan_input* in, bgr_plan_output* out) {
 // The buffer of each list of reads a pass leaves to a later one (bgr::List; greedy mode keeps the follow-up items' rings in `ovf`)
 static DevBuf* list_buf(bgr_aligner* a, bgr::List l) {
     switch (l) {
-        case bgr::List::kSearch: return &a->ovf;
-        case bgr::List::kDepthFirst: case bgr::List::kGeneral: return &a->ovf2;
-        case bgr::List::kFirst: return &a->lst;
-        case bgr::List::kRetry: return &a->retry;
+        case bgr::List::kSearch: return &a->launch.ovf;
+        case bgr::List::kDepthFirst: case bgr::List::kGeneral: return &a->launch.ovf2;
+        case bgr::List::kFirst: return &a->launch.lst;
+        case bgr::List::kRetry: return &a->launch.retry;
         default: return nullptr;
     }
 }
@@ -548,86 +556,120 @@ struct LaunchMarks {
     }
 };
 
-// The counting kernels over the rows that (a->results, a->arena) hold, each only if its feature is enabled, queued on the aligner's stream: behind
-// the passes of a mapping launch, and -- option test.count_with_path_stats -- behind the kernel of bgr_aligner_path_stats over whatever rows the
-// buffers hold then.  mark(name): the launch's timer slot behind each kernel.
-static int queue_counting(bgr_aligner* a, uint64_t arena_cap, const uint64_t* read_offs, uint64_t n_reads, uint64_t total_bases, const bgr::PileupReads& pr, LaunchMarks& mark) {
-    hipError_t e = hipSuccess;
-    // Unitig abundance (bgr_aligner_abundance_enable): one kernel behind the last pass adds this launch's rows to the aligner's table.  Every route
-    // comes through here once per batch (a fetch into larger buffers after BGR_E_CAPACITY launches nothing), so nothing is counted twice.
-    // (The kernel is queued before anybody knows how the launch ends: one that fails later -- an arena overflow, found when its cursors are read -- has
-    // added the rows it did write.  include/bgreat_gpu.h says so: after a failed launch the table is undefined until bgr_aligner_reset_abundance.)
-    if (a->abundance_on) {
-        const uint64_t nu = a->graph->header.n_unitigs;
-        const bgr::AbundancePlan ap = abundance_plan_of(a, n_reads, total_bases);
-        e = bgr::launch_abundance(a->dg, nu, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, read_offs, (uint32_t)n_reads,
-                                  static_cast<unsigned long long*>(a->abundance.p), ap, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_abundance_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_abundance_kernel"));
-    }
-    // Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
-    if (a->links.on) {
-        const bgr::LinksPlan lp = bgr::plan_links(a->links.bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
-        e = bgr::launch_links(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->links.tab,
-                              a->links.cap, lp, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_links_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_links_kernel"));
-    }
-    // Triples (bgr_aligner_triples_enable): likewise one kernel that adds every three consecutive ids of this launch's rows to the aligner's hash table.
-    if (a->triples.on) {
-        e = bgr::launch_triples(a->graph->header.n_unitigs, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), arena_cap, (uint32_t)n_reads, a->triples.tab,
-                                a->triples.cap, (uint32_t)a->num_cus, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_triples_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_triples_kernel"));
-    }
-    // Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches, the read characters from `pr`.
-    if (a->pileup_on) {
-        e = bgr::launch_pileup(a->dg, a->graph->header.n_unitigs, a->graph->header.total_bases / 2, static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p),
-                               arena_cap, read_offs, (uint32_t)n_reads, pr, a->pileup_base_offs, a->pileup_tab, a->strands_on ? a->pileup_fwd_tab : nullptr, (uint32_t)a->num_cus, a->stream);
-        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_pileup_kernel): ") + hipGetErrorString(e));
-        HIP_TRY(mark("bgr_pileup_kernel"));
+// ---- the kernels behind the passes of a launch --------------------------------------------------------------------------------------------
+// What each of them is handed (and queues on a->stream): the rows in a->launch.results / arena, the reads they were mapped from, and the launch's own arena and budget
+struct BehindPasses {
+    bgr_aligner* a;
+    uint64_t arena_cap;
+    const uint64_t* read_offs;
+    uint64_t n_reads, total_bases;
+    bgr::PileupReads reads;      // the read characters where this launch has them
+    uint32_t arena_own = 0, max_read_len = 0, max_mismatch = 0;   // (the inside pass)
+    const uint2* rows() const { return a->launch.results.as<uint2>(); }
+    const int32_t* arena() const { return a->launch.arena.as<int32_t>(); }
+};
+// The inside pass (bgr_aligner_inside_enable) over the reads the passes left without an anchor
+static hipError_t inside_launch(const BehindPasses& c) {
+    bgr_aligner* a = c.a;
+    bgr::InsideLaunch il{a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), a->launch.small.as<uint32_t>(), (uint32_t)c.arena_cap, c.arena_own, c.read_offs, (uint32_t)c.n_reads,
+                         c.max_read_len, c.max_mismatch, c.reads};
+    return bgr::launch_inside(a->dg, a->sh->inside_tab, a->sh->inside_slots, il, reinterpret_cast<unsigned long long*>(a->launch.small.as<char>() + bgr::kSmallInside), (uint32_t)a->num_cus, a->stream);
+}
+// Unitig abundance (bgr_aligner_abundance_enable): one kernel behind the last pass adds this launch's rows to the aligner's table.  Every route
+// comes through here once per batch (a fetch into larger buffers after BGR_E_CAPACITY launches nothing), so nothing is counted twice.
+// (The kernel is queued before anybody knows how the launch ends: one that fails later -- an arena overflow, found when its cursors are read -- has
+// added the rows it did write.  include/bgreat_gpu.h says so: after a failed launch the table is undefined until bgr_aligner_reset_abundance.)
+static hipError_t abundance_launch(const BehindPasses& c) {
+    return bgr::launch_abundance(c.a->dg, c.a->graph->header.n_unitigs, c.rows(), c.arena(), c.arena_cap, c.read_offs, (uint32_t)c.n_reads, c.a->abundance.as<unsigned long long>(),
+                                 abundance_plan_of(c.a, c.n_reads, c.total_bases), c.a->stream);
+}
+// Links (bgr_aligner_links_enable): likewise one kernel that adds the consecutive pairs of this launch's rows to the aligner's hash table.
+static hipError_t links_launch(const BehindPasses& c) {
+    const CountTable& t = c.a->sh->links;
+    const bgr::LinksPlan lp = bgr::plan_links(t.bound, c.n_reads, (uint32_t)c.a->num_cus, (uint32_t)c.a->sh->knob_links_form);
+    return bgr::launch_links(c.a->graph->header.n_unitigs, c.rows(), c.arena(), c.arena_cap, (uint32_t)c.n_reads, t.tab, t.cap, lp, c.a->stream);
+}
+// Triples (bgr_aligner_triples_enable): likewise one kernel that adds every three consecutive ids of this launch's rows to the aligner's hash table.
+static hipError_t triples_launch(const BehindPasses& c) {
+    const CountTable& t = c.a->sh->triples;
+    return bgr::launch_triples(c.a->graph->header.n_unitigs, c.rows(), c.arena(), c.arena_cap, (uint32_t)c.n_reads, t.tab, t.cap, (uint32_t)c.a->num_cus, c.a->stream);
+}
+// Pileup (bgr_aligner_pileup_enable): likewise one kernel that adds per-base depth and mismatches, the read characters from `reads`.
+static hipError_t pileup_launch(const BehindPasses& c) {
+    const PileupTables& t = c.a->sh->pileup;
+    const BgrBlobHeader& h = c.a->graph->header;
+    return bgr::launch_pileup(c.a->dg, h.n_unitigs, h.total_bases / 2, c.rows(), c.arena(), c.arena_cap, c.read_offs, (uint32_t)c.n_reads, c.reads, t.base_offs, t.tab,
+                              t.strands_on ? t.fwd_tab : nullptr, (uint32_t)c.a->num_cus, c.a->stream);
+}
+// One entry per feature, in stream order.  what: the words of its refusal of an exhaustive launch; kernel: its timer slot (bgr_aligner_kernel_times)
+// and its name in the message of a failed launch; writes_rows: it is part of the mapping -- not run over rows that are kept
+struct LaunchFeature {
+    bool (*on)(const AlignerShared&);
+    const char *what, *kernel;
+    hipError_t (*launch)(const BehindPasses&);
+    bool writes_rows;
+};
+static const LaunchFeature kBehindPasses[] = {
+    {[](const AlignerShared& s) { return s.inside_tab != nullptr; }, "runs the inside pass (bgr_aligner_inside_enable), which writes rows", "bgr_align_inside_kernel", inside_launch, true},
+    {[](const AlignerShared& s) { return s.abundance_on; }, "counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows", "bgr_abundance_kernel", abundance_launch, false},
+    {[](const AlignerShared& s) { return s.links.on; }, "counts links (bgr_aligner_links_enable), which are defined on the rows", "bgr_links_kernel", links_launch, false},
+    {[](const AlignerShared& s) { return s.triples.on; }, "counts triples (bgr_aligner_triples_enable), which are defined on the rows", "bgr_triples_kernel", triples_launch, false},
+    {[](const AlignerShared& s) { return s.pileup.on; }, "counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows", "bgr_pileup_kernel", pileup_launch, false},
+};
+// The kernels of the enabled features, queued on the aligner's stream: behind the passes of a mapping launch, and -- option test.count_with_path_stats --
+// behind bgr_aligner_path_stats' kernel over whatever rows the buffers hold then (rows_kept, as under option test.keep_rows: the counting kernels alone)
+static int queue_behind_passes(const BehindPasses& c, bool rows_kept, LaunchMarks& mark) {
+    for (const LaunchFeature& f : kBehindPasses) {
+        if (!f.on(*c.a->sh) || (f.writes_rows && rows_kept)) continue;
+        const hipError_t e = f.launch(c);
+        if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (") + f.kernel + "): " + hipGetErrorString(e));
+        HIP_TRY(mark(f.kernel));
     }
     return BGR_OK;
 }
 
-// The mapping launch of one batch: the passes come from plan_launch (launch_plan.h, a pure function of numbers), this function sizes the
-// buffers and enqueues.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
-// (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
-// d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
-int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
-                             uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
-                             bool cursor_is_zero = false) {
+// ---- the mapping launch of one batch, in stages ---------------------------------------------------------------------------------------------
+// The passes come from plan_launch (launch_plan.h, a pure function of numbers); the stages check, size the buffers and enqueue.
+struct LaunchJob {
+    bgr_aligner* a;
+    const bgr_params* p;
+    const void *d_reads, *d_read_offsets;
+    uint64_t n_reads, total_bases;
+    uint32_t max_read_len;
+    bool planes_ready;
+    const void* d_src_off;
+    uint64_t reads_bytes;
+    // what launch_size adds: the plan, what every pass shares, the graph as the passes see it
+    bgr::LaunchPlan P;
+    bool keep_rows = false, inline_pack = false;
+    bgr::BatchIO io{};
+    bgr::KernelParams kp{};
+    BgrDeviceGraph dg;
+};
+
+// What a launch is refused for before anything of the aligner changes
+static int launch_refusal(const bgr_aligner* a, const bgr_params* p, uint64_t n_reads, uint32_t max_read_len) {
     if (!a || !p) return fail(BGR_E_ARG, "bgr_align_device: null argument");
     if (p->mode > BGR_MODE_ANCHORS) return fail(BGR_E_ARG, "bgr_align_device: unknown mode");
     if (p->mode == BGR_MODE_ANCHORS && !a->graph->header.anc_n)
         return fail(BGR_E_ARG, "bgr_align_device: BGR_MODE_ANCHORS needs a graph built with BGR_BUILD_ANCHORS");
     if (p->mode != BGR_MODE_GREEDY && a->graph->header.wide_keys)
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
-    if (a->abundance_on && p->mode == BGR_MODE_EXHAUSTIVE)
-        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts unitig abundance (bgr_aligner_abundance_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->links.on && p->mode == BGR_MODE_EXHAUSTIVE)
-        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts links (bgr_aligner_links_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->triples.on && p->mode == BGR_MODE_EXHAUSTIVE)
-        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts triples (bgr_aligner_triples_enable), which are defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->pileup_on && p->mode == BGR_MODE_EXHAUSTIVE)
-        return fail(BGR_E_ARG, "bgr_align_device: this aligner counts a pileup (bgr_aligner_pileup_enable), which is defined on the rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->inside_tab && p->mode == BGR_MODE_EXHAUSTIVE)
-        return fail(BGR_E_ARG, "bgr_align_device: this aligner runs the inside pass (bgr_aligner_inside_enable), which writes rows of the greedy modes; exhaustive mode (-b) is refused");
-    if (a->inside_tab && n_reads && max_read_len > bgr::kInsideMaxReadLen)
+    for (const bool writes_rows : {false, true})   // (the counting features first, then the pass that writes rows: the order the refusals have always had)
+        for (const LaunchFeature& f : kBehindPasses)
+            if (f.writes_rows == writes_rows && p->mode == BGR_MODE_EXHAUSTIVE && f.on(*a->sh))
+                return fail(BGR_E_ARG, std::string("bgr_align_device: this aligner ") + f.what + " of the greedy modes; exhaustive mode (-b) is refused");
+    if (a->sh->inside_tab && n_reads && max_read_len > bgr::kInsideMaxReadLen)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner runs the inside pass (bgr_aligner_inside_enable), which takes reads of at most 32 000 characters");
-    a->holder = nullptr;   // (a launch on the aligner's own stream and buffers; bgr_align_device names the twin behind this call when that took it)
-    a->last_n = n_reads;
-    a->last_mode = p->mode;
-    a->deep.open = false;
-    a->deep.runs = 0; a->deep.memo_cap = 0;
-    if (n_reads == 0) return BGR_OK;
-    if ((!d_reads && !planes_ready) || !d_read_offsets) return fail(BGR_E_ARG, "bgr_align_device: null device buffer");
-    if (n_reads >= 0xFFFFFFFFull) return fail(BGR_E_ARG, "bgr_align_device: more than 2^32-2 reads in one batch");
-    HIP_TRY(hipSetDevice(a->device));
-    if (a->ev_used == kTimerRing) { int rc = drain_timers(a); if (rc != BGR_OK) return rc; }
-    HIP_TRY(a->results.ensure(n_reads * 8));
+    return BGR_OK;
+}
 
-    // ---- launch geometry (launch_plan.h) ------------------------------------------------------------
+// The plan, the buffers it needs, and what every pass is handed (j.io, j.kp, j.dg)
+static int launch_size(LaunchJob& j) {
+    bgr_aligner* a = j.a;
+    const bgr_params* p = j.p;
+    const uint64_t n_reads = j.n_reads;
+    HIP_TRY(a->launch.results.ensure(n_reads * 8));
     if (!a->plan_dev_known) {
         a->plan_dev.num_cus = (uint32_t)a->num_cus;
         a->plan_dev.lds_per_cu = a->lds_per_cu;
@@ -635,25 +677,26 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
         a->plan_dev_known = true;
     }
     bgr::PlanBatch pb;
-    pb.mode = p->mode; pb.max_mismatch = p->max_mismatch; pb.partial = p->partial; pb.max_read_len = max_read_len;
-    pb.n_reads = n_reads; pb.total_bases = total_bases;
-    pb.inside = a->inside_tab != nullptr;   // (2 more arena ints per read: the rows of the inside pass)
-    const bgr::LaunchPlan P = bgr::plan_launch(plan_graph_of(a->graph->header), a->plan_dev, plan_tuning_of(a), pb);
+    pb.mode = p->mode; pb.max_mismatch = p->max_mismatch; pb.partial = p->partial; pb.max_read_len = j.max_read_len;
+    pb.n_reads = n_reads; pb.total_bases = j.total_bases;
+    pb.inside = a->sh->inside_tab != nullptr;   // (2 more arena ints per read: the rows of the inside pass)
+    j.P = bgr::plan_launch(plan_graph_of(a->graph->header), a->plan_dev, plan_tuning_of(a), pb);
+    const bgr::LaunchPlan& P = j.P;
     if (P.error) return fail(BGR_E_ARG, P.error);
     const bgr::Pass& first = P.pass[0];
-    if (P.deep_scratch_bytes) HIP_TRY(a->deepbuf.ensure(P.deep_scratch_bytes));
-    // test hook (option test.keep_rows): everything of this launch but its mapping passes -- (a->results, a->arena) keep the rows a test wrote there behind
+    if (P.deep_scratch_bytes) HIP_TRY(a->launch.deepbuf.ensure(P.deep_scratch_bytes));
+    // test hook (option test.keep_rows): everything of this launch but its mapping passes -- (a->launch.results, a->launch.arena) keep the rows a test wrote there behind
     // a first launch of the same reads, and the counting kernels and the text call's format launches read those.  Only over buffers that launch sized.
-    const bool keep_rows = bgr::opt("test.keep_rows") != 0;
-    if (keep_rows && (a->sized_n != n_reads || a->last_arena_cap != P.arena_cap))
+    j.keep_rows = bgr::opt("test.keep_rows") != 0;
+    if (j.keep_rows && (a->sized_n != n_reads || a->last_arena_cap != P.arena_cap))
         return fail(BGR_E_ARG, "bgr_align_device: option test.keep_rows needs the launch before on this aligner to have had the same n_reads and the same arena");
-    HIP_TRY(a->arena.ensure(P.arena_cap * 4));
-    a->last_arena_cap = P.arena_cap; a->last_total_bases = total_bases;
+    HIP_TRY(a->launch.arena.ensure(P.arena_cap * 4));
+    a->last_arena_cap = P.arena_cap; a->last_total_bases = j.total_bases;
     a->sized_n = n_reads;
     for (uint32_t i = 0; i < P.n_passes; ++i) {  // the lists the passes leave each other, and the rings of follow-up items of the sixteen-reads-per-wave kernel
         const bgr::Pass& ps = P.pass[i];
         if (ps.appends != bgr::List::kNone) HIP_TRY(list_buf(a, ps.appends)->ensure(n_reads * 4));
-        if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(a->ovf.ensure((uint64_t)ps.cfg.blocks * ps.cfg.waves_per_block * P.q_cap * 8));
+        if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(a->launch.ovf.ensure((uint64_t)ps.cfg.blocks * ps.cfg.waves_per_block * P.q_cap * 8));
     }
     // (bgr_aligner_launch_info: the first pass; the level search ran unless every read went to the last pass)
     a->last_launch[0] = first.cfg.blocks; a->last_launch[1] = first.cfg.waves_per_block * 64; a->last_launch[2] = first.cfg.lds_bytes;
@@ -666,75 +709,64 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
     // mode keeps the pre-pass: its four-reads-per-wave kernel -- BooPHF arithmetic at 96 VGPRs -- lost more inside than the pre-pass cost: 934 vs 965-1 000 Mreads/s)
     // ... and so do launches without a several-reads-per-wave pass (-i, budgets beyond 254, exception planes, the knobs): the one-read-per-wave kernels alone are
     // faster from planes (depth-first 11.8 vs 12.8 ms per 5 M reads, level search 14.0 vs 14.3 per 2 M)
-    const bool inline_pack = (first.kernel == bgr::KernelId::kGreedyMulti || first.kernel == bgr::KernelId::kExhaustive4) && !planes_ready && d_reads && !a->knob_prepass;
-    if (!reads_bytes) reads_bytes = total_bases;  // (reads end to end: the buffer holds exactly their bases)
-    if (!inline_pack) {
-        HIP_TRY(a->pk_fw3.ensure(P.plane_words * 8));
-        HIP_TRY(a->pk_nm.ensure(P.plane_words * 8));
-        HIP_TRY(a->pk_hasn.ensure((n_reads + 31) / 32 * 4 + 4));
+    j.inline_pack = (first.kernel == bgr::KernelId::kGreedyMulti || first.kernel == bgr::KernelId::kExhaustive4) && !j.planes_ready && j.d_reads && !a->sh->knob_prepass;
+    if (!j.reads_bytes) j.reads_bytes = j.total_bases;  // (reads end to end: the buffer holds exactly their bases)
+    if (!j.inline_pack) {
+        HIP_TRY(a->launch.pk_fw3.ensure(P.plane_words * 8));
+        HIP_TRY(a->launch.pk_nm.ensure(P.plane_words * 8));
+        HIP_TRY(a->launch.pk_hasn.ensure((n_reads + 31) / 32 * 4 + 4));
     }
-    bgr::BatchIO io{};  // what every pass shares; the loop below sets the rest
-    io.ascii = inline_pack ? static_cast<const uint8_t*>(d_reads) : nullptr;
-    io.ascii_src = inline_pack ? static_cast<const uint32_t*>(d_src_off) : nullptr;
-    io.ascii_bytes = reads_bytes;
-    io.fw3 = static_cast<const uint64_t*>(a->pk_fw3.p);
-    io.nmw = static_cast<const uint64_t*>(a->pk_nm.p);
-    io.hasn = static_cast<const uint32_t*>(a->pk_hasn.p);
-    io.read_offs = static_cast<const uint64_t*>(d_read_offsets);
-    io.results = static_cast<uint2*>(a->results.p);
-    io.arena = static_cast<int32_t*>(a->arena.p);
-    io.cursor = static_cast<uint32_t*>(a->small.p);
+    bgr::BatchIO& io = j.io;  // (the loop over the passes sets the rest)
+    io.ascii = j.inline_pack ? static_cast<const uint8_t*>(j.d_reads) : nullptr;
+    io.ascii_src = j.inline_pack ? static_cast<const uint32_t*>(j.d_src_off) : nullptr;
+    io.ascii_bytes = j.reads_bytes;
+    io.fw3 = a->launch.pk_fw3.as<uint64_t>(); io.nmw = a->launch.pk_nm.as<uint64_t>(); io.hasn = a->launch.pk_hasn.as<uint32_t>();
+    io.read_offs = static_cast<const uint64_t*>(j.d_read_offsets);
     io.n_reads = (uint32_t)n_reads;
-    io.path_cap = P.path_cap;
-    io.arena_cap = (uint32_t)P.arena_cap;
-    io.arena_chunk = P.arena_chunk;
+    io.results = a->launch.results.as<uint2>(); io.arena = a->launch.arena.as<int32_t>(); io.cursor = a->launch.small.as<uint32_t>();
+    io.path_cap = P.path_cap; io.arena_cap = (uint32_t)P.arena_cap; io.arena_chunk = P.arena_chunk;
     io.arena_own = (uint32_t)P.arena_own;  // (< 2^32: plan_launch refuses a launch whose arena is larger)
-    io.deep_stride = (uint32_t)P.deep_stride;
-    io.deep_memo_cap = P.memo_cap;
-    io.search_iters = P.search_iters;
-    io.wide_scan = P.wide_scan ? 1u : 0u;
-    io.task_ctr = bgr::kCurTasks;
-    bgr::KernelParams kp = {p->max_mismatch, p->effort, p->partial, p->mode, a->knob_debug_stop};
+    io.deep_stride = (uint32_t)P.deep_stride; io.deep_memo_cap = P.memo_cap;
+    io.search_iters = P.search_iters; io.wide_scan = P.wide_scan ? 1u : 0u; io.task_ctr = bgr::kCurTasks;
+    j.kp = {p->max_mismatch, p->effort, p->partial, p->mode, (uint32_t)a->sh->knob_debug_stop};
     // the filter in front of a large key table pays where many read positions are probed per anchor (greedy scans: chr1-scale graph
     // 1 020 -> 1 184 Mreads/s, L2 requests per read 135 -> 28).  The exhaustive scan meets its first hit within a few positions; with
     // fingerprints behind it the filter cost it more than it saved (4-allele graph: 697 without, 664 with), with the bucket's keys compared
     // directly behind it, it pays there too (4-allele graph 702 -> 720, chr1-scale graph 1 111 -> 1 231): on by default for the minimizer
     // kind (option exh_filter = 0: without); the one-hash kind of short k stays off in exhaustive mode
-    BgrDeviceGraph dgl = a->dg;
-    if (p->mode == BGR_MODE_EXHAUSTIVE && !(dgl.filter_kind == BGR_FILTER_MINIMIZER && a->exh_filter)) dgl.bloom = nullptr;
+    j.dg = a->dg;
+    if (p->mode == BGR_MODE_EXHAUSTIVE && !(j.dg.filter_kind == BGR_FILTER_MINIMIZER && a->sh->exh_filter)) j.dg.bloom = nullptr;
+    return BGR_OK;
+}
 
-    // the cursor block: arena cursor, overflow flag, list counts (the text form: the parse launch cleared it)
-    if (!cursor_is_zero) HIP_TRY(hipMemsetAsync(a->small.p, 0, bgr::kCurWords * 4, a->stream));
-    // HIP events on the aligner's stream: one in front of the launch, one behind every kernel of it (bgr_aligner_kernel_times)
-    // (timing a kernel is not free: the events make the runtime dispatch with completion stamps and keep the kernels of a launch apart -- three events around two
-    // kernels cost a 262 144-read launch 16 of its 167 us, 1 730 -> 1 560 Mreads/s, and stamps taken by the dispatch packets themselves (hipExtLaunchKernelGGL)
-    // cost the same, profiles/r05_mode_by_batch_size.txt; BGR_KNOB_KERNEL_EVENTS 0: none -- bgr_align_all without its timing option)
-    const bool timed = !a->knob_no_events;
-    LaunchMarks mark{a, timed};
-    if (timed) HIP_TRY(hipEventRecord(a->ev[a->ev_used][0], a->stream));
+// The pre-pass, where the launch needs the 2-bit planes made, and the passes, back to back on the stream.  A pass behind a list maps what an earlier
+// pass listed; with an empty list its waves exit at once (no host round trip in between).  The sixteen-reads-per-wave kernel works off the follow-up
+// items of its reads (the next anchors of a read whose first ones failed, then its reverse complement: alignerGreedy.cpp:41-56) in its own per-wave
+// queues, inside the launch.
+static int launch_passes(const LaunchJob& j, LaunchMarks& mark) {
+    bgr_aligner* a = j.a;
+    const bgr::LaunchPlan& P = j.P;
     hipError_t e = hipSuccess;
-    if (!planes_ready && !inline_pack) {
-        HIP_TRY(hipMemsetAsync(a->pk_hasn.p, 0, (n_reads + 31) / 32 * 4, a->stream));
-        e = d_src_off ? bgr::launch_pack_reads_at(static_cast<const uint8_t*>(d_reads), static_cast<const uint32_t*>(d_src_off), io.read_offs, io.n_reads, reads_bytes, total_bases,
-                                                  static_cast<uint64_t*>(a->pk_fw3.p), static_cast<uint64_t*>(a->pk_nm.p), static_cast<uint32_t*>(a->pk_hasn.p), a->stream)
-                      : bgr::launch_pack_reads(static_cast<const uint8_t*>(d_reads), io.read_offs, io.n_reads, total_bases, static_cast<uint64_t*>(a->pk_fw3.p),
-                                               static_cast<uint64_t*>(a->pk_nm.p), static_cast<uint32_t*>(a->pk_hasn.p), a->stream);
+    if (!j.planes_ready && !j.inline_pack) {
+        HIP_TRY(hipMemsetAsync(a->launch.pk_hasn.p, 0, (j.n_reads + 31) / 32 * 4, a->stream));
+        const uint8_t* reads = static_cast<const uint8_t*>(j.d_reads);
+        uint64_t *fw3 = a->launch.pk_fw3.as<uint64_t>(), *nmw = a->launch.pk_nm.as<uint64_t>();
+        uint32_t* hasn = a->launch.pk_hasn.as<uint32_t>();
+        e = j.d_src_off ? bgr::launch_pack_reads_at(reads, static_cast<const uint32_t*>(j.d_src_off), j.io.read_offs, j.io.n_reads, j.reads_bytes, j.total_bases, fw3, nmw, hasn, a->stream)
+                        : bgr::launch_pack_reads(reads, j.io.read_offs, j.io.n_reads, j.total_bases, fw3, nmw, hasn, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("pre-pass launch: ") + hipGetErrorString(e));
         HIP_TRY(mark("bgr_pack_reads_kernel"));
     }
-    // The passes, back to back on the stream.  A pass behind a list maps what an earlier pass listed; with an empty list its waves exit at once
-    // (no host round trip in between).  The sixteen-reads-per-wave kernel works off the follow-up items of its reads (the next anchors of a read whose
-    // first ones failed, then its reverse complement: alignerGreedy.cpp:41-56) in its own per-wave queues, inside the launch.
-    for (uint32_t i = 0; i < (keep_rows ? 0u : P.n_passes); ++i) {
+    for (uint32_t i = 0; i < (j.keep_rows ? 0u : P.n_passes); ++i) {
         const bgr::Pass& ps = P.pass[i];
-        bgr::BatchIO pio = io;
+        bgr::BatchIO pio = j.io;
         pio.words_per_read = ps.words;
         pio.frames_per_wave = ps.frames;
         pio.subset = ps.maps == bgr::List::kNone ? nullptr : static_cast<const uint32_t*>(list_buf(a, ps.maps)->p);
         pio.subset_ctr = bgr::list_word(ps.maps);
         uint32_t* appends = ps.appends == bgr::List::kNone ? nullptr : static_cast<uint32_t*>(list_buf(a, ps.appends)->p);
         if (ps.kernel == bgr::KernelId::kGreedyMulti) {
-            pio.queue = static_cast<uint2*>(a->ovf.p);
+            pio.queue = a->launch.ovf.as<uint2>();
             pio.q_cap = P.q_cap;
             pio.gen_list = appends;
             pio.gen_ctr = bgr::list_word(ps.appends);
@@ -742,49 +774,72 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
             pio.ovf_list = appends;
             pio.ovf_ctr = bgr::list_word(ps.appends);
         }
-        if (ps.kernel == bgr::KernelId::kExhaustiveLast) pio.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
+        if (ps.kernel == bgr::KernelId::kExhaustiveLast) pio.deep_scratch = a->launch.deepbuf.as<uint32_t>();
 #ifdef BGR_PHASE_TIMING
         if (ps.kernel == bgr::KernelId::kGreedyMulti || ps.kernel == bgr::KernelId::kExhaustive4) {  // time stamps per wave (the greedy kernel: then its scan counts)
             const uint64_t waves = (uint64_t)ps.cfg.blocks * ps.cfg.waves_per_block, bytes = waves * (ps.kernel == bgr::KernelId::kGreedyMulti ? 64 : 32);
-            HIP_TRY(a->wave_times.ensure(bytes));
-            if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(hipMemsetAsync(a->wave_times.p, 0, bytes, a->stream));  // (waves with no reads write nothing)
-            pio.wave_times = static_cast<unsigned long long*>(a->wave_times.p);
+            HIP_TRY(a->launch.wave_times.ensure(bytes));
+            if (ps.kernel == bgr::KernelId::kGreedyMulti) HIP_TRY(hipMemsetAsync(a->launch.wave_times.p, 0, bytes, a->stream));  // (waves with no reads write nothing)
+            pio.wave_times = a->launch.wave_times.as<unsigned long long>();
             a->wave_times_n = waves;
         }
 #endif
         // the staged sixteen-reads-per-wave greedy kernel jumps over verified unitig interiors when the graph has the index for it (graph_layout.h):
         // a flag says so, and the kernel finds the section through the blob's header (BgrDeviceGraph must not grow: the kernel is short of
         // SGPRs).  No other kernel is told.  BGR_KNOB_GREEDY_JUMP 1: not this one either.
-        BgrDeviceGraph dgp = dgl;
-        if (ps.kernel == bgr::KernelId::kGreedyMulti && ps.cfg.stage_mphf && a->graph->header.jump_buckets && !a->knob_no_jump) dgp.flags |= BGR_GF_JUMP;
-        e = bgr::launch_align(ps.kernel, ps.variant, dgp, pio, kp, ps.cfg, a->stream);
+        BgrDeviceGraph dgp = j.dg;
+        if (ps.kernel == bgr::KernelId::kGreedyMulti && ps.cfg.stage_mphf && a->graph->header.jump_buckets && !a->sh->knob_no_jump) dgp.flags |= BGR_GF_JUMP;
+        e = bgr::launch_align(ps.kernel, ps.variant, dgp, pio, j.kp, ps.cfg, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (") + ps.name + "): " + hipGetErrorString(e));
         HIP_TRY(mark(ps.name));
         if (ps.kernel == bgr::KernelId::kExhaustiveLast) {  // what settle_launch needs to run the last pass again for the reads it handed back
             a->deep.open = true;
-            a->deep.pass = ps; a->deep.io = pio; a->deep.kp = kp; a->deep.dg = dgl;
-            a->deep.per_wave_lds = bgr::deep_lds_bytes_per_wave(max_read_len);
+            a->deep.pass = ps; a->deep.io = pio; a->deep.kp = j.kp; a->deep.dg = j.dg;
+            a->deep.per_wave_lds = bgr::deep_lds_bytes_per_wave(j.max_read_len);
             a->deep.path_cap = P.path_cap; a->deep.memo_cap = P.memo_cap;
             a->deep.runs = 1;
         }
     }
-    // Behind the last pass: the inside pass (bgr_aligner_inside_enable) over the reads the passes left without an anchor, then the counting kernels -- in
-    // stream order in front of everything that reads the rows.  Both read the read characters where this launch has them: the ASCII bytes when the
-    // mapping kernels packed them themselves, else the 2-bit planes (host-packed, or made by the pre-pass).
-    {
-        bgr::PileupReads pr;
-        if (inline_pack) { pr.ascii = static_cast<const uint8_t*>(d_reads); pr.src_off = static_cast<const uint32_t*>(d_src_off); pr.ascii_bytes = reads_bytes; }
-        else { pr.fw3 = io.fw3; pr.nmw = io.nmw; pr.hasn = io.hasn; }
-        if (a->inside_tab && !keep_rows) {
-            bgr::InsideLaunch il{io.results, io.arena, io.cursor, io.arena_cap, io.arena_own, io.read_offs, io.n_reads, max_read_len, p->max_mismatch, pr};
-            e = bgr::launch_inside(a->dg, a->inside_tab, a->inside_slots, il, reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallInside),
-                                   (uint32_t)a->num_cus, a->stream);
-            if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_align_inside_kernel): ") + hipGetErrorString(e));
-            HIP_TRY(mark("bgr_align_inside_kernel"));
-        }
-        const int crc = queue_counting(a, P.arena_cap, io.read_offs, n_reads, total_bases, pr, mark);
-        if (crc != BGR_OK) return crc;
-    }
+    return BGR_OK;
+}
+
+// Behind the last pass: the inside pass, then the counting kernels (kBehindPasses) -- in stream order in front of everything that reads the rows -- with the
+// read characters where this launch has them: the ASCII bytes when the mapping kernels packed them themselves, else the 2-bit planes (host-packed or pre-pass)
+static int launch_behind_passes(const LaunchJob& j, LaunchMarks& mark) {
+    BehindPasses c{j.a, j.P.arena_cap, j.io.read_offs, j.n_reads, j.total_bases, {}, j.io.arena_own, j.max_read_len, j.p->max_mismatch};
+    if (j.inline_pack) { c.reads.ascii = static_cast<const uint8_t*>(j.d_reads); c.reads.src_off = static_cast<const uint32_t*>(j.d_src_off); c.reads.ascii_bytes = j.reads_bytes; }
+    else { c.reads.fw3 = j.io.fw3; c.reads.nmw = j.io.nmw; c.reads.hasn = j.io.hasn; }
+    return queue_behind_passes(c, j.keep_rows, mark);
+}
+
+// The mapping launch of one batch.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
+// (bgr_align_batch_packed copied them in); else they are made from the ASCII reads at d_reads by the pre-pass.
+// d_src_off (may be null): where each read's characters start in d_reads when they lie scattered in a text (text route); reads_bytes: bytes of d_reads.
+int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads,
+                             uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
+                             bool cursor_is_zero = false) {
+    if (const int rc = launch_refusal(a, p, n_reads, max_read_len); rc != BGR_OK) return rc;
+    a->holder = nullptr;   // (a launch on the aligner's own stream and buffers; bgr_align_device names the twin behind this call when that took it)
+    a->last_n = n_reads; a->last_mode = p->mode;
+    a->deep.open = false; a->deep.runs = 0; a->deep.memo_cap = 0;
+    if (n_reads == 0) return BGR_OK;
+    if ((!d_reads && !planes_ready) || !d_read_offsets) return fail(BGR_E_ARG, "bgr_align_device: null device buffer");
+    if (n_reads >= 0xFFFFFFFFull) return fail(BGR_E_ARG, "bgr_align_device: more than 2^32-2 reads in one batch");
+    HIP_TRY(hipSetDevice(a->device));
+    if (a->ev_used == kTimerRing) { int rc = drain_timers(a); if (rc != BGR_OK) return rc; }
+    LaunchJob j{a, p, d_reads, d_read_offsets, n_reads, total_bases, max_read_len, planes_ready, d_src_off, reads_bytes};
+    if (const int rc = launch_size(j); rc != BGR_OK) return rc;
+    // the cursor block: arena cursor, overflow flag, list counts (the text form: the parse launch cleared it)
+    if (!cursor_is_zero) HIP_TRY(hipMemsetAsync(a->launch.small.p, 0, bgr::kCurWords * 4, a->stream));
+    // HIP events on the aligner's stream: one in front of the launch, one behind every kernel of it (bgr_aligner_kernel_times)
+    // (timing a kernel is not free: the events make the runtime dispatch with completion stamps and keep the kernels of a launch apart -- three events around two
+    // kernels cost a 262 144-read launch 16 of its 167 us, 1 730 -> 1 560 Mreads/s, and stamps taken by the dispatch packets themselves (hipExtLaunchKernelGGL)
+    // cost the same, profiles/r05_mode_by_batch_size.txt; BGR_KNOB_KERNEL_EVENTS 0: none -- bgr_align_all without its timing option)
+    const bool timed = !a->sh->knob_no_events;
+    LaunchMarks mark{a, timed};
+    if (timed) HIP_TRY(hipEventRecord(a->ev[a->ev_used][0], a->stream));
+    if (const int rc = launch_passes(j, mark); rc != BGR_OK) return rc;
+    if (const int rc = launch_behind_passes(j, mark); rc != BGR_OK) return rc;
     if (timed) {
         a->ev_marks[a->ev_used] = mark.marks;
         ++a->ev_used;
@@ -810,34 +865,34 @@ int settle_launch(bgr_aligner* a, uint32_t* cur) {
         if (stride > 0xFFFFFFFFull) return fail(BGR_E_NOMEM, "exhaustive search: a read's table of remembered calls outgrew the 16 GiB a wave can address");
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t room = (uint64_t)free_b + a->deepbuf.cap;
+        const uint64_t room = (uint64_t)free_b + a->launch.deepbuf.cap;
         uint64_t waves = std::min<uint64_t>(n_retry, (uint64_t)D.pass.cfg.blocks * D.pass.cfg.waves_per_block);
         waves = std::min<uint64_t>(waves, std::max<uint64_t>(1, room / 2 / (stride * 4)));
         if (stride * 4 > room - room / 8) return fail(BGR_E_NOMEM, "exhaustive search: not enough device memory for a read's table of remembered calls");
-        HIP_TRY(a->deepbuf.ensure(waves * stride * 4));
+        HIP_TRY(a->launch.deepbuf.ensure(waves * stride * 4));
         // the list handed back becomes the list to map; the kernel appends to the other one
-        DevBuf& other = a->retry2;
+        DevBuf& other = a->launch.retry2;
         HIP_TRY(other.ensure((uint64_t)n_retry * 4));
         bgr::BatchIO io = D.io;
         io.subset = io.ovf_list;
         io.subset_ctr = bgr::kCurRetrySubset;
         io.ovf_list = static_cast<uint32_t*>(other.p);
         io.ovf_ctr = kRetry;
-        io.deep_scratch = static_cast<uint32_t*>(a->deepbuf.p);
+        io.deep_scratch = static_cast<uint32_t*>(a->launch.deepbuf.p);
         io.deep_stride = (uint32_t)stride;
         io.deep_memo_cap = D.memo_cap;
         uint32_t ctr[2] = {0, n_retry};  // the count of the list handed back = 0, the count of the list to map (kCurRetrySubset, the word behind it) = n
-        HIP_TRY(hipMemcpyAsync(static_cast<uint32_t*>(a->small.p) + kRetry, ctr, 8, hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(static_cast<uint32_t*>(a->launch.small.p) + kRetry, ctr, 8, hipMemcpyHostToDevice, a->stream));
         bgr::LaunchCfg cfg = D.pass.cfg;
         cfg.waves_per_block = (uint32_t)std::min<uint64_t>(cfg.waves_per_block, waves);
         cfg.blocks = (uint32_t)std::max<uint64_t>(1, waves / cfg.waves_per_block);
         cfg.lds_bytes = bgr::kLdsFixed + cfg.waves_per_block * D.per_wave_lds;
         hipError_t e = bgr::launch_align(D.pass.kernel, D.pass.variant, D.dg, io, D.kp, cfg, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (last pass, run again): ") + hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(cur, a->small.p, bgr::kCurWords * 4, hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipMemcpyAsync(cur, a->launch.small.p, bgr::kCurWords * 4, hipMemcpyDeviceToHost, a->stream));
         HIP_TRY(wait_stream(a));
         if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
-        std::swap(a->retry, a->retry2);  // (D.io.ovf_list names the list the next round maps)
+        std::swap(a->launch.retry, a->launch.retry2);  // (D.io.ovf_list names the list the next round maps)
         D.io.ovf_list = io.ovf_list;
         ++D.runs;
     }
@@ -848,33 +903,25 @@ int settle_launch(bgr_aligner* a, uint32_t* cur) {
 static int settle_launch_sync(bgr_aligner* a) {
     if (!a->deep.open) return BGR_OK;
     uint32_t cur[bgr::kCurWords];
-    HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(cur, a->launch.small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return settle_launch(a, cur);
 }
 
-// The aligner's first n_twins twins (a chain a -> twin -> twin's twin ...), created on first use, each with the aligner's configuration, knobs and
-// counting features as they stand now: its own abundance table (bgr_aligner_abundance sums them), the aligner's tables of links, triples and pileup.
+// The aligner's first n_twins twins (a chain a -> twin -> twin's twin ...), created on first use.  A twin reads the aligner's shared block (its
+// tuning, knobs, switches, the tables of links, triples and pileup); its abundance table is its own (bgr_aligner_abundance sums them).
 static int twins_setup(bgr_aligner* a, unsigned n_twins) {
     bgr_aligner* prev = a;
-    for (unsigned t = 0; t < n_twins; ++t) {
+    for (unsigned t = 0; t < n_twins; ++t, prev = prev->twin) {
         if (!prev->twin) {
-            int rc = bgr_aligner_create(a->graph, a->device, &prev->twin);
+            const int rc = bgr_aligner_create(a->graph, a->device, &prev->twin);
             if (rc != BGR_OK) return rc;
+            delete prev->twin->sh;
             prev->twin->is_twin = true;
+            prev->twin->sh = a->sh;
         }
-        bgr_aligner* tw = prev->twin;
-        tw->cfg_waves = a->cfg_waves; tw->cfg_blocks_per_cu = a->cfg_blocks_per_cu; tw->cfg_lds_mphf = a->cfg_lds_mphf;
-        tw->knob_frame_cap = a->knob_frame_cap; tw->knob_search = a->knob_search; tw->knob_debug_stop = a->knob_debug_stop;
-        tw->knob_greedy_fast = a->knob_greedy_fast; tw->knob_exh_fast = a->knob_exh_fast; tw->knob_anc_fast = a->knob_anc_fast; tw->knob_memo_cap = a->knob_memo_cap; tw->knob_prepass = a->knob_prepass; tw->knob_no_events = a->knob_no_events; tw->knob_no_jump = a->knob_no_jump;
-        tw->knob_abundance_form = a->knob_abundance_form;
-        tw->knob_links_form = a->knob_links_form;
-        tw->inside_tab = a->inside_tab; tw->inside_slots = a->inside_slots;
-        if (tw->abundance_on != a->abundance_on) { const int rc = abundance_set(tw, a->abundance_on); if (rc != BGR_OK) return rc; }
-        prev = tw;
+        if (a->sh->abundance_on) { const int rc = abundance_table(prev->twin); if (rc != BGR_OK) return rc; }   // (one per stream; nothing to do once it exists)
     }
-    pileup_share(a);   // (one pileup table, one table of links and one of triples for the aligner and its twins: the atomics are device-scope)
-    tables_share(a);
     return BGR_OK;
 }
 
@@ -894,7 +941,7 @@ int bgr_align_device(bgr_aligner* a, const bgr_params* p, const void* d_reads, c
                      uint64_t total_bases, uint32_t max_read_len) {
     if (!a || !p) return fail(BGR_E_ARG, "bgr_align_device: null argument");
     bgr_aligner* taker = a;
-    if (!a->is_twin && !a->knob_device_overlap && p->mode != BGR_MODE_EXHAUSTIVE && n_reads) {
+    if (!a->is_twin && !a->sh->knob_device_overlap && p->mode != BGR_MODE_EXHAUSTIVE && n_reads) {
         HIP_TRY(hipSetDevice(a->device));
         bool primary_idle = true, twin_idle = true;
         int rc = stream_idle(a, &primary_idle);
@@ -952,21 +999,21 @@ int bgr_align_batch_packed(bgr_aligner* a, const bgr_params* p, const bgr_packed
         return fail(BGR_E_ARG, "bgr_align_batch_packed: batch too large for one launch (2*(bases + 16*reads) must stay below 2^32 - 2^28); pack it in pieces");
     HIP_TRY(hipSetDevice(a->device));
     const uint64_t plane_words = bgr::packed_plane_words(n, total);
-    HIP_TRY(a->in_offs.ensure((n + 1) * 8));
-    HIP_TRY(a->pk_fw3.ensure(plane_words * 8));
-    HIP_TRY(a->pk_nm.ensure(plane_words * 8));
-    HIP_TRY(a->pk_hasn.ensure((n + 31) / 32 * 4 + 4));
-    HIP_TRY(hipMemcpyAsync(a->in_offs.p, pk->read_offsets, (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-    HIP_TRY(hipMemcpyAsync(a->pk_fw3.p, pk->fw3, ((total >> 5) + n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-    HIP_TRY(hipMemcpyAsync(a->pk_hasn.p, pk->hasn, (n + 31) / 32 * 4, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(a->launch.in_offs.ensure((n + 1) * 8));
+    HIP_TRY(a->launch.pk_fw3.ensure(plane_words * 8));
+    HIP_TRY(a->launch.pk_nm.ensure(plane_words * 8));
+    HIP_TRY(a->launch.pk_hasn.ensure((n + 31) / 32 * 4 + 4));
+    HIP_TRY(hipMemcpyAsync(a->launch.in_offs.p, pk->read_offsets, (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipMemcpyAsync(a->launch.pk_fw3.p, pk->fw3, ((total >> 5) + n + 1) * 8, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipMemcpyAsync(a->launch.pk_hasn.p, pk->hasn, (n + 31) / 32 * 4, hipMemcpyHostToDevice, a->stream));
     if (pk->nm_count) {  // the N-mask words of the few reads that hold an N: a sparse list, scattered into the plane on the device
         const uint64_t voff = (pk->nm_count * 4 + 7) & ~7ull;  // indices, then the values 8-byte aligned, in the ASCII staging buffer (unused here)
-        HIP_TRY(a->in_reads.ensure(voff + pk->nm_count * 8));
-        char* d = static_cast<char*>(a->in_reads.p);
+        HIP_TRY(a->launch.in_reads.ensure(voff + pk->nm_count * 8));
+        char* d = static_cast<char*>(a->launch.in_reads.p);
         HIP_TRY(hipMemcpyAsync(d, pk->nm_index, pk->nm_count * 4, hipMemcpyHostToDevice, a->stream));
         HIP_TRY(hipMemcpyAsync(d + voff, pk->nm_value, pk->nm_count * 8, hipMemcpyHostToDevice, a->stream));
         hipError_t e = bgr::launch_scatter_words(reinterpret_cast<const uint32_t*>(d), reinterpret_cast<const uint64_t*>(d + voff), pk->nm_count,
-                                                 static_cast<uint64_t*>(a->pk_nm.p), plane_words, a->stream);
+                                                 static_cast<uint64_t*>(a->launch.pk_nm.p), plane_words, a->stream);
         if (e != hipSuccess) return fail(BGR_E_HIP, std::string("N-mask scatter launch: ") + hipGetErrorString(e));
     }
     uint32_t max_len = pk->max_read_len;
@@ -974,7 +1021,7 @@ int bgr_align_batch_packed(bgr_aligner* a, const bgr_params* p, const bgr_packed
         for (uint64_t i = 0; i < n; ++i) max_len = std::max<uint32_t>(max_len, (uint32_t)std::min<uint64_t>(pk->read_offsets[i + 1] - pk->read_offsets[i], 0x7FFFFFFFull));
     }
     // (the host buffers may be reused once the copies are done: bgr_aligner_fetch below synchronises the stream)
-    int rc = align_device_impl(a, p, nullptr, a->in_offs.p, n, total, max_len, true);
+    int rc = align_device_impl(a, p, nullptr, a->launch.in_offs.p, n, total, max_len, true);
     if (rc != BGR_OK) return rc;
     return bgr_aligner_fetch(a, n, paths_out, paths_cap, path_offsets, status);
 }
@@ -1000,9 +1047,9 @@ int bgr_aligner_arena_ints(bgr_aligner* a, uint64_t* ints) {
 int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena, void** d_cursor) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_device_results: null aligner");
     a = holder_of(a);   // (the buffers of the last launch)
-    if (d_results) *d_results = a->results.p;
-    if (d_arena) *d_arena = a->arena.p;
-    if (d_cursor) *d_cursor = a->small.p;
+    if (d_results) *d_results = a->launch.results.p;
+    if (d_arena) *d_arena = a->launch.arena.p;
+    if (d_cursor) *d_cursor = a->launch.small.p;
     return BGR_OK;
 }
 
@@ -1013,15 +1060,15 @@ static int fetch_total(bgr_aligner* a, uint64_t n, uint64_t* total_out) {
     if (a->deep.open) { const int src = settle_launch_sync(a); if (src != BGR_OK) return src; }
     else HIP_TRY(wait_stream(a));
     const uint64_t nb = (n + 4095) / 4096;
-    HIP_TRY(a->csr_sums.ensure(nb * 4 + 64));
-    HIP_TRY(a->csr_poffs.ensure((n + 1) * 8));
-    HIP_TRY(a->csr_status.ensure(n));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallCsrTotal);
-    hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
-                                   static_cast<uint32_t*>(a->csr_sums.p), d_total, nullptr, nullptr, nullptr, 0, 0, a->last_arena_cap, a->stream);
+    HIP_TRY(a->fetch.csr_sums.ensure(nb * 4 + 64));
+    HIP_TRY(a->fetch.csr_poffs.ensure((n + 1) * 8));
+    HIP_TRY(a->fetch.csr_status.ensure(n));
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->launch.small.p) + bgr::kSmallCsrTotal);
+    hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->launch.results.p), static_cast<const int32_t*>(a->launch.arena.p), (uint32_t)n,
+                                   static_cast<uint32_t*>(a->fetch.csr_sums.p), d_total, nullptr, nullptr, nullptr, 0, 0, a->last_arena_cap, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("csr launch: ") + hipGetErrorString(e));
     uint64_t hs[bgr::kSmallCsrTotal / 8 + 1];  // the cursor block at the start, the path-int total at the end
-    HIP_TRY(hipMemcpyAsync(hs, a->small.p, sizeof(hs), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(hs, a->launch.small.p, sizeof(hs), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     const uint32_t* cur = reinterpret_cast<const uint32_t*>(hs);
     if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
@@ -1029,55 +1076,57 @@ static int fetch_total(bgr_aligner* a, uint64_t n, uint64_t* total_out) {
     return BGR_OK;
 }
 static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths_out, uint64_t* path_offsets, uint8_t* status, bool with_end = true) {
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->small.p) + bgr::kSmallCsrTotal);
-    HIP_TRY(a->csr_paths.ensure(total * 4 + 16));
-    hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->results.p), static_cast<const int32_t*>(a->arena.p), (uint32_t)n,
-                                   static_cast<uint32_t*>(a->csr_sums.p), d_total, static_cast<unsigned long long*>(a->csr_poffs.p),
-                                   static_cast<int32_t*>(a->csr_paths.p), static_cast<uint8_t*>(a->csr_status.p), (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull), 1, a->last_arena_cap, a->stream);
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(static_cast<char*>(a->launch.small.p) + bgr::kSmallCsrTotal);
+    HIP_TRY(a->fetch.csr_paths.ensure(total * 4 + 16));
+    hipError_t e = bgr::launch_csr(static_cast<const uint2*>(a->launch.results.p), static_cast<const int32_t*>(a->launch.arena.p), (uint32_t)n,
+                                   static_cast<uint32_t*>(a->fetch.csr_sums.p), d_total, static_cast<unsigned long long*>(a->fetch.csr_poffs.p),
+                                   static_cast<int32_t*>(a->fetch.csr_paths.p), static_cast<uint8_t*>(a->fetch.csr_status.p), (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull), 1, a->last_arena_cap, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("csr launch: ") + hipGetErrorString(e));
     // (with_end = false: entry n, the end of the last read, is left to the caller -- it is the first entry of the next piece)
-    HIP_TRY(hipMemcpyAsync(path_offsets, a->csr_poffs.p, (n + (with_end ? 1 : 0)) * 8, hipMemcpyDeviceToHost, a->stream));
-    HIP_TRY(hipMemcpyAsync(status, a->csr_status.p, n, hipMemcpyDeviceToHost, a->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(paths_out, a->csr_paths.p, total * 4, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(path_offsets, a->fetch.csr_poffs.p, (n + (with_end ? 1 : 0)) * 8, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(status, a->fetch.csr_status.p, n, hipMemcpyDeviceToHost, a->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(paths_out, a->fetch.csr_paths.p, total * 4, hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
+    return BGR_OK;
+}
+
+// what bgr_aligner_path_stats and bgr_aligner_path_diffs refuse of the last launch (a: the aligner that holds it)
+static int path_rows_refusal(const bgr_aligner* a, uint64_t n, const std::string& who) {
+    if (a->graph->header.has_exc) return fail(BGR_E_ARG, who + ": needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
+    if (n != a->last_n) return fail(BGR_E_ARG, who + ": n_reads differs from the last bgr_align_device call");
+    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, who + ": the last launch was exhaustive; paths of the greedy modes only");
     return BGR_OK;
 }
 
 int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n, bgr_path_stat* out) {
     if (!a || (n && (!d_reads || !d_read_offsets || !out))) return fail(BGR_E_ARG, "bgr_aligner_path_stats: null argument");
     a = holder_of(a);   // (the rows of the last launch, on the stream that ran it)
-    if (a->graph->header.has_exc)
-        return fail(BGR_E_ARG, "bgr_aligner_path_stats: needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
-    if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_path_stats: n_reads differs from the last bgr_align_device call");
-    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_path_stats: the last launch was exhaustive; paths of the greedy modes only");
+    if (const int rc = path_rows_refusal(a, n, "bgr_aligner_path_stats"); rc != BGR_OK) return rc;
     if (n == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(a->device));
     static_assert(sizeof(bgr_path_stat) == 24, "six words per read, as the kernel writes them");
-    HIP_TRY(a->path_stats.ensure(n * sizeof(bgr_path_stat)));
-    hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->results.p),
-                                          static_cast<const int32_t*>(a->arena.p), a->last_arena_cap, (uint32_t)n, static_cast<uint32_t*>(a->path_stats.p), a->stream);
+    HIP_TRY(a->fetch.path_stats.ensure(n * sizeof(bgr_path_stat)));
+    hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->launch.results.p),
+                                          static_cast<const int32_t*>(a->launch.arena.p), a->last_arena_cap, (uint32_t)n, static_cast<uint32_t*>(a->fetch.path_stats.p), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path stats launch: ") + hipGetErrorString(e));
     if (bgr::opt("test.count_with_path_stats")) {   // test hook: the counting kernels once over the rows the buffers hold now, the reads' characters from the caller's buffer
-        bgr::PileupReads pr;
-        pr.ascii = static_cast<const uint8_t*>(d_reads); pr.ascii_bytes = a->last_total_bases;
+        BehindPasses c{a, a->last_arena_cap, static_cast<const uint64_t*>(d_read_offsets), n, a->last_total_bases};
+        c.reads.ascii = static_cast<const uint8_t*>(d_reads); c.reads.ascii_bytes = a->last_total_bases;
         LaunchMarks none{a, false};
-        const int crc = queue_counting(a, a->last_arena_cap, static_cast<const uint64_t*>(d_read_offsets), n, a->last_total_bases, pr, none);
+        const int crc = queue_behind_passes(c, true, none);
         if (crc != BGR_OK) return crc;
     }
-    HIP_TRY(hipMemcpyAsync(out, a->path_stats.p, n * sizeof(bgr_path_stat), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(out, a->fetch.path_stats.p, n * sizeof(bgr_path_stat), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return BGR_OK;
 }
 
-// bgr_aligner_path_diffs: count, scan, fill (text_gaf.hip); the refusals are bgr_aligner_path_stats's
+// bgr_aligner_path_diffs: count, scan, fill (text_gaf.hip)
 int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_read_offsets, uint64_t n, uint64_t* diff_offsets, bgr_path_diff* out, uint64_t cap, uint64_t* n_out) {
     if (n_out) *n_out = 0;
     if (!a || !diff_offsets || !n_out || (cap && !out) || (n && (!d_reads || !d_read_offsets))) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: null argument");
     a = holder_of(a);   // (the rows of the last launch, on the stream that ran it)
-    if (a->graph->header.has_exc)
-        return fail(BGR_E_ARG, "bgr_aligner_path_diffs: needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
-    if (n != a->last_n) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: n_reads differs from the last bgr_align_device call");
-    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: the last launch was exhaustive; paths of the greedy modes only");
+    if (const int rc = path_rows_refusal(a, n, "bgr_aligner_path_diffs"); rc != BGR_OK) return rc;
     diff_offsets[0] = 0;
     if (n == 0) return BGR_OK;
     if (a->last_total_bases >= (1ull << 32)) return fail(BGR_E_ARG, "bgr_aligner_path_diffs: launches of fewer than 2^32 bases (a read has at most one difference per base, and their offsets are scanned in 32 bits)");
@@ -1085,12 +1134,12 @@ int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_re
     static_assert(sizeof(bgr_path_diff) == 8, "two words per difference, as the kernel writes them");
     // counts | offsets | offsets' unused twin (launch_scan2_u32 scans two arrays) | the scan's tile sums and the total
     const uint64_t words = n + 4, sums = 2ull * bgr::scan_tiles((uint32_t)n) + 16;
-    HIP_TRY(a->path_diffs.ensure((3 * words + sums + 4) * 4));
-    uint32_t* cnt = a->path_diffs.as<uint32_t>();
+    HIP_TRY(a->fetch.path_diffs.ensure((3 * words + sums + 4) * 4));
+    uint32_t* cnt = a->fetch.path_diffs.as<uint32_t>();
     uint32_t *doff = cnt + words, *twin = doff + words, *tile = twin + words, *total = tile + sums;
     const uint8_t* reads = static_cast<const uint8_t*>(d_reads);
     const uint64_t* offs = static_cast<const uint64_t*>(d_read_offsets);
-    hipError_t e = bgr::launch_path_diffs_count(a->dg, reads, offs, a->results.as<uint2>(), a->arena.as<int32_t>(), a->last_arena_cap, (uint32_t)n, cnt, a->stream);
+    hipError_t e = bgr::launch_path_diffs_count(a->dg, reads, offs, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), a->last_arena_cap, (uint32_t)n, cnt, a->stream);
     if (e == hipSuccess) e = bgr::launch_scan2_u32(cnt, cnt, doff, twin, (uint32_t)n, nullptr, tile, total, total + 1, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs launches: ") + hipGetErrorString(e));
     std::vector<uint32_t> h(n + 1);
@@ -1102,9 +1151,9 @@ int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_re
     *n_out = all;
     if (all > cap) return fail(BGR_E_CAPACITY, "bgr_aligner_path_diffs: out holds fewer differences than the launch has (*n says how many; the offsets are set)");
     if (all == 0) return BGR_OK;
-    DevBuf& buf = a->path_stats;   // (the records: the buffer of bgr_aligner_path_stats' rows is free between calls)
+    DevBuf& buf = a->fetch.path_stats;   // (the records: the buffer of bgr_aligner_path_stats' rows is free between calls)
     HIP_TRY(buf.ensure(all * sizeof(bgr_path_diff)));
-    e = bgr::launch_path_diffs_fill(a->dg, reads, offs, a->results.as<uint2>(), a->arena.as<int32_t>(), (uint32_t)n, cnt, doff, buf.as<uint2>(), a->stream);
+    e = bgr::launch_path_diffs_fill(a->dg, reads, offs, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), (uint32_t)n, cnt, doff, buf.as<uint2>(), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs fill launch: ") + hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(out, buf.p, all * sizeof(bgr_path_diff), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
@@ -1124,29 +1173,30 @@ int bgr_aligner_fetch(bgr_aligner* a, uint64_t n, int32_t* paths_out, uint64_t p
     return fetch_copy(a, n, total, paths_out, path_offsets, status);
 }
 
-// One piece of a batch up to (not including) the copies out: H2D of the characters and offsets, the mapping launch.
-static int batch_piece_launch(bgr_aligner* a, const bgr_params* p, const char* reads, const uint64_t* read_offsets, uint64_t n) {
-    HIP_TRY(hipSetDevice(a->device));
+// A batch of reads on the host up to (not including) the copies out: H2D of the characters and offsets into the aligner's input buffers, the mapping
+// launch (not the public form: the copies are on a->stream).  rel: where the offsets are made relative when they do not start at 0 -- with `keep` in any
+// case, and nothing is waited for: the vector outlives the copy, the caller's array need not
+static int batch_launch(bgr_aligner* a, const bgr_params* p, const char* who, const char* reads, const uint64_t* read_offsets, uint64_t n, std::vector<uint64_t>& rel, bool keep) {
     const uint64_t base = read_offsets[0], total = read_offsets[n] - base;
     uint32_t max_len = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        uint64_t l = read_offsets[i + 1] - read_offsets[i];
-        if (l > 0x7FFFFFFFull) return fail(BGR_E_ARG, "bgr_align_batch: read longer than 2^31 bases");
+        const uint64_t l = read_offsets[i + 1] - read_offsets[i];
+        if (l > 0x7FFFFFFFull) return fail(BGR_E_ARG, std::string(who) + ": read longer than 2^31 bases");
         max_len = std::max<uint32_t>(max_len, (uint32_t)l);
     }
-    HIP_TRY(a->in_reads.ensure(total + 16));
-    HIP_TRY(a->in_offs.ensure((n + 1) * 8));
-    HIP_TRY(hipMemcpyAsync(a->in_reads.p, reads + base, total, hipMemcpyHostToDevice, a->stream));
-    if (base == 0) {
-        HIP_TRY(hipMemcpyAsync(a->in_offs.p, read_offsets, (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipStreamSynchronize(a->stream));
-    } else {
-        std::vector<uint64_t> rel(n + 1);
-        for (uint64_t i = 0; i <= n; ++i) rel[i] = read_offsets[i] - base;
-        HIP_TRY(hipMemcpyAsync(a->in_offs.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipStreamSynchronize(a->stream));
-    }
-    return align_device_impl(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len, false);   // (not the public form: the copies above are on a->stream)
+    rel.resize(keep || base ? n + 1 : 0);
+    for (uint64_t i = 0; i < rel.size(); ++i) rel[i] = read_offsets[i] - base;
+    HIP_TRY(a->launch.in_reads.ensure(total + 16));
+    HIP_TRY(a->launch.in_offs.ensure((n + 1) * 8));
+    HIP_TRY(hipMemcpyAsync(a->launch.in_reads.p, reads + base, total, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipMemcpyAsync(a->launch.in_offs.p, rel.empty() ? read_offsets : rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
+    if (!keep) HIP_TRY(hipStreamSynchronize(a->stream));
+    return align_device_impl(a, p, a->launch.in_reads.p, a->launch.in_offs.p, n, total, max_len, false);
+}
+static int batch_piece_launch(bgr_aligner* a, const bgr_params* p, const char* reads, const uint64_t* read_offsets, uint64_t n) {
+    HIP_TRY(hipSetDevice(a->device));
+    std::vector<uint64_t> rel;
+    return batch_launch(a, p, "bgr_align_batch", reads, read_offsets, n, rel, false);
 }
 
 // A large batch in pieces on several streams (this aligner's and its twins', one host thread each): the copies of one piece run under the
@@ -1229,7 +1279,7 @@ int bgr_align_batch(bgr_aligner* a, const bgr_params* p, const char* reads, cons
     const uint64_t base = read_offsets[0], total = read_offsets[n] - base;
     // One launch addresses its path arena with 32 bits: a batch beyond that (~13 M reads of 150 bp) is mapped in pieces.
     // (BGR_KNOB_BATCH_SPLIT_LIMIT: tests lower the limit to walk this path with small inputs)
-    const uint64_t lim = a->knob_split_limit ? std::max<uint64_t>(4096, a->knob_split_limit) : 0xFFFFFFFFull - (256ull << 20);
+    const uint64_t lim = a->sh->knob_split_limit ? std::max<uint64_t>(4096, a->sh->knob_split_limit) : 0xFFFFFFFFull - (256ull << 20);
     if (n > 1 && (2 * (total + 16 * n) >= lim || n >= 0x7FFFFFFFull)) {
         uint64_t w = 0;
         for (uint64_t i0 = 0; i0 < n;) {
@@ -1246,7 +1296,7 @@ int bgr_align_batch(bgr_aligner* a, const bgr_params* p, const char* reads, cons
         return BGR_OK;
     }
     // a large batch: in pieces on two streams, copies under kernels (BGR_KNOB_BATCH_OVERLAP = 1 turns it off)
-    if (!a->is_twin && !a->knob_overlap && n >= kOverlapMinReads) return align_batch_overlapped(a, p, reads, read_offsets, n, paths_out, paths_cap, path_offsets, status);
+    if (!a->is_twin && !a->sh->knob_overlap && n >= kOverlapMinReads) return align_batch_overlapped(a, p, reads, read_offsets, n, paths_out, paths_cap, path_offsets, status);
     int rc = batch_piece_launch(a, p, reads, read_offsets, n);
     if (rc != BGR_OK) return rc;
     return bgr_aligner_fetch(a, n, paths_out, paths_cap, path_offsets, status);
@@ -1265,20 +1315,7 @@ int bgr_align_batch_begin(bgr_aligner* a, const bgr_params* p, const char* reads
     const uint64_t base = read_offsets[0], total = read_offsets[n] - base;
     if (n >= 0x7FFFFFFFull || 2 * (total + 16 * n) >= 0xFFFFFFFFull - (256ull << 20))
         return fail(BGR_E_ARG, "bgr_align_batch_begin: batch too large for one launch (2 * (bases + 16 * reads) must stay below 2^32 - 2^28); bgr_align_batch cuts such a batch");
-    uint32_t max_len = 0;
-    a->ticket_offs.resize(n + 1);
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t l = read_offsets[i + 1] - read_offsets[i];
-        if (l > 0x7FFFFFFFull) return fail(BGR_E_ARG, "bgr_align_batch_begin: read longer than 2^31 bases");
-        max_len = std::max<uint32_t>(max_len, (uint32_t)l);
-        a->ticket_offs[i] = read_offsets[i] - base;
-    }
-    a->ticket_offs[n] = total;
-    HIP_TRY(a->in_reads.ensure(total + 16));
-    HIP_TRY(a->in_offs.ensure((n + 1) * 8));
-    HIP_TRY(hipMemcpyAsync(a->in_reads.p, reads + base, total, hipMemcpyHostToDevice, a->stream));
-    HIP_TRY(hipMemcpyAsync(a->in_offs.p, a->ticket_offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, a->stream));
-    const int rc = align_device_impl(a, p, a->in_reads.p, a->in_offs.p, n, total, max_len, false);   // (not the public form: the copies above are on a->stream)
+    const int rc = batch_launch(a, p, "bgr_align_batch_begin", reads, read_offsets, n, a->ticket_offs, true);   // (the offsets stay alive in the aligner for the asynchronous copy)
     if (rc != BGR_OK) return rc;
     a->ticket_open = true;
     return BGR_OK;
@@ -1289,10 +1326,9 @@ int bgr_align_batch_test(const bgr_ticket* t) {
     bgr_aligner* a = t->aligner;
     if (!a->ticket_open || t->serial != a->ticket_serial) return fail(BGR_E_ARG, "bgr_align_batch_test: stale ticket");
     if (hipSetDevice(a->device) != hipSuccess) return fail(BGR_E_HIP, "hipSetDevice failed");
-    const hipError_t e = hipStreamQuery(a->stream);
-    if (e == hipSuccess) return 1;
-    if (e == hipErrorNotReady) return 0;
-    return fail(BGR_E_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+    bool idle = false;
+    const int rc = stream_idle(a, &idle);
+    return rc != BGR_OK ? rc : idle ? 1 : 0;
 }
 
 int bgr_align_batch_wait(const bgr_ticket* t, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status) {
@@ -1309,14 +1345,12 @@ int bgr_align_batch_wait(const bgr_ticket* t, int32_t* paths_out, uint64_t paths
 int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]) {
     if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_counters: null argument");
     HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    { const int src = settle_launch_sync(a); if (src != BGR_OK) return src; }  // (exhaustive mode: reads the last pass handed back are mapped -- and counted -- first)
-    HIP_TRY(hipMemcpy(out, static_cast<char*>(a->small.p) + bgr::kSmallCounters, bgr::kCounters * 8, hipMemcpyDeviceToHost));
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
+    for (uint32_t i = 0; i < bgr::kCounters; ++i) out[i] = 0;
+    for (bgr_aligner* x = a; x; x = x->twin) {  // its own stream, and the pieces of overlapped batches its other streams mapped
         uint64_t t[bgr::kCounters];
-        HIP_TRY(hipStreamSynchronize(tw->stream));
-        { const int src = settle_launch_sync(tw); if (src != BGR_OK) return src; }
-        HIP_TRY(hipMemcpy(t, static_cast<char*>(tw->small.p) + bgr::kSmallCounters, sizeof(t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        { const int src = settle_launch_sync(x); if (src != BGR_OK) return src; }  // (exhaustive mode: reads the last pass handed back are mapped -- and counted -- first)
+        HIP_TRY(hipMemcpy(t, x->launch.small.as<char>() + bgr::kSmallCounters, sizeof(t), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < bgr::kCounters; ++i) out[i] += t[i];
     }
     return BGR_OK;
@@ -1325,12 +1359,9 @@ int bgr_aligner_counters(bgr_aligner* a, uint64_t out[5]) {
 int bgr_aligner_reset_counters(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_counters: null aligner");
     HIP_TRY(hipSetDevice(a->device));
-    // (on the aligner's own stream: a fill on the null stream is not ordered with a non-blocking stream's kernels)
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(a->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8 + 8, a->stream));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(tw->small.p) + bgr::kSmallCounters, 0, bgr::kCounters * 8 + 8, tw->stream));
-        HIP_TRY(hipStreamSynchronize(tw->stream));
+    for (bgr_aligner* x = a; x; x = x->twin) {  // (each on its own stream: a fill on the null stream is not ordered with a non-blocking stream's kernels)
+        HIP_TRY(hipMemsetAsync(x->launch.small.as<char>() + bgr::kSmallCounters, 0, bgr::kCounters * 8 + 8, x->stream));
+        HIP_TRY(hipStreamSynchronize(x->stream));
     }
     return BGR_OK;
 }
@@ -1338,15 +1369,13 @@ int bgr_aligner_reset_counters(bgr_aligner* a) {
 int bgr_aligner_kernel_time(bgr_aligner* a, uint64_t* launches, double* total_ms) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_kernel_time: null aligner");
     HIP_TRY(hipSetDevice(a->device));
-    int rc = drain_timers(a);
-    if (rc != BGR_OK) return rc;
-    if (launches) *launches = a->t_launches;
-    if (total_ms) *total_ms = a->t_ms;
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
-        rc = drain_timers(tw);
+    if (launches) *launches = 0;
+    if (total_ms) *total_ms = 0;
+    for (bgr_aligner* x = a; x; x = x->twin) {  // its own stream, and the pieces of overlapped batches its other streams mapped
+        const int rc = drain_timers(x);
         if (rc != BGR_OK) return rc;
-        if (launches) *launches += tw->t_launches;
-        if (total_ms) *total_ms += tw->t_ms;
+        if (launches) *launches += x->t_launches;
+        if (total_ms) *total_ms += x->t_ms;
     }
     return BGR_OK;
 }
@@ -1354,13 +1383,11 @@ int bgr_aligner_kernel_time(bgr_aligner* a, uint64_t* launches, double* total_ms
 int bgr_aligner_kernel_times(bgr_aligner* a, uint64_t* launches, double slot_ms[8], const char* slot_names[8]) {
     if (!a || !slot_ms) return fail(BGR_E_ARG, "bgr_aligner_kernel_times: null argument");
     HIP_TRY(hipSetDevice(a->device));
-    int rc = drain_timers(a);
-    if (rc != BGR_OK) return rc;
-    if (launches) *launches = a->t_launches;
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        rc = drain_timers(tw);
+    if (launches) *launches = 0;
+    for (bgr_aligner* x = a; x; x = x->twin) {
+        const int rc = drain_timers(x);
         if (rc != BGR_OK) return rc;
-        if (launches) *launches += tw->t_launches;
+        if (launches) *launches += x->t_launches;
     }
     for (int j = 0; j < kTimerSlots; ++j) {
         slot_ms[j] = a->t_slot_ms[j];
@@ -1394,28 +1421,21 @@ int bgr_aligner_launch_info(bgr_aligner* a, uint32_t out[4]) {
 }
 
 #ifdef BGR_PHASE_TIMING
-// diagnostic builds only (not part of include/bgreat_gpu.h): the last launch's per-wave time stamps, four u64 per wave (100 MHz ticks)
-int bgr_debug_wave_times(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
+// diagnostic builds only (not part of include/bgreat_gpu.h): four u64 per wave of the last launch, the `part`-th such block of its buffer
+static int debug_wave_block(bgr_aligner* a, uint64_t part, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
     if (!a || !n_waves) return BGR_E_ARG;
     a = holder_of(a);
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     *n_waves = a->wave_times_n;
     const uint64_t n = std::min(cap_waves, a->wave_times_n);
-    if (n && out) HIP_TRY(hipMemcpy(out, a->wave_times.p, n * 32, hipMemcpyDeviceToHost));
+    if (n && out) HIP_TRY(hipMemcpy(out, a->launch.wave_times.as<char>() + part * a->wave_times_n * 32, n * 32, hipMemcpyDeviceToHost));
     return BGR_OK;
 }
-// the greedy multi kernel's anchor-scan counts per wave of the last launch: {scan steps, items scanned, groups of items, 0}
-int bgr_debug_scan_counts(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) {
-    if (!a || !n_waves) return BGR_E_ARG;
-    a = holder_of(a);
-    HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    *n_waves = a->wave_times_n;
-    const uint64_t n = std::min(cap_waves, a->wave_times_n);
-    if (n && out) HIP_TRY(hipMemcpy(out, static_cast<const char*>(a->wave_times.p) + a->wave_times_n * 32, n * 32, hipMemcpyDeviceToHost));
-    return BGR_OK;
-}
+// the per-wave time stamps (100 MHz ticks)
+int bgr_debug_wave_times(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) { return debug_wave_block(a, 0, out, cap_waves, n_waves); }
+// the greedy multi kernel's anchor-scan counts per wave: {scan steps, items scanned, groups of items, 0}
+int bgr_debug_scan_counts(bgr_aligner* a, uint64_t* out, uint64_t cap_waves, uint64_t* n_waves) { return debug_wave_block(a, 1, out, cap_waves, n_waves); }
 #endif
 
 int bgr_aligner_last_pass_runs(const bgr_aligner* a, uint32_t* runs, uint32_t* memo_cap) {
@@ -1432,7 +1452,7 @@ int bgr_aligner_pass_counts(bgr_aligner* a, uint32_t out[4]) {
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));
     uint32_t cur[bgr::kCurWords];
-    HIP_TRY(hipMemcpy(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cur, a->launch.small.p, sizeof(cur), hipMemcpyDeviceToHost));
     static_assert(bgr::kCurFollowUps == bgr::list_word(bgr::List::kSearch), "out[0]: greedy mode's follow-up items, exhaustive mode's first list");
     out[0] = cur[bgr::kCurFollowUps]; out[1] = cur[bgr::list_word(bgr::List::kDepthFirst)];
     out[2] = cur[bgr::list_word(bgr::List::kFirst)]; out[3] = cur[bgr::list_word(bgr::List::kGeneral)];

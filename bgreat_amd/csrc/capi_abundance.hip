@@ -30,25 +30,24 @@ int graph_abundance_end(bgr_graph* g, bool ok) {  // totals only of a run that e
 
 // the geometry and form of the abundance kernel behind a launch of this size (bgr_aligner_abundance_plan reports what this returns)
 bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases) {
-    return bgr::plan_abundance(a->graph->header.n_unitigs, a->dg.k, n_reads, total_bases, (uint32_t)a->num_cus, a->lds_per_cu, a->knob_abundance_form);
+    return bgr::plan_abundance(a->graph->header.n_unitigs, a->dg.k, n_reads, total_bases, (uint32_t)a->num_cus, a->lds_per_cu, (uint32_t)a->sh->knob_abundance_form);
 }
 
 // ---- unitig abundance (bgr_run_options.abundance has the definition) ------------------------------------------------------------------
-int abundance_set(bgr_aligner* a, bool on) {
-    if (on && !a->abundance.p) {
-        HIP_TRY(hipSetDevice(a->device));
-        HIP_TRY(a->abundance.ensure((a->graph->header.n_unitigs + 1) * sizeof(bgr_unitig_abundance)));
-        HIP_TRY(hipMemsetAsync(a->abundance.p, 0, a->abundance.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
-        HIP_TRY(hipStreamSynchronize(a->stream));
-        HIP_TRY(bgr::prepare_abundance(a->lds_per_cu));   // (once per aligner, not per launch: form B's tables beyond 48 KB)
-    }
-    a->abundance_on = on;
+int abundance_table(bgr_aligner* a) {
+    if (a->abundance.p) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(a->abundance.ensure((a->graph->header.n_unitigs + 1) * sizeof(bgr_unitig_abundance)));
+    HIP_TRY(hipMemsetAsync(a->abundance.p, 0, a->abundance.cap, a->stream));   // (on the aligner's own stream, as bgr_aligner_reset_counters)
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    HIP_TRY(bgr::prepare_abundance(a->lds_per_cu));   // (once per aligner, not per launch: form B's tables beyond 48 KB)
     return BGR_OK;
 }
 
 int bgr_aligner_abundance_enable(bgr_aligner* a, uint32_t on) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_abundance_enable: null aligner");
-    for (bgr_aligner* x = a; x; x = x->twin) { const int rc = abundance_set(x, on != 0); if (rc != BGR_OK) return rc; }
+    for (bgr_aligner* x = a; x && on; x = x->twin) { const int rc = abundance_table(x); if (rc != BGR_OK) return rc; }   // (one table per stream: a twin made later gets its own then)
+    a->sh->abundance_on = on != 0;
     return BGR_OK;
 }
 
@@ -59,14 +58,12 @@ int bgr_aligner_abundance(bgr_aligner* a, bgr_unitig_abundance* out, uint64_t n_
     if (!a->abundance.p) return fail(BGR_E_ARG, "bgr_aligner_abundance: abundance was never enabled on this aligner (bgr_aligner_abundance_enable)");
     if (n_rows == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    HIP_TRY(hipMemcpy(out, static_cast<const bgr_unitig_abundance*>(a->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
-    std::vector<bgr_unitig_abundance> t;
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {  // the pieces of overlapped batches its other streams mapped
-        if (!tw->abundance.p) continue;
-        t.resize(n_rows);
-        HIP_TRY(hipStreamSynchronize(tw->stream));
-        HIP_TRY(hipMemcpy(t.data(), static_cast<const bgr_unitig_abundance*>(tw->abundance.p) + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
+    memset(out, 0, n_rows * sizeof(bgr_unitig_abundance));
+    std::vector<bgr_unitig_abundance> t(n_rows);
+    for (bgr_aligner* x = a; x; x = x->twin) {  // its own table, and those of the streams that mapped the pieces of overlapped batches and un-waited launches
+        if (!x->abundance.p) continue;
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        HIP_TRY(hipMemcpy(t.data(), x->abundance.as<bgr_unitig_abundance>() + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < n_rows; ++i) { out[i].reads += t[i].reads; out[i].bases += t[i].bases; out[i].kmers += t[i].kmers; }
     }
     return BGR_OK;
@@ -165,4 +162,4 @@ static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
     return rc;
 }
 static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) { return bgr::end_stages(kStages, kNStages, g, what, ok); }
-static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, run_haplotag_enable, run_gaf_cs_wanted, run_gaf_cs_enable, run_inside_wanted, run_inside_begin, run_inside_enable, run_inside_collect}, true);
+static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, bgr_aligner_haplotag_enable, bgr_graph_gaf_cs_enabled, bgr_aligner_gaf_cs_enable, bgr_graph_inside_enabled, run_inside_begin, bgr_aligner_inside_enable, run_inside_collect}, true);

@@ -90,7 +90,7 @@ int bgr_aligner_bubbles(bgr_aligner* a, uint64_t min_link, bgr_bubble* out, uint
     for (int i = 0; i < 4; ++i) a->bub_ms[i] = 0;
     if (tail[2] == 0) return BGR_OK;   // (an empty table: the passes would read every slot to find nothing)
     DeviceCall c(a->stream);   // (on the aligner's own stream, behind its launches; links_tail has made its device current)
-    return bubbles_call(c, a->links.tab, a->links.cap, a->graph->header.n_unitigs, min_link, "bgr_aligner_bubbles", nullptr, out, cap, n, a->knob_no_events ? nullptr : a->bub_ms);
+    return bubbles_call(c, a->sh->links.tab, a->sh->links.cap, a->graph->header.n_unitigs, min_link, "bgr_aligner_bubbles", nullptr, out, cap, n, a->sh->knob_no_events ? nullptr : a->bub_ms);
 }
 
 int bgr_aligner_bubbles_times(bgr_aligner* a, double ms[4]) {

@@ -44,14 +44,14 @@ int bgr_aligner_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t 
     if (table && n_rows != a->graph->header.n_unitigs + 1) return fail(BGR_E_ARG, "bgr_aligner_haplotag_enable: n_rows is not the graph's number of unitigs + 1");
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipStreamSynchronize(a->stream));   // (a text piece's kernels may still read the table that is about to go)
-    if (!table) { a->haplotag.release(); return BGR_OK; }
-    const hipError_t e = a->haplotag.ensure(n_rows * sizeof(uint32_t));
+    if (!table) { a->tag.table.release(); return BGR_OK; }
+    const hipError_t e = a->tag.table.ensure(n_rows * sizeof(uint32_t));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        a->haplotag.release();
+        a->tag.table.release();
         return fail(e == hipErrorOutOfMemory ? BGR_E_NOMEM : BGR_E_HIP, std::string("bgr_aligner_haplotag_enable: ") + std::to_string(n_rows * sizeof(uint32_t)) + " bytes on the device: " + hipGetErrorString(e));
     }
-    HIP_TRY(hipMemcpyAsync(a->haplotag.p, table, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipMemcpyAsync(a->tag.table.p, table, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));   // (the caller's table may go once this returns)
     return BGR_OK;
 }
@@ -59,18 +59,18 @@ int bgr_aligner_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t 
 int bgr_aligner_haplotags(bgr_aligner* a, uint64_t n_reads, bgr_read_tag* out) {
     if (!a || (n_reads && !out)) return fail(BGR_E_ARG, "bgr_aligner_haplotags: null argument");
     if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_haplotags: an internal twin (ask the aligner it was made for)");
-    const uint32_t* table = static_cast<const uint32_t*>(a->haplotag.p);
+    const uint32_t* table = static_cast<const uint32_t*>(a->tag.table.p);
     if (!table) return fail(BGR_E_ARG, "bgr_aligner_haplotags: no tag table on this aligner (bgr_aligner_haplotag_enable)");
     bgr_aligner* h = holder_of(a);   // (the rows of the last launch, on the stream that ran it; the table is the aligner's own)
     if (n_reads != h->last_n) return fail(BGR_E_ARG, "bgr_aligner_haplotags: n_reads differs from the last bgr_align_device call");
     if (h->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_haplotags: the last launch was exhaustive; rows of the greedy modes only");
     if (n_reads == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(h->haplotag_out.ensure(n_reads * sizeof(bgr_read_tag)));
-    const hipError_t e = bgr::launch_haplotags(table, a->graph->header.n_unitigs, static_cast<const uint2*>(h->results.p), static_cast<const int32_t*>(h->arena.p), h->last_arena_cap,
-                                               (uint32_t)n_reads, static_cast<bgr_read_tag*>(h->haplotag_out.p), h->stream);
+    HIP_TRY(h->tag.out.ensure(n_reads * sizeof(bgr_read_tag)));
+    const hipError_t e = bgr::launch_haplotags(table, a->graph->header.n_unitigs, static_cast<const uint2*>(h->launch.results.p), static_cast<const int32_t*>(h->launch.arena.p), h->last_arena_cap,
+                                               (uint32_t)n_reads, static_cast<bgr_read_tag*>(h->tag.out.p), h->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("haplotags launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(out, h->haplotag_out.p, n_reads * sizeof(bgr_read_tag), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->tag.out.p, n_reads * sizeof(bgr_read_tag), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(wait_stream(h));
     return BGR_OK;
 }
@@ -94,4 +94,3 @@ const uint32_t* run_haplotag_table(const bgr_graph* g, uint64_t* n_rows) {
     *n_rows = g->haplotag.size();
     return g->haplotag.data();
 }
-int run_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t n_rows) { return bgr_aligner_haplotag_enable(a, table, n_rows); }

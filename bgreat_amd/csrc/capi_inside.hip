@@ -73,7 +73,8 @@ int bgr_aligner_inside_enable(bgr_aligner* a, int on) {
         const int rc = inside_on_device(a->graph, a->device, &tab);
         if (rc != BGR_OK) return rc;
     }
-    for (bgr_aligner* x = a; x; x = x->twin) { x->inside_tab = tab; x->inside_slots = tab ? a->graph->inside.slots : 0; }   // (read when a launch is queued)
+    a->sh->inside_tab = tab;   // (read when a launch is queued, on whichever stream)
+    a->sh->inside_slots = tab ? a->graph->inside.slots : 0;
     return BGR_OK;
 }
 
@@ -84,7 +85,7 @@ int bgr_aligner_inside_count(bgr_aligner* a, uint64_t* n) {
     if (rc != BGR_OK) return rc;
     for (bgr_aligner* x = a; x; x = x->twin) {   // (the twins map the pieces of overlapped batches and un-waited launches)
         uint64_t c = 0;
-        HIP_TRY(hipMemcpy(&c, static_cast<char*>(x->small.p) + bgr::kSmallInside, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&c, static_cast<char*>(x->launch.small.p) + bgr::kSmallInside, 8, hipMemcpyDeviceToHost));
         *n += c;
     }
     return BGR_OK;
@@ -105,12 +106,10 @@ int bgr_graph_inside_count(const bgr_graph* g, uint64_t* n) {
 }
 
 // whole runs (run_counts.h)
-int run_inside_wanted(const bgr_graph* g) { return bgr_graph_inside_enabled(g); }
 void run_inside_begin(bgr_graph* g) {
     std::lock_guard<std::mutex> l(g->abundance_m);
     g->inside_run = 0;
 }
-int run_inside_enable(bgr_aligner* a, int on) { return bgr_aligner_inside_enable(a, on); }
 int run_inside_collect(bgr_graph* g, bgr_aligner* a) {
     uint64_t n = 0;
     const int rc = bgr_aligner_inside_count(a, &n);

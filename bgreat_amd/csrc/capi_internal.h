@@ -183,19 +183,79 @@ struct TextRoute {
     }
 };
 
+// What a launch reads and writes on the device: the batch as it came in, its 2-bit planes, the rows, the lists the passes leave each other
+struct LaunchBufs {
+    DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small;  // small: kSmall* (align_kernels.h)
+    DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
+    void release() { for (DevBuf* b : {&in_reads, &in_offs, &pk_fw3, &pk_nm, &pk_hasn, &results, &arena, &ovf, &ovf2, &lst, &deepbuf, &retry, &retry2, &small, &wave_times}) b->release(); }
+};
+// What reads the rows of the last launch back: the dense arrays of a fetch, bgr_aligner_path_stats, bgr_aligner_path_diffs
+struct FetchBufs {
+    DevBuf csr_sums, csr_poffs, csr_status, csr_paths, path_stats;
+    DevBuf path_diffs;            // counts and offsets (two arrays of n + 1 words each way), then the differences
+    void release() { for (DevBuf* b : {&csr_sums, &csr_poffs, &csr_status, &csr_paths, &path_stats, &path_diffs}) b->release(); }
+};
+// haplotags (bgr_aligner_haplotag_enable): the tag table on the device (null: off), the tags of the last call of bgr_aligner_haplotags
+struct HaplotagBufs { DevBuf table, out; void release() { table.release(); out.release(); } };
+// bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
+struct VariantBufs { DevBuf scratch, out, stage; void release() { scratch.release(); out.release(); stage.release(); } };
+
+// links and triples (bgr_aligner_links_enable, bgr_aligner_triples_enable): every greedy / anchors launch is followed by the kernel that adds to the
+// table.  buf: {key words, u64 count}[cap] + the tail words (links_kernels.h, triples_kernels.h), allocated and zeroed on the first enable; tab: the
+// table once it is zeroed
+struct CountTable {
+    bool on = false;
+    DevBuf buf;
+    unsigned long long* tab = nullptr;
+    uint64_t cap = 0, bound = 0;
+};
+// the pileup (bgr_aligner_pileup_enable, bgr_aligner_pileup_strands_enable): every greedy / anchors launch is followed by the pileup kernel, which with
+// strands also adds the forward observations to a second table
+struct PileupTables {
+    bool on = false, strands_on = false;
+    DevBuf table, offs;                    // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
+    DevBuf fwd;                            // the forward table: the layout of `table`, its tail stays 0
+    uint32_t* tab = nullptr;               // the tables once they are ready (a run's variants take them away: capi_variants.hip)
+    const uint64_t* base_offs = nullptr;
+    uint32_t* fwd_tab = nullptr;
+    void release() { table.release(); offs.release(); fwd.release(); }
+};
+
+// What an aligner and its twins (below) have in common: the tuning, the knobs, the switches of the counting features and the tables that every stream
+// adds to (the atomics are device-scope).  The aligner allocates it and a twin points at its owner's, so a setting made on the aligner is the twin's
+// at once; nothing writes it through a twin, and the threads of an overlapped batch only read it.
+struct AlignerShared {
+    uint32_t cfg_waves = 0, cfg_blocks_per_cu = 0, cfg_lds_mphf = 0;
+    bool exh_filter = bgr::opt("exh_filter") != 0;  // exhaustive mode through the minimizer filter too (option exh_filter = 0: without)
+    // bgr_aligner_set_knob (test / diagnostic hooks, read here instead of from the environment on every launch; the table of them is in capi.hip)
+    uint64_t knob_frame_cap = 0, knob_search = 0, knob_split_limit = 0, knob_debug_stop = 0, knob_greedy_fast = 0, knob_exh_fast = 0, knob_anc_fast = 0, knob_memo_cap = 0, knob_prepass = 0;
+    uint64_t knob_no_events = 0, knob_no_jump = 0;   // BGR_KNOB_KERNEL_EVENTS (kept inverted), BGR_KNOB_GREEDY_JUMP
+    uint64_t knob_overlap = 0, knob_device_overlap = 0, knob_abundance_form = 0, knob_links_form = 0;   // BGR_KNOB_BATCH_OVERLAP, .._DEVICE_OVERLAP, .._ABUNDANCE_FORM, .._LINKS_FORM
+    bool abundance_on = false;          // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel (the table is each stream's own)
+    CountTable links, triples;
+    PileupTables pileup;
+    // the inside pass (bgr_aligner_inside_enable): every greedy / anchors launch is followed, in front of the counting kernels, by bgr_align_inside_kernel
+    // over the graph's inside index on this device (inside_tab: null = off); what it mapped is counted at kSmallInside of each stream's `small`
+    const BgrInsideEntry* inside_tab = nullptr;
+    uint64_t inside_slots = 0;
+    void release() { links.buf.release(); triples.buf.release(); pileup.release(); }
+};
+
 struct bgr_aligner {
     bgr_graph* graph = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
     BgrDeviceGraph dg;
+    AlignerShared* sh = nullptr;  // the aligner's own, or (a twin) that of the aligner it belongs to
     TextRoute text;
-    DevBuf path_stats;
-    DevBuf path_diffs;            // bgr_aligner_path_diffs: counts and offsets (two arrays of n + 1 words each way), then the differences
+    LaunchBufs launch;
+    FetchBufs fetch;
+    HaplotagBufs tag;
+    VariantBufs var;
+    DevBuf abundance;             // u64[n_unitigs + 1][3], allocated and zeroed on the first enable: one per stream, summed when it is read
     bool gaf_cs = false;          // bgr_aligner_gaf_cs_enable: the GAF lines of bgr_align_fasta_text end in the cs:Z: field
     bool blocking_sync = bgr::opt("blocking_sync") != 0;
     hipEvent_t ev_wait = nullptr;
-
-    DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small, csr_sums, csr_poffs, csr_status, csr_paths;  // small: kSmall* (align_kernels.h)
     struct DeepRun {  // the last pass of the exhaustive launch in flight, as enqueued: settle_launch runs it again for reads whose table filled up
         bool open = false;
         bgr::Pass pass;
@@ -210,51 +270,15 @@ struct bgr_aligner {
     uint32_t last_mode = 0;       // mode of the last mapping launch (bgr_aligner_path_stats)
     uint64_t last_arena_cap = 0, last_total_bases = 0;   // its arena's ints and its reads' bases (the counting kernels behind bgr_aligner_path_stats: test.count_with_path_stats)
     uint64_t sized_n = 0;         // reads of the last launch that sized the buffers (forget_launch leaves it: option test.keep_rows asks for the same launch again)
-    DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
-    uint64_t wave_times_n = 0;
+    uint64_t wave_times_n = 0;    // diagnostic builds only (-DBGR_PHASE_TIMING)
     uint64_t ticket_serial = 0;       // bgr_align_batch_begin: tickets handed out; the batch of the last one is in flight until its wait
     bool ticket_open = false;
     std::vector<uint64_t> ticket_offs;  // that batch's offsets made relative (kept alive for the asynchronous copy)
     uint32_t last_launch[4] = {0, 0, 0, 0};
-    uint32_t cfg_waves = 0, cfg_blocks_per_cu = 0, cfg_lds_mphf = 0;
-    bool exh_filter = bgr::opt("exh_filter") != 0;  // exhaustive mode through the minimizer filter too (option exh_filter = 0: without)
-    // bgr_aligner_set_knob (test / diagnostic hooks, read here instead of from the environment on every launch)
-    uint32_t knob_frame_cap = 0, knob_search = 0, knob_debug_stop = 0, knob_greedy_fast = 0, knob_exh_fast = 0, knob_anc_fast = 0, knob_memo_cap = 0, knob_prepass = 0, knob_no_events = 0;
-    uint64_t knob_split_limit = 0;
-    uint32_t knob_no_jump = 0;      // BGR_KNOB_GREEDY_JUMP
-    uint32_t knob_overlap = 0;      // BGR_KNOB_BATCH_OVERLAP
-    uint32_t knob_abundance_form = 0;  // BGR_KNOB_ABUNDANCE_FORM
-    bool abundance_on = false;      // bgr_aligner_abundance_enable: every greedy / anchors launch is followed by the abundance kernel
-    DevBuf abundance;               // u64[n_unitigs + 1][3], allocated and zeroed on the first enable
-    uint32_t knob_links_form = 0;   // BGR_KNOB_LINKS_FORM
-    // links and triples (bgr_aligner_links_enable, bgr_aligner_triples_enable): every greedy / anchors launch is followed by the kernel that adds to the
-    // table.  buf: {key words, u64 count}[cap] + the tail words (links_kernels.h, triples_kernels.h), allocated and zeroed on the first enable; tab: the
-    // table this aligner's launches add to -- its own, or (a twin) the one of the aligner it belongs to
-    struct CountTable {
-        bool on = false;
-        DevBuf buf;
-        unsigned long long* tab = nullptr;
-        uint64_t cap = 0, bound = 0;
-    } links, triples;
-    bool pileup_on = false;         // bgr_aligner_pileup_enable: every greedy / anchors launch is followed by the pileup kernel
-    DevBuf pileup, pileup_offs;     // the table (pileup_kernels.h) and base_offs, allocated, zeroed / uploaded on the first enable
-    uint32_t* pileup_tab = nullptr;             // the table this aligner's launches add to: its own, or (a twin) the one of the aligner it belongs to
-    const uint64_t* pileup_base_offs = nullptr;
-    bool strands_on = false;        // bgr_aligner_pileup_strands_enable: the pileup kernel also adds the forward observations to a second table
-    DevBuf pileup_fwd;              // that table: the layout of `pileup`, its tail stays 0
-    uint32_t* pileup_fwd_tab = nullptr;   // as pileup_tab: its own, or (a twin) the one of the aligner it belongs to
-    // haplotags (bgr_aligner_haplotag_enable): the tag table on the device (null: off), the tags of the last call of bgr_aligner_haplotags
-    DevBuf haplotag, haplotag_out;
-    DevBuf var_scratch, var_out, var_stage;   // bgr_aligner_pileup_sites: the passes' tile arrays and the records; bgr_aligner_pileup_add: the staging piece
-    double var_ms[5] = {0, 0, 0, 0, 0};       // the last call's five launches
+    double var_ms[5] = {0, 0, 0, 0, 0};       // bgr_aligner_pileup_sites: the last call's five launches
     double bub_ms[4] = {0, 0, 0, 0};          // bgr_aligner_bubbles: the last call's four launches
-    // the inside pass (bgr_aligner_inside_enable): every greedy / anchors launch is followed, in front of the counting kernels, by bgr_align_inside_kernel
-    // over the graph's inside index on this device (inside_tab: null = off); what it mapped is counted at kSmallInside of `small`
-    const BgrInsideEntry* inside_tab = nullptr;
-    uint64_t inside_slots = 0;
     bgr_aligner* twin = nullptr;    // second stream + buffers: the overlapped form of bgr_align_batch, un-waited consecutive bgr_align_device launches (created on first use)
     bool is_twin = false;
-    uint32_t knob_device_overlap = 0;   // BGR_KNOB_DEVICE_OVERLAP
     bgr_aligner* holder = nullptr;  // who took this aligner's last mapping launch: null = itself, else its twin (launch_taker.h); "the last launch" is read there
     int num_cus = 0;
     size_t lds_per_cu = 0;
@@ -264,6 +288,7 @@ struct bgr_aligner {
     uint64_t t_launches = 0;
     double t_ms = 0, t_slot_ms[kTimerSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
     const char* t_slot_name[kTimerSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~bgr_aligner() { if (!is_twin) delete sh; }   // (its device memory: bgr_aligner_destroy)
 };
 
 // Wait for the aligner's stream.  By default hipStreamSynchronize (the runtime spins: lowest latency, one busy CPU per waiting thread);
@@ -388,10 +413,9 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
 int settle_launch(bgr_aligner* a, uint32_t* cur);   // behind a mapping launch, its stream waited for and the cursor block in `cur`: the arena flag; exhaustive mode: reads handed back are mapped
 }
 // capi_abundance.hip
-int abundance_set(bgr_aligner* a, bool on);   // this one aligner's (or twin's) switch; the table is allocated and zeroed the first time
+int abundance_table(bgr_aligner* a);   // this one aligner's (or twin's) table, allocated and zeroed the first time it is asked for
 bgr::AbundancePlan abundance_plan_of(const bgr_aligner* a, uint64_t n_reads, uint64_t total_bases);   // geometry and form of the abundance kernel behind a launch of this size
 // capi_links.hip: the count tables, links and triples
-void tables_share(bgr_aligner* a);   // the twins add to the aligner's tables of links and triples: its fields copied to each of them
 int links_tail(bgr_aligner* a, const char* who, uint64_t* tail);   // the three words behind the aligner's table of links, every stream that adds to it waited for; BGR_E_ARG when links were never enabled, BGR_E_CAPACITY when the table has overflowed
 void triples_records(const std::vector<std::array<uint64_t, 3>>& rows, bgr_triple* out);   // the rows of a table of triples as the interface's records
 // A whole run (run_counts.h, through the table of stages in capi_abundance.hip).  begin: the totals of the run before are gone; collect: an aligner's
@@ -425,14 +449,9 @@ int chain_stage_end(bgr_graph* g, F& f, bool ok, bool inputs_valid, const char* 
     f.valid = rc == BGR_OK;
     return rc;
 }
-// capi_haplotag.hip: the graph's tag table while its switch is on (else null), and the table onto an aligner's device (run_counts.h)
+// capi_haplotag.hip: the graph's tag table while its switch is on, else null (run_counts.h; where a run needs no more than a call of the interface, that is registered)
 const uint32_t* run_haplotag_table(const bgr_graph* g, uint64_t* n_rows);
-int run_haplotag_enable(bgr_aligner* a, const uint32_t* table, uint64_t n_rows);
-// capi_text.hip: the graph's cs:Z: switch, and the switch of an aligner (run_counts.h)
-int run_gaf_cs_wanted(const bgr_graph* g);
-int run_gaf_cs_enable(bgr_aligner* a, int on);
 // capi_pileup.hip
-void pileup_share(bgr_aligner* a);   // the twins add to the aligner's pileup tables: its fields copied to each of them
 int pileup_guard(const bgr_unitig_abundance* rows, uint64_t n, const char* who);   // BGR_E_CAPACITY when a reads column reached 2^32: a depth may have wrapped
 int guarded_sync(bgr_aligner* a, const char* who);   // the aligner's abundance snapshot through pileup_guard, then sync_all
 int graph_base_offs(bgr_graph* g, const char* who);  // g->base_offs (prefix sums of the unitig lengths) made, once per graph
@@ -442,9 +461,7 @@ int run_pileup_collect(bgr_graph* g, bgr_aligner* a);  // ... the pileup switch 
 int run_pileup_end(bgr_graph* g, bool ok);             // ... behind the abundance's end: BGR_E_CAPACITY when a depth may have wrapped
 // capi_inside.hip
 void inside_free_devices(bgr_graph* g);                // the device copies of the graph's inside index released (bgr_graph_destroy)
-int run_inside_wanted(const bgr_graph* g);             // the graph's switch for whole runs (run_counts.h)
-void run_inside_begin(bgr_graph* g);                   // ... a new run: its count starts at 0
-int run_inside_enable(bgr_aligner* a, int on);         // ... onto an aligner of the run
+void run_inside_begin(bgr_graph* g);                   // a new run (run_counts.h): its count starts at 0
 int run_inside_collect(bgr_graph* g, bgr_aligner* a);  // ... the aligner's count (its streams waited for) joins the run's
 // capi_variants.hip
 int variants_collect(bgr_graph* g, bgr_aligner* a);   // a run's aligner: the first one's tables become the run's (g->variants_run), the others' are added

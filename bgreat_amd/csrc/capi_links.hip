@@ -25,12 +25,12 @@ struct TableDesc {
 template <size_t W> struct Table;
 template <> struct Table<2> {
     static constexpr TableDesc d = {"links", "test.links_capacity", 0, bgr::kLinksTailWords, 2, false, bgr::links_bound_of_blob, bgr::links_capacity, bgr::links_table_bytes, "the bound is counted over its slots"};
-    static bgr_aligner::CountTable& of(bgr_aligner* a) { return a->links; }
+    static CountTable& of(bgr_aligner* a) { return a->sh->links; }
     static CountRows<2>& of(bgr_graph* g) { return g->links; }
 };
 template <> struct Table<3> {
     static constexpr TableDesc d = {"triples", "test.triples_capacity", 1, bgr::kTriplesTailWords, 1, true, bgr::triples_bound_of_blob, bgr::triples_capacity, bgr::triples_table_bytes, "the bound is counted over its unitigs' ends"};
-    static bgr_aligner::CountTable& of(bgr_aligner* a) { return a->triples; }
+    static CountTable& of(bgr_aligner* a) { return a->sh->triples; }
     static CountRows<3>& of(bgr_graph* g) { return g->triples; }
 };
 static_assert(bgr::kTriplesSlotWords == 3, "a slot of the table of triples is a host row");
@@ -53,19 +53,12 @@ static int graph_bound_checked(bgr_graph* g, uint64_t* bound) {
 }
 
 template <size_t W>
-static void table_share(bgr_aligner* a) {   // the twins add to the aligner's table
-    const bgr_aligner::CountTable& t = Table<W>::of(a);
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) { bgr_aligner::CountTable& x = Table<W>::of(tw); x.tab = t.tab; x.cap = t.cap; x.bound = t.bound; x.on = t.on; }
-}
-void tables_share(bgr_aligner* a) { table_share<2>(a); table_share<3>(a); }
-
-template <size_t W>
 static int table_enable(bgr_aligner* a, uint32_t on) {
     const TableDesc& d = Table<W>::d;
     const std::string who = name_of<W>("bgr_aligner_", "_enable");
     if (!a) return fail(BGR_E_ARG, who + ": null aligner");
     if (a->is_twin) return fail(BGR_E_ARG, who + ": an internal stream of another aligner");
-    bgr_aligner::CountTable& t = Table<W>::of(a);
+    CountTable& t = Table<W>::of(a);
     if (on && !t.tab) {
         if (d.narrow_ids && a->graph->header.n_unitigs >= 0x40000000ull) return fail(BGR_E_ARG, who + ": a graph of 2^30 unitigs or more (an id and its sign fit 31 bits of the key)");
         uint64_t bound = 0;
@@ -88,7 +81,6 @@ static int table_enable(bgr_aligner* a, uint32_t on) {
         t.bound = bound;
     }
     t.on = on != 0;
-    table_share<W>(a);
     return BGR_OK;
 }
 
@@ -96,7 +88,7 @@ static int table_enable(bgr_aligner* a, uint32_t on) {
 template <size_t W>
 static int table_tail(bgr_aligner* a, const char* who, uint64_t* tail) {   // (tail: d.tail_words words)
     const TableDesc& d = Table<W>::d;
-    const bgr_aligner::CountTable& t = Table<W>::of(a);
+    const CountTable& t = Table<W>::of(a);
     if (!t.tab) return fail(BGR_E_ARG, std::string(who) + ": " + d.noun + " were never enabled on this aligner (" + name_of<W>("bgr_aligner_", "_enable") + ")");
     if (const int rc = sync_all(a); rc != BGR_OK) return rc;
     HIP_TRY(hipMemcpy(tail, t.tab + W * t.cap, d.tail_words * 8, hipMemcpyDeviceToHost));
@@ -112,7 +104,7 @@ int links_tail(bgr_aligner* a, const char* who, uint64_t* tail) { return table_t
 template <size_t W>
 static int table_snapshot(bgr_aligner* a, const char* who, uint64_t room, Rows<W>& rows, uint64_t* used) {
     const TableDesc& d = Table<W>::d;
-    const bgr_aligner::CountTable& t = Table<W>::of(a);
+    const CountTable& t = Table<W>::of(a);
     uint64_t tail[4];
     const int rc = table_tail<W>(a, who, tail);
     if (rc != BGR_OK) return rc;
@@ -253,9 +245,9 @@ int bgr_link_canonical(int32_t a, int32_t b, bgr_link* out, uint64_t* key) {
 
 int bgr_aligner_links_plan(bgr_aligner* a, uint64_t n_reads, uint32_t out[4]) {
     if (!a || !out) return fail(BGR_E_ARG, "bgr_aligner_links_plan: null argument");
-    uint64_t bound = a->links.bound;
-    if (!a->links.tab) { const int rc = graph_bound<2>(a->graph, &bound); if (rc != BGR_OK) return rc; }
-    const bgr::LinksPlan lp = bgr::plan_links(bound, n_reads, (uint32_t)a->num_cus, a->knob_links_form);
+    uint64_t bound = a->sh->links.bound;
+    if (!a->sh->links.tab) { const int rc = graph_bound<2>(a->graph, &bound); if (rc != BGR_OK) return rc; }
+    const bgr::LinksPlan lp = bgr::plan_links(bound, n_reads, (uint32_t)a->num_cus, (uint32_t)a->sh->knob_links_form);
     out[0] = lp.form; out[1] = lp.blocks; out[2] = lp.threads; out[3] = lp.lds_bytes;
     return BGR_OK;
 }

@@ -23,13 +23,6 @@ int pileup_refusal(const bgr_graph* g, const char* who) {
         return fail(BGR_E_ARG, std::string(who) + ": the pileup (--pileup, --depth) needs a graph of ACGT-only unitigs: on one with other characters the 2-bit store does not spell them and a path read backwards does not spell the reverse complement");
     return BGR_OK;
 }
-void pileup_share(bgr_aligner* a) {   // the twins add to the aligner's table
-    for (bgr_aligner* tw = a->twin; tw; tw = tw->twin) {
-        tw->pileup_tab = a->pileup_tab; tw->pileup_base_offs = a->pileup_base_offs; tw->pileup_on = a->pileup_on;
-        tw->pileup_fwd_tab = a->pileup_fwd_tab; tw->strands_on = a->strands_on;
-    }
-}
-
 // A table of the pileup's layout in `tab` -- and, with `offs`, the graph's base_offs next to it -- on the first enable: allocated (a failure leaves
 // neither and reports `what`), zeroed / uploaded on the aligner's own stream (as bgr_aligner_reset_counters), waited for.
 static int pileup_table_alloc(bgr_aligner* a, DevBuf& tab, DevBuf* offs, const char* who, const char* what) {
@@ -58,37 +51,36 @@ int bgr_aligner_pileup_enable(bgr_aligner* a, uint32_t on) {
         if (rc == BGR_OK) rc = bgr_aligner_abundance_enable(a, 1);   // (its reads column bounds every depth: bgr_aligner_pileup checks it)
         if (rc != BGR_OK) return rc;
     }
-    if (on && !a->pileup_tab) {
-        const int rc = pileup_table_alloc(a, a->pileup, &a->pileup_offs, "bgr_aligner_pileup_enable", "pileup table (20 per base of the graph)");
+    PileupTables& t = a->sh->pileup;
+    if (on && !t.tab) {
+        const int rc = pileup_table_alloc(a, t.table, &t.offs, "bgr_aligner_pileup_enable", "pileup table (20 per base of the graph)");
         if (rc != BGR_OK) return rc;
-        a->pileup_tab = static_cast<uint32_t*>(a->pileup.p);
-        a->pileup_base_offs = static_cast<const uint64_t*>(a->pileup_offs.p);
+        t.tab = t.table.as<uint32_t>();
+        t.base_offs = t.offs.as<const uint64_t>();
     }
-    a->pileup_on = on != 0;
-    pileup_share(a);
+    t.on = on != 0;
     return BGR_OK;
 }
 
 int bgr_aligner_pileup_strands_enable(bgr_aligner* a, uint32_t on) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: null aligner");
     if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_strands_enable: an internal stream of another aligner");
-    bool fresh = false;
-    if (on && !a->pileup_fwd_tab) {   // the second table first: a refusal leaves the aligner as it was
+    PileupTables& t = a->sh->pileup;
+    const bool fresh = on && !t.fwd_tab;
+    if (fresh) {   // the second table first: a refusal leaves the aligner as it was
         int rc = pileup_refusal(a->graph, "bgr_aligner_pileup_strands_enable");
-        if (rc == BGR_OK) rc = pileup_table_alloc(a, a->pileup_fwd, nullptr, "bgr_aligner_pileup_strands_enable", "forward pileup table (20 more per base of the graph)");
+        if (rc == BGR_OK) rc = pileup_table_alloc(a, t.fwd, nullptr, "bgr_aligner_pileup_strands_enable", "forward pileup table (20 more per base of the graph)");
         if (rc != BGR_OK) return rc;
-        a->pileup_fwd_tab = static_cast<uint32_t*>(a->pileup_fwd.p);
-        fresh = true;
+        t.fwd_tab = t.fwd.as<uint32_t>();
     }
     if (on) {
         const int rc = bgr_aligner_pileup_enable(a, 1);   // (as the pileup enables abundance)
         if (rc != BGR_OK) {
-            if (fresh) { a->pileup_fwd.release(); a->pileup_fwd_tab = nullptr; }   // (nothing stays allocated behind a refusal)
+            if (fresh) { t.fwd.release(); t.fwd_tab = nullptr; }   // (nothing stays allocated behind a refusal)
             return rc;
         }
     }
-    a->strands_on = on != 0;
-    pileup_share(a);
+    t.strands_on = on != 0;
     return BGR_OK;
 }
 
@@ -130,12 +122,12 @@ int guarded_sync(bgr_aligner* a, const char* who) {
 }
 // the aligner's table on the host (every stream that adds to it waited for), behind the guard
 static int pileup_snapshot(bgr_aligner* a, const char* who, std::vector<uint32_t>& words, uint64_t* skipped, bool fwd = false) {
-    if (fwd && !a->pileup_fwd_tab) return fail(BGR_E_ARG, std::string(who) + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
-    if (!a->pileup_tab) return fail(BGR_E_ARG, std::string(who) + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
+    if (fwd && !a->sh->pileup.fwd_tab) return fail(BGR_E_ARG, std::string(who) + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
+    if (!a->sh->pileup.tab) return fail(BGR_E_ARG, std::string(who) + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
     const uint64_t n = a->graph->header.n_unitigs, T = a->graph->header.total_bases / 2;
     if (const int rc = guarded_sync(a, who); rc != BGR_OK) return rc;
     words.resize(bgr::pileup_alt_words(T) + bgr::pileup_delta_words(T, n));
-    const uint32_t* tab = fwd ? a->pileup_fwd_tab : a->pileup_tab;
+    const uint32_t* tab = fwd ? a->sh->pileup.fwd_tab : a->sh->pileup.tab;
     if (!words.empty()) HIP_TRY(hipMemcpy(words.data(), tab, words.size() * 4, hipMemcpyDeviceToHost));
     unsigned long long sk = 0;
     HIP_TRY(hipMemcpy(&sk, reinterpret_cast<const char*>(tab) + bgr::pileup_tail_byte(T, n), 8, hipMemcpyDeviceToHost));
@@ -162,10 +154,10 @@ int bgr_aligner_pileup_forward(bgr_aligner* a, bgr_pileup_base* out, uint64_t n_
 int bgr_aligner_reset_pileup(bgr_aligner* a) {
     if (!a) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: null aligner");
     if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_reset_pileup: an internal stream of another aligner");
-    if (!a->pileup.p) return BGR_OK;
+    if (!a->sh->pileup.table.p) return BGR_OK;
     if (const int rc = sync_all(a); rc != BGR_OK) return rc;
-    HIP_TRY(hipMemsetAsync(a->pileup.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
-    if (a->pileup_fwd.p) HIP_TRY(hipMemsetAsync(a->pileup_fwd.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
+    HIP_TRY(hipMemsetAsync(a->sh->pileup.table.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
+    if (a->sh->pileup.fwd.p) HIP_TRY(hipMemsetAsync(a->sh->pileup.fwd.p, 0, bgr::pileup_table_bytes(a->graph->header.total_bases / 2, a->graph->header.n_unitigs), a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     return BGR_OK;   // (the abundance table stays: the guard's column then counts more launches than the pileup holds, which errs on the safe side)
 }
@@ -254,40 +246,27 @@ int bgr_graph_pileup_strands_enable(bgr_graph* g, uint32_t on) {
 
 int bgr_graph_pileup_strands_enabled(const bgr_graph* g) { return g && g->pileup_strands_on ? 1 : 0; }
 
-static int graph_pileup_check(const bgr_graph* g, const char* who) {
-    if (!g->pileup_valid) return fail(BGR_E_ARG, std::string(who) + ": no totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_enable on");
-    return BGR_OK;
+// the totals of the last successful run (fwd: the forward ones) are there
+static int graph_pileup_check(const bgr_graph* g, const char* who, bool fwd = false) {
+    if (g->pileup_valid && (!fwd || g->pileup_fwd_valid)) return BGR_OK;
+    return fail(BGR_E_ARG, std::string(who) + ": no " + (fwd ? "forward " : "") + "totals -- they are those of the last successful bgr_align_all with " + (fwd ? "bgr_graph_pileup_strands_enable" : "bgr_graph_pileup_enable") + " on");
 }
-
-int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) {
-    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup: null argument");
-    const int rc = graph_pileup_check(g, "bgr_graph_pileup");
+static int graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped, bool fwd, const char* who) {
+    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, std::string(who) + ": null argument");
+    const int rc = graph_pileup_check(g, who, fwd);
     if (rc != BGR_OK) return rc;
-    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup: n_bases is not the sum of the graph's unitig lengths");
-    pileup_rows(g, g->pileup_words.data(), out);
+    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, std::string(who) + ": n_bases is not the sum of the graph's unitig lengths");
+    pileup_rows(g, (fwd ? g->pileup_fwd_words : g->pileup_words).data(), out);
     if (skipped) *skipped = g->pileup_skipped;
     return BGR_OK;
 }
-
-static int graph_pileup_fwd_check(const bgr_graph* g, const char* who) {
-    if (!g->pileup_valid || !g->pileup_fwd_valid)
-        return fail(BGR_E_ARG, std::string(who) + ": no forward totals -- they are those of the last successful bgr_align_all with bgr_graph_pileup_strands_enable on");
-    return BGR_OK;
-}
-
-int bgr_graph_pileup_forward(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases) {
-    if (!g || (n_bases && !out)) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: null argument");
-    const int rc = graph_pileup_fwd_check(g, "bgr_graph_pileup_forward");
-    if (rc != BGR_OK) return rc;
-    if (n_bases != g->header.total_bases / 2) return fail(BGR_E_ARG, "bgr_graph_pileup_forward: n_bases is not the sum of the graph's unitig lengths");
-    pileup_rows(g, g->pileup_fwd_words.data(), out);
-    return BGR_OK;
-}
+int bgr_graph_pileup(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases, uint64_t* skipped) { return graph_pileup(g, out, n_bases, skipped, false, "bgr_graph_pileup"); }
+int bgr_graph_pileup_forward(const bgr_graph* g, bgr_pileup_base* out, uint64_t n_bases) { return graph_pileup(g, out, n_bases, nullptr, true, "bgr_graph_pileup_forward"); }
 
 // the writers: host code, deterministic bytes, straight from the graph's totals
 static int pileup_write(const char* path, const bgr_graph* g, bool sites, const char* who, bool strands = false) {
     if (!path || !g) return fail(BGR_E_ARG, std::string(who) + ": null argument");
-    const int rc = strands ? graph_pileup_fwd_check(g, who) : graph_pileup_check(g, who);
+    const int rc = graph_pileup_check(g, who, strands);
     if (rc != BGR_OK) return rc;
     std::vector<bgr_pileup_base> frows(strands ? g->header.max_unitig_len + 1 : 0);
     const uint64_t n = g->header.n_unitigs;

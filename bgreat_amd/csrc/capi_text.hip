@@ -35,7 +35,7 @@ struct TextCall {
 const int kCallDone = 1, kRunAgain = 2;
 
 // TXT_INFO_WORDS u32 behind cursor / counters / CSR total -- two such blocks, taken in turn (text_epochs.h)
-uint32_t* info_block(const bgr_aligner* a, uint32_t which) { return reinterpret_cast<uint32_t*>(a->small.as<char>() + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * which); }
+uint32_t* info_block(const bgr_aligner* a, uint32_t which) { return reinterpret_cast<uint32_t*>(a->launch.small.as<char>() + bgr::kSmallTextInfo + bgr::kSmallTextInfoBytes * which); }
 static_assert(TXT_INFO_WORDS * 4 == bgr::kSmallTextInfoBytes, "two info blocks at small + kSmallTextInfo");
 // tickets and chains of the two one-launch kernels (text_kernels.hip) in TextRoute::state: never cleared between launches -- every launch gets a fresh epoch
 uint32_t* tickets_of(const TextRoute& t) { return t.state.as<uint32_t>(); }
@@ -44,16 +44,16 @@ uint64_t* chains_of(const TextRoute& t) { return reinterpret_cast<uint64_t*>(t.s
 // ---- bgr_aligner_fetch_text ---------------------------------------------------------------------------------------------------------
 // The write launch of the piece in the buffers, by its kind of output: the streams into pout / nout from the offsets its sizes were scanned into.
 hipError_t write_gaf(const bgr_aligner* a, const TextRoute& t) {
-    return bgr::launch_text_gaf_write(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
+    return bgr::launch_text_gaf_write(a->dg, t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
                                       t.noff.as<uint32_t>(), t.psz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), t.pout.as<uint8_t>(), t.nout.as<uint8_t>(),
                                       t.tagged ? t.tags.as<uint4>() : nullptr, t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream);
 }
 hipError_t write_corrected(const bgr_aligner* a, const TextRoute& t) {
-    return bgr::launch_text_correct_write(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc,
+    return bgr::launch_text_correct_write(a->dg, t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc,
                                           t.poff.as<uint32_t>(), t.noff.as<uint32_t>(), t.idx.as<uint32_t>(), t.pout.as<uint8_t>(), t.nout.as<uint8_t>(), a->stream);
 }
 hipError_t write_records(const bgr_aligner* a, const TextRoute& t) {
-    return bgr::launch_text_write(t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
+    return bgr::launch_text_write(t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
                                   t.noff.as<uint32_t>(), t.pout.as<uint8_t>(), t.nout.as<uint8_t>(), a->stream);
 }
 
@@ -175,7 +175,7 @@ int parse_piece(TextCall& c) {
     const uint32_t epoch = t.epochs.next_epoch();
     if (!epoch) return fail(BGR_E_INTERNAL, "bgr_align_fasta_text: more launches than the epochs reserved for a call");
     const hipError_t e = bgr::launch_text_parse(t.text, c.nbytes, c.rec_lines, a->dg.k, tickets_of(t), t.epochs.ticket_base(TextEpochs::kParse), epoch, chains_of(t), t.rec.as<uint4>(),
-                                                t.idx.as<uint32_t>(), t.accrec.as<uint32_t>(), t.accsrc.as<uint32_t>(), t.offs.as<uint64_t>(), c.info, c.R_cap, a->small.as<uint32_t>(),
+                                                t.idx.as<uint32_t>(), t.accrec.as<uint32_t>(), t.accsrc.as<uint32_t>(), t.offs.as<uint64_t>(), c.info, c.R_cap, a->launch.small.as<uint32_t>(),
                                                 bgr::kCurWords, info_next, TXT_INFO_WORDS, a->stream);
     if (e != hipSuccess) return launched(e, "text record launches");
     t.epochs.commit_flip();
@@ -204,13 +204,13 @@ int gaf_sizes(TextCall& c) {
     bgr_aligner* a = c.a;
     TextRoute& t = a->text;
     HIP_TRY(t.gaf.ensure(((uint64_t)c.n_acc + 1) * 16));
-    t.tagged = a->haplotag.p != nullptr;   // (an aligner with a tag table: the tagged instances of both GAF kernels)
+    t.tagged = a->tag.table.p != nullptr;   // (an aligner with a tag table: the tagged instances of both GAF kernels)
     if (t.tagged) HIP_TRY(t.tags.ensure(((uint64_t)c.n_acc + 1) * 16));
     t.with_cs = a->gaf_cs;                 // (bgr_aligner_gaf_cs_enable: the instances whose lines end in the cs:Z: field)
     if (t.with_cs) HIP_TRY(t.cs.ensure(((uint64_t)c.n_acc + 1) * 4));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.info + TXT_INFO_BUG), -1, 1, a->stream));
-    return launched(bgr::launch_text_gaf_sizes(a->dg, t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
-                                               t.nsz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), c.info + TXT_INFO_BUG, t.tagged ? a->haplotag.as<uint32_t>() : nullptr,
+    return launched(bgr::launch_text_gaf_sizes(a->dg, t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
+                                               t.nsz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), c.info + TXT_INFO_BUG, t.tagged ? a->tag.table.as<uint32_t>() : nullptr,
                                                t.tags.as<uint4>(), t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream),
                     "text size launches");
 }
@@ -218,7 +218,7 @@ int correct_sizes(TextCall& c) {
     bgr_aligner* a = c.a;
     TextRoute& t = a->text;
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.info + TXT_INFO_BUG), -1, 1, a->stream));
-    return launched(bgr::launch_text_correct_sizes(a->dg, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
+    return launched(bgr::launch_text_correct_sizes(a->dg, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
                                                    t.nsz.as<uint32_t>(), t.idx.as<uint32_t>(), c.info + TXT_INFO_BUG, a->stream),
                     "text size launches");
 }
@@ -233,7 +233,7 @@ int format_streams(TextCall& c) {
     HIP_TRY(t.nout.ensure(c.ncap_dev + 64));
     const uint32_t epoch = t.epochs.next_epoch();
     if (!epoch) return fail(BGR_E_INTERNAL, "bgr_align_fasta_text: more launches than the epochs reserved for a call");
-    const hipError_t e = bgr::launch_text_format(t.text, a->results.as<uint2>(), a->arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, tickets_of(t) + 1,
+    const hipError_t e = bgr::launch_text_format(t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, tickets_of(t) + 1,
                                                  t.epochs.ticket_base(TextEpochs::kFormat), epoch, chains_of(t), t.poff.as<uint32_t>(), t.noff.as<uint32_t>(), t.pout.as<uint8_t>(),
                                                  t.nout.as<uint8_t>(), c.pcap_dev, c.ncap_dev, c.info, a->stream);
     if (c.n_acc && e == hipSuccess) t.epochs.took_tickets(TextEpochs::kFormat, bgr::format_tiles(c.n_acc));   // (as many tickets as workgroups ran: launch_text_format launches nothing for zero reads)
@@ -260,13 +260,13 @@ int format_once(TextCall& c) {
     bgr_text_batch* b = c.b;
     if (b->record_info_out) {  // what became of every record (the -b progress blocks of the caller), on its way to the host behind the mapping launch
         HIP_TRY(t.info.ensure((uint64_t)c.R * 4));
-        const hipError_t e = bgr::launch_text_record_info(t.rec.as<uint4>(), t.idx.as<uint32_t>(), a->results.as<uint2>(), c.R, t.info.as<uint32_t>(), a->stream);
+        const hipError_t e = bgr::launch_text_record_info(t.rec.as<uint4>(), t.idx.as<uint32_t>(), a->launch.results.as<uint2>(), c.R, t.info.as<uint32_t>(), a->stream);
         if (e != hipSuccess) return launched(e, "record info launch");
         HIP_TRY(hipMemcpyAsync(b->record_info_out, t.info.p, (size_t)c.R * 4, hipMemcpyDeviceToHost, a->stream));
     }
     if (!b->want_output) {  // counters only: the launch still has to be settled
         uint32_t cur[bgr::kCurWords];
-        HIP_TRY(hipMemcpyAsync(cur, a->small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipMemcpyAsync(cur, a->launch.small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
         HIP_TRY(wait_stream(a));
         const int rc = settle_text_launch(a, cur);
         if (rc == kRunAgain && b->record_info_out) return kRunAgain;  // (the record info was made from results that were not final)
@@ -281,9 +281,9 @@ int format_once(TextCall& c) {
         if (rc != BGR_OK) return rc;
     }
     uint32_t all[bgr::kSmallBytes / 4];   // the cursor block (at its start) and the info block lie in the same `small` buffer: one copy
-    HIP_TRY(hipMemcpyAsync(all, a->small.p, sizeof(all), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipMemcpyAsync(all, a->launch.small.p, sizeof(all), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
-    memcpy(c.h, all + (c.info - a->small.as<uint32_t>()), sizeof(c.h));
+    memcpy(c.h, all + (c.info - a->launch.small.as<uint32_t>()), sizeof(c.h));
     c.lap(2);
     return settle_text_launch(a, all);   // (kRunAgain: sizes and offsets once more, from the final results)
 }
@@ -324,10 +324,6 @@ int bgr_graph_gaf_cs_enable(bgr_graph* g, int on) {
 }
 
 int bgr_graph_gaf_cs_enabled(const bgr_graph* g) { return g && g->gaf_cs_on ? 1 : 0; }
-
-// what a whole run calls (run_counts.h, registered by capi_abundance.hip)
-int run_gaf_cs_wanted(const bgr_graph* g) { return bgr_graph_gaf_cs_enabled(g); }
-int run_gaf_cs_enable(bgr_aligner* a, int on) { return bgr_aligner_gaf_cs_enable(a, on); }
 
 int bgr_aligner_fetch_text(bgr_aligner* a, bgr_text_batch* b) {
     if (!a || !b) return fail(BGR_E_ARG, "bgr_aligner_fetch_text: null argument");
@@ -396,8 +392,8 @@ int bgr_align_fasta_text(bgr_aligner* a, const bgr_params* p, bgr_text_batch* b)
     if (p->mode == BGR_MODE_EXHAUSTIVE && !bgr::opt("test.keep_rows")) {
         // The last pass writes no row for a read it hands back (exhaustive_kernels.hip), and format_once reads the rows before the launch is settled: until
         // then they say "no path", not what the buffer held (a new aligner's first piece, a buffer that grew: a row of anything sends the format kernel anywhere)
-        HIP_TRY(a->results.ensure((uint64_t)c.n_acc * 8));
-        HIP_TRY(hipMemsetAsync(a->results.p, 0, (uint64_t)c.n_acc * 8, a->stream));
+        HIP_TRY(a->launch.results.ensure((uint64_t)c.n_acc * 8));
+        HIP_TRY(hipMemsetAsync(a->launch.results.p, 0, (uint64_t)c.n_acc * 8, a->stream));
     }
     rc = align_device_impl(a, p, t.text, t.offs.p, c.n_acc, c.bases, c.max_len, false, t.accsrc.p, c.nbytes, true);
     if (rc != BGR_OK) return rc;

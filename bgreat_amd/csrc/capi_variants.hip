@@ -101,11 +101,11 @@ static int aligner_sites(bgr_aligner* a, const bgr_variant_strand_params* params
     if (a->is_twin) return fail(BGR_E_ARG, who + ": an internal stream of another aligner");
     if (!bgr::variants_params_ok(bgr_variant_params{params->min_depth, params->min_alt, params->min_af_ppm}))
         return fail(BGR_E_ARG, who + ": thresholds out of range (min_depth >= 1, min_alt >= 1, min_af_ppm <= 1000000)");
-    if (strands && (!a->pileup_tab || !a->pileup_fwd_tab)) return fail(BGR_E_ARG, who + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
-    if (!a->pileup_tab) return fail(BGR_E_ARG, who + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
+    if (strands && (!a->sh->pileup.tab || !a->sh->pileup.fwd_tab)) return fail(BGR_E_ARG, who + ": strands were never counted on this aligner (bgr_aligner_pileup_strands_enable)");
+    if (!a->sh->pileup.tab) return fail(BGR_E_ARG, who + ": the pileup was never enabled on this aligner (bgr_aligner_pileup_enable)");
     if (const int rc = guarded_sync(a, who.c_str()); rc != BGR_OK) return rc;
-    return variants_call<Site>(a->dg, a->graph, a->pileup_tab, a->pileup_fwd_tab, a->pileup_base_offs, *params, a->var_scratch, a->var_out, a->stream, who.c_str(), nullptr, out, cap, n,
-                               a->knob_no_events ? nullptr : a->var_ms);
+    return variants_call<Site>(a->dg, a->graph, a->sh->pileup.tab, a->sh->pileup.fwd_tab, a->sh->pileup.base_offs, *params, a->var.scratch, a->var.out, a->stream, who.c_str(), nullptr, out, cap, n,
+                               a->sh->knob_no_events ? nullptr : a->var_ms);
 }
 int bgr_aligner_pileup_sites(bgr_aligner* a, const bgr_variant_params* params, bgr_variant_site* out, uint64_t cap, uint64_t* n) {
     const bgr_variant_strand_params sp = {params ? params->min_depth : 0, params ? params->min_alt : 0, params ? params->min_af_ppm : 0, 0};
@@ -125,43 +125,43 @@ int bgr_aligner_pileup_add(bgr_aligner* dst, bgr_aligner* src) {
     if (!dst || !src) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: null aligner");
     if (dst->is_twin || src->is_twin) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: an internal stream of another aligner");
     if (dst == src || dst->graph != src->graph) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: two different aligners of one graph are needed");
-    if (!dst->pileup_tab || !src->pileup_tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: the pileup was never enabled on one of the aligners (bgr_aligner_pileup_enable)");
-    if (!dst->pileup_fwd_tab != !src->pileup_fwd_tab)
+    if (!dst->sh->pileup.tab || !src->sh->pileup.tab) return fail(BGR_E_ARG, "bgr_aligner_pileup_add: the pileup was never enabled on one of the aligners (bgr_aligner_pileup_enable)");
+    if (!dst->sh->pileup.fwd_tab != !src->sh->pileup.fwd_tab)
         return fail(BGR_E_ARG, "bgr_aligner_pileup_add: one of the aligners has a forward table (bgr_aligner_pileup_strands_enable) and the other has none");
     if (const int rc = sync_all(src); rc != BGR_OK) return rc;
     if (const int rc = sync_all(dst); rc != BGR_OK) return rc;   // (the current device is dst's from here on)
     const uint64_t bytes = bgr::pileup_table_bytes(dst->graph->header.total_bases / 2, dst->graph->header.n_unitigs);
-    const int rc = variants_table_add(dst->pileup_tab, dst->device, src->pileup_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
-    if (rc != BGR_OK || !dst->pileup_fwd_tab) return rc;
-    return variants_table_add(dst->pileup_fwd_tab, dst->device, src->pileup_fwd_tab, src->device, bytes, dst->var_stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
+    const int rc = variants_table_add(dst->sh->pileup.tab, dst->device, src->sh->pileup.tab, src->device, bytes, dst->var.stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
+    if (rc != BGR_OK || !dst->sh->pileup.fwd_tab) return rc;
+    return variants_table_add(dst->sh->pileup.fwd_tab, dst->device, src->sh->pileup.fwd_tab, src->device, bytes, dst->var.stage, (uint32_t)dst->num_cus, dst->stream, "bgr_aligner_pileup_add");
 }
 
 // a run's aligner, its streams idle from here on: the first one's table becomes the run's (the buffers move: nothing is allocated), the others' are added
 int variants_collect(bgr_graph* g, bgr_aligner* a) {
-    if (!a->pileup_tab) return fail(BGR_E_ARG, "bgr_align_all: the pileup was never enabled on an aligner of the run");
+    if (!a->sh->pileup.tab) return fail(BGR_E_ARG, "bgr_align_all: the pileup was never enabled on an aligner of the run");
     const bool strands = g->variants_strands_on;   // the forward table travels with the total one
-    if (strands && !a->pileup_fwd_tab) return fail(BGR_E_ARG, "bgr_align_all: strands were never counted on an aligner of the run");
+    if (strands && !a->sh->pileup.fwd_tab) return fail(BGR_E_ARG, "bgr_align_all: strands were never counted on an aligner of the run");
     if (const int rc = sync_all(a); rc != BGR_OK) return rc;
     std::lock_guard<std::mutex> l(g->abundance_m);   // (the lanes of a split run end side by side: one at a time here)
     if (!g->variants_run) {
         VariantsRun* r = new VariantsRun();
         r->device = a->device; r->num_cus = a->num_cus; r->dg = a->dg;
         if (hipStreamCreate(&r->stream) != hipSuccess) { delete r; (void)hipGetLastError(); return fail(BGR_E_HIP, "bgr_align_all: a stream for the run's pileup table"); }
-        std::swap(r->table, a->pileup);
-        std::swap(r->offs, a->pileup_offs);
-        if (strands) { std::swap(r->table_fwd, a->pileup_fwd); a->pileup_fwd_tab = nullptr; a->strands_on = false; }
-        a->pileup_tab = nullptr; a->pileup_base_offs = nullptr; a->pileup_on = false;
-        pileup_share(a);
-        g->variants_run = r;
+        PileupTables& t = a->sh->pileup;   // (the aligner's twins read the same block: the tables are gone for them too)
+        std::swap(r->table, t.table);
+        std::swap(r->offs, t.offs);
+        if (strands) { std::swap(r->table_fwd, t.fwd); t.fwd_tab = nullptr; t.strands_on = false; }
+        t.tab = nullptr; t.base_offs = nullptr; t.on = false;
+            g->variants_run = r;
         return BGR_OK;
     }
     VariantsRun* r = g->variants_run;
     HIP_TRY(hipSetDevice(r->device));
     const uint64_t bytes = bgr::pileup_table_bytes(g->header.total_bases / 2, g->header.n_unitigs);
-    const int rc = variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->pileup_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
+    const int rc = variants_table_add(static_cast<uint32_t*>(r->table.p), r->device, a->sh->pileup.tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
     if (rc != BGR_OK || !strands) return rc;
     if (!r->table_fwd.p) return fail(BGR_E_INTERNAL, "bgr_align_all: the run's pileup table has no forward table");
-    return variants_table_add(static_cast<uint32_t*>(r->table_fwd.p), r->device, a->pileup_fwd_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
+    return variants_table_add(static_cast<uint32_t*>(r->table_fwd.p), r->device, a->sh->pileup.fwd_tab, a->device, bytes, r->stage, (uint32_t)r->num_cus, r->stream, "bgr_align_all");
 }
 // the run's end: behind the guard of the summed abundance the passes run once on the run's table; the table is freed whatever happens
 int variants_end(bgr_graph* g, bool ok) {

@@ -23,12 +23,15 @@ MAXLEN = 200
 class Case:
     """graph, four batches (host + device) and what the oracle says of each; made once per (k, mode), never changed"""
 
-    def __init__(self, k, mode):
+    def __init__(self, k, mode, inside=False):
         rng = np.random.default_rng(100 + k)
-        s = Synth(60000, max(40, 2 * k), 2, k, 700 + k)
+        # (inside: unitigs of about 400 bases, as in test_gpu_inside.py -- many of the reads then lie inside one and have no anchor -- and the inside index)
+        s = Synth(60000, 400 if inside else max(40, 2 * k), 2, k, 700 + k)
         self.seqs, self.offs = s.unitigs()
         self.k, self.mode = k, mode
         self.graph = B.Graph.build(k, self.seqs, self.offs, anchors=(mode == B.MODE_ANCHORS))
+        if inside:
+            self.graph.inside_build()
         orc = oracle_py.Oracle(k, self.seqs, self.offs, anchors=(mode == B.MODE_ANCHORS))
         self.batches, self.want, self.dev = [], [], []
         self.counters = dict.fromkeys(["reads", "no_overlap", "aligned", "not_aligned", "overlaps"], 0)
@@ -73,8 +76,8 @@ class Case:
 
 
 @functools.lru_cache(maxsize=None)
-def case(k, mode=B.MODE_GREEDY):
-    return Case(k, mode)
+def case(k, mode=B.MODE_GREEDY, inside=False):
+    return Case(k, mode, inside)
 
 
 def same(got, want):
@@ -172,6 +175,12 @@ FEATURES = {
     "links": (lambda al: al.links_enable(), lambda al: al.links().tobytes()),
     "triples": (lambda al: al.triples_enable(), lambda al: al.triples().tobytes()),
     "pileup": (lambda al: al.pileup_enable(), lambda al: al.pileup()[0].tobytes() + al.abundance().tobytes()),
+    "strands": (lambda al: al.pileup_strands_enable(), lambda al: al.pileup_forward().tobytes()),
+    # (on a graph of its own, with the inside index: what the pass mapped, and the rows of the last batch with those it wrote.  With the reads packed by
+    # the pre-pass: behind a launch that stages them from the characters the pass does not map the same reads from run to run at this size, on one stream
+    # too -- 47 170 to 47 304 of the long launch's 74 800 reads in five runs, 48 788 every time from the planes -- so that form has nothing to compare)
+    "inside": (lambda al: (al.set_knob(B.KNOB_GREEDY_PREPASS, 1), al.inside_enable()),
+               lambda al: al.inside_count().to_bytes(8, "little") + b"".join(x.tobytes() for x in al.fetch(SIZES[3], SIZES[3] * (MAXLEN + 8) + 8))),
 }
 
 
@@ -180,7 +189,7 @@ FEATURES = {
 def test_counting_features(k, feature):
     """(d) the feature's table behind un-waited launches (a long one in front, so that both streams count) is, byte for byte, that of an aligner
     that keeps every launch on its own stream; enabled on an aligner whose twin already exists"""
-    c = case(k)
+    c = case(k, inside=(feature == "inside"))
     enable, read = FEATURES[feature]
     ref = c.aligner(overlap=False)
     enable(ref)
@@ -196,6 +205,69 @@ def test_counting_features(k, feature):
     want = read(ref)
     assert read(al) == want and any(want)
     assert al.counters()["reads"] == ref.counters()["reads"] + SIZES[0] + c.long[2]
+    if feature == "inside":
+        assert ref.inside_count() > 0
+
+
+def _twin_in_place(c, al):
+    """-> the aligner's own device pointers; its twin exists from here on and both streams are idle"""
+    c.launch_long(al)   # (sizes the buffers: nothing grows afterwards)
+    al.sync()
+    own = al.device_results()
+    c.launch_long(al)
+    c.launch(al, 0)
+    al.sync()
+    return own
+
+
+@pytest.mark.parametrize("k", [31, 12])
+def test_switching_off_after_the_twin_exists(k):
+    """links and the pileup enabled, the launch sequence, both disabled, the sequence again: the tables stay as they were after the first sequence, and
+    they and the abundance (which stays on) are, byte for byte, those of an aligner that keeps every launch on its own stream and did the same"""
+    c = case(k)
+
+    def tables(x):
+        return x.links().tobytes(), x.pileup()[0].tobytes(), x.abundance().tobytes()
+
+    got = []
+    for x in (c.aligner(overlap=False), c.aligner()):
+        _twin_in_place(c, x)
+        snaps = []
+        for on in (True, False):
+            x.links_enable(on)
+            x.pileup_enable(on)
+            c.launch_long(x)
+            for i in range(4):
+                c.launch(x, i)
+            snaps.append(tables(x))
+        got.append(snaps)
+    ref, al = got
+    assert al[0] == ref[0] and all(any(t) for t in ref[0])
+    assert al[1] == ref[1]
+    assert al[1][:2] == al[0][:2] and al[1][2] != al[0][2]   # (switched off: nothing added to links and pileup; the abundance went on counting)
+
+
+@pytest.mark.parametrize("k", [31, 12])
+def test_a_knob_set_after_the_twin_exists_reaches_the_twin(k):
+    """BGR_KNOB_GREEDY_FAST set on an aligner whose twin exists: the launch the twin takes is the lone aligner's with the same knob -- the general
+    kernel alone, another geometry than the default's -- and its rows are the oracle's"""
+    c = case(k)
+    default = c.aligner()
+    c.launch(default, 1)
+    lone = c.aligner()
+    lone.set_knob(B.KNOB_GREEDY_FAST, 1)
+    c.launch(lone, 1)
+    want_pass, want_info = lone.pass_counts(), lone.launch_info()
+    assert want_info != default.launch_info(), want_info   # (the knob shows in what is compared below)
+    al = c.aligner()
+    own = _twin_in_place(c, al)
+    al.set_knob(B.KNOB_GREEDY_FAST, 1)
+    c.launch_long(al)
+    c.launch(al, 1)
+    other = al.device_results()
+    assert all(other) and all(o != p for o, p in zip(other, own)), (own, other)   # (the twin took the launch)
+    assert al.launch_info() == want_info and al.pass_counts() == want_pass
+    assert same(c.fetch(al, 1), c.want[1])
 
 
 def test_anchors_mode():

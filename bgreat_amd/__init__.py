@@ -54,6 +54,7 @@ SYMBOLS = [
     "bgr_graph_pileup_forward", "bgr_graph_variants_strands_enable", "bgr_graph_variant_strand_sites", "bgr_write_pileup_strands", "bgr_write_vcf_strands", "bgr_parse_min_alt_strand",
     "bgr_graph_inside_build", "bgr_graph_inside_info", "bgr_graph_inside_lookup", "bgr_aligner_inside_enable", "bgr_aligner_inside_count",
     "bgr_graph_inside_enable", "bgr_graph_inside_enabled", "bgr_graph_inside_count",
+    "bgr_aligner_exhaustive_paths_enable", "bgr_aligner_device_rows_view", "bgr_graph_exhaustive_paths_enable", "bgr_graph_exhaustive_paths_enabled",
 ]
 KNOB_EXH_FRAME_CAP, KNOB_EXH_SEARCH, KNOB_BATCH_SPLIT_LIMIT, KNOB_DEBUG_STOP, KNOB_GREEDY_FAST, KNOB_EXH_FAST, KNOB_ANCHORS_FAST, KNOB_BATCH_OVERLAP, KNOB_EXH_MEMO_CAP, KNOB_GREEDY_PREPASS, KNOB_KERNEL_EVENTS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 KNOB_ABUNDANCE_FORM = 12
@@ -369,6 +370,10 @@ def lib():
     L.bgr_aligner_gaf_cs_enable.argtypes = [vp, C.c_int]
     L.bgr_graph_gaf_cs_enable.argtypes = [vp, C.c_int]
     L.bgr_graph_gaf_cs_enabled.argtypes = [vp]
+    L.bgr_aligner_exhaustive_paths_enable.argtypes = [vp, C.c_int]
+    L.bgr_aligner_device_rows_view.argtypes = [vp, C.POINTER(vp)]
+    L.bgr_graph_exhaustive_paths_enable.argtypes = [vp, C.c_int]
+    L.bgr_graph_exhaustive_paths_enabled.argtypes = [vp]
     L.bgr_graph_inside_build.argtypes = [vp]
     L.bgr_graph_inside_info.argtypes = [vp, C.POINTER(InsideInfo)]
     L.bgr_graph_inside_lookup.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -869,6 +874,15 @@ class Graph:
         """bgr_graph_gaf_cs_enabled: the switch as it stands."""
         return bool(lib().bgr_graph_gaf_cs_enabled(self.h))
 
+    def exhaustive_paths_enable(self, on=True):
+        """bgr_graph_exhaustive_paths_enable: sticky -- a later align_all in exhaustive mode writes GAF lines (gaf) and counts what the graph's switches ask
+        for, from the paths exhaustive mode finds (their end offset dropped)."""
+        _check(lib().bgr_graph_exhaustive_paths_enable(self.h, int(bool(on))))
+
+    def exhaustive_paths_enabled(self):
+        """bgr_graph_exhaustive_paths_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_exhaustive_paths_enabled(self.h))
+
     def links_bound(self):
         """bgr_graph_links_bound: how many distinct links any rows on this graph can hold (the table of links has at least twice as many slots)."""
         b = C.c_uint64(0)
@@ -1063,6 +1077,19 @@ class Aligner:
         """bgr_aligner_gaf_cs_enable: the GAF lines of align_fasta_text (want_output=3) end in the cs:Z: field from now on."""
         _check(lib().bgr_aligner_gaf_cs_enable(self.h, int(bool(on))))
 
+    def exhaustive_paths_enable(self, on=True):
+        """bgr_aligner_exhaustive_paths_enable: exhaustive launches are counted (abundance, links, triples, pileup) once they are settled, path_stats,
+        path_diffs and haplotags accept an exhaustive last launch, and align_fasta_text writes GAF lines in exhaustive mode -- all through the view
+        of the rows without their end offset."""
+        _check(lib().bgr_aligner_exhaustive_paths_enable(self.h, int(bool(on))))
+
+    def device_rows_view(self):
+        """bgr_aligner_device_rows_view -> the device pointer of the view of the last (exhaustive) launch: uint2 per read, as device_results()' first
+        pointer with every mapped row one int shorter (valid until the next launch)."""
+        v = C.c_void_p()
+        _check(lib().bgr_aligner_device_rows_view(self.h, C.byref(v)))
+        return v.value
+
     def haplotag_enable(self, table):
         """bgr_aligner_haplotag_enable: `table` (n_unitigs + 1 uint32) onto the aligner's device -- haplotags() and the GAF lines of align_fasta_text
         are tagged from it; None switches it off and frees the copy."""
@@ -1252,14 +1279,23 @@ class Aligner:
 
 def align_all(graph, reads_csv, paths_file, notaligned_file, m=2, effort=2, mode=MODE_GREEDY, partial=False, n_gpus=1, threads=1,
               batch_reads=0, chunk_bytes=0, fastq=False, write_exhaustive=False, correction=False, no_overlap_file=None, first_device=0, route=0, numa=0, split_output=False,
-              gaf=False, abundance=False, links=None, pileup=None):
+              gaf=False, abundance=False, links=None, pileup=None, exhaustive_paths=None):
     """Aligner::alignAll (aligner.cpp:550-597) as one call -> (counters dict, mapping seconds).  route: 0 = FASTA goes through the device as
     text when it can (bgr_align_fasta_text), 1 = host parser + host formatter always.  split_output: one pipeline per device, device d
     writing `<paths_file>.<d>` / `<notaligned_file>.<d>` (their concatenation = the single-file bytes).  gaf: the paths file holds one GAF line per
     mapped read instead of header + path ints (bgr_run_options.gaf: greedy modes, ACGT-only unitigs, not with correction).  abundance: count per unitig the reads, bases and k-mers mapped onto it
     (bgr_run_options.abundance; greedy modes); Graph.abundance() then has the run's totals.  links: True / False sets the graph's switch (Graph.links_enable) for this call and puts it back
     afterwards -- the run counts unitig abundance and links, Graph.abundance() and Graph.links() then have its totals; None leaves the switch as it is.
-    pileup: likewise the graph's pileup switch (Graph.pileup_enable); Graph.pileup() then has the run's per-base totals."""
+    pileup: likewise the graph's pileup switch (Graph.pileup_enable); Graph.pileup() then has the run's per-base totals.
+    exhaustive_paths: likewise the graph's switch of the same name (Graph.exhaustive_paths_enable): a run in exhaustive mode then takes gaf and the counting switches."""
+    if exhaustive_paths is not None:
+        before = graph.exhaustive_paths_enabled()
+        graph.exhaustive_paths_enable(exhaustive_paths)
+        try:
+            return align_all(graph, reads_csv, paths_file, notaligned_file, m, effort, mode, partial, n_gpus, threads, batch_reads, chunk_bytes, fastq, write_exhaustive,
+                             correction, no_overlap_file, first_device, route, numa, split_output, gaf, abundance, links, pileup)
+        finally:
+            graph.exhaustive_paths_enable(before)
     if pileup is not None:
         before = graph.pileup_enabled()
         graph.pileup_enable(pileup)

@@ -35,6 +35,7 @@
 #include "options.h"
 #include "capi_internal.h"
 #include "inside_kernels.h"
+#include "exhaustive_rows_kernels.h"
 
 namespace bgr {
 static thread_local std::string tl_err;
@@ -549,10 +550,11 @@ struct LaunchMarks {
     bgr_aligner* a;
     bool timed;
     int marks = 0;
+    int launch = -1;   // the launch's place in the ring (-1: the one being queued, a->ev_used; else one whose kernels behind its settling join it)
     hipError_t operator()(const char* name) {
         if (!timed || marks >= kTimerSlots) return hipSuccess;
         a->t_slot_name[marks] = name;
-        return hipEventRecord(a->ev[a->ev_used][++marks], a->stream);
+        return hipEventRecord(a->ev[launch < 0 ? a->ev_used : launch][++marks], a->stream);
     }
 };
 
@@ -565,7 +567,8 @@ struct BehindPasses {
     uint64_t n_reads, total_bases;
     bgr::PileupReads reads;      // the read characters where this launch has them
     uint32_t arena_own = 0, max_read_len = 0, max_mismatch = 0;   // (the inside pass)
-    const uint2* rows() const { return a->launch.results.as<uint2>(); }
+    const uint2* view = nullptr; // an exhaustive launch (bgr_aligner_exhaustive_paths_enable): its rows without their end offset, a->launch.rows_view
+    const uint2* rows() const { return view ? view : a->launch.results.as<uint2>(); }
     const int32_t* arena() const { return a->launch.arena.as<int32_t>(); }
 };
 // The inside pass (bgr_aligner_inside_enable) over the reads the passes left without an anchor
@@ -656,8 +659,8 @@ static int launch_refusal(const bgr_aligner* a, const bgr_params* p, uint64_t n_
     if (p->mode != BGR_MODE_GREEDY && a->graph->header.wide_keys)
         return fail(BGR_E_ARG, "bgr_align_device: a graph with k > 32 (two-word keys) maps in greedy mode only; exhaustive mode (-b) needs k <= 32");
     for (const bool writes_rows : {false, true})   // (the counting features first, then the pass that writes rows: the order the refusals have always had)
-        for (const LaunchFeature& f : kBehindPasses)
-            if (f.writes_rows == writes_rows && p->mode == BGR_MODE_EXHAUSTIVE && f.on(*a->sh))
+        for (const LaunchFeature& f : kBehindPasses)   // (bgr_aligner_exhaustive_paths_enable: the counting features read an exhaustive launch through its view; the inside pass writes greedy rows)
+            if (f.writes_rows == writes_rows && p->mode == BGR_MODE_EXHAUSTIVE && f.on(*a->sh) && !(a->sh->exhaustive_paths && !f.writes_rows))
                 return fail(BGR_E_ARG, std::string("bgr_align_device: this aligner ") + f.what + " of the greedy modes; exhaustive mode (-b) is refused");
     if (a->sh->inside_tab && n_reads && max_read_len > bgr::kInsideMaxReadLen)
         return fail(BGR_E_ARG, "bgr_align_device: this aligner runs the inside pass (bgr_aligner_inside_enable), which takes reads of at most 32 000 characters");
@@ -805,11 +808,23 @@ static int launch_passes(const LaunchJob& j, LaunchMarks& mark) {
 
 // Behind the last pass: the inside pass, then the counting kernels (kBehindPasses) -- in stream order in front of everything that reads the rows -- with the
 // read characters where this launch has them: the ASCII bytes when the mapping kernels packed them themselves, else the 2-bit planes (host-packed or pre-pass)
+// An exhaustive launch (bgr_aligner_exhaustive_paths_enable; without the switch launch_refusal has left no feature on): its last pass writes no row for a read
+// it hands back, and settle_launch maps those again -- the rows are final, and every read is counted exactly once, only behind that.  So nothing is queued
+// here: what the counting kernels are handed is kept in a->deep_count, and settle_launch queues the view kernel and them (count_settled).
 static int launch_behind_passes(const LaunchJob& j, LaunchMarks& mark) {
     BehindPasses c{j.a, j.P.arena_cap, j.io.read_offs, j.n_reads, j.total_bases, {}, j.io.arena_own, j.max_read_len, j.p->max_mismatch};
     if (j.inline_pack) { c.reads.ascii = static_cast<const uint8_t*>(j.d_reads); c.reads.src_off = static_cast<const uint32_t*>(j.d_src_off); c.reads.ascii_bytes = j.reads_bytes; }
     else { c.reads.fw3 = j.io.fw3; c.reads.nmw = j.io.nmw; c.reads.hasn = j.io.hasn; }
-    return queue_behind_passes(c, j.keep_rows, mark);
+    if (j.p->mode != BGR_MODE_EXHAUSTIVE) return queue_behind_passes(c, j.keep_rows, mark);
+    bool counting = false;
+    for (const LaunchFeature& f : kBehindPasses) counting = counting || (!f.writes_rows && f.on(*j.a->sh));
+    if (!counting) return BGR_OK;
+    HIP_TRY(j.a->launch.rows_view.ensure(j.n_reads * 8));
+    bgr_aligner::DeepCount& C = j.a->deep_count;
+    C.open = true;
+    C.arena_cap = c.arena_cap; C.n_reads = c.n_reads; C.total_bases = c.total_bases; C.read_offs = c.read_offs; C.reads = c.reads;
+    C.ev_launch = -1; C.marks = 0;   // (align_device_impl sets them once the launch has its place in the ring)
+    return BGR_OK;
 }
 
 // The mapping launch of one batch.  planes_ready: the aligner's 2-bit planes (pk_fw3 / pk_nm / pk_hasn) already hold the batch
@@ -819,6 +834,9 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
                              uint64_t total_bases, uint32_t max_read_len, bool planes_ready, const void* d_src_off = nullptr, uint64_t reads_bytes = 0,
                              bool cursor_is_zero = false) {
     if (const int rc = launch_refusal(a, p, n_reads, max_read_len); rc != BGR_OK) return rc;
+    // an exhaustive launch whose counting is still to come (bgr_aligner_exhaustive_paths_enable) is settled and counted before its buffers are written again
+    if (a->deep_count.open) { if (const int rc = settle_pending(a); rc != BGR_OK) return rc; }
+    a->view_ready = false;
     a->holder = nullptr;   // (a launch on the aligner's own stream and buffers; bgr_align_device names the twin behind this call when that took it)
     a->last_n = n_reads; a->last_mode = p->mode;
     a->deep.open = false; a->deep.runs = 0; a->deep.memo_cap = 0;
@@ -841,10 +859,38 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
     if (const int rc = launch_passes(j, mark); rc != BGR_OK) return rc;
     if (const int rc = launch_behind_passes(j, mark); rc != BGR_OK) return rc;
     if (timed) {
+        if (a->deep_count.open) { a->deep_count.ev_launch = a->ev_used; a->deep_count.marks = mark.marks; }   // (count_settled times its kernels as this launch's)
         a->ev_marks[a->ev_used] = mark.marks;
         ++a->ev_used;
     }
     return BGR_OK;
+}
+
+// The view of the rows in a->launch.results (exhaustive_rows_kernels.h), queued on the aligner's stream
+int view_launch(bgr_aligner* a, uint64_t n_reads, uint64_t arena_cap) {
+    HIP_TRY(a->launch.rows_view.ensure(n_reads * 8));
+    const hipError_t e = bgr::launch_exhaustive_rows(a->launch.results.as<uint2>(), (uint32_t)n_reads, arena_cap, a->launch.rows_view.as<uint2>(), a->stream);
+    if (e != hipSuccess) return fail(BGR_E_HIP, std::string("kernel launch (bgr_exhaustive_rows_kernel): ") + hipGetErrorString(e));
+    return BGR_OK;
+}
+
+// Behind a settled exhaustive launch whose counting waited for that (a->deep_count): the view of its rows, now final, then the counting kernels over the view.
+// Timed as kernels of that launch while it is the ring's newest entry: one slot for the host's wait in between, one for the view kernel, one per feature.
+static int count_settled(bgr_aligner* a) {
+    bgr_aligner::DeepCount& C = a->deep_count;
+    if (!C.open) return BGR_OK;
+    C.open = false;   // (whatever happens below: nothing is counted twice)
+    const bool timed = C.ev_launch >= 0 && C.ev_launch == a->ev_used - 1;
+    LaunchMarks mark{a, timed, C.marks, C.ev_launch};
+    HIP_TRY(mark("settle_launch (host)"));
+    if (const int rc = view_launch(a, C.n_reads, C.arena_cap); rc != BGR_OK) return rc;
+    HIP_TRY(mark("bgr_exhaustive_rows_kernel"));
+    a->view_ready = true;
+    BehindPasses c{a, C.arena_cap, C.read_offs, C.n_reads, C.total_bases, C.reads};
+    c.view = a->launch.rows_view.as<uint2>();
+    const int rc = queue_behind_passes(c, true, mark);
+    if (timed) a->ev_marks[C.ev_launch] = mark.marks;
+    return rc;
 }
 
 // Behind a mapping launch, with its stream waited for and the cursor block on the host (`cur`): the arena must not have overflowed, and in
@@ -853,7 +899,7 @@ int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, 
 // none is left.  A search visits at most positions x halves x 2 nodes, so this ends; what can end it early is the device's memory.
 int settle_launch(bgr_aligner* a, uint32_t* cur) {
     if (cur[bgr::kCurOverflow]) return fail(BGR_E_INTERNAL, "path arena overflow (internal sizing error)");
-    if (!a->deep.open) return BGR_OK;
+    if (!a->deep.open) return count_settled(a);   // (a launch whose passes were not run: option test.keep_rows)
     const uint32_t kRetry = bgr::list_word(bgr::List::kRetry);
     while (cur[kRetry]) {
         const uint32_t n_retry = cur[kRetry];
@@ -897,15 +943,35 @@ int settle_launch(bgr_aligner* a, uint32_t* cur) {
         ++D.runs;
     }
     a->deep.open = false;
-    return BGR_OK;
+    return count_settled(a);   // (bgr_aligner_exhaustive_paths_enable: the rows are final -- the counting kernels that waited for this)
 }
 // ... for callers that have not looked at the cursor yet (exhaustive launches only: nothing to settle otherwise but the arena flag, which every fetch checks)
 static int settle_launch_sync(bgr_aligner* a) {
-    if (!a->deep.open) return BGR_OK;
+    if (!a->deep.open && !a->deep_count.open) return BGR_OK;
     uint32_t cur[bgr::kCurWords];
     HIP_TRY(hipMemcpyAsync(cur, a->launch.small.p, sizeof(cur), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
     return settle_launch(a, cur);
+}
+
+int settle_pending(bgr_aligner* a) {
+    if (!a->deep.open && !a->deep_count.open) return BGR_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    return settle_launch_sync(a);
+}
+
+int last_rows(bgr_aligner* h, const std::string& who, const uint2** rows) {
+    *rows = h->launch.results.as<uint2>();
+    if (h->last_mode != BGR_MODE_EXHAUSTIVE) return BGR_OK;
+    if (!h->sh->exhaustive_paths) return fail(BGR_E_ARG, who + ": the last launch was exhaustive; " + (who == "bgr_aligner_haplotags" ? "rows" : "paths") + " of the greedy modes only");
+    if (const int rc = settle_pending(h); rc != BGR_OK) return rc;
+    if (!h->view_ready && h->last_n) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (const int rc = view_launch(h, h->last_n, h->last_arena_cap); rc != BGR_OK) return rc;
+        h->view_ready = true;
+    }
+    *rows = h->launch.rows_view.as<uint2>();
+    return BGR_OK;
 }
 
 // The aligner's first n_twins twins (a chain a -> twin -> twin's twin ...), created on first use.  A twin reads the aligner's shared block (its
@@ -999,6 +1065,7 @@ int bgr_align_batch_packed(bgr_aligner* a, const bgr_params* p, const bgr_packed
         return fail(BGR_E_ARG, "bgr_align_batch_packed: batch too large for one launch (2*(bases + 16*reads) must stay below 2^32 - 2^28); pack it in pieces");
     HIP_TRY(hipSetDevice(a->device));
     const uint64_t plane_words = bgr::packed_plane_words(n, total);
+    if (const int rc = settle_pending(a); rc != BGR_OK) return rc;   // (an exhaustive launch still to be counted reads the planes that are written next)
     HIP_TRY(a->launch.in_offs.ensure((n + 1) * 8));
     HIP_TRY(a->launch.pk_fw3.ensure(plane_words * 8));
     HIP_TRY(a->launch.pk_nm.ensure(plane_words * 8));
@@ -1032,8 +1099,10 @@ int bgr_aligner_sync(bgr_aligner* a) {
     // its own stream and its twins': un-waited bgr_align_device launches may run on the first twin's, and every launch has completed when this returns
     for (bgr_aligner* x = a; x; x = x->twin) {
         HIP_TRY(hipStreamSynchronize(x->stream));
+        const bool counts = x->deep_count.open;
         const int rc = settle_launch_sync(x);  // (exhaustive mode: reads the last pass handed back are mapped before the results count as final)
         if (rc != BGR_OK) return rc;
+        if (counts) HIP_TRY(hipStreamSynchronize(x->stream));   // (... and the counting kernels that waited for that have run)
     }
     return BGR_OK;
 }
@@ -1053,11 +1122,41 @@ int bgr_aligner_device_results(bgr_aligner* a, void** d_results, void** d_arena,
     return BGR_OK;
 }
 
+int bgr_aligner_exhaustive_paths_enable(bgr_aligner* a, int on) {
+    if (!a) return fail(BGR_E_ARG, "bgr_aligner_exhaustive_paths_enable: null aligner");
+    if (a->is_twin) return fail(BGR_E_ARG, "bgr_aligner_exhaustive_paths_enable: an internal twin (the switch belongs to the aligner it was made for)");
+    if (const int rc = sync_all(a); rc != BGR_OK) return rc;   // (a launch in flight ends under the switch it began under)
+    a->sh->exhaustive_paths = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_exhaustive_paths_enable(bgr_graph* g, int on) {
+    if (!g) return fail(BGR_E_ARG, "bgr_graph_exhaustive_paths_enable: null graph");
+    std::lock_guard<std::mutex> l(g->abundance_m);
+    g->exhaustive_paths_on = on != 0;
+    return BGR_OK;
+}
+
+int bgr_graph_exhaustive_paths_enabled(const bgr_graph* g) { return g && g->exhaustive_paths_on ? 1 : 0; }
+
+int bgr_aligner_device_rows_view(bgr_aligner* a, void** d_view) {
+    if (!a || !d_view) return fail(BGR_E_ARG, "bgr_aligner_device_rows_view: null argument");
+    *d_view = nullptr;
+    a = holder_of(a);   // (the buffers of the last launch)
+    if (a->last_mode != BGR_MODE_EXHAUSTIVE || !a->sh->exhaustive_paths || !a->last_n)
+        return fail(BGR_E_ARG, "bgr_aligner_device_rows_view: the view is that of an exhaustive last launch on an aligner with bgr_aligner_exhaustive_paths_enable");
+    const uint2* rows = nullptr;
+    if (const int rc = last_rows(a, "bgr_aligner_device_rows_view", &rows); rc != BGR_OK) return rc;
+    HIP_TRY(wait_stream(a));
+    *d_view = const_cast<uint2*>(rows);
+    return BGR_OK;
+}
+
 // results -> CSR on the device in two steps: the number of path ints of the launch (fetch_total), then the dense arrays and
 // their copies into the caller's memory (fetch_copy: relative path_offsets[0..n], status[0..n), total ints at paths_out)
 static int fetch_total(bgr_aligner* a, uint64_t n, uint64_t* total_out) {
     HIP_TRY(hipSetDevice(a->device));
-    if (a->deep.open) { const int src = settle_launch_sync(a); if (src != BGR_OK) return src; }
+    if (a->deep.open || a->deep_count.open) { const int src = settle_launch_sync(a); if (src != BGR_OK) return src; }
     else HIP_TRY(wait_stream(a));
     const uint64_t nb = (n + 4095) / 4096;
     HIP_TRY(a->fetch.csr_sums.ensure(nb * 4 + 64));
@@ -1094,7 +1193,7 @@ static int fetch_copy(bgr_aligner* a, uint64_t n, uint64_t total, int32_t* paths
 static int path_rows_refusal(const bgr_aligner* a, uint64_t n, const std::string& who) {
     if (a->graph->header.has_exc) return fail(BGR_E_ARG, who + ": needs a graph of ACGT-only unitigs (the walk is read from the 2-bit store)");
     if (n != a->last_n) return fail(BGR_E_ARG, who + ": n_reads differs from the last bgr_align_device call");
-    if (a->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, who + ": the last launch was exhaustive; paths of the greedy modes only");
+    if (a->last_mode == BGR_MODE_EXHAUSTIVE && !a->sh->exhaustive_paths) return fail(BGR_E_ARG, who + ": the last launch was exhaustive; paths of the greedy modes only");
     return BGR_OK;
 }
 
@@ -1106,12 +1205,15 @@ int bgr_aligner_path_stats(bgr_aligner* a, const void* d_reads, const void* d_re
     HIP_TRY(hipSetDevice(a->device));
     static_assert(sizeof(bgr_path_stat) == 24, "six words per read, as the kernel writes them");
     HIP_TRY(a->fetch.path_stats.ensure(n * sizeof(bgr_path_stat)));
-    hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), static_cast<const uint2*>(a->launch.results.p),
+    const uint2* rows = nullptr;   // (an exhaustive launch: settled, and read through its view)
+    if (const int rc = last_rows(a, "bgr_aligner_path_stats", &rows); rc != BGR_OK) return rc;
+    hipError_t e = bgr::launch_path_stats(a->dg, static_cast<const uint8_t*>(d_reads), static_cast<const uint64_t*>(d_read_offsets), rows,
                                           static_cast<const int32_t*>(a->launch.arena.p), a->last_arena_cap, (uint32_t)n, static_cast<uint32_t*>(a->fetch.path_stats.p), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path stats launch: ") + hipGetErrorString(e));
     if (bgr::opt("test.count_with_path_stats")) {   // test hook: the counting kernels once over the rows the buffers hold now, the reads' characters from the caller's buffer
         BehindPasses c{a, a->last_arena_cap, static_cast<const uint64_t*>(d_read_offsets), n, a->last_total_bases};
         c.reads.ascii = static_cast<const uint8_t*>(d_reads); c.reads.ascii_bytes = a->last_total_bases;
+        if (a->last_mode == BGR_MODE_EXHAUSTIVE) c.view = rows;
         LaunchMarks none{a, false};
         const int crc = queue_behind_passes(c, true, none);
         if (crc != BGR_OK) return crc;
@@ -1139,7 +1241,9 @@ int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_re
     uint32_t *doff = cnt + words, *twin = doff + words, *tile = twin + words, *total = tile + sums;
     const uint8_t* reads = static_cast<const uint8_t*>(d_reads);
     const uint64_t* offs = static_cast<const uint64_t*>(d_read_offsets);
-    hipError_t e = bgr::launch_path_diffs_count(a->dg, reads, offs, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), a->last_arena_cap, (uint32_t)n, cnt, a->stream);
+    const uint2* rows = nullptr;   // (an exhaustive launch: settled, and read through its view)
+    if (const int rc = last_rows(a, "bgr_aligner_path_diffs", &rows); rc != BGR_OK) return rc;
+    hipError_t e = bgr::launch_path_diffs_count(a->dg, reads, offs, rows, a->launch.arena.as<int32_t>(), a->last_arena_cap, (uint32_t)n, cnt, a->stream);
     if (e == hipSuccess) e = bgr::launch_scan2_u32(cnt, cnt, doff, twin, (uint32_t)n, nullptr, tile, total, total + 1, a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs launches: ") + hipGetErrorString(e));
     std::vector<uint32_t> h(n + 1);
@@ -1153,7 +1257,7 @@ int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_re
     if (all == 0) return BGR_OK;
     DevBuf& buf = a->fetch.path_stats;   // (the records: the buffer of bgr_aligner_path_stats' rows is free between calls)
     HIP_TRY(buf.ensure(all * sizeof(bgr_path_diff)));
-    e = bgr::launch_path_diffs_fill(a->dg, reads, offs, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), (uint32_t)n, cnt, doff, buf.as<uint2>(), a->stream);
+    e = bgr::launch_path_diffs_fill(a->dg, reads, offs, rows, a->launch.arena.as<int32_t>(), (uint32_t)n, cnt, doff, buf.as<uint2>(), a->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("path diffs fill launch: ") + hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(out, buf.p, all * sizeof(bgr_path_diff), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(wait_stream(a));
@@ -1184,6 +1288,7 @@ static int batch_launch(bgr_aligner* a, const bgr_params* p, const char* who, co
         if (l > 0x7FFFFFFFull) return fail(BGR_E_ARG, std::string(who) + ": read longer than 2^31 bases");
         max_len = std::max<uint32_t>(max_len, (uint32_t)l);
     }
+    if (const int rc = settle_pending(a); rc != BGR_OK) return rc;   // (an exhaustive launch still to be counted reads the buffers that are written next)
     rel.resize(keep || base ? n + 1 : 0);
     for (uint64_t i = 0; i < rel.size(); ++i) rel[i] = read_offsets[i] - base;
     HIP_TRY(a->launch.in_reads.ensure(total + 16));
@@ -1372,6 +1477,7 @@ int bgr_aligner_kernel_time(bgr_aligner* a, uint64_t* launches, double* total_ms
     if (launches) *launches = 0;
     if (total_ms) *total_ms = 0;
     for (bgr_aligner* x = a; x; x = x->twin) {  // its own stream, and the pieces of overlapped batches its other streams mapped
+        if (const int src = settle_pending(x); src != BGR_OK) return src;
         const int rc = drain_timers(x);
         if (rc != BGR_OK) return rc;
         if (launches) *launches += x->t_launches;
@@ -1385,6 +1491,7 @@ int bgr_aligner_kernel_times(bgr_aligner* a, uint64_t* launches, double slot_ms[
     HIP_TRY(hipSetDevice(a->device));
     if (launches) *launches = 0;
     for (bgr_aligner* x = a; x; x = x->twin) {
+        if (const int src = settle_pending(x); src != BGR_OK) return src;   // (the kernels behind an exhaustive launch's settling are that launch's)
         const int rc = drain_timers(x);
         if (rc != BGR_OK) return rc;
         if (launches) *launches += x->t_launches;

@@ -62,6 +62,7 @@ int bgr_aligner_abundance(bgr_aligner* a, bgr_unitig_abundance* out, uint64_t n_
     std::vector<bgr_unitig_abundance> t(n_rows);
     for (bgr_aligner* x = a; x; x = x->twin) {  // its own table, and those of the streams that mapped the pieces of overlapped batches and un-waited launches
         if (!x->abundance.p) continue;
+        if (const int rc = settle_pending(x); rc != BGR_OK) return rc;   // (an exhaustive launch whose counting is still to come)
         HIP_TRY(hipStreamSynchronize(x->stream));
         HIP_TRY(hipMemcpy(t.data(), x->abundance.as<bgr_unitig_abundance>() + 1, n_rows * sizeof(bgr_unitig_abundance), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < n_rows; ++i) { out[i].reads += t[i].reads; out[i].bases += t[i].bases; out[i].kmers += t[i].kmers; }
@@ -162,4 +163,4 @@ static int run_counts_collect(bgr_graph* g, bgr_aligner* a, uint32_t what) {
     return rc;
 }
 static int run_counts_end(bgr_graph* g, uint32_t what, bool ok) { return bgr::end_stages(kStages, kNStages, g, what, ok); }
-static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, bgr_aligner_haplotag_enable, bgr_graph_gaf_cs_enabled, bgr_aligner_gaf_cs_enable, bgr_graph_inside_enabled, run_inside_begin, bgr_aligner_inside_enable, run_inside_collect}, true);
+static const bool g_run_counts_registered = (bgr::g_run_counts = bgr::RunCounts{run_counts_wanted, run_counts_begin, run_counts_enable, run_counts_collect, run_counts_end, run_haplotag_table, bgr_aligner_haplotag_enable, bgr_graph_gaf_cs_enabled, bgr_aligner_gaf_cs_enable, bgr_graph_inside_enabled, run_inside_begin, bgr_aligner_inside_enable, run_inside_collect, bgr_graph_exhaustive_paths_enabled, bgr_aligner_exhaustive_paths_enable}, true);

@@ -63,11 +63,13 @@ int bgr_aligner_haplotags(bgr_aligner* a, uint64_t n_reads, bgr_read_tag* out) {
     if (!table) return fail(BGR_E_ARG, "bgr_aligner_haplotags: no tag table on this aligner (bgr_aligner_haplotag_enable)");
     bgr_aligner* h = holder_of(a);   // (the rows of the last launch, on the stream that ran it; the table is the aligner's own)
     if (n_reads != h->last_n) return fail(BGR_E_ARG, "bgr_aligner_haplotags: n_reads differs from the last bgr_align_device call");
-    if (h->last_mode == BGR_MODE_EXHAUSTIVE) return fail(BGR_E_ARG, "bgr_aligner_haplotags: the last launch was exhaustive; rows of the greedy modes only");
+    if (h->last_mode == BGR_MODE_EXHAUSTIVE && !h->sh->exhaustive_paths) return fail(BGR_E_ARG, "bgr_aligner_haplotags: the last launch was exhaustive; rows of the greedy modes only");
     if (n_reads == 0) return BGR_OK;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->tag.out.ensure(n_reads * sizeof(bgr_read_tag)));
-    const hipError_t e = bgr::launch_haplotags(table, a->graph->header.n_unitigs, static_cast<const uint2*>(h->launch.results.p), static_cast<const int32_t*>(h->launch.arena.p), h->last_arena_cap,
+    const uint2* rows = nullptr;   // (an exhaustive launch, bgr_aligner_exhaustive_paths_enable: settled, and read through its view)
+    if (const int rc = last_rows(h, "bgr_aligner_haplotags", &rows); rc != BGR_OK) return rc;
+    const hipError_t e = bgr::launch_haplotags(table, a->graph->header.n_unitigs, rows, static_cast<const int32_t*>(h->launch.arena.p), h->last_arena_cap,
                                                (uint32_t)n_reads, static_cast<bgr_read_tag*>(h->tag.out.p), h->stream);
     if (e != hipSuccess) return fail(BGR_E_HIP, std::string("haplotags launch: ") + hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(out, h->tag.out.p, n_reads * sizeof(bgr_read_tag), hipMemcpyDeviceToHost, h->stream));

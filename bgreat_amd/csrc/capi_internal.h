@@ -21,6 +21,7 @@
 #include "../../include/bgreat_gpu.h"
 #include "abundance_kernels.h"
 #include "align_kernels.h"
+#include "pileup_kernels.h"
 #include "graph_build.h"
 #include "inside_index.h"
 #include "launch_plan.h"
@@ -87,6 +88,7 @@ struct bgr_graph {
     // and the later stages of the chain run; haplotypes.seq: the characters the records point into
     // haplotags (bgr_graph_haplotag_enable): the sticky switch and the graph's copy of the tag table, n_unitigs + 1 words
     bool haplotag_on = false;
+    bool exhaustive_paths_on = false;   // bgr_graph_exhaustive_paths_enable: sticky -- a later bgr_align_all in exhaustive mode writes GAF lines and counts, every aligner of it with the switch
     bool gaf_cs_on = false;   // bgr_graph_gaf_cs_enable: sticky -- the GAF lines of every later bgr_align_all end in the cs:Z: field
     std::vector<uint32_t> haplotag;
     struct Bubbles : ChainSwitch, RunRows<bgr_bubble> { int device = -1; } bubbles;
@@ -170,6 +172,7 @@ struct TextRoute {
     DevBuf in, sums, state, rec, idx, accrec, accsrc, offs, psz, nsz, poff, noff, pout, nout, info, gaf;
     DevBuf tags;                    // GAF output of an aligner with a tag table: the tags per accepted read, next to gaf
     DevBuf cs;                      // GAF output with the cs:Z: field (bgr_aligner_gaf_cs_enable): the bytes of its ops per accepted read, next to gaf
+    DevBuf idx_kept;                // GAF output with record info (exhaustive launches): idx as the parse launch left it -- the GAF sizes launch reuses idx, and the record info may be made twice
     uint64_t n_acc = 0, pbytes = 0, nbytes = 0;
     const uint8_t* text = nullptr;  // where the last call's piece lies in HBM (in, or the caller's stage)
     bgr::TextEpochs epochs;         // the one-launch kernels' chains (epoch of the last launch, tickets earlier launches took) and which of the two info blocks a piece uses
@@ -177,9 +180,10 @@ struct TextRoute {
     uint32_t want = 0;              // the piece's want_output (2 = correction mode: mapped reads as spelled by their paths, 3 = GAF lines)
     bool tagged = false;            // the sizes launch of the piece in the buffers was a tagged one (the write launch follows it)
     bool with_cs = false;           // ... was one of the instances that carry the cs:Z: field (the same)
+    bool view = false;              // ... read an exhaustive launch through its view, launch.rows_view (bgr_aligner_exhaustive_paths_enable; the same)
     double phase_s[5] = {0, 0, 0, 0, 0};  // BGREAT_TIMING: host wall seconds to the call's four waits (mark, records, mapping + sizes, streams) + calls
     void release() {
-        for (DevBuf* b : {&in, &sums, &state, &rec, &idx, &accrec, &accsrc, &offs, &psz, &nsz, &poff, &noff, &pout, &nout, &info, &gaf, &tags, &cs}) b->release();
+        for (DevBuf* b : {&in, &sums, &state, &rec, &idx, &accrec, &accsrc, &offs, &psz, &nsz, &poff, &noff, &pout, &nout, &info, &gaf, &tags, &cs, &idx_kept}) b->release();
     }
 };
 
@@ -187,7 +191,8 @@ struct TextRoute {
 struct LaunchBufs {
     DevBuf in_reads, in_offs, pk_fw3, pk_nm, pk_hasn, results, arena, ovf, ovf2, lst, deepbuf, retry, retry2, small;  // small: kSmall* (align_kernels.h)
     DevBuf wave_times;            // diagnostic builds only (-DBGR_PHASE_TIMING)
-    void release() { for (DevBuf* b : {&in_reads, &in_offs, &pk_fw3, &pk_nm, &pk_hasn, &results, &arena, &ovf, &ovf2, &lst, &deepbuf, &retry, &retry2, &small, &wave_times}) b->release(); }
+    DevBuf rows_view;             // bgr_aligner_exhaustive_paths_enable: 8 bytes per read, the rows of an exhaustive launch without their end offset (exhaustive_rows_kernels.h); allocated once the switch is on
+    void release() { for (DevBuf* b : {&in_reads, &in_offs, &pk_fw3, &pk_nm, &pk_hasn, &results, &arena, &ovf, &ovf2, &lst, &deepbuf, &retry, &retry2, &small, &wave_times, &rows_view}) b->release(); }
 };
 // What reads the rows of the last launch back: the dense arrays of a fetch, bgr_aligner_path_stats, bgr_aligner_path_diffs
 struct FetchBufs {
@@ -238,6 +243,9 @@ struct AlignerShared {
     // over the graph's inside index on this device (inside_tab: null = off); what it mapped is counted at kSmallInside of each stream's `small`
     const BgrInsideEntry* inside_tab = nullptr;
     uint64_t inside_slots = 0;
+    // bgr_aligner_exhaustive_paths_enable: the paths of exhaustive launches are output -- the counting kernels run behind such a launch once it is settled,
+    // and whatever reads the rows of the last launch reads an exhaustive one through its view (launch.rows_view)
+    bool exhaustive_paths = false;
     void release() { links.buf.release(); triples.buf.release(); pileup.release(); }
 };
 
@@ -264,6 +272,15 @@ struct bgr_aligner {
         BgrDeviceGraph dg;
         uint32_t per_wave_lds = 0, path_cap = 0, memo_cap = 0, runs = 0;
     } deep;
+    struct DeepCount {  // the counting kernels of the exhaustive launch in flight (exhaustive_paths): what they are handed, kept until settle_launch has made the rows final and queues them
+        bool open = false;
+        uint64_t arena_cap = 0, n_reads = 0, total_bases = 0;
+        const uint64_t* read_offs = nullptr;
+        bgr::PileupReads reads;
+        int ev_launch = -1;       // the launch's place in the timer ring (-1: not timed)
+        int marks = 0;            // ... and the kernels timed in it so far
+    } deep_count;
+    bool view_ready = false;      // launch.rows_view holds the view of the last launch (an exhaustive one, settled)
     bgr::PlanDevice plan_dev;     // CUs, LDS, resident waves per kernel: asked once
     bool plan_dev_known = false;
     uint64_t last_n = 0;
@@ -299,10 +316,16 @@ inline hipError_t wait_stream(bgr_aligner* a) {
     hipError_t e = hipEventRecord(a->ev_wait, a->stream);
     return e == hipSuccess ? hipEventSynchronize(a->ev_wait) : e;
 }
-// Wait for every stream that adds to the aligner's tables: its own and its twins'.
+// capi.hip: an exhaustive launch still in flight on this one aligner (or twin) is settled -- reads its last pass handed back are mapped -- and, where its
+// counting kernels waited for that (bgr_aligner_exhaustive_paths_enable), those are queued on its stream; nothing to do otherwise
+extern "C" int settle_pending(bgr_aligner* a);
+// Wait for every stream that adds to the aligner's tables: its own and its twins' (an exhaustive launch whose counting is still to come counts first).
 inline int sync_all(bgr_aligner* a) {
     HIP_TRY(hipSetDevice(a->device));
-    for (bgr_aligner* x = a; x; x = x->twin) HIP_TRY(hipStreamSynchronize(x->stream));
+    for (bgr_aligner* x = a; x; x = x->twin) {
+        if (const int rc = settle_pending(x); rc != BGR_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(x->stream));
+    }
     return BGR_OK;
 }
 
@@ -410,7 +433,11 @@ void forget_launch(bgr_aligner* a);   // no single launch whose results could be
 extern "C" {   // (defined among the functions of the interface)
 int align_device_impl(bgr_aligner* a, const bgr_params* p, const void* d_reads, const void* d_read_offsets, uint64_t n_reads, uint64_t total_bases, uint32_t max_read_len,
                       bool planes_ready, const void* d_src_off, uint64_t reads_bytes, bool cursor_is_zero);   // the mapping launch of one batch (see there)
-int settle_launch(bgr_aligner* a, uint32_t* cur);   // behind a mapping launch, its stream waited for and the cursor block in `cur`: the arena flag; exhaustive mode: reads handed back are mapped
+int settle_launch(bgr_aligner* a, uint32_t* cur);   // behind a mapping launch, its stream waited for and the cursor block in `cur`: the arena flag; exhaustive mode: reads handed back are mapped, then the counting kernels that waited for that are queued
+// the rows of the last launch of `h` (the aligner that holds it) as a reader of greedy rows takes them: its results, or -- an exhaustive launch, which is
+// settled first -- its view, made on h's stream if it is not there.  `who` refuses an exhaustive launch of an aligner without bgr_aligner_exhaustive_paths_enable
+int last_rows(bgr_aligner* h, const std::string& who, const uint2** rows);
+int view_launch(bgr_aligner* a, uint64_t n_reads, uint64_t arena_cap);   // the view of the rows in a->launch.results into a->launch.rows_view, queued on a->stream (the text route's GAF kernels read an exhaustive launch through it)
 }
 // capi_abundance.hip
 int abundance_table(bgr_aligner* a);   // this one aligner's (or twin's) table, allocated and zeroed the first time it is asked for

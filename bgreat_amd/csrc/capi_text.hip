@@ -28,6 +28,7 @@ struct TextCall {
     uint32_t* info = nullptr;             // the piece's info block on the device
     uint32_t h[TXT_INFO_WORDS];           // ... and on the host: as the parse launch left it, then as the format step did
     uint64_t pcap_dev = 0, ncap_dev = 0;  // default output: the capacities the format launch wrote below
+    uint32_t format_runs = 0;             // times the format step has run
     double tw = 0;                        // BGREAT_TIMING: the wall clock at the last mark
     void lap(int i) { const double t = wall_now(); a->text.phase_s[i] += t - tw; tw = t; }
 };
@@ -44,7 +45,7 @@ uint64_t* chains_of(const TextRoute& t) { return reinterpret_cast<uint64_t*>(t.s
 // ---- bgr_aligner_fetch_text ---------------------------------------------------------------------------------------------------------
 // The write launch of the piece in the buffers, by its kind of output: the streams into pout / nout from the offsets its sizes were scanned into.
 hipError_t write_gaf(const bgr_aligner* a, const TextRoute& t) {
-    return bgr::launch_text_gaf_write(a->dg, t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
+    return bgr::launch_text_gaf_write(a->dg, t.text, (t.view ? a->launch.rows_view : a->launch.results).as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), (uint32_t)t.n_acc, t.poff.as<uint32_t>(),
                                       t.noff.as<uint32_t>(), t.psz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), t.pout.as<uint8_t>(), t.nout.as<uint8_t>(),
                                       t.tagged ? t.tags.as<uint4>() : nullptr, t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream);
 }
@@ -115,9 +116,11 @@ int check_text_call(const bgr_aligner* a, const bgr_params* p, const bgr_text_ba
         return fail(BGR_E_ARG, "bgr_align_fasta_text: a FASTQ piece holds whole four-line records and ends with a newline");
     if (b->want_output == 2 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
         return fail(BGR_E_ARG, "bgr_align_fasta_text: correction on the device needs a graph of ACGT-only unitigs and greedy mode (format such a run on the host)");
-    if (b->want_output == 3 && (a->graph->header.has_exc || p->mode == BGR_MODE_EXHAUSTIVE))
+    if (b->want_output == 3 && (a->graph->header.has_exc || (p->mode == BGR_MODE_EXHAUSTIVE && !a->sh->exhaustive_paths)))
         return fail(BGR_E_ARG, "bgr_align_fasta_text: GAF output needs a graph of ACGT-only unitigs (a path read backwards does not spell the reverse complement on one with other characters) and a greedy mode");
-    if (b->record_info_out && (b->want_output >= 2 || b->record_info_cap < b->text_bytes / 24 + 1024))
+    // (the GAF lines of an exhaustive launch, bgr_aligner_exhaustive_paths_enable: the record info is what the caller prints the -b progress blocks from)
+    const bool info_with_gaf = b->want_output == 3 && p->mode == BGR_MODE_EXHAUSTIVE;
+    if (b->record_info_out && ((b->want_output >= 2 && !info_with_gaf) || b->record_info_cap < b->text_bytes / 24 + 1024))
         return fail(BGR_E_ARG, "bgr_align_fasta_text: record_info_out needs room for text_bytes / 24 + 1024 words and is not available in correction mode or with GAF output");
     return BGR_OK;
 }
@@ -208,8 +211,12 @@ int gaf_sizes(TextCall& c) {
     if (t.tagged) HIP_TRY(t.tags.ensure(((uint64_t)c.n_acc + 1) * 16));
     t.with_cs = a->gaf_cs;                 // (bgr_aligner_gaf_cs_enable: the instances whose lines end in the cs:Z: field)
     if (t.with_cs) HIP_TRY(t.cs.ensure(((uint64_t)c.n_acc + 1) * 4));
+    // an exhaustive launch (bgr_aligner_exhaustive_paths_enable): both GAF kernels read its rows without their end offset -- the view, made here every time this
+    // step runs (the second time, behind a launch that had to be settled, from the final rows)
+    t.view = c.p->mode == BGR_MODE_EXHAUSTIVE;
+    if (t.view) { if (const int rc = view_launch(a, c.n_acc, a->last_arena_cap); rc != BGR_OK) return rc; }
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.info + TXT_INFO_BUG), -1, 1, a->stream));
-    return launched(bgr::launch_text_gaf_sizes(a->dg, t.text, a->launch.results.as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
+    return launched(bgr::launch_text_gaf_sizes(a->dg, t.text, (t.view ? a->launch.rows_view : a->launch.results).as<uint2>(), a->launch.arena.as<int32_t>(), t.rec.as<uint4>(), t.accrec.as<uint32_t>(), c.n_acc, t.psz.as<uint32_t>(),
                                                t.nsz.as<uint32_t>(), t.idx.as<uint32_t>(), t.gaf.as<uint4>(), c.info + TXT_INFO_BUG, t.tagged ? a->tag.table.as<uint32_t>() : nullptr,
                                                t.tags.as<uint4>(), t.with_cs ? t.cs.as<uint32_t>() : nullptr, a->stream),
                     "text size launches");
@@ -244,7 +251,11 @@ int format_streams(TextCall& c) {
 // are mapped again, settle_launch).  BGR_OK: the results were final when the kernels behind the launch read them; kRunAgain: they were not
 int settle_text_launch(bgr_aligner* a, uint32_t* cur) {
     const bool handed_back = a->deep.open && cur[bgr::list_word(bgr::List::kRetry)] != 0;
+    const bool counts = a->deep_count.open;
     const int rc = settle_launch(a, cur);
+    // (bgr_aligner_exhaustive_paths_enable: the counting kernels, queued by settle_launch, read the piece -- the pileup its characters --, and the caller's
+    // stage may take the next piece once this call returns: they have run when it does)
+    if (rc == BGR_OK && counts) HIP_TRY(wait_stream(a));
     return rc != BGR_OK ? rc : handed_back ? kRunAgain : BGR_OK;
 }
 
@@ -260,7 +271,15 @@ int format_once(TextCall& c) {
     bgr_text_batch* b = c.b;
     if (b->record_info_out) {  // what became of every record (the -b progress blocks of the caller), on its way to the host behind the mapping launch
         HIP_TRY(t.info.ensure((uint64_t)c.R * 4));
-        const hipError_t e = bgr::launch_text_record_info(t.rec.as<uint4>(), t.idx.as<uint32_t>(), a->launch.results.as<uint2>(), c.R, t.info.as<uint32_t>(), a->stream);
+        const uint32_t* idx = t.idx.as<uint32_t>();
+        if (b->want_output == 3) {   // (the GAF sizes launch below takes idx for the lengths of the names: this step may run again and needs it as it was)
+            const uint64_t bytes = ((uint64_t)c.R_cap + 4) * 4;
+            HIP_TRY(t.idx_kept.ensure(bytes));
+            if (c.format_runs == 0) HIP_TRY(hipMemcpyAsync(t.idx_kept.p, t.idx.p, bytes, hipMemcpyDeviceToDevice, a->stream));
+            idx = t.idx_kept.as<uint32_t>();
+        }
+        ++c.format_runs;
+        const hipError_t e = bgr::launch_text_record_info(t.rec.as<uint4>(), idx, a->launch.results.as<uint2>(), c.R, t.info.as<uint32_t>(), a->stream);
         if (e != hipSuccess) return launched(e, "record info launch");
         HIP_TRY(hipMemcpyAsync(b->record_info_out, t.info.p, (size_t)c.R * 4, hipMemcpyDeviceToHost, a->stream));
     }

@@ -63,6 +63,11 @@
 //                                                               looks up a sample of their k-mers in an exact index of the unitigs' k-mers and maps them as [offset, +-unitig], so
 //                                                               they reach `paths` and every counting flag instead of notAligned.fa; one last line on stdout counts them; not with
 //                                                               -b, k > 32 or non-ACGT unitig characters: include/bgreat_gpu.h)
+//                                                   --exhaustive-paths (with -b: the paths exhaustive mode finds are output -- --gaf with --cs and --haplotag, --abundance, --gfa, --pileup / --depth,
+//                                                               --vcf, --strands, --bubbles, --triples, --phase, --blocks and --haplotypes read them as they read the paths of
+//                                                               the greedy modes, without the end offset an exhaustive row carries; with --gaf the two files are filled as
+//                                                               --write-exhaustive fills them, GAF lines in `paths`; not without -b, with -i, --inside, or --gaf together
+//                                                               with --write-exhaustive: include/bgreat_gpu.h)
 //                                                   --set name=value (library option, bgr_set_option: INTEGRATION.md 5; e.g. --set timing=1)
 #include <getopt.h>
 
@@ -96,7 +101,7 @@ int main(int argc, char** argv) {
     uint64_t min_block = 1;        // --min-block
     bool min_block_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
-    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false, inside = false;
+    bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false, inside = false, exh_paths = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
                                 {"write-exhaustive", no_argument, nullptr, 1002}, {"chunk-bytes", required_argument, nullptr, 1003},
                                 {"no-overlap", required_argument, nullptr, 1004}, {"host-route", no_argument, nullptr, 1005}, {"split-output", no_argument, nullptr, 1006},
@@ -109,6 +114,7 @@ int main(int argc, char** argv) {
                                 {"blocks", required_argument, nullptr, 1023}, {"min-phase", required_argument, nullptr, 1024},
                                 {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
                                 {"haplotag", required_argument, nullptr, 1027}, {"cs", no_argument, nullptr, 1028}, {"inside", no_argument, nullptr, 1029},
+                                {"exhaustive-paths", no_argument, nullptr, 1030},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -207,6 +213,7 @@ int main(int argc, char** argv) {
             case 1027: haplotagFile = optarg; break;
             case 1028: gaf_cs = true; break;
             case 1029: inside = true; break;
+            case 1030: exh_paths = true; break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -225,7 +232,11 @@ int main(int argc, char** argv) {
     if (min_phase_given && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-phase is the threshold of --blocks FILE and --haplotypes FILE\n"); return 2; }
     if (min_block_given && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-block is the threshold of --haplotypes FILE\n"); return 2; }
     if (!haplotagFile.empty() && !gaf) { fprintf(stderr, "bgreat: --haplotag BLOCKS_FILE adds its fields to the lines of --gaf\n"); return 2; }
-    if (!haplotagFile.empty() && brute) { fprintf(stderr, "bgreat: --haplotag tags GAF lines, which are for the greedy modes; exhaustive mode (-b) writes no paths\n"); return 2; }
+    if (exh_paths && !brute) { fprintf(stderr, "bgreat: --exhaustive-paths outputs the paths of exhaustive mode: it needs -b\n"); return 2; }
+    if (exh_paths && incomplete) { fprintf(stderr, "bgreat: --exhaustive-paths is not defined with -i: a partial path of exhaustive mode may lack its end offset\n"); return 2; }
+    if (exh_paths && inside) { fprintf(stderr, "bgreat: --exhaustive-paths and --inside: the inside pass writes rows of the greedy modes; exhaustive mode (-b) is refused\n"); return 2; }
+    if (exh_paths && gaf && write_exh) { fprintf(stderr, "bgreat: --gaf and --write-exhaustive both claim the paths file; choose one\n"); return 2; }
+    if (!haplotagFile.empty() && brute && !exh_paths) { fprintf(stderr, "bgreat: --haplotag tags GAF lines, which are for the greedy modes; exhaustive mode (-b) writes no paths\n"); return 2; }
     if (gaf_cs && !gaf) { fprintf(stderr, "bgreat: --cs adds the cs:Z: field to the lines of --gaf\n"); return 2; }
     if (inside && brute) { fprintf(stderr, "bgreat: --inside maps the reads greedy mode leaves without an anchor; exhaustive mode (-b) is refused\n"); return 2; }
     if (inside && ka > 32) { fprintf(stderr, "bgreat: --inside indexes one-word k-mers: k <= 32\n"); return 2; }
@@ -242,6 +253,7 @@ int main(int argc, char** argv) {
         if (bgr_read_blocks_tags(haplotagFile.c_str(), gi.n_unitigs, table.data(), nullptr) != BGR_OK || bgr_graph_haplotag_enable(graph, table.data(), table.size()) != BGR_OK) die("--haplotag");
     }
     if (gaf_cs && bgr_graph_gaf_cs_enable(graph, 1) != BGR_OK) die("--cs");
+    if (exh_paths && bgr_graph_exhaustive_paths_enable(graph, 1) != BGR_OK) die("--exhaustive-paths");
     if (inside && (bgr_graph_inside_build(graph) != BGR_OK || bgr_graph_inside_enable(graph, 1) != BGR_OK)) die("--inside");   // (k > 32, non-ACGT unitig characters: refused here, status 2)
     // one host -> device copy, then device to device over xGMI (RCCL broadcast, or peer copies): include/bgreat_gpu.h
     int64_t one_device = 0, timing = 0;  // (test hook: every lane on device 0)

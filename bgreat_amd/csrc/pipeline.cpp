@@ -23,7 +23,7 @@
 #include "pipeline_stages.h"
 
 namespace bgr {
-RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
+RunCounts g_run_counts = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // run_counts.h: registered by the library's C-ABI units
 }
 
 extern "C" void bgr_host_cache_release(void) {
@@ -213,10 +213,21 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
         }
     }
     const bool progress_blocks = run_progress_blocks(prm, opt), correction = run_correction(prm, opt);
+    // bgr_graph_exhaustive_paths_enable: the paths of an exhaustive run are output -- GAF lines and everything that is counted read them without their end
+    // offset.  What the definition leaves out is refused before any device work.
+    const bool exhaustive_paths = bgr::g_run_counts.exhaustive_paths_wanted && bgr::g_run_counts.exhaustive_paths_wanted(graph) != 0;
+    if (exhaustive_paths) {
+        if (prm->mode != BGR_MODE_EXHAUSTIVE)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: the paths of exhaustive mode (--exhaustive-paths, bgr_graph_exhaustive_paths_enable) need exhaustive mode (-b)");
+        if (prm->partial)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: the paths of exhaustive mode (--exhaustive-paths, bgr_graph_exhaustive_paths_enable) are not defined with partial paths (-i): such a row may lack its end offset");
+        if (opt->gaf && opt->write_exhaustive)
+            return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) and --write-exhaustive both claim the paths file; choose one");
+    }
     if (opt->gaf) {   // GAF output: what it cannot describe is refused before any device work
         bgr_graph_info_t gi;
         if (bgr_graph_info(graph, &gi) != BGR_OK) return BGR_E_ARG;
-        if (prm->mode == BGR_MODE_EXHAUSTIVE)
+        if (prm->mode == BGR_MODE_EXHAUSTIVE && !exhaustive_paths)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) is for the greedy modes; exhaustive mode (-b) writes no paths");
         if (opt->correction)
             return bgr::set_error(BGR_E_ARG, "bgr_align_all: GAF output (--gaf) and correction (-c) both claim the paths file; choose one");
@@ -250,7 +261,7 @@ extern "C" int bgr_align_all(bgr_graph* graph, const bgr_params* prm, const bgr_
         {bgr::kCountTriples, "bgr_align_all: triple counting (--triples, bgr_graph_triples_enable) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
         {bgr::kCountAbundance, "bgr_align_all: unitig abundance (--abundance) is for the greedy modes; the rows of exhaustive mode (-b) have another layout"},
     };
-    if (prm->mode == BGR_MODE_EXHAUSTIVE)
+    if (prm->mode == BGR_MODE_EXHAUSTIVE && !exhaustive_paths)   // (with the switch every one of them reads an exhaustive launch through its view)
         for (const auto& r : kGreedyOnly)
             if (counts & r.bit) return bgr::set_error(BGR_E_ARG, r.refusal);
     if (counts && !bgr::g_run_counts.begin) return bgr::set_error(BGR_E_ARG, "bgr_align_all: unitig abundance is not available in this build");

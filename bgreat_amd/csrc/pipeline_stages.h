@@ -175,6 +175,7 @@ struct RunShape {
     uint64_t tag_rows = 0;               // aligner's device, and the host formatter tags from the same words
     bool gaf_cs = false;                 // the cs:Z: field (bgr_graph_gaf_cs_enable; the same refusal): every aligner's switch is set, the host formatter writes it too
     bool inside = false;                 // the inside pass (bgr_graph_inside_enable; bgr_align_all has refused it in exhaustive mode): every aligner's switch is set
+    bool exhaustive_paths = false;       // an exhaustive run with bgr_graph_exhaustive_paths_enable: every aligner's switch is set, the host formatter reads the rows without their end offset
     int device_of(unsigned g) const { return (int)(one_device ? first_device : first_device + g); }
 };
 
@@ -188,9 +189,10 @@ int plan_run(bgr_graph* graph, const bgr_params* prm, const bgr_run_options* opt
     s.threads = threads;
     s.fastq = opt->fastq != 0;
     s.echo_files = opt->echo_files != 0;
-    s.writes = prm->mode != BGR_MODE_EXHAUSTIVE || opt->write_exhaustive;
+    s.exhaustive_paths = prm->mode == BGR_MODE_EXHAUSTIVE && bgr::g_run_counts.exhaustive_paths_wanted && bgr::g_run_counts.exhaustive_paths_wanted(graph) != 0;
+    s.writes = prm->mode != BGR_MODE_EXHAUSTIVE || opt->write_exhaustive || (s.exhaustive_paths && opt->gaf);   // (GAF lines of an exhaustive run: the two files as --write-exhaustive fills them)
     s.correction = run_correction(prm, opt);
-    s.gaf = opt->gaf != 0;  // (bgr_align_all has refused it in exhaustive mode, with -c and on a graph with exception planes)
+    s.gaf = opt->gaf != 0;  // (bgr_align_all has refused it in exhaustive mode without bgr_graph_exhaustive_paths_enable, with -c and on a graph with exception planes)
     s.split_no_overlap = opt->no_overlap_file != nullptr;
     s.extended = s.correction || s.gaf || s.split_no_overlap;
     s.progress_blocks = run_progress_blocks(prm, opt);
@@ -265,6 +267,7 @@ int make_aligners(bgr_graph* graph, const RunShape& s, uint32_t counts, std::vec
             if (rc == BGR_OK && s.tag_table) rc = bgr::g_run_counts.haplotag_enable(a, s.tag_table, s.tag_rows);
             if (rc == BGR_OK && s.gaf_cs) rc = bgr::g_run_counts.gaf_cs_enable(a, 1);
             if (rc == BGR_OK && s.inside) rc = bgr::g_run_counts.inside_enable(a, 1);
+            if (rc == BGR_OK && s.exhaustive_paths) rc = bgr::g_run_counts.exhaustive_paths_enable(a, 1);
             if (rc != BGR_OK) return rc;
         }
     }
@@ -973,7 +976,7 @@ struct OrderedWriter {
             if (lo >= hi) return;
             if (!s.extended) format_range(cur.recs.data(), paths, poffs, lo, hi, o.pb[t], o.nb[t]);
             else okv[t] = format_range_ext(cur.recs.data(), paths, poffs, status, lo, hi, (s.correction || s.gaf) ? &s.unitigs : nullptr, s.gaf, s.split_no_overlap, o.pb[t], o.nb[t],
-                                           o.ob[t], bugv[t], s.tag_table, s.tag_rows, s.gaf_cs) ? 1 : 0;
+                                           o.ob[t], bugv[t], s.tag_table, s.tag_rows, s.gaf_cs, s.exhaustive_paths && s.gaf) ? 1 : 0;
         }, 3);
         unsigned t_stop = threads;
         for (unsigned t = 0; t < threads; ++t)

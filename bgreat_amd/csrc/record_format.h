@@ -183,6 +183,10 @@ void format_range(const RecSlice* recs, const int32_t* paths, const uint64_t* po
     pbuf.resize(pmax ? (size_t)(po - p0) : 0);
 }
 
+// The host twin of the view of an exhaustive row (exhaustive_rows_kernels.h; a fetched row has left the arena, so that condition has gone): the ints of
+// the row as a reader of greedy rows takes it -- without its end offset, or none where the row is not a whole [begin, ids .., end] row of a mapped read.
+inline uint64_t exhaustive_view_ints(uint64_t np, uint8_t status) { return ((status & BGR_ST_MASK) == BGR_ST_ALIGNED && np >= 3) ? np - 1 : 0; }
+
 // The same with the opt-in output variants (`status`: the device's byte per read): GAF lines in the place of the path records (`gaf`; needs `correct`,
 // the unitigs), correction mode (mapped reads are written as header + corrected read, alignerGreedy.cpp:394-404) and the no-overlap split (reads
 // without any anchor go to a third buffer).
@@ -191,15 +195,16 @@ void format_range(const RecSlice* recs, const int32_t* paths, const uint64_t* po
 // `bug` the two strings the reference prints.
 // tag_table (n_unitigs + 1 words, or null): a GAF line gains the fields of its read's haplotag (haplotag_host.h), computed from the path ints held here.
 // gaf_cs: a GAF line ends in the cs:Z: field, behind the tags.
+// exhaustive_rows: the rows are those of exhaustive mode (bgr_graph_exhaustive_paths_enable) and are read through exhaustive_view_ints.
 bool format_range_ext(const RecSlice* recs, const int32_t* paths, const uint64_t* poffs, const uint8_t* status, uint64_t lo, uint64_t hi, const Unitigs* correct, bool gaf,
                       bool split_no_overlap, std::string& pbuf, std::string& nbuf, std::string& obuf, std::string& bug, const uint32_t* tag_table = nullptr, uint64_t tag_rows = 0,
-                      bool gaf_cs = false) {
+                      bool gaf_cs = false, bool exhaustive_rows = false) {
     pbuf.clear(); nbuf.clear(); obuf.clear();
     std::string walk, tmp, rc, cs;
     std::vector<uint8_t> fwd;
     for (uint64_t i = lo; i < hi; ++i) {
         const RecSlice& r = recs[i];
-        const uint64_t np = poffs[i + 1] - poffs[i];
+        const uint64_t np = exhaustive_rows ? exhaustive_view_ints(poffs[i + 1] - poffs[i], status[i]) : poffs[i + 1] - poffs[i];
         if (np && gaf) {
             if (np < 2) { walk.clear(); tmp.clear(); }
             if (np < 2 || !gaf_line(*correct, paths + poffs[i], np, r.h, r.hl, r.s, r.sl, (status[i] & BGR_ST_RC) != 0, pbuf, walk, tmp, rc, fwd, gaf_cs ? &cs : nullptr)) {

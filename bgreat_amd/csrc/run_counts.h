@@ -35,6 +35,10 @@ struct RunCounts {
     void (*inside_begin)(bgr_graph* g);
     int (*inside_enable)(bgr_aligner* a, int on);
     int (*inside_collect)(bgr_graph* g, bgr_aligner* a);
+    // the paths of exhaustive mode as output (bgr_graph_exhaustive_paths_enable), the same way: the graph's switch as 1 or 0 and the call that sets an
+    // aligner's; the host formatter reads the rows without their end offset by the same rule (record_format.h)
+    int (*exhaustive_paths_wanted)(const bgr_graph* g);
+    int (*exhaustive_paths_enable)(bgr_aligner* a, int on);
 };
 extern RunCounts g_run_counts;   // pipeline.cpp; all null until the library's C-ABI units have registered
 

@@ -351,6 +351,37 @@ int bgr_aligner_path_diffs(bgr_aligner* a, const void* d_reads, const void* d_re
 int bgr_aligner_gaf_cs_enable(bgr_aligner* a, int on);
 int bgr_graph_gaf_cs_enable(bgr_graph* g, int on);
 int bgr_graph_gaf_cs_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+/* The paths of exhaustive launches as output (--exhaustive-paths).  Off by default: an aligner with the switch off refuses what it always refused
+ * and launches the kernels it always did.
+ * A row of exhaustive mode is [begin offset, +-u_1 .. +-u_n, end offset] (alignerExhaustive.cpp:96-104, 193-201, 249-257): a row of the greedy modes
+ * with one more int behind it, |readLeft| + k - 1 in the last unitig or 0 when the read ends with the anchor.  With L the read's length and
+ * e = row[0] + L - (the walk's length - the last unitig's length), that int is e -- or, only where e is the last unitig's length, 0: the same position,
+ * the read's last character on the unitig's last, spelled two ways.  Dropping it loses no position.
+ * The VIEW of an exhaustive launch is a second array of result words.  For the pair {off, w} of a read, n = w & 0xFFFFFF and st = w >> 24, its entry is
+ * {off, (n - 1) | st << 24} when (st & BGR_ST_MASK) == BGR_ST_ALIGNED, n >= 3 and off + n <= the launch's arena ints (the sum in 64 bits), else
+ * {off, st << 24}: an empty row with the status as stored -- the rule every reader applies to a row outside the arena.  The rows themselves and
+ * the arena are untouched: bgr_aligner_fetch and bgr_aligner_device_results deliver the reference's rows with the end offset, as ever.
+ * (tests/exhaustive_rows_ref.py is the rule in plain Python; the kernel, "bgr_exhaustive_rows_kernel" in bgr_aligner_kernel_times, is
+ * bgreat_amd/csrc/exhaustive_rows_kernels.hip.)
+ * bgr_aligner_exhaustive_paths_enable(a, on), refused on an internal twin.  While on:
+ *  - an exhaustive launch of an aligner that counts abundance, links, triples or a pileup (with or without strands) is accepted, and counted through
+ *    its view.  The inside pass is still refused.  An exhaustive launch is final only once it is SETTLED (bgr_aligner_sync above), so its view and
+ *    counting kernels are queued behind that, exactly once per launch, by whichever comes first: a call that reads a counting table, a fetch, sync,
+ *    counters or kernel-times call, or the next launch on the same aligner.  The read buffers of the launch must stay untouched until then -- longer
+ *    than the rule for un-waited launches at bgr_align_device asks, which ends at the wait;
+ *  - bgr_aligner_path_stats, bgr_aligner_path_diffs and bgr_aligner_haplotags accept an exhaustive last launch: they settle it and read its view
+ *    (mismatches may exceed max_mismatch for a read that holds a character outside ACGT: exhaustive mode counts those as the reference does);
+ *  - bgr_align_fasta_text accepts want_output = 3 in exhaustive mode -- its GAF kernels read the view, cs:Z: and haplotags included -- and
+ *    record_info_out together with it; a call on a counting aligner returns once the counting kernels have run.
+ * bgr_aligner_device_rows_view: the view of the last launch in the aligner's HBM, uint32[n][2], made and waited for (the launch is settled first);
+ * valid until the next launch.  BGR_E_ARG when the last launch was not exhaustive or the switch is off.
+ * bgr_graph_exhaustive_paths_enable(g, on) is sticky, for whole runs: a later bgr_align_all in exhaustive mode accepts gaf and every counting
+ * output.  BGR_E_ARG from such a run that is not exhaustive, has partial (-i) set -- a row may then lack the end offset -- or has the graph's inside
+ * switch on.  Correction (-c) stays ignored and k > 32 stays refused in exhaustive mode. */
+int bgr_aligner_exhaustive_paths_enable(bgr_aligner* a, int on);
+int bgr_aligner_device_rows_view(bgr_aligner* a, void** d_view);
+int bgr_graph_exhaustive_paths_enable(bgr_graph* g, int on);
+int bgr_graph_exhaustive_paths_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
 /* Copy the last device results to the host in input order (same output contract as bgr_align_batch). */
 int bgr_aligner_fetch(bgr_aligner* a, uint64_t n_reads, int32_t* paths_out, uint64_t paths_cap, uint64_t* path_offsets, uint8_t* status);
 

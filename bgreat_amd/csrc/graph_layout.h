@@ -183,7 +183,7 @@ typedef struct {
 // The index is a HINT -- everything it says is verified against `seq` -- and therefore lossy: a hash table over a SAMPLE of the (k-1)-mers of
 // every forward strand, keyed by the canonical (k-1)-mer through m = bgr_mix64 (the scan's hash).  The sample is chosen by the hash itself: one
 // (k-1)-mer in BGR_JUMP_STRIDE, those with bgr_jump_selects(m) (palindromes left out) -- so a read knows, without touching memory, which of its
-// windows can be in the index at all, and probes ONE of them per item (sampling every 4th offset instead costs four probes per item, each its own
+// windows can be in the index at all, and probes ONE of them per item and set of windows (sampling every 4th offset instead costs four probes per item, each its own
 // cache line of a table far larger than the L2: measured, the probes then cost most of what the jump saves).  bucket = mulhi32(low word of m,
 // jump_buckets), tag = bgr_tab_fp(m).  A bucket is 16 bytes = two entries, one load per probe; an entry that finds its bucket full is dropped
 // (one bucket per sampled (k-1)-mer on average: about one in ten), and so is one whose offset does not fit its field.
@@ -194,7 +194,11 @@ typedef struct {
 #define BGR_JUMP_FWD_CANON 0x40000000u
 #define BGR_JUMP_MAX_T 0x00FFFFFFu
 #define BGR_JUMP_STRIDE 4u     /* a power of two */
-#define BGR_JUMP_WINDOWS 3u    /* the kernel hashes the first 4 x BGR_JUMP_WINDOWS windows of an item for one that is sampled (12: 97 in 100 have one) */
+// the windows of an item the kernel hashes for one that is sampled: the first BGR_JUMP_NEAR, and BGR_JUMP_FAR more that start k-1 bases behind
+// them, i.e. at BGR_JUMP_NEAR + (k-1) from the item's first position, so that no base is shared: a substitution that spoils every near window
+// leaves the far ones alone.  One window of either set is probed.  8 near windows: 90 in 100 items have a sampled one; 4 far windows: 68 in 100.
+#define BGR_JUMP_NEAR 8u       /* a multiple of 4 (the lanes of an item) */
+#define BGR_JUMP_FAR 4u        /* a multiple of 4 */
 // the index must stay resident in the device's last-level cache next to the rest of the graph and the reads in flight: a quarter of the
 // MI355X's 256 MiB Infinity Cache.  (E. coli scale: 18 MB.  The chr1-scale graph would need 900 MB -- its key table is not staged anyway.)
 #define BGR_JUMP_CAP_BYTES (64ull << 20)

@@ -226,6 +226,7 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
     unsigned long long wt2 = 0;
     uint32_t dbg_steps = 0, dbg_items = 0, dbg_groups = 0;  // tools/scan_steps.py: scan steps, items scanned, groups of items taken
     uint32_t dbg_jumped = 0, dbg_raised = 0;                // items the jump settled without a scan step, items whose resume position it raised
+    uint32_t dbg_far = 0, dbg_bounded = 0;                  // of the settled ones: by the far entry; items left a range the jump cut at either end
 #endif
     uint32_t ktab_words;
     const uint32_t* ktab = block_prologue<STAGE>(g, lds, &ktab_words);
@@ -300,7 +301,11 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             }
             const uint32_t Wr = (L + 31) >> 5;
             uint32_t chars = 0;
-            for (uint32_t j = sub; j < W; j += GL) {
+            // (the lane's first word is worked out from the lane number here, behind an empty asm: what the loop derives from `sub` would
+            // otherwise be hoisted out of the kernel's loop and held in registers through the scan and the extension, which have none to spare)
+            uint32_t j0 = threadIdx.x;
+            asm volatile("" : "+v"(j0));
+            for (uint32_t j = j0 % GL; j < W; j += GL) {
                 u64 f = 0;
                 if (act && j < Wr) {
                     if (ASCII) {
@@ -353,12 +358,19 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
             uint32_t to_scan = (act != 0 && g_from < g_npos) ? 1u : 0u;
             // The jump (graph_layout.h, jump index): most positions a scan looks up are interior (k-1)-mers of the unitig the read lies on, and
             // under property P none of those is a key.  For all sixteen items at once: the four lanes of an item hash the item's first
-            // 4 x BGR_JUMP_WINDOWS windows and the first window whose hash selects it (one in BGR_JUMP_STRIDE does, and only those are in the index)
-            // is probed -- ONE load per item; a hit names a unitig and an offset, i.e. a diagonal; the lanes compare the read with `seq` along it,
-            // from the resume position to the first mismatch (or the end of either).  Every window of that stretch is the unitig's own, so it
-            // is a key exactly where the diagonal passes a unitig end: the item's anchor -- or the fact that it has none -- is arithmetic, and an
-            // item the stretch does not settle resumes its scan behind it.  The index is only a hint: nothing is concluded from what was not
-            // compared, and an item without a hit (or whose stretch starts behind its resume position) is scanned as it always was.
+            // BGR_JUMP_NEAR windows and BGR_JUMP_FAR windows that share no base with them (a substitution under the near windows loses every one
+            // of them, and the far ones with it unless they lie clear of it).  Of either set the first window whose hash selects it (one in
+            // BGR_JUMP_STRIDE does, and only those are in the index) is probed, both loads in flight together; the near entry is used when it hits,
+            // else the far one.  A hit names a unitig and an offset, i.e. a diagonal: the strand occupies read positions [A, A + len), A below,
+            // at or above the resume position (a far window often lies in the NEXT unitig).  The lanes compare the read with `seq` along it over
+            // [cs, ce) = [max(A, resume), min(A + len, L)), past every mismatch, and keep the first and the last one.  A window is VERIFIED iff
+            // all its k-1 bases lie in the stretch and none is a mismatch: it is the strand's own (k-1)-mer, a key exactly at strand offset 0 and
+            // len - (k-1).  The verified windows in front of the first mismatch and behind the last one are what counts: fb = the smallest
+            // verified key position, and the scan is left the range [lo, hi) -- from the first unverified window to one past the last unverified
+            // window below fb (below npos without one) -- with a_pos / a_rec pre-set to fb: the range's first hit overwrites them, as the plain
+            // scan's would.  An empty range settles the item.  Verified windows between two mismatches are scanned needlessly; they are no keys.
+            // The index is only a hint: nothing is concluded from a window that was not compared in full, and an item without a hit is scanned
+            // as it always was.
 #ifdef BGR_PHASE_TIMING
             if ((g.flags & BGR_GF_JUMP) && prm.debug_stop != 1) {  // (1 = stops behind the staging of the reads)
 #else
@@ -371,103 +383,148 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
                 const uint4* jtab = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(jh) + jh->off_jump);
                 const BgrUnitigMeta* jmeta = reinterpret_cast<const BgrUnitigMeta*>(reinterpret_cast<const char*>(jh) + jh->off_meta);
                 const uint32_t jnb = (uint32_t)jh->jump_buckets;
-                // lane `sub` looks at the positions g_from + sub + 4 j; my_rel: its first selected window, counted from g_from (none: 255), with
-                // the window's tag in bits 8-15 and "it is its own canonical form" in bit 31; my_bk: its bucket
-                uint32_t my_rel = 255u, my_bk = 0;
+                // lane `sub` looks at the near positions g_from + sub + 4 j and at the far ones, k-1 further on (the first far window starts behind
+                // the last near window's last base); my_rel / my_far: its first selected window of either set, counted from g_from (none: 255),
+                // with the window's tag in bits 8-15 and "it is its own canonical form" in bit 31; my_bk / my_fbk: the bucket.  A far window
+                // past the read's last one is not looked at: a short read has none.
+                static_assert(BGR_JUMP_NEAR % GL == 0 && BGR_JUMP_FAR % GL == 0 && BGR_JUMP_NEAR + BGR_JUMP_FAR + 32u < 255u, "whole rounds of the quad; the offset fits its byte");
+                uint32_t my_rel = 255u, my_bk = 0, my_far = 255u, my_fbk = 0;
 #pragma unroll 1
-                for (uint32_t rel = sub; rel < GL * BGR_JUMP_WINDOWS; rel += GL) {
-                    if (to_scan && my_rel == 255u && g_from + rel < g_npos) {
+                for (uint32_t r0 = 0; r0 < BGR_JUMP_NEAR + BGR_JUMP_FAR; r0 += GL) {
+                    const uint32_t far = r0 >= BGR_JUMP_NEAR ? 1u : 0u;
+                    const uint32_t rel = r0 + sub + (far ? K1 : 0u);
+                    if (to_scan && (far ? my_far : my_rel) == 255u && g_from + rel < g_npos) {
                         const u64 num = lds_win32(F, g_from + rel) >> (64 - 2 * K1);
                         const u64 rcn = rcb_fast(num, K1);
                         const u64 mx = bgr_mix64(num < rcn ? num : rcn);
                         if (bgr_jump_selects(mx) && num != rcn) {
-                            my_rel = rel | (bgr_tab_fp(mx) << 8) | (num < rcn ? 0x80000000u : 0u);
-                            my_bk = __umulhi((uint32_t)mx, jnb);
+                            const uint32_t v = rel | (bgr_tab_fp(mx) << 8) | (num < rcn ? 0x80000000u : 0u);
+                            const uint32_t bk = __umulhi((uint32_t)mx, jnb);
+                            if (far) { my_far = v; my_fbk = bk; }
+                            else { my_rel = v; my_bk = bk; }
                         }
                     }
                 }
-                uint32_t w_sub = my_rel & 255u;  // the quad's first selected window: its lane probes
-                { const uint32_t o = quad_xor1(w_sub); w_sub = o < w_sub ? o : w_sub; }
-                { const uint32_t o = quad_xor2(w_sub); w_sub = o < w_sub ? o : w_sub; }
-                uint32_t w_idc = 0, w_tt = 0;  // the entry; bit 31 of w_idc: the read's window is its own canonical form
-                if ((my_rel & 255u) == w_sub && w_sub != 255u) {
-                    const uint4 b = jtab[my_bk];
-                    const uint32_t tag = (my_rel >> 8) & 0xFFu;
-                    if ((b.y & 0xFFu) == tag) { w_idc = b.x; w_tt = b.y; }
-                    else if ((b.w & 0xFFu) == tag) { w_idc = b.z; w_tt = b.w; }
-                    if (w_tt) w_idc = (w_idc & 0x7FFFFFFFu) | (my_rel & 0x80000000u);
-                    else w_idc = 0;
-                }
-                w_tt |= quad_xor1(w_tt); w_tt |= quad_xor2(w_tt);      // (one lane of the quad holds it: into all four)
+                // the quad's first selected window of either set: the lane that holds it probes (two lanes: one load instruction for both)
+                uint32_t n_sub = my_rel & 255u, f_sub = my_far & 255u;
+                { const uint32_t o = quad_xor1(n_sub); n_sub = o < n_sub ? o : n_sub; }
+                { const uint32_t o = quad_xor1(f_sub); f_sub = o < f_sub ? o : f_sub; }
+                { const uint32_t o = quad_xor2(n_sub); n_sub = o < n_sub ? o : n_sub; }
+                { const uint32_t o = quad_xor2(f_sub); f_sub = o < f_sub ? o : f_sub; }
+                uint4 bn = make_uint4(0, 0, 0, 0), bf = make_uint4(0, 0, 0, 0);
+                if ((my_rel & 255u) == n_sub && n_sub != 255u) bn = jtab[my_bk];
+                if ((my_far & 255u) == f_sub && f_sub != 255u) bf = jtab[my_fbk];
+                // the entry whose tag is the window's (tags are 1 .. 255: a lane that did not load matches nothing); bit 31 of idc: the read's
+                // window is its own canonical form
+                auto entry = [](const uint4& b, uint32_t mine, uint32_t& idc, uint32_t& tt) {
+                    const uint32_t tag = (mine >> 8) & 0xFFu;
+                    const bool first = (b.y & 0xFFu) == tag;
+                    tt = first ? b.y : (b.w & 0xFFu) == tag ? b.w : 0u;
+                    idc = tt ? ((first ? b.x : b.z) & 0x7FFFFFFFu) | (mine & 0x80000000u) : 0u;
+                };
+                uint32_t w_idc, w_tt, f_idc, f_tt;
+                entry(bn, my_rel, w_idc, w_tt);
+                entry(bf, my_far, f_idc, f_tt);
+                uint32_t near_hit = w_tt;  // (one lane of the quad holds an entry: into all four)
+                near_hit |= quad_xor1(near_hit); near_hit |= quad_xor2(near_hit);
+                if (!near_hit) { w_tt = f_tt; w_idc = f_idc; }
+                w_tt |= quad_xor1(w_tt); w_tt |= quad_xor2(w_tt);
                 w_idc |= quad_xor1(w_idc); w_idc |= quad_xor2(w_idc);
-                // the diagonal: the read on strand rcs of the unitig (0: forward, 1: the copy at F + len), its base g_from at offset u0 of that strand
-                uint32_t live = 0, ulen = 0, rcs = 0, u0 = 0, rb = 0, re = 0, mfl = 0, hi_p = 0;
-                uint32_t sw = 0, ss = 0;  // base g_from of the read lies at bit ss of seq word sw (the store stays below 2^32 bytes)
+                const uint32_t w_sub = near_hit ? n_sub : f_sub;  // the probed window, counted from g_from
+                // the diagonal: the read on strand rcs of the unitig (0: forward, 1: the copy at F + len); the stretch starts at read position
+                // cs = max(A, g_from), which is offset soff of that strand (soff == 0: A >= g_from, cs == g_from: A <= g_from), and ends at ce
+                // (0: no diagonal).  The strand's (k-1)-mers are keys at offset 0 -- read position cs when soff == 0 -- and at len - (k-1) -- read
+                // position p1 -- and nowhere else.  rec0, rec1: what the two are as anchors (strand offset 0 is the unitig's beg forward and rc(end)
+                // on the other strand, the far end the other way round); BGR_NONE: not among the item's positions [g_from, npos), or, the far end,
+                // behind the read's last base
+                uint32_t rec0 = BGR_NONE, rec1 = BGR_NONE, p1 = 0, cs = g_from, ce = 0;
+                uint32_t sw = 0, ss = 0;  // base cs of the read lies at bit ss of seq word sw (the store stays below 2^32 bytes)
                 if (w_tt) {
                     const BgrUnitigMeta* mp = jmeta + (w_idc & BGR_SLOT_ID_MASK);
                     const uint4 m0 = *reinterpret_cast<const uint4*>(mp);  // len, flags, rec_beg, rec_end
                     const u64 Fm = mp->F;
-                    ulen = m0.x; mfl = m0.y; rb = m0.z; re = m0.w;
+                    const uint32_t ulen = m0.x;
                     const uint32_t t = w_tt >> 8;
-                    rcs = ((w_idc >> 31) ^ (w_idc >> 30)) & 1u;
+                    const uint32_t rcs = ((w_idc >> 31) ^ (w_idc >> 30)) & 1u;
                     if (t + K1 <= ulen) {
                         const uint32_t u = rcs ? ulen - K1 - t : t;  // the probed window's offset on that strand
-                        if (u >= w_sub) {                            // the stretch starts at the resume position (else: the plain scan)
-                            u0 = u - w_sub;
-                            const u64 sbase = Fm + (rcs ? ulen : 0u) + u0;
-                            sw = (uint32_t)(sbase >> 5);
-                            ss = 2u * ((uint32_t)sbase & 31u);
-                            const uint32_t room = ulen - u0;         // bases of the unitig from u0 on
-                            hi_p = L - g_from < room ? L : g_from + room;
-                            live = 1;
-                        }
+                        const uint32_t soff = u > w_sub ? u - w_sub : 0u;
+                        cs = g_from + (w_sub > u ? w_sub - u : 0u);
+                        const u64 sbase = Fm + (rcs ? ulen : 0u) + soff;
+                        sw = (uint32_t)(sbase >> 5);
+                        ss = 2u * ((uint32_t)sbase & 31u);
+                        const uint32_t room = ulen - soff;           // bases of the strand from soff on
+                        ce = L - cs < room ? L : cs + room;
+                        p1 = cs + (room - K1);
+                        if (soff == 0 && cs < g_npos) rec0 = (rcs ? m0.w : m0.z) | ((m0.y & (rcs ? BGR_META_CANON_RCEND : BGR_META_CANON_BEG)) ? G4_CANON : 0u);
+                        if (ce == cs + room && p1 < g_npos) rec1 = (rcs ? m0.z : m0.w) | ((m0.y & (rcs ? BGR_META_CANON_RCBEG : BGR_META_CANON_END)) ? G4_CANON : 0u);
                     }
                 }
-                // compare: lane `sub` takes the 64-base chunks sub, sub + 4, ... of [g_from, hi_p) -- three words of either side, two windows --
-                // so reads of up to 256 bases behind g_from take one round; e = the first mismatch, or hi_p.  The third word is read only when
-                // the chunk's second half is needed: the read's row and `seq` hold it then (scan_take_word.h: a row has a word to spare;
-                // the store ends in two pad words).
-                uint32_t e = hi_p;
-                const uint32_t fs = 2u * (g_from & 31u);
-                for (uint32_t c0 = 0; __any(live != 0 && g_from + 64u * c0 < hi_p); c0 += GL) {
-                    const uint32_t rp = g_from + 64u * (c0 + sub);
-                    if (live && rp < hi_p) {
-                        const bool two = rp + 32u < hi_p;
+                // compare: lane `sub` takes the 64-base chunks sub, sub + 4, ... of [cs, ce) -- three words of either side, two windows --
+                // so reads of up to 256 bases behind cs take one round; e1 = the first mismatch, or ce; eL = the last one, or -1.  The third
+                // word is read only when the chunk's second half is needed: the read's row and `seq` hold it then (scan_take_word.h: a row
+                // has a word to spare; the store ends in two pad words).  What a chunk holds from ce on is no part of the stretch: masked off.
+                uint32_t e1 = ce;
+                int32_t eL = -1;
+                const uint32_t fs = 2u * (cs & 31u);
+                for (uint32_t c0 = 0; __any(cs + 64u * c0 < ce); c0 += GL) {
+                    const uint32_t rp = cs + 64u * (c0 + sub);
+                    if (rp < ce) {
+                        const uint32_t nv = ce - rp;  // the chunk's bases inside the stretch (64: or more)
+                        const bool two = nv > 32u;
                         const u64* fp = F + (rp >> 5);
                         const u64* sp = g.seq + sw + 2u * (c0 + sub);
                         const u64 f0 = fp[0], f1 = fp[1], f2 = two ? fp[2] : 0;
                         const u64 s0 = sp[0], s1 = sp[1], s2 = two ? sp[2] : 0;
-                        const u64 xa = ((f0 << fs) | ((f1 >> 1) >> (63 - fs))) ^ ((s0 << ss) | ((s1 >> 1) >> (63 - ss)));
-                        const u64 xb = two ? ((f1 << fs) | ((f2 >> 1) >> (63 - fs))) ^ ((s1 << ss) | ((s2 >> 1) >> (63 - ss))) : 0;
-                        const uint32_t q = xa ? rp + ((uint32_t)__builtin_clzll(xa) >> 1) : xb ? rp + 32u + ((uint32_t)__builtin_clzll(xb) >> 1) : e;
-                        e = q < e ? q : e;
+                        u64 xa = ((f0 << fs) | ((f1 >> 1) >> (63 - fs))) ^ ((s0 << ss) | ((s1 >> 1) >> (63 - ss)));
+                        u64 xb = two ? ((f1 << fs) | ((f2 >> 1) >> (63 - fs))) ^ ((s1 << ss) | ((s2 >> 1) >> (63 - ss))) : 0;
+                        // (the stretch ends in the chunk's first half, nv < 32, or in its second, 32 < nv < 64: one mask, for that half)
+                        const u64 keep = ~0ULL << (2u * ((0u - (nv < 64u ? nv : 64u)) & 31u));
+                        if (two) xb &= keep;
+                        else xa &= keep;
+                        if (xa | xb) {
+                            const uint32_t q = xa ? rp + ((uint32_t)__builtin_clzll(xa) >> 1) : rp + 32u + ((uint32_t)__builtin_clzll(xb) >> 1);
+                            const uint32_t z = xb ? rp + 63u - ((uint32_t)__builtin_ctzll(xb) >> 1) : rp + 31u - ((uint32_t)__builtin_ctzll(xa) >> 1);
+                            e1 = q < e1 ? q : e1;
+                            eL = (int32_t)z > eL ? (int32_t)z : eL;
+                        }
                     }
                 }
-                { const uint32_t o = quad_xor1(e); e = o < e ? o : e; }
-                { const uint32_t o = quad_xor2(e); e = o < e ? o : e; }
-                const int32_t last = (int32_t)e - (int32_t)K1;  // the last window of the compared stretch
-                uint32_t jumped = 0, raised = 0;
-                if (live && last >= (int32_t)g_from) {
-                    // windows g_from .. last are the strand's (k-1)-mers u0 .. u0 + last - g_from: keys at offset 0 and at ulen - (k-1), nowhere else
-                    const uint32_t p1 = g_from + (ulen - K1 - u0);
-                    uint32_t found = 0, at_end = 0;
-                    if (u0 == 0) found = 1;
-                    else if ((int32_t)p1 <= last && p1 < g_npos) { found = 1; at_end = 1; }
-                    if (found) {
-                        a_pos = at_end ? p1 : g_from;
-                        // strand offset 0 is the unitig's beg forward and rc(end) on the other strand; the far end the other way round
-                        const uint32_t cbit = at_end ? (rcs ? BGR_META_CANON_RCBEG : BGR_META_CANON_END) : (rcs ? BGR_META_CANON_RCEND : BGR_META_CANON_BEG);
-                        a_rec = ((at_end ^ rcs) ? re : rb) | ((mfl & cbit) ? G4_CANON : 0u);
-                        to_scan = 0;
-                        jumped = 1;
-                    } else if (last >= (int32_t)g_npos - 1) { to_scan = 0; jumped = 1; }  // every position compared, no end passed: no anchor
-                    else { g_from = (uint32_t)last + 1; raised = 1; }
+                { const uint32_t o = quad_xor1(e1); e1 = o < e1 ? o : e1; }
+                { const int32_t o = (int32_t)quad_xor1((uint32_t)eL); eL = o > eL ? o : eL; }
+                { const uint32_t o = quad_xor2(e1); e1 = o < e1 ? o : e1; }
+                { const int32_t o = (int32_t)quad_xor2((uint32_t)eL); eL = o > eL ? o : eL; }
+                uint32_t jumped = 0, raised = 0, by_far = 0, bounded = 0;
+                if (ce) {
+                    // the key at the stretch's first window is verified iff no mismatch lies in it, the one at its last window iff the last
+                    // mismatch lies in front of it
+                    const uint32_t v0 = e1 >= cs + K1 ? 1u : 0u;  // the stretch's first window is verified, and all up to e1 - (k-1)
+                    uint32_t fb = BGR_NONE;
+                    if (rec0 != BGR_NONE && v0) { fb = cs; a_rec = rec0; }
+                    else if (rec1 != BGR_NONE && eL < (int32_t)p1) { fb = p1; a_rec = rec1; }
+                    if (fb != BGR_NONE) a_pos = fb;
+                    // [lo, hi): from the first unverified window to one past the last unverified window below fb (below npos without one).  The
+                    // window below the limit is verified iff it lies in the stretch behind the last mismatch: so are all down to that mismatch.
+                    const uint32_t lo = (cs == g_from && v0) ? e1 - K1 + 1u : g_from;
+                    const uint32_t lim = fb != BGR_NONE ? fb : g_npos;
+                    const int32_t t = (int32_t)lim - 1;
+                    uint32_t hi = lim;
+                    if (t >= (int32_t)cs && (uint32_t)t + K1 <= ce && eL < t) hi = (uint32_t)(eL + 1) > cs ? (uint32_t)(eL + 1) : cs;
+                    if (lo >= hi) { to_scan = 0; jumped = 1; by_far = near_hit ? 0u : 1u; }  // nothing left to scan: the anchor is fb, or there is none
+                    else {
+                        raised = lo > g_from ? 1u : 0u;
+                        bounded = (raised || hi < g_npos) ? 1u : 0u;
+                        g_from = lo;
+                        g_npos = hi;
+                    }
                 }
 #ifdef BGR_PHASE_TIMING
                 dbg_jumped += (uint32_t)__popcll(__ballot(jumped != 0 && sub == 0));
                 dbg_raised += (uint32_t)__popcll(__ballot(raised != 0 && sub == 0));
+                dbg_far += (uint32_t)__popcll(__ballot(by_far != 0 && sub == 0));
+                dbg_bounded += (uint32_t)__popcll(__ballot(bounded != 0 && sub == 0));
 #endif
-                (void)jumped; (void)raised;
+                (void)jumped; (void)raised; (void)by_far; (void)bounded;
             }
             u64 pend = __ballot(to_scan != 0 && sub == 0);
 #ifdef BGR_PHASE_TIMING
@@ -728,7 +785,8 @@ __global__ void __launch_bounds__(1024, BGR_G4_OCC) bgr_align_greedy_multi_kerne
         w[0] = wt0; w[1] = wt1; w[2] = wt2; w[3] = wall_clock64();
         // behind the time stamps of all waves: the wave's scan counts (two-scanner instances; 0 steps for the others)
         unsigned long long* c = io.wave_times + 4ull * (gridDim.x * waves) + 4ull * (blockIdx.x * waves + wave);
-        c[0] = dbg_steps; c[1] = dbg_items; c[2] = dbg_groups; c[3] = (unsigned long long)dbg_jumped | ((unsigned long long)dbg_raised << 32);
+        c[0] = dbg_steps; c[1] = (unsigned long long)dbg_items | ((unsigned long long)dbg_far << 32);
+        c[2] = (unsigned long long)dbg_groups | ((unsigned long long)dbg_bounded << 32); c[3] = (unsigned long long)dbg_jumped | ((unsigned long long)dbg_raised << 32);
     }
 #endif
     __syncthreads();

@@ -2,16 +2,19 @@
 """A CPU model of the jump in front of the greedy multi kernel's anchor scan (no GPU; greedy_kernels.hip, graph_layout.h: jump index), in the
 style of tools/scan_halves.py, from bench.py's seeded reads.  The index holds one (k-1)-mer in --stride of every unitig, chosen by a hash of its canonical form
 (canonical form -> unitig, offset, strand; palindromes left out; a share --drop of the entries is lost, as the two-entry buckets of the real
-table lose them).  An item hashes its first --probes windows and probes the index once, with the first window the hash selects (--by-offset:
-the index holds every --stride-th offset instead and all --probes windows are probed -- the first scheme tried; it costs --probes loads per
-item where the hash scheme costs one); a hit names a diagonal, the read is compared with the unitig along
-it from the item's first position to the first mismatch, and the windows of that stretch are keys exactly where the diagonal passes a unitig
-end (property P, checked here as the builder checks it).  The item is then settled (its first anchor, or none), or its scan starts behind the
-stretch, or -- no hit, or a stretch that starts behind the item's first position -- it is scanned as before.  The model asserts that a
-settled item's answer is the plain scan's first anchor and that no raised start skips one.  Printed: the share of items settled, of items
-whose start was raised, and the steps of two 32-lane scanners per sixteen items before and after (a scanner starts at the item's start rounded
-down to 16).  Items: the forward first items, and with them the reverse-complement items of the reads the oracle marks (status bit 2).
-The defaults are bench.py's default workload (configs[2]); configs[1]:  python tools/scan_jump.py --genome 250000 --site-spacing 75 --read-len 100
+table lose them).  An item hashes its first --near windows and --far windows from --far-offset on (default: --near + k-1, so that they share
+no base with the near ones) and probes the index with the first window of either set that the hash selects; the near entry is used when
+it hits, else the far one.  A hit names a diagonal: the strand occupies read positions [A, A + len), and the read is compared with it over
+[max(A, start), min(A + len, L)), past --past mismatches (-1, the kernel: past all of them, keeping the first and the last; n >= 0: the
+mismatch number n + 1 cuts the stretch, and the verified windows between two mismatches count as well).  A window is verified iff all its k-1 bases
+lie in the stretch and none is a mismatch; a verified window is a key exactly where the diagonal passes a unitig end (property P, checked here
+as the builder checks it).  fb = the smallest verified key position; the item's scan is left the range from its first unverified window to one
+past the last unverified window below fb (below npos without one); an empty range settles the item.  The model asserts for every item that
+the range's first key -- fb without one -- is the plain scan's first anchor.  Printed: the share of items settled (and by the far entry),
+of items left a bounded range, and the steps of two 32-lane scanners per sixteen items before and after (a scanner starts at the range's start
+rounded down to 16).  Items: the forward first items, and with them the reverse-complement items of the reads the oracle marks (status bit 2).
+The defaults are the kernel's constants and bench.py's default workload (configs[2]); configs[1]:
+python tools/scan_jump.py --genome 250000 --site-spacing 75 --read-len 100.  The scheme before the far probe: --near 12 --far 0 --past 0.
 tools/scan_steps.py on the diagnostic build is the measured counterpart."""
 import argparse
 import os
@@ -38,8 +41,10 @@ ap.add_argument("--mismatch", type=int, default=2)
 ap.add_argument("--seed-graph", type=int, default=20261003)
 ap.add_argument("--seed-reads", type=int, default=77)
 ap.add_argument("--stride", type=int, default=4)
-ap.add_argument("--probes", type=int, default=12, help="windows of an item that are looked at (the kernel: 4 x BGR_JUMP_WINDOWS)")
-ap.add_argument("--by-offset", action="store_true", help="sample every --stride-th offset and probe every window (use --probes 4)")
+ap.add_argument("--near", type=int, default=8, help="near windows of an item that are hashed (BGR_JUMP_NEAR)")
+ap.add_argument("--far", type=int, default=4, help="far windows of an item that are hashed (BGR_JUMP_FAR)")
+ap.add_argument("--far-offset", type=int, default=-1, help="the first far window, counted from the item's first position (default: near + k-1)")
+ap.add_argument("--past", type=int, default=-1, help="mismatches the compare goes past (-1: all, the kernel)")
 ap.add_argument("--drop", type=float, default=0.10, help="share of the sampled (k-1)-mers that the table loses")
 a = ap.parse_args()
 K1, N, Lr = a.k - 1, a.reads, a.read_len
@@ -77,10 +82,10 @@ def selects(canon):
 
 
 for i, u in enumerate(U):
-    for t in range(0, len(u) - K1 + 1, a.stride if a.by_offset else 1):
+    for t in range(0, len(u) - K1 + 1):
         w = u[t:t + K1]
         r = rc(w)
-        if w == r or not (a.by_offset or selects(min(w, r))):
+        if w == r or not selects(min(w, r)):
             continue
         n_sampled += 1
         if rng.random() < a.drop:
@@ -89,52 +94,67 @@ for i, u in enumerate(U):
 print("unitigs %d, sampled (k-1)-mers %d, entries %d (%.1f MB at 8 B per entry, one 16-byte bucket per sample)" % (len(U), n_sampled, len(index), 16 * n_sampled / 1e6))
 
 
-def first_anchor(r, start=0):
-    return next((j for j in range(start, npos) if r[j:j + K1] in J), -1)
+FAR0 = a.far_offset if a.far_offset >= 0 else a.near + K1
 
 
-def jump(r, g_from=0):
-    """-> ('settled', anchor or -1) | ('raised', new start) | ('scan', g_from)"""
-    for sub in range(a.probes):
-        p = g_from + sub
+def first_key(r, lo, hi):
+    return next((j for j in range(lo, hi) if r[j:j + K1] in J), -1)
+
+
+def probe(r, g_from, rels):
+    """the first window of `rels` (offsets from g_from) that the hash selects -> (offset, entry or None) | None"""
+    for rel in rels:
+        p = g_from + rel
         if p >= npos:
             break
         w = r[p:p + K1]
         c = rc(w)
-        if not a.by_offset and (w == c or not selects(min(w, c))):
+        if w == c or not selects(min(w, c)):
             continue
-        e = index.get(min(w, c))
-        if e is None:
-            if a.by_offset:
-                continue
-            return ("scan", g_from)                 # one probe per item
-        i, t, fwd_canon = e
-        rcs = (w <= c) != fwd_canon                 # the read runs along the unitig's other strand
-        ulen = len(U[i])
-        u = ulen - K1 - t if rcs else t             # the probed window's offset on that strand
-        if u < sub:
-            return ("scan", g_from)                 # the stretch would start behind the item's first position
-        u0 = u - sub
-        strand = URC[i] if rcs else U[i]
-        hi = min(Lr, g_from + ulen - u0)
-        e_pos = next((q for q in range(g_from, hi) if r[q] != strand[u0 + q - g_from]), hi)
-        last = e_pos - K1
-        if last < g_from:
-            return ("scan", g_from)
-        p1 = g_from + (ulen - K1 - u0)
-        if u0 == 0:
-            return ("settled", g_from)
-        if p1 <= last and p1 < npos:
-            return ("settled", p1)
-        if last >= npos - 1:
-            return ("settled", -1)
-        return ("raised", last + 1)
-    return ("scan", g_from)
+        return rel, w <= c, index.get(min(w, c))
+    return None
 
 
-def scan_steps(start, anchor):  # steps of a 32-lane scanner that starts at `start` rounded down to 16
+def jump(r, g_from=0):
+    """-> (lo, hi, fb, by_far): the range left to the scan, the fallback anchor (-1: none), whether the far entry was used"""
+    near = probe(r, g_from, range(a.near))
+    far = probe(r, g_from, range(FAR0, FAR0 + a.far))
+    by_far = not (near and near[2])
+    hit = far if by_far else near
+    if not hit or not hit[2]:
+        return g_from, npos, -1, False
+    rel, w_canon, (i, t, fwd_canon) = hit
+    rcs = w_canon != fwd_canon                      # the read runs along the unitig's other strand
+    ulen = len(U[i])
+    u = ulen - K1 - t if rcs else t                 # the probed window's offset on that strand
+    strand = URC[i] if rcs else U[i]
+    A = g_from + rel - u                            # the strand occupies read positions [A, A + ulen)
+    cs, ce = max(A, g_from), min(A + ulen, Lr)
+    mis = [q for q in range(cs, ce) if r[q] != strand[q - A]]
+    between = []                                    # verified windows between two mismatches (the kernel keeps none)
+    if a.past >= 0:
+        if len(mis) > a.past:
+            ce, mis = mis[a.past], mis[:a.past]
+        between = [(mis[n] + 1, mis[n + 1] - K1) for n in range(len(mis) - 1)]
+    e1, eL = (mis[0], mis[-1]) if mis else (ce, -1)
+
+    def verified(j):
+        return cs <= j and j + K1 <= ce and (j + K1 <= e1 or j > eL or any(x <= j <= y for x, y in between))
+    fb = -1
+    p1 = A + ulen - K1
+    if A >= g_from and A < npos and verified(A):
+        fb = A
+    elif p1 >= g_from and p1 < npos and verified(p1):
+        fb = p1
+    lim = fb if fb >= 0 else npos
+    lo = next((j for j in range(g_from, lim) if not verified(j)), lim)
+    hi = next((j + 1 for j in range(lim - 1, lo - 1, -1) if not verified(j)), lo)
+    return lo, hi, fb, by_far
+
+
+def scan_steps(start, anchor, end):  # steps of a 32-lane scanner that starts at `start` rounded down to 16 and covers [start, end)
     hb = start & ~15
-    return (anchor - hb) // 32 + 1 if anchor >= 0 else (npos - hb + 31) // 32
+    return (anchor - hb) // 32 + 1 if anchor >= 0 else (end - hb + 31) // 32
 
 
 def wave_steps(st):  # list scheduling of one wave's items, in order, on two scanners
@@ -146,24 +166,27 @@ def wave_steps(st):  # list scheduling of one wave's items, in order, on two sca
 
 
 def model(items, label):
-    before, after, settled, raised = [], [], 0, 0
+    before, after, settled, far_settled, bounded, raised = [], [], 0, 0, 0, 0
     for r in items:
-        fa = first_anchor(r)
-        what, v = jump(r)
-        before.append(scan_steps(0, fa))
-        if what == "settled":
-            assert v == fa, "the jump's answer differs from the plain scan's first anchor"
+        fa = first_key(r, 0, npos)
+        lo, hi, fb, by_far = jump(r)
+        h = first_key(r, lo, hi)
+        assert (h if h >= 0 else fb) == fa, "range + fallback differ from the plain scan's first anchor"
+        before.append(scan_steps(0, fa, npos))
+        if lo >= hi:
             settled += 1
+            far_settled += by_far
             after.append(0)
         else:
-            assert first_anchor(r, v) == fa, "a raised start skipped an anchor"
-            raised += what == "raised"
-            after.append(scan_steps(v, fa))
+            raised += lo > 0
+            bounded += lo > 0 or hi < npos
+            after.append(scan_steps(lo, h, hi))
     W = len(items) // 16
     b = np.mean([wave_steps(before[w * 16:(w + 1) * 16]) for w in range(W)])
     f = np.mean([wave_steps(after[w * 16:(w + 1) * 16]) for w in range(W)])
-    print("%s: %d items, settled without a scan step %.1f %%, start raised %.1f %%; steps per sixteen items %.2f -> %.2f" % (
-        label, len(items), 100 * settled / len(items), 100 * raised / len(items), b, f))
+    n = len(items)
+    print("%s: %d items, settled without a scan step %.1f %% (by the far entry %.1f %%), scanned a bounded range %.1f %% (start raised %.1f %%); "
+          "steps per sixteen items %.2f -> %.2f" % (label, n, 100 * settled / n, 100 * far_settled / n, 100 * bounded / n, 100 * raised / n, b, f))
 
 
 fw = [R[i * Lr:(i + 1) * Lr] for i in range(N)]

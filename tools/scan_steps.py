@@ -37,14 +37,19 @@ n = C.c_uint64()
 B._check(lib.bgr_debug_scan_counts(al.h, None, 0, C.byref(n)))
 buf = np.zeros(4 * n.value, dtype=np.uint64)
 B._check(lib.bgr_debug_scan_counts(al.h, buf.ctypes.data, n.value, C.byref(n)))
-c = buf.reshape(-1, 4).astype(np.float64)
-steps, items, groups = c[:, 0].sum(), c[:, 1].sum(), c[:, 2].sum()
+w = buf.reshape(-1, 4)
+lo32, sh32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+steps, items, groups = float(w[:, 0].sum()), float((w[:, 1] & lo32).sum()), float((w[:, 2] & lo32).sum())
 # the jump in front of the scan (graphs with a jump index): items it settled without a scan step (not among the items scanned), items whose
 # resume position it raised (tools/scan_jump.py is the model)
-jumped, raised = float((buf.reshape(-1, 4)[:, 3] & np.uint64(0xFFFFFFFF)).sum()), float((buf.reshape(-1, 4)[:, 3] >> np.uint64(32)).sum())
+jumped, raised = float((w[:, 3] & lo32).sum()), float((w[:, 3] >> sh32).sum())
+# of the settled ones: by the far entry; of the scanned ones: those left a range the jump cut at either end (raised ones are among them)
+by_far, bounded = float((w[:, 1] >> sh32).sum()), float((w[:, 2] >> sh32).sum())
 print("workload %s, %d reads, %d waves (launch %s)" % (args.workload, R, n.value, al.launch_info()))
 print("scan steps %d, items scanned %d (%.3f per read), groups of items %d (%.2f items each)" % (steps, items, items / R, groups, items / max(groups, 1)))
 print("jump index: %s; items settled by the jump %d (%.1f %% of all items), resume position raised %d (%.1f %%)" % (
     g.jump_info()["jump_entries"] or "none", jumped, 100 * jumped / max(items + jumped, 1), raised, 100 * raised / max(items + jumped, 1)))
+print("            settled by the far entry %d (%.1f %%), scanned a bounded range %d (%.1f %%)" % (
+    by_far, 100 * by_far / max(items + jumped, 1), bounded, 100 * bounded / max(items + jumped, 1)))
 print("steps per sixteen items, settled ones included: %.2f" % (16 * steps / max(items + jumped, 1)))
 print("steps per read %.3f, per item %.3f, per sixteen items %.2f, per group %.2f" % (steps / R, steps / max(items, 1), 16 * steps / max(items, 1), steps / max(groups, 1)))

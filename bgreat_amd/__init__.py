@@ -44,6 +44,7 @@ SYMBOLS = [
     "bgr_bubbles_phase", "bgr_graph_phase_enable", "bgr_graph_phase_enabled", "bgr_graph_phase", "bgr_write_phase",
     "bgr_phase_blocks", "bgr_phase_blocks_times", "bgr_graph_blocks_enable", "bgr_graph_blocks_enabled", "bgr_graph_blocks", "bgr_write_blocks",
     "bgr_blocks_haplotypes", "bgr_blocks_haplotypes_times", "bgr_graph_haplotypes_enable", "bgr_graph_haplotypes_enabled", "bgr_graph_haplotypes", "bgr_write_haplotypes",
+    "bgr_graph_recompact", "bgr_graph_recompact_times", "bgr_graph_recompact_enable", "bgr_graph_recompact_enabled", "bgr_graph_recompact_result", "bgr_write_recompact",
     "bgr_blocks_tag_table", "bgr_read_blocks_tags", "bgr_aligner_haplotag_enable", "bgr_aligner_haplotags", "bgr_graph_haplotag_enable", "bgr_graph_haplotag_enabled",
     "bgr_aligner_path_diffs", "bgr_aligner_gaf_cs_enable", "bgr_graph_gaf_cs_enable", "bgr_graph_gaf_cs_enabled",
     "bgr_aligner_pileup_enable", "bgr_aligner_pileup", "bgr_aligner_reset_pileup", "bgr_graph_pileup_enable", "bgr_graph_pileup_enabled", "bgr_graph_pileup",
@@ -153,6 +154,8 @@ class Haplotype(C.Structure):  # bgr_haplotype
     _fields_ = [("block", C.c_uint32), ("hap", C.c_uint32), ("size", C.c_uint32), ("flags", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64)]
 
 
+CHAIN_DTYPE = np.dtype([("seq_off", np.uint64), ("seq_len", np.uint64), ("walk_off", np.uint64), ("n_unitigs", np.uint32), ("flags", np.uint32)])   # an array of bgr_chain
+CHAIN_CIRCULAR = 1
 HAPLOTYPE_DTYPE = np.dtype([("block", np.uint32), ("hap", np.uint32), ("size", np.uint32), ("flags", np.uint32), ("offset", np.uint64), ("length", np.uint64)])   # an array of bgr_haplotype
 
 
@@ -360,6 +363,12 @@ def lib():
     L.bgr_graph_haplotypes_enabled.argtypes = [vp]
     L.bgr_graph_haplotypes.argtypes = [vp, vp, u64, vp, vp, u64, vp]
     L.bgr_write_haplotypes.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, u64, vp, u64]
+    L.bgr_graph_recompact.argtypes = [vp, C.c_int, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, vp]
+    L.bgr_graph_recompact_times.argtypes = [vp]
+    L.bgr_graph_recompact_enable.argtypes = [vp, u32, u64]
+    L.bgr_graph_recompact_enabled.argtypes = [vp]
+    L.bgr_graph_recompact_result.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp]
+    L.bgr_write_recompact.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, u64]
     L.bgr_blocks_tag_table.argtypes = [vp, u64, vp, u64, u64, u64, vp, vp]
     L.bgr_read_blocks_tags.argtypes = [C.c_char_p, u64, vp, vp]
     L.bgr_aligner_haplotag_enable.argtypes = [vp, vp, u64]
@@ -852,6 +861,27 @@ class Graph:
         """bgr_graph_haplotypes: the sequences of the last align_all with the switch on -> (array of HAPLOTYPE_DTYPE, block after block, A before B;
         the characters as one uint8 array the records point into)."""
         return _fetch_haplotypes(lambda out, cap, n, seq, seq_cap, seq_bytes: lib().bgr_graph_haplotypes(self.h, out, cap, n, seq, seq_cap, seq_bytes))
+
+    def recompact(self, keep, device=0):
+        """bgr_graph_recompact: the unitigs with a non-zero byte in `keep` (one per unitig 1..n) merged into maximal non-branching chains on `device`,
+        where the graph must be resident -> (array of CHAIN_DTYPE in the reported order, the walks' oriented ids as one int32 array, the characters
+        as one uint8 array).  The sizing call comes first."""
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        return _fetch_chains(lambda out, cap, n, walk, walk_cap, walk_n, seq, seq_cap, seq_bytes: lib().bgr_graph_recompact(
+            self.h, int(device), keep.ctypes.data if len(keep) else None, keep.shape[0], out, cap, n, walk, walk_cap, walk_n, seq, seq_cap, seq_bytes))
+
+    def recompact_enable(self, on=True, min_reads=1):
+        """bgr_graph_recompact_enable: sticky -- every later align_all on this graph counts unitig abundance and, when it ends, compacts the unitigs
+        with reads >= min_reads (0 keeps everything) on the device."""
+        _check(lib().bgr_graph_recompact_enable(self.h, int(bool(on)), int(min_reads)))
+
+    def recompact_enabled(self):
+        """bgr_graph_recompact_enabled: the switch as it stands."""
+        return bool(lib().bgr_graph_recompact_enabled(self.h))
+
+    def recompact_result(self):
+        """bgr_graph_recompact_result: the chains of the last align_all with the switch on -> (CHAIN_DTYPE records, int32 walk, uint8 characters)."""
+        return _fetch_chains(lambda *a: lib().bgr_graph_recompact_result(self.h, *a))
 
     def haplotag_enable(self, table):
         """bgr_graph_haplotag_enable: sticky -- every later align_all with gaf on this graph tags its lines from `table` (n_unitigs + 1 uint32, as
@@ -1487,6 +1517,35 @@ def _fetch_haplotypes(call):
     out, seq = np.zeros(n.value, dtype=HAPLOTYPE_DTYPE), np.zeros(nb.value, dtype=np.uint8)
     _check(call(out.ctypes.data, n.value, C.byref(n), seq.ctypes.data if nb.value else None, nb.value, C.byref(nb)))
     return out[: n.value], seq[: nb.value]
+
+
+def _fetch_chains(call):
+    """the two-call form with three buffers: the sizes first (BGR_E_CAPACITY with them), then the records, the walk and the characters"""
+    n, nw, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = call(None, 0, C.byref(n), None, 0, C.byref(nw), None, 0, C.byref(nb))
+    if rc != -4 or n.value == 0:   # (no chains, or an error that is not "there are n of them")
+        _check(rc)
+        return np.zeros(0, dtype=CHAIN_DTYPE), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8)
+    out, walk, seq = np.zeros(n.value, dtype=CHAIN_DTYPE), np.zeros(nw.value, dtype=np.int32), np.zeros(nb.value, dtype=np.uint8)
+    _check(call(out.ctypes.data, n.value, C.byref(n), walk.ctypes.data, nw.value, C.byref(nw), seq.ctypes.data, nb.value, C.byref(nb)))
+    return out[: n.value], walk[: nw.value], seq[: nb.value]
+
+
+def recompact_times():
+    """bgr_graph_recompact_times: milliseconds of this thread's last Graph.recompact -> dict(links, rank, place, spell, records)."""
+    ms = (C.c_double * 5)()
+    _check(lib().bgr_graph_recompact_times(ms))
+    return dict(zip(("links", "rank", "place", "spell", "records"), (float(x) for x in ms)))
+
+
+def write_recompact(path, graph, records, walk, seq):
+    """bgr_write_recompact: per chain the line ">{ordinal} LN:i:{length} unitigs={m} ring={.|circular} walk={>12<7>9}" and the sequence on one line: a
+    unitig file that Graph.from_fasta / bgreat -g reads."""
+    records = np.ascontiguousarray(records, dtype=CHAIN_DTYPE)
+    walk = np.ascontiguousarray(walk, dtype=np.int32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    _check(lib().bgr_write_recompact(path.encode(), graph.h, records.ctypes.data if len(records) else None, records.shape[0], walk.ctypes.data if len(walk) else None, walk.shape[0],
+                                     seq.ctypes.data if len(seq) else None, seq.shape[0]))
 
 
 def blocks_haplotypes(graph, bubbles, entries, min_block=1, device=0):

@@ -140,6 +140,7 @@ static const bgr::RunStage kStages[] = {
     {bgr::kCountPhase, run_phase_begin, nullptr, nullptr, run_phase_end, bgr::kTierDerived},
     {bgr::kCountBlocks, run_blocks_begin, nullptr, nullptr, run_blocks_end, bgr::kTierDerived},
     {bgr::kCountHaplotypes, run_haplotypes_begin, nullptr, nullptr, run_haplotypes_end, bgr::kTierDerived},
+    {bgr::kCountRecompact, run_recompact_begin, nullptr, run_recompact_collect, run_recompact_end, bgr::kTierDerived},
     {bgr::kCountPileup, run_pileup_begin, pileup_enable, run_pileup_collect, run_pileup_end, bgr::kTierPileup},
     {bgr::kCountAbundance, graph_abundance_begin, abundance_enable, run_abundance_collect, graph_abundance_end, bgr::kTierAbundance},
 };
@@ -147,7 +148,7 @@ const int kNStages = sizeof(kStages) / sizeof(kStages[0]);
 
 static uint32_t run_counts_wanted(const bgr_graph* g) {
     if (!g) return 0;
-    return bgr::counts_wanted(bgr::RunSwitches{g->links.on, g->bubbles.on, g->triples.on, g->phase.on, g->blocks.on, g->haplotypes.on, g->pileup_on, g->variants_on, g->pileup_strands_on, g->variants_strands_on});
+    return bgr::counts_wanted(bgr::RunSwitches{g->links.on, g->bubbles.on, g->triples.on, g->phase.on, g->blocks.on, g->haplotypes.on, g->pileup_on, g->variants_on, g->pileup_strands_on, g->variants_strands_on, g->recompact.on});
 }
 static void run_counts_begin(bgr_graph* g, uint32_t what) {
     for (const bgr::RunStage& s : kStages) if (what & s.bit) s.begin(g);

@@ -98,6 +98,16 @@ struct bgr_graph {
         std::vector<char> seq;
         void forget() { RunRows<bgr_haplotype>::forget(); std::vector<char>().swap(seq); }
     } haplotypes;
+    // the re-compaction (bgr_graph_recompact_enable): the sticky switch with its threshold, the device of the first aligner a run collected (-1: none yet), and
+    // the chains of the last successful run: records, the walks' oriented ids, the characters
+    struct Recompact : RunRows<bgr_chain> {
+        bool on = false;
+        uint64_t min_reads = 1;
+        int device = -1;
+        std::vector<int32_t> walk;
+        std::vector<char> seq;
+        void forget() { RunRows<bgr_chain>::forget(); std::vector<int32_t>().swap(walk); std::vector<char>().swap(seq); }
+    } recompact;
     // pileup (bgr_graph_pileup_enable): the sticky switch, where every unitig's bases start in a table (prefix sums of the lengths, from the host blob
     // the first time they are asked for), and the totals of the last bgr_align_all with the switch on: the aligners' tables summed mod 2^32
     bool pileup_on = false, pileup_valid = false;
@@ -463,6 +473,9 @@ void run_blocks_begin(bgr_graph* g);                     // capi_blocks.hip
 int run_blocks_end(bgr_graph* g, bool ok);               // ... behind the phase's end
 void run_haplotypes_begin(bgr_graph* g);                 // capi_haplotypes.hip
 int run_haplotypes_end(bgr_graph* g, bool ok);           // ... behind the blocks' end: spelled from the resident graph
+void run_recompact_begin(bgr_graph* g);                  // capi_recompact.hip
+int run_recompact_collect(bgr_graph* g, bgr_aligner* a); // ... the first aligner's device is where the run's kept unitigs will be compacted
+int run_recompact_end(bgr_graph* g, bool ok);            // ... behind the abundance's end: keep = reads >= min_reads
 // The end of a chain stage under abundance_m: what it kept is forgotten; with ok, `call` makes the new rows (BGR_OK, or what it refuses with) provided
 // the stages it reads (`inputs_valid`, else BGR_E_INTERNAL with `missing`) have theirs and, where there is something to call from, an aligner was collected
 template <class F, class Call>

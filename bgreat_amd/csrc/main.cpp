@@ -52,6 +52,10 @@
 //                                                               the device from the graph's 2-bit store: per sequence a line ">block<b>_<A|B> bubbles= length= ring= walk=" and
 //                                                               the sequence on one line; blocks of fewer than N (1) bubbles are left out; counts, calls and chains what
 //                                                               --blocks does: include/bgreat_gpu.h)
+//                                                   --recompact FILE [--min-reads N] (the unitigs that at least N (1; 0 keeps all) mapped reads' paths hold, merged into maximal
+//                                                               non-branching chains on the device and written as a unitig file for the next run's -g: per chain a line
+//                                                               ">ordinal LN:i: unitigs= ring= walk=" and the sequence on one line; counts what --abundance does:
+//                                                               include/bgreat_gpu.h)
 //                                                   --haplotag BLOCKS_FILE (with --gaf: tag every read with the haplotype it lies on -- BLOCKS_FILE is the --blocks file of an earlier run on the same
 //                                                               unitig file, of these reads or of others; a line whose path crosses a branch of a block gains
 //                                                               PS:i:<block> HP:i:<0|1|2> ha:i: hb:i: ho:i: (votes for haplotype A, for B, for other blocks), computed on the
@@ -82,6 +86,7 @@
 #include <vector>
 
 #include "../../include/bgreat_gpu.h"
+#include "recompact_host.h"
 
 static void die(const char* what) {
     fprintf(stderr, "bgreat: %s: %s\n", what, bgr_last_error());
@@ -89,7 +94,7 @@ static void die(const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile, haplotypesFile, haplotagFile;
+    std::string reads, unitigs("unitig.fa"), pathFile("paths"), notAlignedFile("notAligned.fa"), noOverlapFile, abundanceFile, gfaFile, pileupFile, depthFile, vcfFile, bubblesFile, triplesFile, phaseFile, blocksFile, haplotypesFile, haplotagFile, recompactFile;
     int errors = 2, threads = 1, ka = 30, effort = 2, gpus = 1;  // bgreat.cpp:56-66 defaults (k is 30, not 31)
     bgr_variant_params vprm = {2, 2, 200000};   // --min-depth, --min-alt, --min-af
     bool vprm_given = false, strands = false, strand_given = false;
@@ -100,6 +105,8 @@ int main(int argc, char** argv) {
     bool min_phase_given = false;
     uint64_t min_block = 1;        // --min-block
     bool min_block_given = false;
+    uint64_t min_reads = 1;        // --min-reads
+    bool min_reads_given = false;
     long batch = 0, chunk_bytes = 0;  // batch 0 = the pipeline's default per route
     bool brute = false, incomplete = false, fastq = false, correction = false, dog = false, write_exh = false, host_route = false, split_out = false, gaf = false, gaf_cs = false, inside = false, exh_paths = false;
     static option longopts[] = {{"gpus", required_argument, nullptr, 1000}, {"batch", required_argument, nullptr, 1001},
@@ -115,6 +122,7 @@ int main(int argc, char** argv) {
                                 {"haplotypes", required_argument, nullptr, 1025}, {"min-block", required_argument, nullptr, 1026},
                                 {"haplotag", required_argument, nullptr, 1027}, {"cs", no_argument, nullptr, 1028}, {"inside", no_argument, nullptr, 1029},
                                 {"exhaustive-paths", no_argument, nullptr, 1030},
+                                {"recompact", required_argument, nullptr, 1031}, {"min-reads", required_argument, nullptr, 1032},
                                 {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "r:k:g:m:t:e:f:o:a:biqpcG", longopts, nullptr)) != -1) {  // bgreat.cpp:67
@@ -214,6 +222,14 @@ int main(int argc, char** argv) {
             case 1028: gaf_cs = true; break;
             case 1029: inside = true; break;
             case 1030: exh_paths = true; break;
+            case 1031: recompactFile = optarg; break;
+            case 1032:   // a non-negative integer, digits only: 0 keeps every unitig
+                if (!bgr::recompact_parse_min_reads(optarg, &min_reads)) {
+                    fprintf(stderr, "bgreat: --min-reads takes a non-negative integer of at most nine digits, not '%s'\n", optarg);
+                    return 2;
+                }
+                min_reads_given = true;
+                break;
             default: break;  // -o and -p are accepted and ignored, as in the reference (no `case`)
         }
     }
@@ -231,6 +247,7 @@ int main(int argc, char** argv) {
     if (min_link_given && bubblesFile.empty() && phaseFile.empty() && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-link is the threshold of --bubbles FILE, --phase FILE, --blocks FILE and --haplotypes FILE\n"); return 2; }
     if (min_phase_given && blocksFile.empty() && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-phase is the threshold of --blocks FILE and --haplotypes FILE\n"); return 2; }
     if (min_block_given && haplotypesFile.empty()) { fprintf(stderr, "bgreat: --min-block is the threshold of --haplotypes FILE\n"); return 2; }
+    if (min_reads_given && recompactFile.empty()) { fprintf(stderr, "bgreat: --min-reads is the threshold of --recompact FILE\n"); return 2; }
     if (!haplotagFile.empty() && !gaf) { fprintf(stderr, "bgreat: --haplotag BLOCKS_FILE adds its fields to the lines of --gaf\n"); return 2; }
     if (exh_paths && !brute) { fprintf(stderr, "bgreat: --exhaustive-paths outputs the paths of exhaustive mode: it needs -b\n"); return 2; }
     if (exh_paths && incomplete) { fprintf(stderr, "bgreat: --exhaustive-paths is not defined with -i: a partial path of exhaustive mode may lack its end offset\n"); return 2; }
@@ -287,6 +304,7 @@ int main(int argc, char** argv) {
     if (!phaseFile.empty() && bgr_graph_phase_enable(graph, 1, min_link) != BGR_OK) die("--phase");   // (likewise; it implies links, triples and the bubbles)
     if (!blocksFile.empty() && bgr_graph_blocks_enable(graph, 1, min_link, min_phase) != BGR_OK) die("--blocks");   // (likewise; it implies what --phase does)
     if (!haplotypesFile.empty() && bgr_graph_haplotypes_enable(graph, 1, min_link, min_phase, min_block) != BGR_OK) die("--haplotypes");   // (likewise; it implies what --blocks does)
+    if (!recompactFile.empty() && bgr_graph_recompact_enable(graph, 1, min_reads) != BGR_OK) die("--recompact");   // (likewise: unitig abundance, and the kept unitigs compacted when the run ends)
     const bool pileup = !pileupFile.empty() || !depthFile.empty();   // either file switches the counting on (the graph's switch, as --gfa's)
     if (pileup && bgr_graph_pileup_enable(graph, 1) != BGR_OK) die(pileupFile.empty() ? "--depth" : "--pileup");
     const bgr_variant_strand_params sprm = {vprm.min_depth, vprm.min_alt, vprm.min_af_ppm, min_alt_strand};
@@ -357,6 +375,15 @@ int main(int argc, char** argv) {
         std::vector<char> seq(seq_bytes);
         if (n_haps && bgr_graph_haplotypes(graph, haps.data(), n_haps, &n_haps, seq.data(), seq_bytes, &seq_bytes) != BGR_OK) die("--haplotypes");
         if (bgr_write_haplotypes(haplotypesFile.c_str(), graph, bubbles.data(), bubbles.size(), entries.data(), entries.size(), haps.data(), n_haps, seq.data(), seq_bytes) != BGR_OK) die("--haplotypes");
+    }
+    if (!recompactFile.empty()) {  // (the run has compacted the unitigs its reads support: a unitig file for the next run)
+        uint64_t n_chains = 0, walk_n = 0, seq_bytes = 0;
+        if (bgr_graph_recompact_result(graph, nullptr, 0, &n_chains, nullptr, 0, &walk_n, nullptr, 0, &seq_bytes) != BGR_OK && n_chains == 0) die("--recompact");
+        std::vector<bgr_chain> chains(n_chains);
+        std::vector<int32_t> walk(walk_n);
+        std::vector<char> seq(seq_bytes);
+        if (n_chains && bgr_graph_recompact_result(graph, chains.data(), n_chains, &n_chains, walk.data(), walk_n, &walk_n, seq.data(), seq_bytes, &seq_bytes) != BGR_OK) die("--recompact");
+        if (bgr_write_recompact(recompactFile.c_str(), graph, chains.data(), n_chains, walk.data(), walk_n, seq.data(), seq_bytes) != BGR_OK) die("--recompact");
     }
     if (!pileupFile.empty() && (strands ? bgr_write_pileup_strands(pileupFile.c_str(), graph) : bgr_write_pileup(pileupFile.c_str(), graph)) != BGR_OK) die("--pileup");   // (likewise: straight from the graph's totals)
     if (!depthFile.empty() && bgr_write_depth(depthFile.c_str(), graph) != BGR_OK) die("--depth");

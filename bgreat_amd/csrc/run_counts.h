@@ -14,7 +14,7 @@
 
 namespace bgr {
 
-enum : uint32_t { kCountAbundance = 1, kCountLinks = 2, kCountPileup = 4, kCountVariants = 8, kCountStrands = 16, kCountBubbles = 32, kCountTriples = 64, kCountPhase = 128, kCountBlocks = 256, kCountHaplotypes = 512 };   // `what` a run counts
+enum : uint32_t { kCountAbundance = 1, kCountLinks = 2, kCountPileup = 4, kCountVariants = 8, kCountStrands = 16, kCountBubbles = 32, kCountTriples = 64, kCountPhase = 128, kCountBlocks = 256, kCountHaplotypes = 512, kCountRecompact = 1024 };   // `what` a run counts
 struct RunCounts {
     uint32_t (*wanted)(const bgr_graph* g);                        // the graph's sticky switches as a mask (links, triples and pileup imply abundance, bubbles imply links, phase implies bubbles and triples, blocks imply phase, haplotypes imply blocks)
     void (*begin)(bgr_graph* g, uint32_t what);                    // a new run: the totals of the one before are gone, whatever becomes of this one

@@ -41,7 +41,7 @@ inline int end_stages(const RunStage* st, int n, bgr_graph* g, uint32_t what, bo
 // The graph's sticky switches as the mask of what a run counts: haplotypes imply blocks, blocks imply phase, phase implies bubbles and triples,
 // bubbles imply links, variants imply the pileup, strands count only next to the pileup or variants switch they belong to, and whatever is
 // counted implies abundance.
-struct RunSwitches { bool links, bubbles, triples, phase, blocks, haplotypes, pileup, variants, pileup_strands, variants_strands; };
+struct RunSwitches { bool links, bubbles, triples, phase, blocks, haplotypes, pileup, variants, pileup_strands, variants_strands, recompact; };
 inline uint32_t counts_wanted(const RunSwitches& s) {
     const bool blocks = s.blocks || s.haplotypes, phase = s.phase || blocks, bubbles = s.bubbles || phase;
     uint32_t what = 0;
@@ -54,6 +54,7 @@ inline uint32_t counts_wanted(const RunSwitches& s) {
     if (s.pileup || s.variants) what |= kCountPileup;
     if (s.variants) what |= kCountVariants;
     if ((s.pileup && s.pileup_strands) || (s.variants && s.variants_strands)) what |= kCountStrands;
+    if (s.recompact) what |= kCountRecompact;   // (it keeps unitigs by the abundance totals and counts nothing of its own)
     return what ? what | kCountAbundance : 0;
 }
 

@@ -979,6 +979,55 @@ int bgr_graph_haplotypes(const bgr_graph* g, bgr_haplotype* out, uint64_t cap, u
 int bgr_write_haplotypes(const char* path, const bgr_graph* g, const bgr_bubble* bubbles, uint64_t n_bubbles, const bgr_block_entry* entries, uint64_t n_entries,
                          const bgr_haplotype* haps, uint64_t n, const char* seq, uint64_t seq_bytes);
 
+/* Re-compaction: a kept subset of the graph's unitigs merged into maximal non-branching chains and spelled as new unitigs -- the graph the reads
+ * support, as a unitig file that a next run takes as its graph.  All integers, every byte deterministic (tests/recompact_ref.py is the executable
+ * definition).
+ * Terms: K = k - 1.  An oriented id x is +u or -u with 1 <= u <= n; spell(x) is unitig u, or its reverse complement when x is negative; first(x)
+ * and last(x) are the first and last K characters of spell(x).  Nodes are ordered by (|x|, x < 0).  keep[u] is 0 or 1 per unitig.
+ * Edges: x -> y is an edge when both are kept and last(x) == first(y); y may be x or -x, and two different unitigs with equal ends both count.
+ * out(x) is the number of edges leaving x, in(x) = out(-x); the mate of x -> y is -y -> -x.
+ * Merge links: x -> y is a merge link when out(x) == 1, in(y) == 1 and |x| != |y| (no self-loop x -> x, no hairpin x -> -x).  Every node has at
+ * most one merge successor and one predecessor, the links are closed under mating, the components are paths and rings, and no component holds both
+ * z and -z.
+ * Chains: a component and its mate are two readings of one chain, reported once, in the reading whose first node is smaller: a path's first node
+ * is its head (head is compared with -tail; a single unitig is reported as +u); a ring's first node is its smallest node, so it is read in the
+ * direction in which its smallest-|id| unitig is forward, opened at the link that enters that node and flagged circular.
+ * Sequence: the first unitig goes in whole, every later one without its first K characters: length = the sum of the lengths - (m - 1) K.  An opened
+ * ring is spelled as the linear walk: its last K characters equal its first K.
+ * Order: chains are ordered by first node ascending and numbered from 1.
+ * Properties: every kept unitig lies in exactly one chain; the multiset of canonical k-mers of the output equals that of the kept unitigs;
+ * compacting the output again with everything kept merges nothing.
+ * A record: seq_off, seq_len into one byte buffer of ACGT characters (the chains back to back), walk_off into one array of oriented ids (the chains'
+ * walks back to back), n_unitigs, flags (BGR_CHAIN_CIRCULAR).
+ * bgr_graph_recompact works on `device`, where the graph must be resident, for any subset: keep has one byte per unitig 1..n and n_keep must equal
+ * the graph's number of unitigs (bgreat_amd/csrc/recompact_kernels.h has the passes: the ends counted in a table indexed by meta's key indices,
+ * unique successors, pointer jumping with rings cut, count / scan / place, the spelling assigned by output in aligned 16-byte stores, the records;
+ * launches in stream order on one stream, no workgroup waits for another, no atomics on any output).  *n, *walk_n and *seq_bytes are set once the
+ * sizing passes have run; when a capacity is smaller the call returns BGR_E_CAPACITY with nothing copied (a call with capacities of 0 is the
+ * sizing call).  BGR_E_ARG with nothing copied for a graph with exception planes (non-ACGT unitig characters), a wrong n_keep, or a graph not on
+ * the device.  The scratch (169 bytes per unitig and 16 per key index) and the output live on the device for the call: BGR_E_NOMEM, with nothing
+ * left allocated, when it lacks them.  bgr_graph_recompact_times: the milliseconds of the calling thread's last call -- ends + successors, ranking,
+ * place + scans, spell, records (events on the call's stream).
+ * bgr_graph_recompact_enable(g, on, min_reads) is sticky and implies unitig abundance for the run: when the run ends,
+ * keep[u] = (reads[u] >= min_reads) from the run's summed abundance (reads counts the occurrences of u in the paths of MAPPED reads; min_reads 0
+ * keeps everything) is uploaded once to the device of the first aligner the run collected and compacted there; bgr_graph_recompact_result delivers
+ * the last successful run's records, walk and characters with the same two-call convention (BGR_E_ARG when there are none: a failed run,
+ * BGR_E_COMPACTION too, leaves none).  Exhaustive mode is refused as with abundance.
+ * bgr_write_recompact (host code, deterministic bytes) writes FASTA that a next run reads as its unitig file; per chain the line
+ *   >{ordinal} LN:i:{length} unitigs={m} ring={.|circular} walk={>12<7>9}
+ * (the walk in GAF notation over the 1-based ordinals of the INPUT graph) and the sequence on one line.  Records that do not lie back to back in
+ * walk and seq, or a walk id outside the graph, are BGR_E_ARG. */
+#define BGR_CHAIN_CIRCULAR 1u
+typedef struct { uint64_t seq_off, seq_len, walk_off; uint32_t n_unitigs, flags; } bgr_chain;   /* 32 bytes */
+int bgr_graph_recompact(const bgr_graph* g, int device, const uint8_t* keep, uint64_t n_keep, bgr_chain* out, uint64_t cap, uint64_t* n, int32_t* walk, uint64_t walk_cap,
+                        uint64_t* walk_n, char* seq, uint64_t seq_cap, uint64_t* seq_bytes);
+int bgr_graph_recompact_times(double ms[5]);
+int bgr_graph_recompact_enable(bgr_graph* g, uint32_t on, uint64_t min_reads);
+int bgr_graph_recompact_enabled(const bgr_graph* g);   /* the switch as it stands: 1 or 0 */
+int bgr_graph_recompact_result(const bgr_graph* g, bgr_chain* out, uint64_t cap, uint64_t* n, int32_t* walk, uint64_t walk_cap, uint64_t* walk_n, char* seq, uint64_t seq_cap,
+                               uint64_t* seq_bytes);
+int bgr_write_recompact(const char* path, const bgr_graph* g, const bgr_chain* chains, uint64_t n, const int32_t* walk, uint64_t walk_n, const char* seq, uint64_t seq_bytes);
+
 /* Haplotags: which haplotype of which block a READ lies on, from blocks that are given -- the --blocks file of an earlier run on the same unitig
  * file, or its structs -- so the reads tagged need not be the reads the blocks were phased from.  All integers, every result deterministic.
  * The tag table: uint32_t table[n_unitigs + 1], table[0] = 0; table[u] = block << 1 | hap with block >= 1 when unitig u is the branch of a bubble
